@@ -27,6 +27,8 @@ Besides the contract's fields the JSON line carries
                  result conversion and D2H) as Mpx.template/s
   verified       a window of the result checked against the oracle after the
                  timed loop (every template of the search, near-tie policy)
+  outputs        with --dump-outputs DIR: the .npy files of the last timed
+                 step's result planes written to DIR (result_sample)
 
 Other workloads: --config C1|C2|C5 (BASELINE.json configs as SURVEY.md 8d
 defines them), --emulate-ranks R (the R rank blocks of the tiled search run one
@@ -99,7 +101,16 @@ def parse():
                          "environment untouched, 'auto' tries '0' and, if the ranks fail, 'env'")
     ap.add_argument("--halo", default="rccl", choices=["rccl", "host", "gloo"],
                     help="halo exchange executor for --gpus > 1 (host: host arrays over gloo, for bring-up)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the result planes the timed path computed in its last step "
+                         "(amp, age, angle, snr: float64) as DIR/<name>.npy - whole planes where they fit 64 MB in all, "
+                         "else the same seeded sample of cells of every plane - and DIR/outputs.json describing them")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.emulate_ranks:
+        ap.error("--dump-outputs: the emulated ranks' step leaves no result of the whole search")
+    return a
 
 
 # ----------------------------------------------------------------------------- workloads
@@ -349,6 +360,52 @@ def other_mode_leg(step, ctx, a, units, like_main=False):
                 "roofline_frac": round(units / (dt / b.steps) * ALGO_BYTES_PER_UNIT / 1e9 / HBM_PEAK_GBS, 4)}
     except Exception as e:
         return {"error": "%s: %s" % (type(e).__name__, e)}
+
+
+# ----------------------------------------------------------------------------- --dump-outputs
+RESULT_PLANES = ("amp", "age", "angle", "snr")      # the (4, h, w) float64 result a caller of the search receives
+DUMP_MAX_BYTES = 64 * 10 ** 6                       # all files together
+DUMP_SEED = 20261015
+
+
+def result_sample(results, max_bytes=DUMP_MAX_BYTES, seed=DUMP_SEED):
+    """({name: float64 array}, manifest) of the planes of every (prefix, (4, h, w) result) in ``results``: whole planes
+    where all of them fit ``max_bytes``, else the same cells of every plane - the sorted unique ones among k flat
+    (row-major) indices drawn from default_rng(seed), k as large as the budget allows.  The cells depend on the shapes
+    alone: two runs, or two builds, with the same arguments write the same cells."""
+    n_planes = sum(len(r) for _, r in results)
+    budget = max_bytes - 4096 * n_planes             # (room for the .npy headers)
+    whole = sum(8 * r[0].size * len(r) for _, r in results) <= budget
+    arrays, files = {}, {}
+    for prefix, r in results:
+        h, w = r.shape[1:]
+        cells = None if whole else np.unique(np.random.default_rng(seed).integers(0, h * w, size=budget // (8 * n_planes)))
+        for name, plane in zip(RESULT_PLANES, r):
+            v = np.asarray(plane, dtype=np.float64)
+            if cells is not None:
+                v = v[cells // w, cells % w]
+            arrays[prefix + name] = v
+            files[prefix + name] = {"shape": list(v.shape), "plane_shape": [int(h), int(w)],
+                                    "cells": "all" if cells is None else int(cells.size)}
+    manifest = {"planes": list(RESULT_PLANES), "dtype": "float64", "files": files,
+                "sample": None if whole else
+                "np.unique(np.random.default_rng(%d).integers(0, h * w, size=k)) - flat row-major indices; k = %d"
+                % (seed, budget // (8 * n_planes))}
+    return arrays, manifest
+
+
+def write_outputs(dirpath, sample):
+    """Writes result_sample()'s arrays as dirpath/<name>.npy and its manifest as dirpath/outputs.json; returns the
+    line's `outputs` block."""
+    arrays, manifest = sample
+    os.makedirs(dirpath, exist_ok=True)
+    nbytes = 0
+    for name, v in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), v)
+        nbytes += os.path.getsize(os.path.join(dirpath, name + ".npy"))
+    with open(os.path.join(dirpath, "outputs.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    return {"dir": dirpath, "files": sorted(arrays), "bytes": nbytes, "sampled": manifest["sample"] is not None}
 
 
 # ----------------------------------------------------------------------------- the other BASELINE configs
@@ -814,7 +871,7 @@ def run_shardings(a, rank, world, device, dist, transport, pool, g, Template, sc
     "transport": "host (RCCL failed: <message>)" and rccl.nranks 0.  Same process, nothing restarted."""
     shards = ["orientations", "tiles"] if a.shard == "auto" else [a.shard]
     first_backend = "host" if a.halo in ("host", "gloo") else "rccl"
-    runs = {}
+    runs, dumps = {}, {}
     for sh in shards:
         label, built, errors = None, None, []
         for backend in ([first_backend] + (["host"] if first_backend == "rccl" else [])):
@@ -841,6 +898,10 @@ def run_shardings(a, rank, world, device, dist, transport, pool, g, Template, sc
                 raise RuntimeError("; ".join(errors) or "set-up failed")
             dt, prof = timed_loop(built["step"], built["ctx"], a, dist, built["after_warmup"],
                                   max_over_ranks=lambda v: max_over(transport, v))
+            if rank == 0 and getattr(a, "dump_outputs", ""):
+                r_ = built["result"]()                 # the last timed step's result (the folded record / the gathered maps)
+                dumps[sh] = result_sample([("", r_)]) if r_ is not None else None
+                del r_
             ctx, plan = built["ctx"], built["plan"]
             # what RCCL itself says about the communicator this sharding ran on, from every rank
             infos = transport.gather(ctx.comm_info(), 0)
@@ -906,6 +967,8 @@ def run_shardings(a, rank, world, device, dist, transport, pool, g, Template, sc
         out["failed"] = True
         return out
     out["sharding"] = first
+    if dumps.get(first):
+        out["outputs"] = write_outputs(a.dump_outputs, dumps[first])
     for k, v in runs.items():
         if k != first:
             out["c4_tiles" if k == "tiles" else "orientations"] = v
@@ -1123,12 +1186,29 @@ def main():
         if emu:
             emu[3][:] = 0.0
     dt, prof = timed_loop(step, ctx, a, None, after_warmup)
+    dumped = None
+    if a.dump_outputs:
+        # read before anything else runs on the context: the record the last timed step left is the last scale's; the
+        # earlier scales of a multi-scale config (C5) are searched once more, untimed, from the same descriptors
+        ids = (np.repeat(params, len(angles)), np.tile(angles, len(params)))
+        last = ctx.get_result(*ids)
+        results = []
+        for (arr_, sp_, _, win_, twin_) in descs[:-1]:
+            m.run_described(arr_, sp_, win_ if a.mode == "exact" else 0.0, twin_)
+            results.append(ctx.get_result(*ids))
+        results.append(last)
+        pre = (lambda sc: "scale%g_" % sc) if len(scales) > 1 else (lambda sc: "")
+        dumped = write_outputs(a.dump_outputs, result_sample([(pre(sc), r_) for sc, r_ in zip(scales, results)]))
+        del last, results
+        sl.release_host_buffers()              # (the end-to-end call's first result gets fresh pages, as without the dump)
 
     ms = 1e3 * dt / a.steps
     value = units / (dt / a.steps) / 1e6
     if emu:
         plan = emu[5][0]
     out = base_line(value, ms, plan, "1 (whole DEM)", prof, 1)
+    if dumped:
+        out["outputs"] = dumped
     if emu:
         R, part_label, cores_, per_block, halo_bytes, plans = emu
         pb = per_block / a.steps
