@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 9
+#define SC_ABI_VERSION 10
 
 #define SC_OK               0
 #define SC_ERR_INVALID     -1   /* bad argument                                */
@@ -153,7 +153,9 @@ int sc_set_dem_device(sc_ctx* ctx, const void* z_dev, int ly, int lx, int gy0,
                       const double* xaxis, const double* yaxis);
 
 /* Explicit template window for SC_KIND_WINDOW (generic plugins): w is the
- * h x w float64 block W[ny//2+pmin .., nx//2+qmin ..]; returns the slot. */
+ * h x w float64 block W[ny//2+pmin .., nx//2+qmin ..]; returns the slot.
+ * The slot keeps it twice: in float32 for the searches and as given, in
+ * float64, for the float64 scorers (sc_settle_exact, sc_score_*_f64; ABI 10). */
 int sc_upload_window(sc_ctx* ctx, const double* w, int h, int wd, int* slot);
 /* Optional per-cell masks for generic plugins (ny x nx uint8, global):
  * get_window_limits() and get_err_mask() results; pass NULL to clear. */
@@ -335,7 +337,9 @@ int sc_get_near_ties(sc_ctx* ctx, uint8_t* out);
  * for the m cells given (global row, column pairs) and EVERY template of the last sc_match in this context, in
  * the order they were handed over: amp, snr = m x n doubles each, masks applied (core.py:369-375).  The last step
  * of scarplet_amd.match(..., exact=True): the cells where two templates lie inside the float32 paths' own rounding
- * are settled the way the reference settles them.  Built-in templates only (SC_ERR_UNSUPPORTED otherwise); the
+ * are settled the way the reference settles them.  Host-uploaded windows (SC_KIND_WINDOW) are scored from their slots'
+ * float64 copies, with the curvature of the descriptor's (cc, sc2, ss) - the search orientation's, not the plugin's alpha -
+ * and their per-cell masks (ABI 10; SC_ERR_INVALID when a slot no longer holds its template's window); the
  * context must hold the cells' neighbourhoods (a whole DEM does).  n_templates: what the caller sized amp / snr for -
  * SC_ERR_INVALID unless it is the number of templates of that last sc_match (ABI 8). */
 int sc_score_cells_f64(sc_ctx* ctx, const int32_t* cells, int m, int n_templates, double* amp, double* snr);
@@ -375,9 +379,13 @@ int sc_score_pairs_f64(sc_ctx* ctx, const int32_t* cells, const int32_t* templat
  *             cell - the record's holder where its class is named - as itself (its amplitude carries its own sign)
  *   max_work  > 0: nothing is scored when pairs x the largest support box exceeds it (SC_ERR_UNSUPPORTED)
  *   stats     8 values: flagged cells, pairs listed, pairs scored, cells scored, cells whose template changed, events,
- *             0, taps the scores weighed
- * SC_ERR_UNSUPPORTED also when the event list overflowed (the caller takes a longer route: sc_get_near_ties +
- * sc_score_cells_f64) and for templates with host-uploaded windows.
+ *             the audit, taps the scores weighed.  The audit (stats[6], ABI 10): over the cells whose record holder was
+ *             scored in float64, the largest |snr32 - snr64| / snr64 of its float32 record against that score, as an
+ *             integer in units of 1e-9, rounded up (at most 1e18; 0 when no holder was scored).  A lower bound on the
+ *             search's float32 SNR error - only holders of near-tie cells are seen - measured at no extra cost.
+ * Templates with host-uploaded windows (SC_KIND_WINDOW) are settled like the built-ins since ABI 10 (sc_score_cells_f64).
+ * SC_ERR_UNSUPPORTED when the event list overflowed (the caller takes a longer route: sc_get_near_ties +
+ * sc_score_cells_f64).
  */
 int sc_settle_exact(sc_ctx* ctx, int n_twin, double max_work, long long* stats);
 
@@ -406,7 +414,8 @@ int sc_set_best(sc_ctx* ctx, const float* amp, const float* snr, const uint32_t*
 int sc_rank_candidates(sc_ctx* ctx, uint32_t* pairs, long long capacity, long long* n_pairs);
 /* settle the union of all ranks' candidates: t[0..n) = the descriptors of the WHOLE search in fold order (they become the
  * context's template table; nothing is matched), pairs as sc_rank_candidates wrote them (ids = sc_template.id);
- * n_twin, max_work, stats as sc_settle_exact. */
+ * n_twin, max_work, stats as sc_settle_exact.  Built-in template classes only: a template with a host-uploaded window
+ * (SC_KIND_WINDOW) answers SC_ERR_UNSUPPORTED - the other ranks' window slots do not exist in this context. */
 int sc_settle_pairs(sc_ctx* ctx, const sc_template* t, int n, const uint32_t* pairs, long long n_pairs, int n_twin,
                     double max_work, long long* stats);
 /* the exchange on the devices: after sc_rank_candidates (capacity 0 will do: the list stays on the device) every rank's

@@ -17,9 +17,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCARPLET_HIP_LIB") or os.path.join(_HERE, "libscarplet_hip.so")
 
 SC_OK = 0
-ABI_VERSION = 9
+ABI_VERSION = 10
 ID_NONE = 0xFFFFFFFF
 COMM_ID_BYTES = 128
+KIND_WINDOW = 2             # SC_KIND_WINDOW: a template whose window the host uploaded (sc_upload_window)
 
 K_NAMES = ("k_curv", "k_windows", "k_direct", "k_fwd_rows", "k_fwd_cols",
            "k_inv_cols", "k_inv_rows", "k_settle")
@@ -460,9 +461,11 @@ class Context(object):
 
     @staticmethod
     def _settle_stats(st):
+        """The settle's counters as a dict.  ``max_f32_err``: the audit (stats[6], units of 1e-9) - the largest relative
+        error of a scored record holder's float32 SNR against its float64 score: a lower bound on the search's error."""
         return {"flagged_cells": int(st[0]), "pairs_listed": int(st[1]), "float64_pairs": int(st[2]),
                 "float64_cells": int(st[3]), "changed_cells": int(st[4]), "events": int(st[5]),
-                "taps": int(st[7])}
+                "max_f32_err": int(st[6]) * 1e-9, "taps": int(st[7])}
 
     # ---- exact mode of an orientation-sharded search (include/scarplet_hip.h: sc_settle_pairs) ----
     def snapshot_best(self):
@@ -508,6 +511,10 @@ class Context(object):
         """Settle the union of all ranks' candidates with the descriptors of the WHOLE search (sc_settle_pairs); the
         counters as settle_exact returns them.  ``pairs``: an (n, 2) uint32 array, or None for the list
         exchange_candidates left on the device."""
+        if any(int(t.kind) == KIND_WINDOW for t in templates):
+            # (the library refuses them as well: another rank's window slots do not exist in this context)
+            raise ScarpletHipError("sc_settle_pairs: templates with host-uploaded windows (generic plugins) are not settled "
+                                   "across ranks - the orientation-sharded exact mode takes the built-in template classes only")
         st = (C.c_longlong * 8)()
         if pairs is None:
             ptr, n = None, int(getattr(self, "_exchanged", 0))

@@ -391,8 +391,12 @@ class Matcher(object):
         benchmark DEM).  With the flag on, the search marks the cells where some template came within EXACT_WINDOW of the
         running best and lists which; the float64 argmax of a marked cell can only be among those templates, and exactly
         those (cell, template) pairs are scored in float64 on the device, which also picks the winner and writes it into
-        the record (_search_exact, sc_settle_exact).  ``exact=None``: on for the built-in template classes, off for
-        plugins whose windows the host uploads (no float64 form on the device).  Cost: 13 % on the row pass plus the
+        the record (_search_exact, sc_settle_exact).  Plugins whose windows the host uploads (the Shifted classes, any
+        user template) are settled from the float64 windows the device keeps; their float32 error is checked in every
+        search (exact_stats["max_f32_err"]; one retry with a wider window where it exceeds half the window).  Their
+        per-cell masks take the real-space path - not where that would cost beyond a hundred times the FFT search: then
+        the float32 result stands, with a warning and exact_stats["skipped"].  ``exact=None``: on for the built-in
+        template classes, off for plugins whose windows the host uploads.  Cost: 13 % on the row pass plus the
         pairs."""
         params = np.atleast_1d(np.asarray(params, dtype=float))
         angles = np.atleast_1d(np.asarray(angles, dtype=float))
@@ -497,12 +501,54 @@ class Matcher(object):
         Which path: the FFT tiles where the planner chose them and the row kernel can flag (no per-cell masks); the
         real-space path otherwise - by name, by `auto` for a small support, for UpperBreak's error masks, or because the
         device's own statistic says the FFT convolution cannot resolve this surface in float32 (method="auto", as without
-        the mode).  A list that overflows, or more float64 work than EXACT_MAX_F64, takes the longer routes of round 5."""
+        the mode).  A list that overflows, or more float64 work than EXACT_MAX_F64, takes the longer routes of round 5.
+
+        Templates whose windows the host uploads (generic plugins, the Shifted classes) are settled the same way, from the
+        float64 windows their slots keep.  Their float32 error is nobody's measurement: the settle's audit (max_f32_err,
+        the largest relative float32 error of a scored record holder) checks it in every search, and where it exceeds
+        half the window the search and the settle run once more with a window of 2.2 x that error (at least the path's
+        default, at most EXACT_RETRY_MAX) - exact_stats["retried"] = (old window, new window)."""
+        import warnings
+        self.exact_stats["max_f32_err"] = float("nan")          # (measured by the device route only)
+        windows = int(arr[0].kind) == _WT.KIND_WINDOW
+        if not self._exact_pass(arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs, windows):
+            return
+        err, win = self.exact_stats["max_f32_err"], self._exact_window
+        if not (windows and err > 0.5 * win):
+            return
+        new = min(max(2.2 * err, self._default_exact_window(arr, self.method_used == "fft")), self.EXACT_RETRY_MAX)
+        first = dict(self.exact_stats)
+        self.exact_stats = {"flagged_cells": 0, "patches": 0, "changed_cells": 0, "float64_cells": 0,
+                            "max_f32_err": float("nan"), "retried": (win, new), "first_pass": first}
+        self.ctx.reset_best()
+        self._exact_pass(arr, self._exact_sp, bbox, max_area, self.method_used, group, Template, scale, params, angles,
+                         kwargs, windows, window=new)
+        err = self.exact_stats["max_f32_err"]
+        if err > 0.5 * new:
+            warnings.warn("exact=True: the float32 SNR error the settle measured (%.2e) is still above half the near-tie "
+                          "window (%.2e) after one retry - some cells may keep the float32 argmax" % (err, new))
+
+    # exact=True, window templates: the widest near-tie window a retry after the audit takes
+    EXACT_RETRY_MAX = 5e-3
+
+    def _default_exact_window(self, arr, fft):
+        """The path's near-tie window as the class states it (an instance may override EXACT_WINDOW[_DIRECT])."""
+        if not fft:
+            return type(self).EXACT_WINDOW_DIRECT
+        kinds = {int(arr[0].kind), int(arr[len(arr) - 1].kind)}
+        table = type(self).EXACT_WINDOW
+        return max(table.get(k, max(table.values())) for k in kinds)
+
+    def _exact_pass(self, arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs, windows,
+                    window=None):
+        """One search with its near-ties flagged and settled (``window``: the near-tie window of both paths instead of
+        the defaults).  True when the device settled it (exact_stats holds its counters and the audit)."""
         import warnings
         n_par = len(params)
         n_twin = self.end_twins(arr, n_par, angles)
         fft = sp.method == _plan.METHOD_FFT
-        win_fft = self.exact_window_for(arr, sp) if fft else 0.0
+        win_fft = (self.exact_window_for(arr, sp) if window is None else window) if fft else 0.0
+        win_direct = self.EXACT_WINDOW_DIRECT if window is None else window
         try:
             if fft:
                 self.ctx.set_option("near_window", win_fft)
@@ -514,16 +560,24 @@ class Matcher(object):
                     if "near-tie flags" not in str(e):
                         raise
                     fft = False
+                    if windows and not self._direct_affordable(bbox, max_area, n_par):
+                        # (a plugin's window on a grid where the real-space path would take beyond a hundred times the
+                        # FFT search: the float32 answer, said)
+                        self.ctx.set_option("near_window", 0.0)
+                        self.ctx.match(arr, sp, sync=True)
+                        self.method_used = "fft"
+                        warnings.warn("exact=True: this plugin's templates carry per-cell masks, which only the real-space "
+                                      "path flags, and a real-space search would take beyond a hundred times the FFT "
+                                      "search here - the float32 FFT result stands")
+                        self.exact_stats["skipped"] = True
+                        return False
                 if fft and method == "auto":
                     wins, near = self.ctx.resolution_stats()
                     self.unresolved_frac = near / wins if wins else 0.0
                     if self.unresolved_frac > self.UNRESOLVED_MAX:
                         note = ("the FFT path cannot resolve %.1f %% of this surface's cells in float32 (no noise floor "
                                 "of its own)" % (100 * self.unresolved_frac))
-                        ww = bbox[3] - bbox[2] + 1
-                        n_cells = (self.core[1] - self.core[0]) * (self.core[3] - self.core[2])
-                        if not _plan.direct_window_fits(ww) or \
-                                _plan.direct_cost(max_area) > 100 * _plan.fft_cost(self.plan, n_cells, n_par):
+                        if not self._direct_affordable(bbox, max_area, n_par):
                             warnings.warn(note + "; method='direct' is exact but much slower here - not taken automatically")
                         else:
                             warnings.warn(note + ": searched again on the exact real-space path")
@@ -534,23 +588,20 @@ class Matcher(object):
                     self.plan, sp = self.plan_for(bbox, max_area, "direct", group, n_params=n_par)
                     self.ctx.reset_best()
             if not fft:
-                self.ctx.set_option("near_window", self.EXACT_WINDOW_DIRECT)
+                self.ctx.set_option("near_window", win_direct)
                 self.ctx.match(arr, sp, sync=True)
         finally:
             self.ctx.set_option("near_window", 0.0)
         self.method_used = "fft" if fft else "direct"
+        self._exact_sp = sp
+        self._exact_window = win_fft if fft else win_direct
         if self.EXACT_USE_EVENTS:
             try:
                 st = self.ctx.settle_exact(n_twin, self.EXACT_MAX_F64)
-                self.exact_stats.update(st, route="device")
-                return
+                self.exact_stats.update(st, route="device", window=self._exact_window)
+                return True
             except _lib.ScarpletHipError as e:
                 msg = str(e)
-                if "built-in templates only" in msg:
-                    warnings.warn("exact=True: a plugin's window exists in float32 on the device only - the float32 result "
-                                  "stands (the built-in template classes are settled in float64)")
-                    self.exact_stats["skipped"] = True
-                    return
                 if "overflowed" not in msg and "too much float64 work" not in msg:
                     raise
                 self.exact_stats["settle"] = msg
@@ -558,13 +609,21 @@ class Matcher(object):
         if not self.whole:
             warnings.warn("exact=True: the near-ties of this block were not settled (%s)" % self.exact_stats.get("settle", "host route off"))
             self.exact_stats["skipped"] = True
-            return
+            return False
         if fft:
             self._rescore_near_ties(Template, scale, params, angles, kwargs)
         else:
             last = [tuple(c) for c in np.argwhere(self.ctx.near_ties())]
             self.exact_stats["flagged_cells"] = len(last)
             self._score_float64([(i + self.core[0], j + self.core[2]) for i, j in last], arr, bbox)
+        return False
+
+    def _direct_affordable(self, bbox, max_area, n_par):
+        """The guard of the real-space re-plans: the window fits the real-space kernel's slab and its search costs at
+        most a hundred times the FFT plan's (self.plan)."""
+        n_cells = (self.core[1] - self.core[0]) * (self.core[3] - self.core[2])
+        return _plan.direct_window_fits(bbox[3] - bbox[2] + 1) and \
+            _plan.direct_cost(max_area) <= 100 * _plan.fft_cost(self.plan, n_cells, n_par)
 
     @staticmethod
     def _without_end_twin(arr, n_params, angles):
@@ -698,12 +757,7 @@ class Matcher(object):
             # in the auxiliary context
             pass
         cells = np.asarray(sorted(set(last)), dtype=np.int32).reshape(-1, 2)
-        try:
-            amp, snr = self.ctx.score_cells_f64(cells, n_t)
-        except _lib.ScarpletHipError as e:
-            if "built-in templates only" in str(e):
-                return
-            raise
+        amp, snr = self.ctx.score_cells_f64(cells, n_t)
         k = np.argmax(snr, axis=1)                       # (first maximum: the fold order is the order of arr_main)
         rows = np.arange(len(cells))
         ids = np.array([arr_main[int(v)].id for v in k], dtype=np.int64)
@@ -864,7 +918,10 @@ def calculate_best_fit_parameters_serial(dem, Template, scale,
                                          ang_min=-np.pi / 2, **kwargs):
     """Full (age, orientation) search, orientation-major, forwarding extra
     keyword arguments to the template (core.py:65-136).  Returns the 4-tuple
-    (best_amp, best_age, best_angle, best_snr)."""
+    (best_amp, best_age, best_angle, best_snr).  ``exact=True`` gives every
+    cell the float64 reference's (age, orientation) for any template class,
+    the Shifted classes and user plugins included (Matcher.search); the
+    default (None) settles the built-in classes only."""
     device = kwargs.pop("device", 0)
     method = kwargs.pop("method", "auto")
     exact = kwargs.pop("exact", None)
@@ -901,7 +958,8 @@ def match(data, Template, **kwargs):
     'direct'), ``ages=`` (override the age grid), ``exact=`` (default: on for
     the built-in template classes - every cell's (age, orientation) is the
     float64 reference's argmax: the near-ties of the float32 search are scored
-    in float64 on the device, Matcher.search; ``exact=False``: the float32
+    in float64 on the device, Matcher.search; ``exact=True`` does the same for
+    plugins whose windows the host uploads; ``exact=False``: the float32
     search as it is, 5 - 10 % faster) and ``fold=``:
 
     ``fold="fused"`` (default): ONE device search, the running best folded in

@@ -49,7 +49,7 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt};
     size_t s = 0;
     for (DevBuf* b : arr) s += b->cap;
-    for (auto& w : c->windows) s += (size_t)w.h * w.wd * 5;
+    for (auto& w : c->windows) s += (size_t)w.h * w.wd * 13;
     return s;
 }
 
@@ -200,6 +200,7 @@ extern "C" int sc_clear_windows(sc_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& w : ctx->windows) {
         if (w.w) (void)hipFree(w.w);
+        if (w.w64) (void)hipFree(w.w64);
         if (w.m) (void)hipFree(w.m);
         if (w.mask_lim) (void)hipFree(w.mask_lim);
         if (w.mask_err) (void)hipFree(w.mask_err);
@@ -412,8 +413,10 @@ extern "C" int sc_upload_window(sc_ctx* ctx, const double* w, int h, int wd, int
     s.wd = wd;
     SC_HIP(ctx, hipMalloc((void**)&s.w, n * sizeof(float)));
     SC_HIP(ctx, hipMalloc((void**)&s.m, n));
+    SC_HIP(ctx, hipMalloc((void**)&s.w64, n * sizeof(double)));      // (the float64 scorers read the window as uploaded)
     SC_HIP(ctx, hipMemcpy(s.w, wf.data(), n * sizeof(float), hipMemcpyHostToDevice));
     SC_HIP(ctx, hipMemcpy(s.m, wm.data(), n, hipMemcpyHostToDevice));
+    SC_HIP(ctx, hipMemcpy(s.w64, w, n * sizeof(double), hipMemcpyHostToDevice));
     ctx->windows.push_back(s);
     *slot = (int)ctx->windows.size() - 1;
     return SC_OK;
@@ -529,8 +532,6 @@ static int score_f64(sc_ctx* ctx, const int32_t* cells, const int32_t* tsel, int
     if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
     const int n = ctx->last_batch;
     if (n <= 0) return sc_fail(ctx, SC_ERR_INVALID, "%s: no search has run in this context", who);
-    if (ctx->templ_windows)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: built-in templates only (a plugin's window is float32 on the device)", who);
     SC_HIP(ctx, hipSetDevice(ctx->device));
     for (int k = 0; k < m; ++k) {
         if (cells[2 * k] < 0 || cells[2 * k] >= ctx->g.ny || cells[2 * k + 1] < 0 || cells[2 * k + 1] >= ctx->g.nx)
@@ -639,6 +640,20 @@ static void templ_from_descriptor(const sc_ctx* ctx, const sc_template& s, Templ
     }
 }
 
+// What the float64 scorers need of a search beyond TemplDev: every template's window slot and orientation mix
+static void keep_f64_side(sc_ctx* ctx, const sc_template* t, int n) {
+    ctx->h_wslot.assign(n, -1);
+    ctx->h_mix.assign(3 * (size_t)n, 0.0);
+    ctx->templ_windows = false;
+    for (int j = 0; j < n; ++j) {
+        if (t[j].kind == SC_KIND_WINDOW) ctx->h_wslot[j] = t[j].window;
+        ctx->h_mix[3 * (size_t)j] = t[j].cc;
+        ctx->h_mix[3 * (size_t)j + 1] = t[j].sc2;
+        ctx->h_mix[3 * (size_t)j + 2] = t[j].ss;
+        ctx->templ_windows = ctx->templ_windows || t[j].kind == SC_KIND_WINDOW;
+    }
+}
+
 // The descriptors of a whole search as the template table the float64 scorer reads, without matching them
 // (sc_settle_pairs: a rank of an orientation-sharded search settles candidates of templates other ranks matched)
 int sc_load_templates(sc_ctx* ctx, const sc_template* t, int n) {
@@ -654,11 +669,8 @@ int sc_load_templates(sc_ctx* ctx, const sc_template* t, int n) {
     h.assign(n, TemplDev{});
     ctx->h_sums.assign(2 * (size_t)n, 0.0);
     ctx->h_wl1.assign(n, 0.0);
-    ctx->templ_windows = false;
-    for (int j = 0; j < n; ++j) {
-        templ_from_descriptor(ctx, t[j], h[j], &ctx->h_sums[2 * (size_t)j], &ctx->h_wl1[j]);
-        ctx->templ_windows = ctx->templ_windows || t[j].kind == SC_KIND_WINDOW;
-    }
+    for (int j = 0; j < n; ++j) templ_from_descriptor(ctx, t[j], h[j], &ctx->h_sums[2 * (size_t)j], &ctx->h_wl1[j]);
+    keep_f64_side(ctx, t, n);
     if ((rc = sc_ensure(ctx, ctx->templ, sizeof(TemplDev) * n))) return rc;
     ctx->async_in_flight = true;
     SC_HIP(ctx, hipMemcpyAsync(ctx->templ.p, h.data(), sizeof(TemplDev) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -847,8 +859,7 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
     SC_HIP(ctx, hipMemcpyAsync(ctx->wl1.p, wl1.data(), sizeof(double) * n,
                                hipMemcpyHostToDevice, ctx->stream));
     ctx->last_batch = n;
-    ctx->templ_windows = false;
-    for (int k = 0; k < n; ++k) ctx->templ_windows = ctx->templ_windows || t[k].kind == SC_KIND_WINDOW;
+    keep_f64_side(ctx, t, n);
 
     double cur[3] = {0, 0, 0};
     bool have_curv = false;

@@ -61,6 +61,7 @@ struct DevBuf {
 struct WindowSlot {
     double l1 = 0.0;           // sum |W|
     float* w = nullptr;        // h x wd float32
+    double* w64 = nullptr;     // h x wd float64, as uploaded: the float64 scorers' window (score_prepare_f64)
     uint8_t* m = nullptr;      // h x wd
     int h = 0, wd = 0;
     uint8_t* mask_lim = nullptr;
@@ -119,6 +120,11 @@ struct sc_ctx {
     // the copy, so they live here - no stream synchronisation between the upload and the launches
     std::vector<TemplDev> h_templ;
     std::vector<double> h_sums, h_wl1;
+    // the float64 scorers' side of the last search's descriptors: per template the window slot (SC_KIND_WINDOW; -1
+    // otherwise) and the orientation's curvature mix (cc, sc2, ss) - what a window template's score mixes the curvature
+    // with (TemplDev's cos_a / sin_a are the plugin's own alpha there)
+    std::vector<int> h_wslot;
+    std::vector<double> h_mix;
     std::vector<unsigned char> h_tiles;  // the tile list the device holds (bytes), to skip its re-upload
     bool async_in_flight = false;        // an sc_match_async has not been followed by sc_sync yet
     int last_batch = 0;
@@ -140,7 +146,7 @@ struct sc_ctx {
     DevBuf score;              // sc_score_cells_f64: the cell list and the two float64 outputs
     DevBuf score_w;            // ... and the templates' float64 windows (offsets, then the windows)
     DevBuf score_abc;          // ... and the three stencil planes of the block in float64 (rebuilt at every call)
-    bool templ_windows = false;   // the last sc_match carried host-uploaded windows (no float64 form on the device)
+    bool templ_windows = false;   // the last sc_match carried host-uploaded windows (scored from their slots' float64 copies)
     int batch_templ = 0;       // sc_set_option "batch_templ": templates one batched launch sequence may carry (0: SC_MAX_BATCH)
     int split_i1 = 1;          // sc_set_option "split_i1": under-filled column passes deal their transforms out along grid.z
     long long split_fill = 0;  // sc_set_option "split_fill": waves a dealt-out row pass may come to (0: 4096)
@@ -213,7 +219,9 @@ int launch_curv_alpha(sc_ctx* ctx, float cc, float sc2, float ss, int plane = 0)
 int launch_curv_f64(sc_ctx* ctx, double c2, double sn, double cs, double s2, double* out_dev);
 int launch_curv_alpha_batch(sc_ctx* ctx, const float (*coef)[3], int nb);
 // tsel_dev: nullptr - every cell against every template (m x n_templ outputs); else pair k = (cell k, template tsel[k]) (m outputs)
-int score_prepare_f64(sc_ctx* ctx, int n_templ, const unsigned long long** woff_out, const double** wbuf_out, const double** planes_out);
+// mix_out: (cc, sc2, ss) per template, read for SC_KIND_WINDOW templates only
+int score_prepare_f64(sc_ctx* ctx, int n_templ, const unsigned long long** woff_out, const double** wbuf_out, const double** planes_out,
+                      const double** mix_out);
 int launch_score_f64(sc_ctx* ctx, const int* cells_dev, const int* tsel_dev, int m, int n_templ, double* amp_dev, double* snr_dev);
 int launch_windows(sc_ctx* ctx, int first, int n, int wh_max, int ww_max);
 int launch_direct(sc_ctx* ctx, int first, int n, bool to_maps, int nb, int wh_max, int ww_max, bool long_runs);
@@ -335,6 +343,27 @@ __device__ __forceinline__ void sc_apply_masks(const TemplDev& t, const Geom& g,
     bool keep = gi >= t.ilo && gi <= t.ihi && gj >= t.jlo && gj <= t.jhi;
     if (t.mask_lim && t.mask_lim[(size_t)gi * g.nx + gj]) keep = false;
     if (!keep) { amp = 0.f; snr = 0.f; }
+}
+
+// The float64 scorers (k_score_f64, k_st_score) mix a tap's curvature as
+//   (A k_cc - ((2 B) sa) ca) + C k_ss          (dem.py:103-104 in numpy's order, ca / sa of the orientation)
+// A host-uploaded window's descriptor carries its plugin's alpha, not the orientation: its template's mix is the
+// search orientation's (cc, sc2, ss) from the side table, put into that form as ca = 1, sa = sc2 / 2, for which
+// ((2 B) sa) ca = B sc2 exactly (powers of two).
+__device__ __forceinline__ void sc_window_mix(const double* __restrict__ mix, int it, double& ca, double& sa,
+                                              double& k_cc, double& k_ss) {
+    k_cc = mix[3 * it];
+    sa = 0.5 * mix[3 * it + 1];
+    k_ss = mix[3 * it + 2];
+    ca = 1.0;
+}
+
+// The per-cell masks of a generic plugin (core.py:369-375) at global cell (i, j) for the float64 scorers: get_err_mask()
+// zeroes the SNR, get_window_limits() amplitude and SNR (sc_apply_masks' planes, global ny x nx)
+__device__ __forceinline__ void sc_window_masks(const TemplDev& t, const Geom& g, int i, int j, double& amp, double& snr) {
+    const size_t c = (size_t)i * g.nx + j;
+    if (t.mask_err && t.mask_err[c]) snr = 0.0;
+    if (t.mask_lim && t.mask_lim[c]) { amp = 0.0; snr = 0.0; }
 }
 
 // One step of compare() (core.py:230-240) on a (snr, amp, id) record:

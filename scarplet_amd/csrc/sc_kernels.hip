@@ -2,6 +2,7 @@
 // (sliding window) matcher.  gfx950 only.
 #include "sc_internal.h"
 #include <algorithm>
+#include <string.h>
 
 // ---------------------------------------------------------------------------
 // K1: the three alpha-independent curvature stencils (dem.py:88-101).
@@ -92,17 +93,23 @@ k_curv_f64(const double* __restrict__ z, Geom g, double dx, double dy, double c2
 // over the template's support box, W evaluated with k_windows' float64 expressions, the curvature with
 // k_curv_f64's (stencils of dem.py:88-101 on the float64 elevations, global borders zero), then core.py:360-375.
 // grid = (cells, templates), one workgroup each; the support box is dealt out over the threads.
-// Built-in templates only (a generic plugin's window exists in float32 on the device).
+// A generic plugin's window (SC_KIND_WINDOW) is the float64 block its host uploaded (sc_upload_window), its curvature mixed
+// with the search orientation's (cc, sc2, ss) - the plugin's alpha says nothing about it - and its per-cell masks applied.
 // ---------------------------------------------------------------------------
 // The float64 windows of the scorer, once per template instead of once per (cell, template): W over the template's support
 // box, 0 where the reference's W is 0 (outside the grid, outside |xr| < c & |yr| < d, at xr = 0, beyond the float64
 // underflow of a Ricker's exponential - core.py:348's M is literally W != 0).  grid = (ceil(largest box / 256), templates).
+// SC_KIND_WINDOW: the slot's float64 copy (wsrc[template], wh x ww), as the host's template() produced it.
 __global__ void __launch_bounds__(256)
 k_window_f64(const TemplDev* __restrict__ templ, Geom g, const double* __restrict__ xaxis, const double* __restrict__ yaxis,
-             const unsigned long long* __restrict__ woff, double* __restrict__ wbuf) {
+             const unsigned long long* __restrict__ woff, const double* const* __restrict__ wsrc, double* __restrict__ wbuf) {
     const TemplDev t = templ[blockIdx.y];
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= t.wh * t.ww) return;
+    if (t.kind == SC_KIND_WINDOW) {
+        wbuf[woff[blockIdx.y] + e] = wsrc[blockIdx.y][e];
+        return;
+    }
     const int a = e / t.ww, b = e - a * t.ww;
     const int k = g.ny / 2 + t.pmin + a, l = g.nx / 2 + t.qmin + b;
     double w = 0.0;
@@ -128,7 +135,7 @@ __global__ void __launch_bounds__(256)
 k_score_f64(const double* __restrict__ pa, const double* __restrict__ pb, const double* __restrict__ pc, Geom g,
             const TemplDev* __restrict__ templ, int n_templ, const double* __restrict__ sums,
             const double* __restrict__ xaxis, const double* __restrict__ yaxis,
-            const unsigned long long* __restrict__ woff, const double* __restrict__ wbuf,
+            const unsigned long long* __restrict__ woff, const double* __restrict__ wbuf, const double* __restrict__ mix,
             const int* __restrict__ cells, const int* __restrict__ tsel, double* __restrict__ amp_out, double* __restrict__ snr_out) {
     // tsel: (cell, template) PAIRS - block ci scores cell ci against template tsel[ci] (grid.y = 1) - instead of the full table
     const int ci = blockIdx.x, it = tsel ? tsel[ci] : (int)blockIdx.y;
@@ -137,8 +144,9 @@ k_score_f64(const double* __restrict__ pa, const double* __restrict__ pb, const 
     // curvature mix of this template's orientation: cc, sc2, ss are not in TemplDev - the same expression as the
     // reference's from its alpha = -orientation: cos(a)^2, 2 sin(a) cos(a), sin(a)^2 with a = -alpha, i.e. the
     // orientation; cos_a / sin_a of the descriptor are those of alpha
-    const double ca = t.cos_a, sa = -t.sin_a;                             // cos / sin of the ORIENTATION
-    const double k_cc = __dmul_rn(ca, ca), k_ss = __dmul_rn(sa, sa);
+    double ca = t.cos_a, sa = -t.sin_a;                                   // cos / sin of the ORIENTATION
+    double k_cc = __dmul_rn(ca, ca), k_ss = __dmul_rn(sa, sa);
+    if (t.kind == SC_KIND_WINDOW) sc_window_mix(mix, it, ca, sa, k_cc, k_ss);
     const double* __restrict__ wt = wbuf + woff[it];
     double xc = 0.0, t3 = 0.0;
     const int box = t.wh * t.ww;
@@ -183,6 +191,7 @@ k_score_f64(const double* __restrict__ pa, const double* __restrict__ pb, const 
             if ((t.flags & SC_FLAG_ERR_XR_LE0) ? (xr <= 0.0) : (xr >= 0.0)) snr = 0.0;
         }
         if (!(i >= t.ilo && i <= t.ihi && j >= t.jlo && j <= t.jhi)) { amp = 0.0; snr = 0.0; }
+        sc_window_masks(t, g, i, j, amp, snr);
         const size_t oo = tsel ? (size_t)ci : (size_t)ci * n_templ + it;
         amp_out[oo] = amp;
         snr_out[oo] = snr;
@@ -190,25 +199,46 @@ k_score_f64(const double* __restrict__ pa, const double* __restrict__ pb, const 
 }
 
 // What the float64 scorers read, rebuilt at every call: the templates' float64 windows (offsets from the host's copy of the
-// last search's descriptors, one kernel for all templates) and the three stencil planes of the block in float64.
-int score_prepare_f64(sc_ctx* ctx, int n_templ, const unsigned long long** woff_out, const double** wbuf_out, const double** planes_out) {
-    std::vector<unsigned long long> off((size_t)n_templ + 1, 0ull);
+// last search's descriptors, one kernel for all templates - built-in kinds evaluated, host-uploaded windows copied from their
+// slots), the orientations' curvature mix and the three stencil planes of the block in float64.
+// score_w: offsets (n + 1 words) | window sources (n pointers) | mix (3 n doubles) | windows
+int score_prepare_f64(sc_ctx* ctx, int n_templ, const unsigned long long** woff_out, const double** wbuf_out, const double** planes_out,
+                      const double** mix_out) {
+    const size_t n = (size_t)n_templ;
+    if (ctx->h_wslot.size() != n || ctx->h_mix.size() != 3 * n)
+        return sc_fail(ctx, SC_ERR_INVALID, "float64 scorer: no descriptors of the last search");
+    const size_t hbytes = 8 * (n + 1) + 8 * n + 24 * n;
+    std::vector<unsigned long long> head(hbytes / 8, 0ull);
+    unsigned long long* off = head.data();
+    const double** src = (const double**)(off + n + 1);
+    memcpy(off + 2 * n + 1, ctx->h_mix.data(), 24 * n);
     int maxbox = 1;
     for (int k = 0; k < n_templ; ++k) {
         const int box = ctx->h_templ[k].wh * ctx->h_templ[k].ww;
         off[k + 1] = off[k] + (unsigned long long)box;
         maxbox = std::max(maxbox, box);
+        src[k] = nullptr;
+        if (ctx->h_templ[k].kind == SC_KIND_WINDOW) {
+            // the slot must still hold the window the search matched (sc_clear_windows in between drops it)
+            const int ws = ctx->h_wslot[k];
+            if (ws < 0 || ws >= (int)ctx->windows.size() || !ctx->windows[ws].w64 ||
+                ctx->windows[ws].h != ctx->h_templ[k].wh || ctx->windows[ws].wd != ctx->h_templ[k].ww)
+                return sc_fail(ctx, SC_ERR_INVALID, "float64 scorer: template %d: its window slot %d no longer holds its window", k, ws);
+            src[k] = ctx->windows[ws].w64;
+        }
     }
-    const size_t obytes = sizeof(unsigned long long) * ((size_t)n_templ + 1);
+    const size_t obytes = (hbytes + 63) & ~(size_t)63;
     int rc = sc_ensure(ctx, ctx->score_w, obytes + sizeof(double) * (size_t)off[n_templ] + 64);
     if (rc) return rc;
     unsigned long long* woff = (unsigned long long*)ctx->score_w.p;
-    double* wbuf = (double*)((char*)ctx->score_w.p + ((obytes + 63) & ~(size_t)63));
-    SC_HIP(ctx, hipMemcpyAsync(woff, off.data(), obytes, hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));                       // (`off` is a local)
+    const double* const* wsrc = (const double* const*)(woff + n + 1);
+    const double* mix = (const double*)(woff + 2 * n + 1);
+    double* wbuf = (double*)((char*)ctx->score_w.p + obytes);
+    SC_HIP(ctx, hipMemcpyAsync(woff, head.data(), hbytes, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));                       // (`head` is a local)
     hipLaunchKernelGGL(k_window_f64, dim3((maxbox + 255) / 256, n_templ), dim3(256), 0, ctx->stream,
                        (const TemplDev*)ctx->templ.p, ctx->g, (const double*)ctx->xaxis.p, (const double*)ctx->yaxis.p,
-                       (const unsigned long long*)woff, wbuf);
+                       (const unsigned long long*)woff, wsrc, wbuf);
     SC_HIP(ctx, hipGetLastError());
     const size_t nc = (size_t)ctx->g.ly * ctx->g.lx;
     if ((rc = sc_ensure(ctx, ctx->score_abc, 3 * nc * sizeof(double)))) return rc;
@@ -219,18 +249,19 @@ int score_prepare_f64(sc_ctx* ctx, int n_templ, const unsigned long long** woff_
     *woff_out = woff;
     *wbuf_out = wbuf;
     *planes_out = pa;
+    *mix_out = mix;
     return SC_OK;
 }
 
 int launch_score_f64(sc_ctx* ctx, const int* cells_dev, const int* tsel_dev, int m, int n_templ, double* amp_dev, double* snr_dev) {
     const unsigned long long* woff = nullptr;
-    const double *wbuf = nullptr, *pa = nullptr;
-    int rc = score_prepare_f64(ctx, n_templ, &woff, &wbuf, &pa);
+    const double *wbuf = nullptr, *pa = nullptr, *mix = nullptr;
+    int rc = score_prepare_f64(ctx, n_templ, &woff, &wbuf, &pa, &mix);
     if (rc) return rc;
     const size_t nc = (size_t)ctx->g.ly * ctx->g.lx;
     hipLaunchKernelGGL(k_score_f64, dim3(m, tsel_dev ? 1 : n_templ), dim3(256), 0, ctx->stream, pa, pa + nc, pa + 2 * nc, ctx->g,
                        (const TemplDev*)ctx->templ.p, n_templ, (const double*)ctx->sums.p, (const double*)ctx->xaxis.p,
-                       (const double*)ctx->yaxis.p, woff, wbuf, cells_dev, tsel_dev, amp_dev, snr_dev);
+                       (const double*)ctx->yaxis.p, woff, wbuf, mix, cells_dev, tsel_dev, amp_dev, snr_dev);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
 }

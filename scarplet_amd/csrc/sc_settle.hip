@@ -24,14 +24,20 @@
 //   k_st_spans                                  the windows' row runs (their supports are a seventh of their boxes)
 //   k_st_score                                  one wave per pair; repeats of a template in a list and lists of one
 //                                               template are not scored
-//   k_st_resolve                                per slot the largest float64 SNR, ties to the earlier template
+//   k_st_resolve                                per slot the largest float64 SNR, ties to the earlier template; the audit:
+//                                               the largest relative float32 error of a scored holder's SNR (stats[6])
+//
+// Host-uploaded windows (SC_KIND_WINDOW, generic plugins) take the same steps: score_prepare_f64 copies their slots' float64
+// blocks into the window table, their curvature is mixed with the search orientation's (cc, sc2, ss) and their per-cell masks
+// are applied (core.py:369-375).
 #include "sc_internal.h"
 #include <algorithm>
 
 namespace {
 
 constexpr int ST_CH = 4096;                    // cells / counts per workgroup of the scans: 256 threads x 16
-constexpr unsigned ST_STATS = 8;               // 64-bit counters: 0 flagged cells, 1 pairs listed, 2 pairs scored, 3 cells scored, 4 changed
+constexpr unsigned ST_STATS = 8;               // 64-bit counters: 0 flagged cells, 1 pairs listed, 2 pairs scored, 3 cells scored, 4 changed,
+                                               // 6 the audit (largest float32 error of a holder, units of 1e-9), 7 taps
 
 __device__ __forceinline__ unsigned wave_incl_scan(unsigned v) {
 #pragma unroll
@@ -294,8 +300,8 @@ k_st_score(const double* __restrict__ pa, const double* __restrict__ pb, const d
            const unsigned long long* __restrict__ woff, const double* __restrict__ wbuf,
            const unsigned* __restrict__ soff, const int2* __restrict__ spans, const int* __restrict__ maxlen,
            const unsigned* __restrict__ off, const int32_t* __restrict__ pair_t, const uint32_t* __restrict__ pair_slot,
-           const uint32_t* __restrict__ cell_of, IdMap map, unsigned n_pairs, double* __restrict__ amp_out,
-           double* __restrict__ snr_out) {
+           const uint32_t* __restrict__ cell_of, IdMap map, unsigned n_pairs, const double* __restrict__ mix,
+           double* __restrict__ amp_out, double* __restrict__ snr_out) {
     // workgroups are dealt round-robin to the eight XCDs (each with an L2 of its own): XCD x takes the x-th EIGHTH of the pair
     // list in order, so that the waves that share an L2 work on neighbouring cells
     const unsigned nb8 = (gridDim.x + 7) / 8;
@@ -326,9 +332,11 @@ k_st_score(const double* __restrict__ pa, const double* __restrict__ pb, const d
     const uint32_t cell = cell_of[slot];
     const int i = g.cy0 + (int)(cell / (uint32_t)cw), j = g.cx0 + (int)(cell % (uint32_t)cw);     // global cell
     const TemplDev t = templ[it];
-    // the orientation's curvature mix, dem.py:103-104 (cos_a / sin_a of the descriptor are those of alpha = -orientation)
-    const double ca = t.cos_a, sa = -t.sin_a;
-    const double k_cc = __dmul_rn(ca, ca), k_ss = __dmul_rn(sa, sa);
+    // the orientation's curvature mix, dem.py:103-104 (cos_a / sin_a of the descriptor are those of alpha = -orientation;
+    // a host-uploaded window's are its plugin's: the side table's mix)
+    double ca = t.cos_a, sa = -t.sin_a;
+    double k_cc = __dmul_rn(ca, ca), k_ss = __dmul_rn(sa, sa);
+    if (t.kind == SC_KIND_WINDOW) sc_window_mix(mix, it, ca, sa, k_cc, k_ss);
     const double* __restrict__ wt = wbuf + woff[it];
     double xc = 0.0, t3 = 0.0;
     // The runs of the window's rows (k_st_spans).  L = the template's longest run rounded up to a power of two lanes per
@@ -463,6 +471,7 @@ k_st_score(const double* __restrict__ pa, const double* __restrict__ pb, const d
             if ((t.flags & SC_FLAG_ERR_XR_LE0) ? (xr <= 0.0) : (xr >= 0.0)) snr = 0.0;
         }
         if (!(i >= t.ilo && i <= t.ihi && j >= t.jlo && j <= t.jhi)) { amp = 0.0; snr = 0.0; }
+        sc_window_masks(t, g, i, j, amp, snr);
         if (!(snr >= 0.0)) snr = 0.0;                                      // (a NaN never wins a cell here)
         amp_out[pos] = amp;
         snr_out[pos] = snr;
@@ -473,6 +482,9 @@ k_st_score(const double* __restrict__ pa, const double* __restrict__ pb, const d
 // what the device's own fold keeps).  The winner goes into the record (id; amp and snr rounded to float32) and into the
 // patch (float64).  A class is scored once per cell, the record's holder standing for its own: an unchanged cell keeps
 // its id and gets the float64 values of that very template.
+// The audit: where the holder (entry 0) was scored, |snr32 - snr64| / snr64 of its float32 record against its float64 score,
+// before the record is overwritten - the largest over the slots, rounded UP to units of 1e-9 (at most 1e18), into stats[6].
+// A maximum: the same bits every run.
 __global__ void __launch_bounds__(256)
 k_st_resolve(unsigned n_slots, const unsigned* __restrict__ off, const int32_t* __restrict__ pair_t,
              const double* __restrict__ pair_amp, const double* __restrict__ pair_snr, const uint32_t* __restrict__ cell_of,
@@ -482,8 +494,15 @@ k_st_resolve(unsigned n_slots, const unsigned* __restrict__ off, const int32_t* 
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
     unsigned scored = 0, changed = 0;
     unsigned long long taps = 0;                   // (what the scores cost: the taps they weighed)
+    unsigned long long audit = 0;
     if (s < n_slots) {
         const unsigned lo = off[s], hi = off[s + 1];
+        const double h64 = pair_snr[lo];
+        if (h64 > 0.0) {
+            const double h32 = (double)best_snr[cell_of[s]];
+            const double e = fabs(h32 - h64) / h64;
+            if (e == e) audit = (unsigned long long)ceil(fmin(e, 1e9) * 1e9);
+        }
         double bs = -1.0, ba = 0.0;
         int bt = -1;
         for (unsigned k = lo; k < hi; ++k) {
@@ -513,7 +532,10 @@ k_st_resolve(unsigned n_slots, const unsigned* __restrict__ off, const int32_t* 
         changed += __shfl_down(changed, sft, 64);
         c1 += __shfl_down(c1, sft, 64);
         taps += __shfl_down(taps, sft, 64);
+        const unsigned long long a = __shfl_down(audit, sft, 64);
+        audit = a > audit ? a : audit;
     }
+    if ((threadIdx.x & 63) == 0 && audit) atomicMax(stats + 6, audit);
     if ((threadIdx.x & 63) == 0 && scored) {
         atomicAdd(stats + 2, (unsigned long long)scored);
         atomicAdd(stats + 3, (unsigned long long)c1);
@@ -575,8 +597,6 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
     const int n = ctx->last_batch;
     if (n <= 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_settle_exact: no search has run in this context");
     if (n_twin > n / 2) return sc_fail(ctx, SC_ERR_INVALID, "sc_settle_exact: %d end twins of %d templates", n_twin, n);
-    if (ctx->templ_windows)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_settle_exact: built-in templates only (a plugin's window is float32 on the device)");
     ctx->patch_n = 0;
     if (!ctx->near.p || !ctx->near_ev.p) return SC_OK;                    // no search has run with the option on: nothing flagged
     SC_HIP(ctx, hipSetDevice(ctx->device));
@@ -697,8 +717,8 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
     SC_HIP(ctx, hipGetLastError());
     // ---- float64 scores ------------------------------------------------------------------------------------------
     const unsigned long long* woff = nullptr;
-    const double *wbuf = nullptr, *pa = nullptr;
-    if ((rc = score_prepare_f64(ctx, n, &woff, &wbuf, &pa))) return rc;
+    const double *wbuf = nullptr, *pa = nullptr, *mix = nullptr;
+    if ((rc = score_prepare_f64(ctx, n, &woff, &wbuf, &pa, &mix))) return rc;
     const size_t npl = (size_t)g.ly * g.lx;
     hipLaunchKernelGGL(k_st_sums, dim3(n), dim3(256), 0, ctx->stream, (const TemplDev*)ctx->templ.p, woff, wbuf, sums64);
     if ((rc = sc_ensure(ctx, ctx->st_spans, sizeof(int2) * (size_t)h_soff[n] + 64))) return rc;
@@ -710,14 +730,15 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
                        pa + 2 * npl, g, (const TemplDev*)ctx->templ.p, (const double*)sums64, (const double*)ctx->xaxis.p,      \
                        (const double*)ctx->yaxis.p, woff, wbuf, (const unsigned*)soff, (const int2*)ctx->st_spans.p,            \
                        (const int*)maxlen, (const unsigned*)off, (const int32_t*)pair_t,                                        \
-                       (const uint32_t*)pair_slot, (const uint32_t*)cell_of, map, (unsigned)np, pair_amp, pair_snr)
+                       (const uint32_t*)pair_slot, (const uint32_t*)cell_of, map, (unsigned)np, mix, pair_amp, pair_snr)
     // a wave per pair fills the chip from a few thousand pairs on; shorter lists of WIDE windows spread every pair over 4 or
     // 16 waves (taps of the widest window from its descriptor: the rotated rectangle 2c x 2d cut to its box - a Scarp of a
     // few hundred taps settles faster on the one wave: C1 0.20 against 0.23 ms)
     double taps_max = 0.0;
     for (int k = 0; k < n; ++k) {
         const TemplDev& tk = ctx->h_templ[k];
-        taps_max = std::max(taps_max, std::min((double)tk.wh * tk.ww, 4.0 * tk.c * tk.d / fabs(ctx->dx * ctx->dy)));
+        const double taps = tk.kind == SC_KIND_WINDOW ? tk.p0 : 4.0 * tk.c * tk.d / fabs(ctx->dx * ctx->dy);   // (p0: count(W != 0))
+        taps_max = std::max(taps_max, std::min((double)tk.wh * tk.ww, taps));
     }
     const bool wide = taps_max >= 8192.0 && ctx->variant != 20;
     if (wide && np < 4096) ST_SCORE(16, np, 1024);
@@ -734,6 +755,7 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
     stats_out[2] = (long long)h[2];
     stats_out[3] = (long long)h[3];
     stats_out[4] = (long long)h[4];
+    stats_out[6] = (long long)h[6];
     stats_out[7] = (long long)h[7];
     ctx->patch_n = ns;
     ctx->async_in_flight = false;
@@ -876,6 +898,11 @@ extern "C" int sc_settle_pairs(sc_ctx* ctx, const sc_template* t, int n, const u
     const bool from_device = pairs == nullptr && n_pairs > 0;             // what sc_exchange_candidates left on the device
     if (from_device && n_pairs != ctx->xch_n)
         return sc_fail(ctx, SC_ERR_INVALID, "sc_settle_pairs: %lld pairs without a host list, %lld exchanged", n_pairs, ctx->xch_n);
+    // another rank's window slots do not exist in this context: the float64 windows of a plugin's templates are not all here
+    for (int k = 0; k < n; ++k)
+        if (t[k].kind == SC_KIND_WINDOW)
+            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_settle_pairs: template %d has a host-uploaded window (generic plugin); the "
+                           "orientation-sharded settle takes the built-in template classes only", k);
     SC_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = sc_load_templates(ctx, t, n))) return rc;                    // the WHOLE search's descriptors: the scorer's table

@@ -353,7 +353,10 @@ class DistMatcher(object):
         """This rank's part of the tiled search.  ``exact`` (default: on for the built-in template classes, as in
         ``scarplet_amd.match``): the near-ties of the rank's own block are settled in float64 on its device before the
         gather (sc_settle_exact: the halo covers the templates' reach and the curvature stencil) - the record that
-        travels carries the float64 argmax, its amplitude and SNR rounded to float32."""
+        travels carries the float64 argmax, its amplitude and SNR rounded to float32.  ``exact=True`` settles plugins
+        whose windows the host uploads as well (every rank uploads its own windows and settles its own block; the near-tie
+        flags need the real-space path for templates with per-cell masks - method="direct"); exact_stats["max_f32_err"]
+        is the settle's audit.  Untested on more than one rank for plugins."""
         params = np.atleast_1d(np.asarray(params, dtype=float))
         angles = np.atleast_1d(np.asarray(angles, dtype=float))
         arr, bbox, max_area = self.m.describe(Template, scale, params, angles, **kwargs)
