@@ -102,7 +102,7 @@ typedef struct sc_plan {
 /* ---- lifetime ---------------------------------------------------------- */
 int  sc_abi_version(void);
 /* Which sources this binary was compiled from: the first 16 hex digits of the SHA-256 over the
- * library's sources (the five .hip files of csrc, sc_internal.h, this header) in the Makefile's order, worked out
+ * library's sources (the six .hip files of csrc, sc_internal.h, this header) in the Makefile's order, worked out
  * at build time - `make -C scarplet_amd/csrc print-build-id` prints the same string for the tree
  * at hand.  bench.py prints it in every line and __graft_entry__.build() compares the two: a
  * stale prebuilt binary is visible instead of silently benchmarked. */
@@ -312,6 +312,23 @@ int sc_curvature(sc_ctx* ctx, double cc, double sc2, double ss, float* out);
 int sc_curvature_f64(sc_ctx* ctx, double cos2, double sin_a, double cos_a, double sin2,
                      double* out);
 
+/* The moments behind CalculationMixin._estimate_curvature_noiselevel (dem.py:152-179), float64.  With A, B, C the
+ * three stencil planes of the grid (d2z_dx2, d2z_dxdy, d2z_dy2, as sc_curvature_f64 forms them) and
+ * H_P = P - G * P, G the separable filter whose 2 radius + 1 correlation weights the caller passes
+ * (gaussian_filter's, mode 'reflect': half-sample symmetric, period 2 n, so any radius holds on any grid):
+ *   out[0..9]    n, mean[3], C[6] of (H_A, H_B, H_C) over all cells; C = sum of centred products, upper
+ *                triangle, row-major (AA, AB, AC, BB, BC, CC);
+ *   out[10..19]  the same over the cells farther than radius (Chebyshev distance) from every cell nan_mask
+ *                flags (ny x nx bytes, nonzero = NaN in the caller's grid) - the cells the reference's first
+ *                orientation keeps; with nan_mask NULL a copy of out[0..9].
+ * Works on the whole grid sc_set_dem set: a context holding a block of it (tile sharding) gets
+ * SC_ERR_INVALID, and so does radius < 0; radius > SC_NOISE_MAX_RADIUS gets SC_ERR_UNSUPPORTED.  The grid
+ * must be finite (the caller zero-fills NaN cells, as dem.py:84-86 does).  Deterministic: the same bits on
+ * every run.  Timed as one bracket, SC_K_NOISE. */
+#define SC_NOISE_MAX_RADIUS 1048576
+int sc_curvature_noise(sc_ctx* ctx, const double* weights, int radius, const uint8_t* nan_mask,
+                       double* out);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -439,7 +456,8 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_INV_COLS    5
 #define SC_K_INV_ROWS    6
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
-#define SC_K_COUNT       8
+#define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
+#define SC_K_COUNT       9
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);
 int sc_profile_get(sc_ctx* ctx, int kernel, long long* launches,

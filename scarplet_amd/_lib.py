@@ -23,8 +23,9 @@ COMM_ID_BYTES = 128
 KIND_WINDOW = 2             # SC_KIND_WINDOW: a template whose window the host uploaded (sc_upload_window)
 
 K_NAMES = ("k_curv", "k_windows", "k_direct", "k_fwd_rows", "k_fwd_cols",
-           "k_inv_cols", "k_inv_rows", "k_settle")
-K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE = range(8)
+           "k_inv_cols", "k_inv_rows", "k_settle", "k_noise")
+K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE, K_NOISE = range(9)
+NOISE_MAX_RADIUS = 1048576  # SC_NOISE_MAX_RADIUS: the largest filter radius sc_curvature_noise takes
 
 XFER_RECV, XFER_SEND, XFER_LOCAL = 0, 1, 2
 
@@ -103,6 +104,7 @@ SIGNATURES = {
                                  C.POINTER(C.c_longlong)]),
     "sc_curvature": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _fp]),
     "sc_curvature_f64": (C.c_int, [_P] + [C.c_double] * 4 + [_dp]),
+    "sc_curvature_noise": (C.c_int, [_P, _dp, C.c_int, _bp, _dp]),
     "sc_get_near_ties": (C.c_int, [_P, _bp]),
     "sc_score_cells_f64": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_int, _dp, _dp]),
     "sc_get_near_events": (C.c_int, [_P, _up, C.c_longlong, C.POINTER(C.c_longlong)]),
@@ -296,6 +298,21 @@ class Context(object):
         self._check(self.lib.sc_curvature_f64(self._h, float(np.cos(alpha) ** 2), float(np.sin(alpha)),
                                               float(np.cos(alpha)), float(np.sin(alpha) ** 2),
                                               _as(out, _dp)), "sc_curvature_f64")
+        return out
+
+    def curvature_noise(self, weights, nan_mask=None):
+        """sc_curvature_noise: (n, mean[3], C[6]) of the high-passed stencil planes over all cells, then over
+        the cells farther than the filter radius from every cell ``nan_mask`` flags (20 float64)."""
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        assert w.ndim == 1 and w.size % 2 == 1
+        m = None
+        if nan_mask is not None:
+            m = np.ascontiguousarray(nan_mask, dtype=np.uint8)
+            assert m.shape == self.shape
+        out = np.empty(20, dtype=np.float64)
+        self._check(self.lib.sc_curvature_noise(self._h, _as(w, _dp), w.size // 2,
+                                                None if m is None else _as(m, _bp), _as(out, _dp)),
+                    "sc_curvature_noise")
         return out
 
     # -- generic plugin windows --------------------------------------------

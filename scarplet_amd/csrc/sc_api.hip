@@ -1162,7 +1162,7 @@ extern "C" int sc_profile_get(sc_ctx* ctx, int kernel, long long* launches, doub
 
 extern "C" const char* sc_kernel_name(int kernel) {
     static const char* names[SC_K_COUNT] = {"k_curv", "k_windows", "k_direct", "k_fwd_rows",
-                                            "k_fwd_cols", "k_inv_cols", "k_inv_rows", "k_settle"};
+                                            "k_fwd_cols", "k_inv_cols", "k_inv_rows", "k_settle", "k_noise"};
     return (kernel >= 0 && kernel < SC_K_COUNT) ? names[kernel] : "?";
 }
 

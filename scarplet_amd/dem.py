@@ -151,6 +151,15 @@ class DEMGrid(object):
 
     _calculate_directional_laplacian_numexpr = _calculate_directional_laplacian   # dem.py:109-150
 
+    def _estimate_curvature_noiselevel(self, sigma=100., angles=None, device=0):
+        """Noise level of the curvature as a function of direction (dem.py:152-179): returns
+        ``(angles, mean, sd)`` - 180 orientations over [0, pi] by default, the mean and standard
+        deviation of the curvature minus its Gaussian low-pass (``sigma`` cells) in each.
+        Computed on the GPU: ``scarplet_amd.noise.estimate_curvature_noiselevel``.  Like the
+        reference, the grid keeps zeros where it held NaNs afterwards."""
+        from scarplet_amd.noise import estimate_curvature_noiselevel
+        return estimate_curvature_noiselevel(self, sigma=sigma, angles=angles, device=device)
+
     def _fill_nodata(self, device=0, max_passes=64):
         """Fill nodata (NaN) cells by interpolation so that the matcher's NaN-free
         precondition holds (dem.py:388-414).  Like the reference: repeat
