@@ -431,6 +431,29 @@ def snr_stack(z, dx, dy, kind, scale, ages, angles, workers=1):
     return amp, snr
 
 
+def _snr_at_cells_chunk(job):
+    """A run of templates on the whole DEM (match_template), only the SNR at the probed cells kept (snr_at_cells)."""
+    (z, dx, dy, kind, scale, pairs, ii, jj) = job
+    out = np.empty((len(pairs), len(ii)))
+    for k, (age, ang) in enumerate(pairs):
+        out[k] = match_template(z, dx, dy, kind, scale, age, ang)[3][ii, jj]
+    return out
+
+
+def snr_at_cells(z, dx, dy, kind, scale, ages, angles, cells, pool=None):
+    """(n_ages * n_angles, n_cells): the float64 SNR of every template of the grid (age-major, as snr_stack's reshape) at
+    the given (i, j) cells - the whole-DEM match_template of each template, of which only those cells are kept.  For probes
+    on DEMs too small for snr_stack_windows_direct's crops (a template reaching across the whole DEM)."""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+    ii, jj = cells[:, 0], cells[:, 1]
+    pairs = [(float(age), float(ang)) for age in ages for ang in angles]
+    nproc = (getattr(pool, "_processes", None) or 1) if pool is not None else 1
+    per = max(1, -(-len(pairs) // (4 * nproc)))
+    jobs = [(np.asarray(z, dtype=float), dx, dy, kind, scale, pairs[a:a + per], ii, jj) for a in range(0, len(pairs), per)]
+    res = pool.map(_snr_at_cells_chunk, jobs, chunksize=1) if pool is not None else [_snr_at_cells_chunk(j) for j in jobs]
+    return np.concatenate(res, axis=0)
+
+
 def window_limit_axes(nx, ny, de, alpha, c, d):
     """WindowedTemplate.py:66-84 again, as the two 1-D conditions the mask is
     made of: ``lim[i, j] = ymask[i] | xmask[j]`` (X and Y are meshgrids of the

@@ -190,6 +190,8 @@ class Context(object):
         self.dem_nan = 0           # NaN cells the device found in it
         self.dem_unchanged = False # the last set_dem handed over what the context already held
         self.spectra_mb = 0.0
+        self.variant = 0           # option "variant" as last set (0: none)
+        self.masked_slots = set()  # window slots whose templates carry per-cell masks (set_masks)
         # searches small enough for it keep their curvature spectra (sc_set_option "spectra_mb"): the
         # next search of the same DEM with the same tiles and orientations - the next scale of a
         # multi-scale job - starts from them
@@ -220,6 +222,8 @@ class Context(object):
                     "sc_set_option(%s)" % name)
         if name == "spectra_mb":
             self.spectra_mb = float(value)
+        elif name == "variant":
+            self.variant = int(value)   # (Matcher.can_flag_near_ties: variant 9 turns the fast row kernel off)
 
     def forget_spectra(self):
         """Drop the curvature spectra kept from earlier searches (option
@@ -334,9 +338,15 @@ class Context(object):
         ea, ep = conv(err)
         self._check(self.lib.sc_set_masks(self._h, slot, lp, ep),
                     "sc_set_masks")
+        # (the slots whose templates carry per-cell masks: Matcher.can_flag_near_ties)
+        if lp is not None or ep is not None:
+            self.masked_slots.add(int(slot))
+        else:
+            self.masked_slots.discard(int(slot))
 
     def clear_windows(self):
         self._check(self.lib.sc_clear_windows(self._h), "sc_clear_windows")
+        self.masked_slots.clear()
 
     # -- hot path -----------------------------------------------------------
     def reset_best(self):

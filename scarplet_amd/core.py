@@ -551,26 +551,18 @@ class Matcher(object):
         win_direct = self.EXACT_WINDOW_DIRECT if window is None else window
         try:
             if fft:
-                self.ctx.set_option("near_window", win_fft)
-                try:
+                route = self.exact_route(arr, sp, bbox, max_area, n_par)
+                if route == "float32":
+                    self.ctx.set_option("near_window", 0.0)
                     self.ctx.match(arr, sp, sync=True)
-                except _lib.ScarpletHipError as e:
-                    # per-cell masks (generic plugins, UpperBreak error masks) or a tile size the flagging row kernel is
-                    # not built for: the whole search on the real-space path instead
-                    if "near-tie flags" not in str(e):
-                        raise
-                    fft = False
-                    if windows and not self._direct_affordable(bbox, max_area, n_par):
-                        # (a plugin's window on a grid where the real-space path would take beyond a hundred times the
-                        # FFT search: the float32 answer, said)
-                        self.ctx.set_option("near_window", 0.0)
-                        self.ctx.match(arr, sp, sync=True)
-                        self.method_used = "fft"
-                        warnings.warn("exact=True: this plugin's templates carry per-cell masks, which only the real-space "
-                                      "path flags, and a real-space search would take beyond a hundred times the FFT "
-                                      "search here - the float32 FFT result stands")
-                        self.exact_stats["skipped"] = True
-                        return False
+                    self.method_used = "fft"
+                    self._warn_exact_skipped()
+                    self.exact_stats["skipped"] = True
+                    return False
+                fft = route == "fft"
+                if fft:
+                    self.ctx.set_option("near_window", win_fft)
+                    self.ctx.match(arr, sp, sync=True)
                 if fft and method == "auto":
                     wins, near = self.ctx.resolution_stats()
                     self.unresolved_frac = near / wins if wins else 0.0
@@ -617,6 +609,38 @@ class Matcher(object):
             self.exact_stats["flagged_cells"] = len(last)
             self._score_float64([(i + self.core[0], j + self.core[2]) for i, j in last], arr, bbox)
         return False
+
+    def can_flag_near_ties(self, arr, sp):
+        """Whether an FFT search of the descriptors ``arr`` with the plan ``sp`` can flag its near-ties: only the fast row
+        kernel does (tiles 512, 1024 or 2048 wide, not turned off by option "variant" 9), and only for templates without
+        per-cell masks - no UpperBreak error masks (FLAG_ERR_XR_*), no plugin window with masks (sc_fft.hip's condition
+        for the near-tie flags; SC_ERR_UNSUPPORTED otherwise)."""
+        if sp.method != _plan.METHOD_FFT or sp.Tx not in (512, 1024, 2048) or not len(arr) or \
+                getattr(self.ctx, "variant", 0) == 9:
+            return False
+        T = _lib.sc_template
+        words = np.frombuffer(arr, dtype=np.int32).reshape(len(arr), _lib.C.sizeof(T) // 4)
+        if (words[:, T.flags.offset // 4] & (_WT.FLAG_ERR_XR_LE0 | _WT.FLAG_ERR_XR_GE0)).any():
+            return False
+        masked = getattr(self.ctx, "masked_slots", ())
+        return not (masked and np.isin(words[:, T.window.offset // 4], list(masked)).any())
+
+    def exact_route(self, arr, sp, bbox, max_area, n_par):
+        """Where an exact search of the planned FFT search ``sp`` runs: "fft" where the row kernel can flag its near-ties
+        (can_flag_near_ties), else "direct" - the real-space path, which flags every template, at any cost for the
+        built-in classes and where _direct_affordable for windows the host uploads - or "float32": the FFT search without
+        the settle (a plugin's masked windows on a grid where the real-space path would cost beyond a hundred times)."""
+        if self.can_flag_near_ties(arr, sp):
+            return "fft"
+        windows = int(arr[0].kind) == _WT.KIND_WINDOW
+        return "float32" if windows and not self._direct_affordable(bbox, max_area, n_par) else "direct"
+
+    @staticmethod
+    def _warn_exact_skipped():
+        import warnings
+        warnings.warn("exact=True: this plugin's templates carry per-cell masks, which only the real-space path flags, "
+                      "and a real-space search would take beyond a hundred times the FFT search here - the float32 FFT "
+                      "result stands")
 
     def _direct_affordable(self, bbox, max_area, n_par):
         """The guard of the real-space re-plans: the window fits the real-space kernel's slab and its search costs at

@@ -280,7 +280,7 @@ class DistMatcher(object):
     ``transport`` ('gloo' is accepted as an alias of 'host')."""
 
     def __init__(self, rank, nranks, shape, dx, dy, device=0, backend="rccl",
-                 broadcast_bytes=None, transport=None):
+                 broadcast_bytes=None, transport=None, matcher=None):
         from scarplet_amd.core import Matcher
         self.rank, self.nranks = rank, nranks
         self.ny, self.nx = shape
@@ -294,7 +294,9 @@ class DistMatcher(object):
             raise ValueError("the host backend needs a transport (scarplet_amd/dist.py docstring)")
         self.py, self.px = grid_dims(nranks, self.ny, self.nx)
         self.cores = None                     # None: the even py x px grid; else partition_for's
-        self.m = Matcher(device=device)
+        # (matcher=: a ready Matcher instead of one on the shared context of ``device`` - ranks as threads of one
+        #  process, each with a context of its own; the CPU tests hand in stubs)
+        self.m = matcher if matcher is not None else Matcher(device=device)
         # describe() only needs the grid geometry
         self.m.ny, self.m.nx, self.m.de = self.ny, self.nx, dx
         if backend == "rccl" and nranks > 1:
@@ -355,19 +357,43 @@ class DistMatcher(object):
         gather (sc_settle_exact: the halo covers the templates' reach and the curvature stencil) - the record that
         travels carries the float64 argmax, its amplitude and SNR rounded to float32.  ``exact=True`` settles plugins
         whose windows the host uploads as well (every rank uploads its own windows and settles its own block; the near-tie
-        flags need the real-space path for templates with per-cell masks - method="direct"); exact_stats["max_f32_err"]
-        is the settle's audit.  Untested on more than one rank for plugins."""
+        flags need the real-space path for templates with per-cell masks: Matcher.exact_route, as in Matcher.search);
+        exact_stats["max_f32_err"] is the settle's audit.  A settle this rank cannot finish (an overflowed event list, more
+        float64 work than EXACT_MAX_F64) leaves its float32 record, with a warning and exact_stats["skipped"] - the
+        other ranks are not kept waiting in the gather.  Untested on more than one rank for plugins."""
+        import warnings
         params = np.atleast_1d(np.asarray(params, dtype=float))
         angles = np.atleast_1d(np.asarray(angles, dtype=float))
-        arr, bbox, max_area = self.m.describe(Template, scale, params, angles, **kwargs)
+        m = self.m
+        arr, bbox, max_area = m.describe(Template, scale, params, angles, **kwargs)
         self.load(z_core, bbox)
-        self.m.plan, sp = self.m.plan_for(bbox, max_area, method, group,
-                                          n_params=len(params))
+        m.plan, sp = m.plan_for(bbox, max_area, method, group, n_params=len(params))
         if exact is None:
             exact = all(int(arr[k].kind) != 2 for k in (0, len(arr) - 1))         # (2: SC_KIND_WINDOW, a host-uploaded plugin)
-        self.exact_stats = self.m.run_described(arr, sp, self.m.exact_window_for(arr, sp) if exact else 0.0,
-                                                self.m.end_twins(arr, len(params), angles))
-        self.m.params, self.m.angles = params, angles
+        route = "fft" if sp.method == _plan.METHOD_FFT else "direct"
+        if exact and route == "fft":
+            # (per rank: the blocks - and their tile plans and real-space costs - may differ, and so may the routes; each
+            #  rank settles its own block, so a rank on the real-space path next to one on the FFT tiles is fine)
+            route = m.exact_route(arr, sp, bbox, max_area, len(params))
+            if route == "direct":
+                m.plan, sp = m.plan_for(bbox, max_area, "direct", group, n_params=len(params))
+        self.method_used = m.method_used = "direct" if route == "direct" else "fft"
+        m.params, m.angles = params, angles
+        if route == "float32":
+            m.run_described(arr, sp)
+            m._warn_exact_skipped()
+            self.exact_stats = {"skipped": True}
+            return self
+        try:
+            self.exact_stats = m.run_described(arr, sp, m.exact_window_for(arr, sp) if exact else 0.0,
+                                               m.end_twins(arr, len(params), angles))
+        except _lib.ScarpletHipError as e:
+            msg = str(e)
+            if "overflowed" not in msg and "too much float64 work" not in msg:
+                raise
+            # (the match ran, the settle did not touch the record: this rank's float32 answer stands)
+            warnings.warn("exact=True: rank %d did not settle the near-ties of its block (%s)" % (self.rank, msg))
+            self.exact_stats = {"skipped": True, "settle": msg}
         return self
 
     def result(self):
@@ -502,6 +528,7 @@ class OrientationMatcher(object):
         arr, bbox, area = m.describe(Template, scale, params, angles,
                                      id_of=lambda ia, ib: ib * n_par + ia, **kwargs)
         m.plan, sp = m.plan_for(bbox, area, method, group, n_params=n_par)
+        self._bbox, self._area, self._group = bbox, area, group
         b0, b1 = orientation_chunks(len(angles), self.nranks)[self.rank]
         n = (b1 - b0) * n_par
         mine = (_lib.sc_template * n).from_buffer(arr, b0 * n_par * _lib.C.sizeof(_lib.sc_template)) \
@@ -597,7 +624,10 @@ class OrientationMatcher(object):
 
     def search(self, Template, scale, params, angles, method="auto", group=None, exact=None, **kwargs):
         """``exact`` (default: on for the built-in template classes wherever the ranks can exchange their candidate
-        lists - one rank, RCCL, or a transport): the float64 argmax of the whole search, as ``scarplet_amd.match`` delivers."""
+        lists - one rank, RCCL, or a transport): the float64 argmax of the whole search, as ``scarplet_amd.match`` delivers.
+        Where the FFT row pass cannot flag the near-ties (UpperBreak's error masks, a plugin's masks, tiles 4096 wide) the
+        search runs on the real-space path instead, as in Matcher.search (Matcher.exact_route: every rank plans from the
+        whole grid, so every rank decides alike)."""
         if getattr(self.m, "nan_dem", False):      # the reference's all-NaN maps, on every rank
             self.m.search(Template, scale, params, angles, method=method, **kwargs)
             self._nan = True
@@ -605,11 +635,23 @@ class OrientationMatcher(object):
         self._nan = False
         mine, sp = self.describe(Template, scale, params, angles, method, group, **kwargs)
         arr = self._keep
+        m = self.m
         if exact is None:
             exact = all(int(arr[k].kind) != 2 for k in (0, len(arr) - 1)) and \
                 (self.nranks == 1 or self.backend == "rccl" or self.transport is not None)
-        self.run(mine, sp, self.m.exact_window_for(arr, sp) if exact else 0.0,
-                 self.m.end_twins(arr, len(self.m.params), self.m.angles))
+        route = "fft" if sp.method == _plan.METHOD_FFT else "direct"
+        if exact and route == "fft":
+            route = m.exact_route(arr, sp, self._bbox, self._area, len(m.params))
+            if route == "direct":
+                m.plan, sp = m.plan_for(self._bbox, self._area, "direct", self._group, n_params=len(m.params))
+        self.method_used = m.method_used = "direct" if route == "direct" else "fft"
+        if route == "float32":
+            self.run(mine, sp)
+            m._warn_exact_skipped()
+            self.exact_stats = {"skipped": True}
+            return self
+        self.run(mine, sp, m.exact_window_for(arr, sp) if exact else 0.0,
+                 m.end_twins(arr, len(m.params), m.angles))
         return self
 
     def result_array(self):

@@ -607,3 +607,92 @@ def test_gather_ships_the_record_over_gloo(world):
     for p in procs:
         p.join(timeout=60)
     assert sorted(res) == [(r, True) for r in range(world)], res
+
+
+# ---- the tile sharding's exact mode: a settle that fails on one rank -------------------------------------------------
+class _SettleContext(object):
+    """A rank's device in the tile sharding's exact mode: sc_match writes a float32 record naming template 1 in every cell,
+    sc_settle_exact turns it into template 0 - or fails as the device does when the float64 work exceeds the bound it is
+    handed, or with ``error`` (the message of any other failure)."""
+
+    def __init__(self, shape, error=None):
+        self.shape, self.error, self.opt = shape, error, {}
+
+    def set_option(self, key, value):
+        self.opt[key] = value
+
+    def reset_best(self):
+        self.rec = (np.zeros(self.shape, np.float32), np.zeros(self.shape, np.float32),
+                    np.full(self.shape, 0xFFFFFFFF, np.uint32))
+
+    def match(self, templates, plan, sync=True):
+        self.rec = (np.full(self.shape, 2.0, np.float32), np.full(self.shape, 1.5, np.float32),
+                    np.ones(self.shape, np.uint32))
+
+    def settle_exact(self, n_twin, max_work):
+        from scarplet_amd import _lib
+        if self.error:
+            raise _lib.ScarpletHipError(self.error)
+        if max_work < 100.0:
+            raise _lib.ScarpletHipError("sc_settle_exact: too much float64 work (up to 12 pairs on 6 cells, boxes of up to 9 cells)")
+        self.rec[2][:] = 0
+        return {"flagged_cells": int(np.prod(self.shape)), "changed_cells": int(np.prod(self.shape))}
+
+    def get_best(self):
+        return self.rec
+
+
+def _settle_ranks(world, failing, error=None):
+    """DistMatcher.search + gather on ``world`` thread ranks (host backend) whose devices are _SettleContext; rank
+    ``failing`` is handed a tiny EXACT_MAX_F64."""
+    import warnings
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from thread_transport import run_ranks
+    import scarplet_amd as sl
+    from scarplet_amd.core import Matcher
+    ny, nx = 40, 36
+    z = np.random.default_rng(5).standard_normal((ny, nx))
+
+    def body(rank, transport):
+        m = object.__new__(Matcher)                          # host side only: descriptors and plans need no device
+        m.ny, m.nx, m.de, m.whole = ny, nx, 1.0, False
+        dm = sd.DistMatcher(rank, world, (ny, nx), 1.0, 1.0, backend="host", transport=transport, matcher=m)
+        c = dm.core()
+        m.core = c
+        m.ctx = _SettleContext((c[1] - c[0], c[3] - c[2]), error if rank == failing else None)
+        m.set_block = lambda *a, **k: None
+        if rank == failing:
+            m.EXACT_MAX_F64 = 1.0
+        dm.search(sl.Scarp, 6, [1.0, 4.0], [-0.3, 0.3], z[c[0]:c[1], c[2]:c[3]], method="fft")
+        return dm.gather(0), dm.exact_stats, c
+
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        outs = run_ranks(world, body, timeout=60.0)
+    return outs, [str(w.message) for w in caught]
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_tile_sharding_keeps_going_when_one_rank_cannot_settle(world):
+    """DistMatcher.search in the exact mode (the default): a settle that fails on ONE rank - too much float64 work, an
+    overflowed event list - leaves that rank's float32 record, with a warning and exact_stats["skipped"], as
+    Matcher._exact_pass does for a block; the rank does not raise while the others wait in the gather.  Any other
+    failure of the settle still raises."""
+    failing = world - 1
+    outs, msgs = _settle_ranks(world, failing)
+    full = outs[0][0]
+    assert full is not None and all(o[0] is None for o in outs[1:])
+    for r, (_, st, c) in enumerate(outs):
+        age, ang = full[1][c[0]:c[1], c[2]:c[3]], full[2][c[0]:c[1], c[2]:c[3]]      # (ids: ia * 2 + ib)
+        if r == failing:
+            assert st.get("skipped") and "too much float64 work" in st["settle"], st
+            assert (ang == 0.3).all() and (age == 1.0).all()      # the float32 record: template 1 = (1.0, +0.3)
+        else:
+            assert not st.get("skipped") and st["changed_cells"] > 0, st
+            assert (ang == -0.3).all() and (age == 1.0).all()     # settled: template 0 = (1.0, -0.3)
+    assert any("rank %d did not settle" % failing in m_ for m_ in msgs), msgs
+    outs, _ = _settle_ranks(world, failing, error="sc_settle_exact: the event list overflowed (9 near-ties, room for 4)")
+    assert outs[failing][1].get("skipped") and "overflowed" in outs[failing][1]["settle"]
+    from scarplet_amd import _lib
+    with pytest.raises(_lib.ScarpletHipError, match="no DEM set"):
+        _settle_ranks(world, failing, error="no DEM set")

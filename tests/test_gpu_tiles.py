@@ -2,6 +2,7 @@
 searched on its own (non-periodic block, window limits in global coordinates)
 and the stitched tiles must reproduce the whole-DEM search.  Also runs the RCCL
 entry points with a single-rank communicator (periodic self-images only)."""
+import hashlib
 import os
 import sys
 
@@ -288,7 +289,7 @@ def test_exact_orientation_sharding_equals_the_single_context(nranks, method):
              (synthetic.synthetic_scarp(160, seed=2, sigma=0.0), sl.Scarp, orc.SCARP, 10, [1.0, 4.0, 4.05, 20.0], grid[::3]),
              (synthetic.synthetic_scarp(150, seed=6, ny=140), sl.Ricker, orc.RICKER, 8, [2.0, 4.0, 4.0003], paired)]
     teeth = 0
-    for (g, Template, kind, scale, params, angles) in cases:
+    for ic, (g, Template, kind, scale, params, angles) in enumerate(cases):
         single = sl.Matcher(g, ctx=_lib.Context(0))
         want = np.stack(single.search(Template, scale, params, angles, method=method, exact=True).result())
         want_rec = [a.copy() for a in single.ctx.get_best()]
@@ -323,6 +324,12 @@ def test_exact_orientation_sharding_equals_the_single_context(nranks, method):
         a_tol = P_AMP[0] * np.abs(want[0]) + P_AMP[1] * np.nanmax(np.abs(want[0]))
         assert (np.abs(arr0[0] - want[0])[same] <= a_tol[same]).all()
         assert (np.abs(np.abs(arr0[0]) - np.abs(want[0])) <= a_tol).all()
+        if ic == 1:
+            continue          # (sigma = 0: no noise floor - outside the regime the float32 error bound covers)
+        # ... and the ranks' record against the float64 oracle: the argmax in every cell (end twins as one maximum)
+        chk = _check_oracle(arr0, g, kind, scale, params, angles, method)
+        print("  vs oracle: n_inexact=%d n_bad=%d" % (chk["n_inexact"], chk["n_bad"]))
+        assert chk["n_inexact"] == 0 and chk["n_bad"] == 0, (chk["n_inexact"], chk["n_bad"])
     assert teeth >= 20, teeth
 
 
@@ -365,3 +372,173 @@ def test_exact_orientation_exchange_on_the_device(with_comm):
     assert np.array_equal(arr[1], want[1]) and np.array_equal(_fold_twin(arr[2]), _fold_twin(want[2]))
     if with_comm:
         ctx.comm_destroy()
+
+
+# ---- the drivers' exact mode against the float64 oracle ----------------------------------------
+_STACKS = {}
+
+
+def _oracle_stack(g, kind, scale, params, angles):
+    """orc.snr_stack of a case as (T, ny, nx) stacks with the (age, angle) of every template - once per session."""
+    z = np.asarray(g._griddata, dtype=float)
+    key = (z.shape, hashlib.sha256(z.tobytes()).hexdigest(), kind, scale, tuple(params), tuple(np.asarray(angles, float)))
+    if key not in _STACKS:
+        a_st, s_st = orc.snr_stack(z, float(g._georef_info.dx), float(g._georef_info.dy), kind, scale, params, angles)
+        T = len(params) * len(angles)
+        _STACKS[key] = (a_st.reshape((T,) + z.shape), s_st.reshape((T,) + z.shape),
+                        np.repeat(params, len(angles)), np.tile(angles, len(params)))
+    return _STACKS[key]
+
+
+def _check_oracle(res, g, kind, scale, params, angles, method="fft"):
+    """check_fold of a (4, ny, nx) result against the oracle: PARITY's value tolerances, the path's tie window."""
+    a_st, s_st, par, ang = _oracle_stack(g, kind, scale, params, angles)
+    rtol, afac = orc.snr_tolerance(kind)
+    return orc.check_fold(res, a_st, s_st, par, ang, tie_rtol=orc.tie_window(method, kind),
+                          amp_tol=(P_AMP[0], P_AMP[1] * np.max(np.abs(a_st))), snr_tol=(rtol, afac * np.max(s_st)))
+
+
+def _paired_angles():
+    """every 23rd orientation of the grid twice, 2e-5 rad apart (near-ties inside the float32 error), the grid's end
+    twins -pi/2 and +pi/2 first and last"""
+    grid = _plan.angle_grid(-np.pi / 2, np.pi / 2)
+    base = grid[:-1:23]
+    return np.concatenate([base, base[1:] + 2e-5, grid[-1:]])
+
+
+def _tile_ranks(nranks, g, Template, scale, params, angles, method="fft", setup=None, **kw):
+    """DistMatcher on ``nranks`` threads (host backend, a context each): [(gathered maps on rank 0 or None, exact_stats,
+    method_used, core)] in rank order.  ``setup(rank, dm)`` runs before the search."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from thread_transport import run_ranks
+    z = np.asarray(g._griddata, dtype=float)
+    dx, dy = float(g._georef_info.dx), float(g._georef_info.dy)
+
+    def rank_body(rank, transport):
+        m = sl.Matcher(ctx=_lib.Context(0))
+        dm = sd.DistMatcher(rank, nranks, z.shape, dx, dy, backend="host", transport=transport, matcher=m)
+        if setup is not None:
+            setup(rank, dm)
+        c = dm.core()
+        dm.search(Template, scale, params, angles, z[c[0]:c[1], c[2]:c[3]], method=method, **kw)
+        out = dm.gather(0)
+        return (None if out is None else np.stack(out)), dm.exact_stats, dm.method_used, c
+
+    return run_ranks(nranks, rank_body)
+
+
+@pytest.mark.parametrize("nranks", [2, 4])
+def test_exact_tile_sharding_against_the_oracle(nranks):
+    """The tile sharding's default search (DistMatcher.search: exact for the built-in classes) on 2 and 4 ranks as
+    threads: every rank settles the near-ties of its own block, the float32 records travel.  The gathered (age,
+    orientation) is the single context's exact=True answer in every cell, and the oracle's float64 argmax (check_fold's
+    n_inexact == 0; the grid's end twins are one maximum), amplitude and SNR within PARITY."""
+    cases = [(synthetic.synthetic_scarp(230, seed=4, ny=200), sl.Scarp, orc.SCARP, 14, [1.0, 4.0, 4.0004, 20.0, 100.0]),
+             (synthetic.synthetic_scarp(150, seed=6, ny=140), sl.Ricker, orc.RICKER, 8, [2.0, 4.0, 4.0003])]
+    angles = _paired_angles()
+    teeth = 0
+    for (g, Template, kind, scale, params) in cases:
+        single = sl.Matcher(g, ctx=_lib.Context(0))
+        want = np.stack(single.search(Template, scale, params, angles, method="fft", exact=True).result())
+        assert single.method_used == "fft" and single.exact_stats.get("route") == "device", single.exact_stats
+        f32 = np.stack(single.search(Template, scale, params, angles, method="fft", exact=False).result())
+        outs = _tile_ranks(nranks, g, Template, scale, params, angles)
+        got = outs[0][0]
+        assert all(o[0] is None for o in outs[1:])
+        for (_, st, used, c) in outs:
+            assert used == "fft" and st is not None and not st.get("skipped"), (used, st)
+        off = (got[1] != want[1]) | (_fold_twin(got[2]) != _fold_twin(want[2]))
+        chk = _check_oracle(got, g, kind, scale, params, angles)
+        chk32 = _check_oracle(f32, g, kind, scale, params, angles)
+        print("tile sharding, exact, %s %s on %d ranks: %d cells differ from one context's exact=True; vs oracle: "
+              "n_inexact=%d n_bad=%d (float32, one context: n_inexact=%d); flagged per rank %s"
+              % (Template.__name__, g._griddata.shape, nranks, int(off.sum()), chk["n_inexact"], chk["n_bad"],
+                 chk32["n_inexact"], [o[1]["flagged_cells"] for o in outs]))
+        assert not off.any(), int(off.sum())
+        assert chk["n_inexact"] == 0 and chk["n_bad"] == 0, (chk["n_inexact"], chk["n_bad"])
+        teeth += chk32["n_inexact"]
+    # (the float32 search of the same inputs is off the argmax somewhere: the count above can fail)
+    assert teeth >= 1, teeth
+
+
+def test_exact_drivers_take_the_real_space_path_for_masked_templates():
+    """UpperBreak carries per-cell error masks, which the FFT row pass cannot flag near-ties under
+    (Matcher.can_flag_near_ties).  method="fft" with the default exact mode through DistMatcher and OrientationMatcher, on
+    1 and 2 ranks: no SC_ERR_UNSUPPORTED - the drivers re-plan on the real-space path, as Matcher.search does - and the
+    result is the oracle's float64 argmax in every cell.  Every orientation but the ends has a twin 2e-6 rad away: SNRs
+    about 1e-6 apart in float64, which the float32 real-space search does not resolve (it is off the argmax in some
+    cells; the settle must not be)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from thread_transport import run_ranks
+    from scarplet_amd import WindowedTemplate as WT
+    g = synthetic.synthetic_scarp(150, seed=7, ny=160)
+    z = np.asarray(g._griddata, dtype=float)
+    Template, kind, scale, params = WT.LeftFacingUpperBreakScarp, orc.LEFT_UPPER, 12, [2.0, 30.0]
+    base = _plan.angle_grid(-np.pi / 2, np.pi / 2)[::17]
+    angles = np.concatenate([base, base[1:-1] + 2e-6])
+    # one rank, the shared context, as a user constructs them
+    dm = sd.DistMatcher(0, 1, z.shape, 1.0, 1.0, backend="host")
+    dm.search(Template, scale, params, angles, z, method="fft")
+    res = {"tiles, 1 rank": (np.stack(dm.gather(0)), dm.exact_stats, dm.method_used)}
+    om = sd.OrientationMatcher(0, 1, g, backend="host")
+    om.search(Template, scale, params, angles, method="fft")
+    res["orientations, 1 rank"] = (np.array(om.result_array()), om.exact_stats, om.method_used)
+    out = _tile_ranks(2, g, Template, scale, params, angles)
+    res["tiles, 2 ranks"] = (out[0][0], out[0][1], out[0][2])
+    assert all(o[2] == "direct" and o[1] is not None and not o[1].get("skipped") for o in out), [o[1:3] for o in out]
+
+    def orient_body(rank, transport):
+        om = sd.OrientationMatcher(rank, 2, None, backend="host", transport=transport,
+                                   matcher=sl.Matcher(g, ctx=_lib.Context(0)))
+        om.search(Template, scale, params, angles, method="fft")
+        return np.array(om.result_array()), om.exact_stats, om.method_used
+
+    res["orientations, 2 ranks"] = run_ranks(2, orient_body)[0]
+    f32 = np.stack(sl.Matcher(g).search(Template, scale, params, angles, method="direct", exact=False).result())
+    n32 = _check_oracle(f32, g, kind, scale, params, angles, "direct")["n_inexact"]
+    for name, (got, st, used) in res.items():
+        chk = _check_oracle(got, g, kind, scale, params, angles, "direct")
+        print("UpperBreak, method='fft', default exact mode, %s: route %s, %s; vs oracle n_inexact=%d n_bad=%d "
+              "(float32 real-space search: n_inexact=%d)" % (name, used, st, chk["n_inexact"], chk["n_bad"], n32))
+        assert used == "direct" and st is not None and not st.get("skipped"), (name, used, st)
+        assert chk["n_inexact"] == 0 and chk["n_bad"] == 0, (name, chk["n_inexact"], chk["n_bad"])
+    assert n32 >= 1, n32                       # (the float32 search of the same inputs: the count above can fail)
+    # the predicate the drivers decide by: no near-tie flags on this FFT plan, on a plain Scarp's
+    m = sl.Matcher(g)
+    for T_, can in ((Template, False), (sl.Scarp, True)):
+        arr, bbox, area = m.describe(T_, scale, np.asarray(params), angles)
+        _, sp = m.plan_for(bbox, area, "fft", n_params=len(params))
+        assert m.can_flag_near_ties(arr, sp) == can, T_
+
+
+def test_exact_tile_sharding_survives_a_settle_that_fails_on_one_rank():
+    """A settle one rank cannot finish (here: more float64 work than its EXACT_MAX_F64, set tiny on rank 1 alone) must not
+    strand the other ranks in the gather: that rank keeps its float32 record and says so (exact_stats["skipped"]), the
+    gather completes, and rank 0's cells carry the float64 argmax."""
+    g = synthetic.synthetic_scarp(230, seed=4, ny=200)
+    params, angles = [1.0, 4.0, 4.0004, 20.0, 100.0], _paired_angles()
+    want = np.stack(sl.Matcher(g, ctx=_lib.Context(0)).search(sl.Scarp, 14, params, angles, method="fft", exact=True).result())
+
+    def setup(rank, dm):
+        if rank == 1:
+            dm.m.EXACT_MAX_F64 = 1.0
+
+    outs = _tile_ranks(2, g, sl.Scarp, 14, params, angles, setup=setup)
+    got = outs[0][0]
+    (_, st0, _, c0), (_, st1, _, c1) = outs
+    print("settle failing on rank 1 of 2: rank 0 %s; rank 1 %s" % (st0, st1))
+    assert got is not None and outs[1][0] is None
+    assert not st0.get("skipped") and st0["flagged_cells"] > 0, st0
+    assert st1.get("skipped") and "too much float64 work" in st1.get("settle", ""), st1
+    sub = (slice(c0[0], c0[1]), slice(c0[2], c0[3]))
+    off = (got[1][sub] != want[1][sub]) | (_fold_twin(got[2][sub]) != _fold_twin(want[2][sub]))
+    assert not off.any(), int(off.sum())
+    a_st, s_st, par, ang = _oracle_stack(g, orc.SCARP, 14, params, angles)
+    rtol, afac = orc.snr_tolerance(orc.SCARP)
+    chk = orc.check_fold(got[(slice(None),) + sub], a_st[(slice(None),) + sub], s_st[(slice(None),) + sub], par, ang,
+                         tie_rtol=orc.tie_window("fft", orc.SCARP), amp_tol=(P_AMP[0], P_AMP[1] * np.max(np.abs(a_st))),
+                         snr_tol=(rtol, afac * np.max(s_st)))
+    print("  rank 0's cells vs oracle: n_inexact=%d n_bad=%d" % (chk["n_inexact"], chk["n_bad"]))
+    assert chk["n_inexact"] == 0 and chk["n_bad"] == 0, (chk["n_inexact"], chk["n_bad"])
+    # rank 1's block holds its own float32 record, placed by the gather
+    assert (got[3][c1[0]:c1[1], c1[2]:c1[3]] > 0).any()

@@ -159,3 +159,35 @@ def test_cross_lane_exchange_feeds_stage_3_what_the_lds_path_reads():
         fed, want = _xlane_model(T)
         assert np.array_equal(fed, want), T
         assert len(np.unique(fed)) == fed.size == T          # every element of the line exactly once
+
+
+def test_can_flag_near_ties_mirrors_the_row_kernel():
+    """Matcher.can_flag_near_ties - how Matcher and the dist drivers choose the exact mode's path before matching - states
+    sc_fft.hip's condition for the near-tie flags: an FFT plan with tiles 512, 1024 or 2048 wide, option "variant" not 9,
+    no template with UpperBreak error masks, no host-uploaded window with masks."""
+    import types
+    from scarplet_amd import _lib
+    from scarplet_amd.core import Matcher
+    m = object.__new__(Matcher)                          # host side only: descriptors and plans need no device
+    m.ny, m.nx, m.de, m.core, m.whole = 160, 150, 1.0, (0, 160, 0, 150), True
+    m.ctx = types.SimpleNamespace(variant=0, masked_slots=set())
+    angles = _plan.angle_grid(-np.pi / 2, np.pi / 2)[::30]
+    arr, bbox, area = m.describe(WT.Scarp, 12, np.array([2.0, 30.0]), angles)
+    _, sp = m.plan_for(bbox, area, "fft", n_params=2)
+    assert sp.Tx in (512, 1024, 2048) and m.can_flag_near_ties(arr, sp)
+    assert m.exact_route(arr, sp, bbox, area, 2) == "fft"
+    m.ctx.variant = 9
+    assert not m.can_flag_near_ties(arr, sp) and m.exact_route(arr, sp, bbox, area, 2) == "direct"
+    m.ctx.variant = 0
+    for Cls in (WT.LeftFacingUpperBreakScarp, WT.RightFacingUpperBreakScarp):
+        arr_u, _, _ = m.describe(Cls, 12, np.array([2.0, 30.0]), angles)
+        assert not m.can_flag_near_ties(arr_u, sp) and m.exact_route(arr_u, sp, bbox, area, 2) == "direct"
+    _, sp_d = m.plan_for(bbox, area, "direct", n_params=2)
+    assert not m.can_flag_near_ties(arr, sp_d)
+    wide = _lib.sc_plan(method=sp.method, Ty=sp.Ty, Tx=4096, Vy=sp.Vy, Vx=sp.Vx, nty=1, ntx=1, group=sp.group)
+    assert not m.can_flag_near_ties(arr, wide)
+    # a host-uploaded window: flags unless its slot carries masks
+    arr[len(arr) - 1].window = 3
+    assert m.can_flag_near_ties(arr, sp)
+    m.ctx.masked_slots.add(3)
+    assert not m.can_flag_near_ties(arr, sp)
