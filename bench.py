@@ -1,34 +1,42 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpixel.template/s of one full template search.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" is one search of the 35-age x 181-orientation Scarp grid (scale
 100) over the 10000 x 10000 synthetic DEM of BASELINE.md (config C3), DEM
 already resident in HBM - in the mode sl.match delivers by default (--mode
 exact: the float32 search with its near-ties listed, then sc_settle_exact -
-the argmax (age, orientation) of every cell is the float64 reference's); the
-float32 search alone (--mode float32) is timed beside it (`float32_mode`).  With N > 1 (launched by torch.distributed.run, one
+the argmax (age, orientation) of every cell is the float64 reference's); with
+--full the float32 search alone (--mode float32) is timed beside it (`float32_mode`).  With N > 1 (launched by torch.distributed.run, one
 rank per GPU) the same DEM is cut into a py x px tile grid (C4: 2 x 4), every
 rank exchanges halos over RCCL and searches its tile: total work is fixed, so
 scaling is "strong".  torch is used for the launcher contract only (rank
 rendezvous, barrier, max-reduce of the timings); the product path is
 ctypes -> libscarplet_hip.so.
 
-Besides the contract's fields the JSON line carries
-  config.mode, settle, float32_mode   the mode timed, the settle's counters of a
-                 step, the other mode's short loop and its verification
+A plain run does what the headline needs and nothing more: it sets up, warms
+up, times the K steps, writes --dump-outputs and prints the line.  Besides the
+contract's fields that line carries
+  config.mode, settle   the mode timed, the settle's counters of a step
   roofline       dominant kernel against the 28-B / 8 TB/s HBM roofline; its
                  `traffic` is the PMC-measured bytes per launch, printed only
                  when profiles/traffic.json was measured on this very .so
+  outputs        with --dump-outputs DIR: the .npy files of the last timed
+                 step's result planes written to DIR (result_sample)
+
+--full adds everything else the benchmark measures and checks, after the
+timed loop (--no-cpu-baseline, --no-verify, --no-e2e, --no-other-configs leave
+parts of it out):
+  float32_mode   the other mode's short loop and its verification (exact_mode
+                 when --mode float32 is timed)
   cpu_baseline   the oracle timed on this box's host cores:
                  whole-DEM templates, process-pool fan-out like core.py:180-183
   end_to_end     sl.match() wall time (H2D of the DEM, descriptors, search,
                  result conversion and D2H) as Mpx.template/s
   verified       a window of the result checked against the oracle after the
                  timed loop (every template of the search, near-tie policy)
-  outputs        with --dump-outputs DIR: the .npy files of the last timed
-                 step's result planes written to DIR (result_sample)
+  other_configs  C1, C2, C5 and C1F timed and verified after the headline
 
 Other workloads: --config C1|C2|C5 (BASELINE.json configs as SURVEY.md 8d
 defines them), --emulate-ranks R (the R rank blocks of the tiled search run one
@@ -53,7 +61,7 @@ KERNEL_SYMBOLS = {"k_inv_cols": "k_inv_cols_w8<T> (column length 512: k_inv_cols
                   "k_inv_rows": "k_inv_rows_fast<T,false,false,false,false,NEAR> (NEAR = true in the exact mode)"}
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
@@ -73,11 +81,16 @@ def parse():
                          "orientation) of every cell is the float64 reference's, what sl.match delivers by default; float32: "
                          "the float32 search as it is (sl.match(..., exact=False))")
     ap.add_argument("--group", type=int, default=0, help="templates per inverse launch (0: auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures and checks: the other mode's "
+                         "timed loop, the end-to-end sl.match calls, the oracle's check of a window of the result, the "
+                         "other BASELINE configs and the CPU baseline.  Without it a run sets up, warms up, times its "
+                         "steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the oracle's checks")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end sl.match calls")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the other_configs block (C1, C2, C5 timed and verified after the headline)")
+                    help="with --full: skip the other_configs block (C1, C2, C5 timed and verified after the headline)")
     ap.add_argument("--other-configs-budget", type=float, default=150.0,
                     help="seconds the other_configs block may take in all (timing + oracle verification); configs "
                          "that would start beyond it are reported as skipped")
@@ -105,11 +118,13 @@ def parse():
                     help="after the timed steps, write the result planes the timed path computed in its last step "
                          "(amp, age, angle, snr: float64) as DIR/<name>.npy - whole planes where they fit 64 MB in all, "
                          "else the same seeded sample of cells of every plane - and DIR/outputs.json describing them")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
     if a.dump_outputs and a.emulate_ranks:
         ap.error("--dump-outputs: the emulated ranks' step leaves no result of the whole search")
+    if not a.full:                     # the headline alone: none of the legs after the timed loop, no oracle pool
+        a.no_cpu_baseline = a.no_verify = a.no_e2e = a.no_other_configs = True
     return a
 
 
@@ -1275,7 +1290,7 @@ def main():
         rx = None
         if a.mode == "exact":
             out["settle"] = dict(settle_stats)
-        if default_workload:
+        if default_workload and a.full:
             other = "float32" if a.mode == "exact" else "exact"
             out[other + "_mode"] = other_mode_leg(make_step(a.mode != "exact"), ctx, a, units)
             if not a.no_e2e and not a.no_verify:

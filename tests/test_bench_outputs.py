@@ -1,5 +1,5 @@
 """bench.py --dump-outputs: the result planes of the last timed step as .npy files, within 64 MB, the same cells
-from run to run; and --steps as the number of timed steps."""
+from run to run; --steps as the number of timed steps; and a plain run as the headline alone, the rest behind --full."""
 import json
 import os
 import subprocess
@@ -88,3 +88,30 @@ def test_dump_outputs_of_a_small_config_repeat(tmp_path):
         a_, b_ = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
         assert a_.dtype == np.float64 and a_.shape == (900, 505)
         assert np.array_equal(a_, b_, equal_nan=True), name
+
+
+def test_a_plain_run_leaves_every_leg_after_the_timed_loop_to_full():
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.no_cpu_baseline and a.no_verify and a.no_e2e and a.no_other_configs
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert a.full and not (a.no_cpu_baseline or a.no_verify or a.no_e2e or a.no_other_configs)
+    a = bench.parse(["--full", "--no-cpu-baseline", "--no-other-configs"])
+    assert a.no_cpu_baseline and a.no_other_configs and not (a.no_verify or a.no_e2e)
+
+
+@pytest.mark.gpu
+def test_full_adds_the_checks_to_the_plain_line():
+    """C1 plain: the contract's fields and nothing from after the timed loop; C1 --full (CPU baseline left out): the
+    same fields, plus the end-to-end call and the oracle's check of the result, which passes."""
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = _bench(["--gpus", "1", "--config", "C1", "--steps", "3", "--warmup", "1"] + extra, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[run] = json.loads(r.stdout.strip().splitlines()[-1])
+    for ln in lines.values():
+        assert ln["n_gpus"] == 1 and ln["steps"] == 3 and ln["warmup"] == 1 and ln["dtype"] == "f32"
+        assert ln["higher_is_better"] is True and ln["value"] > 0 and ln["ms_per_step"] > 0
+        assert ln["config"]["mode"] == "exact" and "settle" in ln and "roofline" in ln
+    assert not {"verified", "verification", "end_to_end", "cpu_baseline", "float32_mode", "other_configs"} & set(lines["plain"])
+    assert lines["full"]["verified"] is True and lines["full"]["verification"]["cells_off_the_oracle_argmax"] == 0
+    assert "end_to_end" in lines["full"] and "cpu_baseline" not in lines["full"]

@@ -12,7 +12,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 LEAN="--no-cpu-baseline --no-verify --no-e2e --no-other-configs"
-python3 bench.py "$@" > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full "$@" > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py "$@" $LEAN > $OUT/trace.log 2>&1
 # (--mode float32: a two-orientation sample is -pi/2 and +pi/2 - ONE template - which tie in every cell: with the near-tie
 #  variant on, the sample's row pass would list 1e8 events a launch, nothing like the 181-orientation search's 8 000)
