@@ -102,7 +102,7 @@ typedef struct sc_plan {
 /* ---- lifetime ---------------------------------------------------------- */
 int  sc_abi_version(void);
 /* Which sources this binary was compiled from: the first 16 hex digits of the SHA-256 over the
- * library's sources (the six .hip files of csrc, sc_internal.h, this header) in the Makefile's order, worked out
+ * library's sources (the seven .hip files of csrc, sc_internal.h, this header) in the Makefile's order, worked out
  * at build time - `make -C scarplet_amd/csrc print-build-id` prints the same string for the tree
  * at hand.  bench.py prints it in every line and __graft_entry__.build() compares the two: a
  * stale prebuilt binary is visible instead of silently benchmarked. */
@@ -329,6 +329,45 @@ int sc_curvature_f64(sc_ctx* ctx, double cos2, double sin_a, double cos_a, doubl
 int sc_curvature_noise(sc_ctx* ctx, const double* weights, int radius, const uint8_t* nan_mask,
                        double* out);
 
+/*
+ * Traces of a result (docs/traces.md): the line one cell wide along the strike that a scarp or a channel leaves in
+ * the result planes, cut into connected segments, one row of a table each.  Nothing in the reference does this (its
+ * CHANGELOG lists non-maximum suppression as open; docs/source/examples/scarps.ipynb walks the rows in a Python loop).
+ * A cell is valid when its snr is finite and > 0 and its angle finite with |angle| <= 1e6.  Steps:
+ *   1. thinning: q = floor((angle / pi) * 4 + 0.5), s = q - 4 floor(q / 4) picks the step d = (drow, dcol) =
+ *      (0,+1), (+1,-1), (+1,0), (+1,+1) for s = 0..3 - along the profile of the template that won the cell, whose
+ *      alpha is -angle (x along the columns, y along the rows); correctly rounded float64 operations only.  With
+ *      v(n) = snr(n) inside the grid where finite, -inf otherwise: thin(c) = valid(c) && snr(c) >= snr_low &&
+ *      snr(c) > v(c - d) && snr(c) >= v(c + d) (of a plateau of two equal cells one stays);
+ *   2. connected components of thin under 8-connectivity; a cell is strong where snr >= snr_high; a component with
+ *      at least one strong cell and at least min_cells cells is a segment; segments are numbered 1..K in ascending
+ *      order of their smallest linear index (r * nx + c);
+ *   3. one sc_segment per segment, in label order.  Sums are float64 and the same bits on every run (no float atomics).
+ * thin: ny x nx bytes (1 = thinned cell), labels: ny x nx int32 (0 outside segments), either may be NULL;
+ * *n_segments = K.  SC_ERR_INVALID for snr_low not finite or <= 0, snr_high < snr_low or not finite, min_cells < 1;
+ * SC_ERR_UNSUPPORTED for more than 2^31 - 1 cells.  The buffers are the trace's own: the record, the result planes,
+ * the curvature spectra and the fill buffers are not touched.  One read-back of K (and the cell count) mid-sequence.
+ */
+typedef struct sc_segment {
+    int64_t  first;           /* smallest linear index                          */
+    int64_t  n_cells;         /* cells of the segment                           */
+    int64_t  n_strong;        /* cells with snr >= snr_high                     */
+    int32_t  row_min, row_max, col_min, col_max;   /* bounding box               */
+    int64_t  peak;            /* linear index of the largest snr (ties: the smallest index) */
+    double   snr_peak, amp_peak, age_peak, angle_peak;  /* the planes at peak, as they are */
+    double   sum_amp, sum_abs_amp, sum_age, sum_snr;    /* sums over the cells    */
+    double   sum_cos2a, sum_sin2a;                      /* of cos(2 angle), sin(2 angle): the axial mean orientation */
+} sc_segment;
+/* planes: 4 x ny x nx float64 on the host, (amp, age, angle, snr) as sc_get_result writes them; uploaded, then traced */
+int sc_trace_planes(sc_ctx* ctx, const double* planes, int ny, int nx, double snr_low, double snr_high,
+                    long long min_cells, uint8_t* thin, int32_t* labels, long long* n_segments);
+/* the same on the context's own result: the planes sc_get_result would return (param_of_id, angle_of_id, n_ids as
+ * there, the exact mode's patches laid over them), formed on the device and traced there - no upload */
+int sc_trace_result(sc_ctx* ctx, const double* param_of_id, const double* angle_of_id, int n_ids, double snr_low,
+                    double snr_high, long long min_cells, uint8_t* thin, int32_t* labels, long long* n_segments);
+/* the first n rows (n <= K) of the last trace's table */
+int sc_trace_segments(sc_ctx* ctx, sc_segment* out, long long n);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -457,7 +496,8 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_INV_ROWS    6
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
-#define SC_K_COUNT       9
+#define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
+#define SC_K_COUNT       10
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);
 int sc_profile_get(sc_ctx* ctx, int kernel, long long* launches,

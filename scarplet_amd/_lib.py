@@ -23,8 +23,8 @@ COMM_ID_BYTES = 128
 KIND_WINDOW = 2             # SC_KIND_WINDOW: a template whose window the host uploaded (sc_upload_window)
 
 K_NAMES = ("k_curv", "k_windows", "k_direct", "k_fwd_rows", "k_fwd_cols",
-           "k_inv_cols", "k_inv_rows", "k_settle", "k_noise")
-K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE, K_NOISE = range(9)
+           "k_inv_cols", "k_inv_rows", "k_settle", "k_noise", "k_trace")
+K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE, K_NOISE, K_TRACE = range(10)
 NOISE_MAX_RADIUS = 1048576  # SC_NOISE_MAX_RADIUS: the largest filter radius sc_curvature_noise takes
 
 XFER_RECV, XFER_SEND, XFER_LOCAL = 0, 1, 2
@@ -53,6 +53,24 @@ class sc_plan(C.Structure):
                 ("ntx", C.c_int32), ("circ_y", C.c_int32),
                 ("circ_x", C.c_int32), ("Py", C.c_int32), ("Qx", C.c_int32),
                 ("group", C.c_int32)]
+
+
+class sc_segment(C.Structure):
+    """One row of the table of sc_trace_planes / sc_trace_result (docs/traces.md)."""
+    _fields_ = [("first", C.c_int64), ("n_cells", C.c_int64), ("n_strong", C.c_int64),
+                ("row_min", C.c_int32), ("row_max", C.c_int32), ("col_min", C.c_int32), ("col_max", C.c_int32),
+                ("peak", C.c_int64),
+                ("snr_peak", C.c_double), ("amp_peak", C.c_double), ("age_peak", C.c_double), ("angle_peak", C.c_double),
+                ("sum_amp", C.c_double), ("sum_abs_amp", C.c_double), ("sum_age", C.c_double), ("sum_snr", C.c_double),
+                ("sum_cos2a", C.c_double), ("sum_sin2a", C.c_double)]
+
+
+# the same layout as a numpy structured dtype (the table is copied into such an array)
+SEGMENT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment._fields_],
+                          "formats": [np.int64, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32, np.int64]
+                          + [np.float64] * 10,
+                          "offsets": [getattr(sc_segment, f).offset for f, _ in sc_segment._fields_],
+                          "itemsize": C.sizeof(sc_segment)})
 
 
 class sc_xfer(C.Structure):
@@ -116,6 +134,11 @@ SIGNATURES = {
     "sc_settle_pairs": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, _up, C.c_longlong, C.c_int, C.c_double,
                                   C.POINTER(C.c_longlong)]),
     "sc_exchange_candidates": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "sc_trace_planes": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_longlong, _bp,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_longlong)]),
+    "sc_trace_result": (C.c_int, [_P, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_longlong, _bp,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_longlong)]),
+    "sc_trace_segments": (C.c_int, [_P, C.c_void_p, C.c_longlong]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -397,6 +420,33 @@ class Context(object):
                                                   _as(b, _dp)),
                     "sc_get_template_sums")
         return a, b
+
+    # -- traces of a result (docs/traces.md) ---------------------------------------
+    def _trace_out(self, shape, rc_fn, what):
+        thin = np.empty(shape, dtype=np.uint8)
+        labels = np.empty(shape, dtype=np.int32)
+        k = C.c_longlong(0)
+        self._check(rc_fn(_as(thin, _bp), labels.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(k)), what)
+        seg = np.empty(int(k.value), dtype=SEGMENT_DTYPE)
+        if k.value:
+            self._check(self.lib.sc_trace_segments(self._h, seg.ctypes.data_as(C.c_void_p), k.value), "sc_trace_segments")
+        return thin, labels, seg
+
+    def trace_planes(self, planes, snr_low, snr_high, min_cells):
+        """sc_trace_planes on a (4, ny, nx) float64 C-contiguous host array: (thin u8, labels int32, table)."""
+        assert planes.dtype == np.float64 and planes.flags.c_contiguous and planes.ndim == 3 and planes.shape[0] == 4
+        ny, nx = planes.shape[1:]
+        return self._trace_out((ny, nx), lambda t, l, k: self.lib.sc_trace_planes(
+            self._h, _as(planes, _dp), ny, nx, float(snr_low), float(snr_high), int(min_cells), t, l, k),
+            "sc_trace_planes")
+
+    def trace_result(self, param_of_id, angle_of_id, snr_low, snr_high, min_cells):
+        """sc_trace_result: the same on the planes get_result would return, formed and traced on the device."""
+        par = np.ascontiguousarray(param_of_id, dtype=np.float64)
+        ang = np.ascontiguousarray(angle_of_id, dtype=np.float64)
+        return self._trace_out(self.core_shape(), lambda t, l, k: self.lib.sc_trace_result(
+            self._h, _as(par, _dp), _as(ang, _dp), len(par), float(snr_low), float(snr_high), int(min_cells), t, l, k),
+            "sc_trace_result")
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

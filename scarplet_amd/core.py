@@ -870,6 +870,22 @@ class Matcher(object):
             out = self._apply_patches(out)
         return out
 
+    def extract_traces(self, snr_low, snr_high=None, min_cells=1):
+        """``sl.extract_traces`` of this matcher's result (docs/traces.md), traced where it lies: the device forms the
+        planes of result_array() and traces them there (sc_trace_result) - no 3.2 GB round trip for a 10000^2 DEM.
+        A result that carries host-side patches, or the NaN maps of a DEM with NaN cells, is traced from its host
+        planes instead; the bytes are the same either way."""
+        from scarplet_amd import traces
+        lo, hi, mc = traces.check_args(snr_low, snr_high, min_cells)
+        if getattr(self, "_nan_result", None) is not None or getattr(self, "_patches", None) \
+                or getattr(self, "_cells64", None) is not None:
+            return traces._traces(*self.ctx.trace_planes(traces._planes_of(self.result_array()), lo, hi, mc))
+        if getattr(self, "_id_par", None) is None or not len(self._id_par):
+            par, ang = np.repeat(self.params, len(self.angles)), np.tile(self.angles, len(self.params))
+        else:
+            par, ang = self._id_par, self._id_ang
+        return traces._traces(*self.ctx.trace_result(par, ang, lo, hi, mc))
+
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one
         sl.match per scale on the same data, docs/source/examples/channels.ipynb - its 4-plane result has no scale

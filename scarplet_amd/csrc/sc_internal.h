@@ -179,6 +179,10 @@ struct sc_ctx {
     DevBuf halo_z, halo_stage;
     DevBuf res;                // sc_get_result: four float64 planes + the id tables
     DevBuf fill[4];            // sc_fill_nodata: z, result, up / down tables (+ the counter)
+    // sc_trace_*: the trace's own buffers - uploaded planes, thin mask, parents, labels, per-root counters, scan block
+    // sums and totals, the radix sort's keys / values (two of each) and histograms, the segment table
+    DevBuf tr_planes, tr_thin, tr_par, tr_lab, tr_cnt, tr_bsum, tr_tot, tr_sort, tr_hist, tr_rbsum, tr_seg;
+    long long tr_k = 0;        // segments of the last trace
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);
