@@ -34,6 +34,13 @@ class ScarpletHipError(RuntimeError):
     pass
 
 
+def is_settle_limit(err):
+    """Whether ``err`` is a float64 settle that stopped at one of its bounds - an overflowed event list, more float64
+    work than it was allowed - rather than failed: the float32 record it left stands."""
+    msg = str(err)
+    return "overflowed" in msg or "too much float64 work" in msg
+
+
 class sc_template(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32),
                 ("cos_a", C.c_double), ("sin_a", C.c_double),

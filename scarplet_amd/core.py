@@ -27,6 +27,9 @@ Differences a caller can observe (DESIGN.md "Parity"):
     pass: call ``data._fill_nodata()`` first, as ``load`` does.
 """
 
+import collections
+import contextlib
+
 import numpy as np
 
 from scarplet_amd import _lib, _plan
@@ -46,6 +49,23 @@ def _context(device):
         ctx = _lib.Context(device)
         _CONTEXTS[device] = ctx
     return ctx
+
+
+@contextlib.contextmanager
+def _near_window(ctx, w):
+    """Option "near_window" at ``w`` for the searches inside, back at 0.0 on the way out, exceptions included.  Yields
+    a setter for a search inside that takes another window."""
+    def set_window(w_):
+        ctx.set_option("near_window", float(w_))
+    set_window(w)
+    try:
+        yield set_window
+    finally:
+        set_window(0.0)
+
+
+# what the passes of an exact search and the longer host routes need of its inputs (Matcher._search_exact)
+_Search = collections.namedtuple("_Search", "Template scale params angles kwargs bbox max_area group")
 
 
 def _grid_of(data):
@@ -424,27 +444,24 @@ class Matcher(object):
             from scarplet_amd import _hostpool
             pre = _hostpool.prefault((4, self.core[1] - self.core[0], self.core[3] - self.core[2]))
         if exact is None:
-            exact = bool(reset and sync and len(arr) and all(int(arr[k].kind) != _WT.KIND_WINDOW for k in (0, len(arr) - 1)))
+            exact = bool(reset and sync and len(arr) and self.exact_by_default(arr))
         if exact:
             if not (reset and sync):
                 raise ValueError("exact=True needs reset=True and sync=True")
             self.exact_stats = {"flagged_cells": 0, "patches": 0, "changed_cells": 0, "float64_cells": 0}
-            self._search_exact(arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs)
-            del pre
-            self.params, self.angles = params, angles
-            self.n_templates = len(arr)
-            self._id_par = np.concatenate([self._id_par, np.repeat(params, len(angles))])
-            self._id_ang = np.concatenate([self._id_ang, np.tile(angles, len(params))])
-            return self
-        self.ctx.match(arr, sp, sync=sync)
+            self._search_exact(arr, sp, method, _Search(Template, scale, params, angles, kwargs, bbox, max_area, group))
+        else:
+            self.ctx.match(arr, sp, sync=sync)
+            self.method_used = "direct" if sp.method == _plan.METHOD_DIRECT else "fft"
+            if method in ("auto", "fft") and reset and sync and self.method_used == "fft" and \
+                    self._unresolved(method, bbox, max_area, len(params)):
+                self.plan, sp = self.plan_for(bbox, max_area, "direct", group, n_params=len(params))
+                self.ctx.reset_best()
+                self.ctx.match(arr, sp, sync=True)
+                self.method_used = "direct"
         # (not joined: a search shorter than the touching finds the block still referenced by the thread and takes a
         #  fresh one, as before - never slower than without)
         del pre
-        self.method_used = "direct" if sp.method == _plan.METHOD_DIRECT else "fft"
-        if method == "auto" and reset and sync and self.method_used == "fft":
-            self._exact_path_if_unresolved(arr, bbox, max_area, group, len(params))
-        elif method == "fft" and reset and sync:
-            self._warn_if_unresolved()
         self.params, self.angles = params, angles
         self.n_templates = len(arr)
         self._id_par = np.concatenate([self._id_par, np.repeat(params, len(angles))])
@@ -460,38 +477,25 @@ class Matcher(object):
         if not exact_window > 0.0:
             self.ctx.match(arr, sp, sync=True)
             return None
-        self.ctx.set_option("near_window", float(exact_window))
-        try:
+        with _near_window(self.ctx, exact_window):
             self.ctx.match(arr, sp, sync=True)
-        finally:
-            self.ctx.set_option("near_window", 0.0)
         return self.ctx.settle_exact(n_twin, self.EXACT_MAX_F64)
 
-    def exact_window_for(self, arr, sp):
-        """The near-tie window exact=True searches these descriptors with: by path and template family."""
+    def exact_window_for(self, arr, sp, of_class=False):
+        """The near-tie window exact=True searches these descriptors with: by path and template family - from this
+        matcher's tables, or (``of_class``) as the class states them, whatever an instance overrides."""
+        tables = type(self) if of_class else self
         if sp.method != _plan.METHOD_FFT:
-            return self.EXACT_WINDOW_DIRECT
+            return tables.EXACT_WINDOW_DIRECT
         kinds = {int(arr[0].kind), int(arr[len(arr) - 1].kind)}
-        return max(self.EXACT_WINDOW.get(k, max(self.EXACT_WINDOW.values())) for k in kinds)
+        return max(tables.EXACT_WINDOW.get(k, max(tables.EXACT_WINDOW.values())) for k in kinds)
 
     def end_twins(self, arr, n_params, angles):
         """How many templates at the end of the orientation-major list ``arr`` repeat its first ones: n_params where the
         grid runs from -pi/2 to +pi/2 and the class is one of the symmetric built-ins (_without_end_twin), else 0."""
         return len(arr) - len(self._without_end_twin(arr, n_params, angles))
 
-    def _warn_if_unresolved(self):
-        """The FFT path was asked for by name: it is handed out as it is, but not silently where the device's own
-        statistic says it cannot resolve this surface in float32."""
-        wins, near = self.ctx.resolution_stats()
-        self.unresolved_frac = near / wins if wins else 0.0
-        if self.unresolved_frac > self.UNRESOLVED_MAX:
-            import warnings
-            warnings.warn("method='fft': %.1f %% of the cells this search won lie within the float32 "
-                          "resolution floor of the FFT convolution (a surface without a noise floor of its "
-                          "own); their argmax is rounding noise - method='auto' or 'direct' gives the exact "
-                          "real-space answer" % (100 * self.unresolved_frac))
-
-    def _search_exact(self, arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs):
+    def _search_exact(self, arr, sp, method, s):
         """exact=True (round 6: settled on the device).  The search runs with option "near_window" on - either path then
         flags its near-ties and lists them as events (cell, template scored, holder of the record) - and sc_settle_exact
         scores exactly the (cell, template) pairs those events name in float64 and gives every flagged cell its float64
@@ -511,18 +515,17 @@ class Matcher(object):
         import warnings
         self.exact_stats["max_f32_err"] = float("nan")          # (measured by the device route only)
         windows = int(arr[0].kind) == _WT.KIND_WINDOW
-        if not self._exact_pass(arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs, windows):
+        if not self._exact_pass(arr, sp, method, s):
             return
         err, win = self.exact_stats["max_f32_err"], self._exact_window
         if not (windows and err > 0.5 * win):
             return
-        new = min(max(2.2 * err, self._default_exact_window(arr, self.method_used == "fft")), self.EXACT_RETRY_MAX)
+        new = min(max(2.2 * err, self.exact_window_for(arr, self._exact_sp, of_class=True)), self.EXACT_RETRY_MAX)
         first = dict(self.exact_stats)
         self.exact_stats = {"flagged_cells": 0, "patches": 0, "changed_cells": 0, "float64_cells": 0,
                             "max_f32_err": float("nan"), "retried": (win, new), "first_pass": first}
         self.ctx.reset_best()
-        self._exact_pass(arr, self._exact_sp, bbox, max_area, self.method_used, group, Template, scale, params, angles,
-                         kwargs, windows, window=new)
+        self._exact_pass(arr, self._exact_sp, self.method_used, s, window=new)
         err = self.exact_stats["max_f32_err"]
         if err > 0.5 * new:
             warnings.warn("exact=True: the float32 SNR error the settle measured (%.2e) is still above half the near-tie "
@@ -531,84 +534,73 @@ class Matcher(object):
     # exact=True, window templates: the widest near-tie window a retry after the audit takes
     EXACT_RETRY_MAX = 5e-3
 
-    def _default_exact_window(self, arr, fft):
-        """The path's near-tie window as the class states it (an instance may override EXACT_WINDOW[_DIRECT])."""
-        if not fft:
-            return type(self).EXACT_WINDOW_DIRECT
-        kinds = {int(arr[0].kind), int(arr[len(arr) - 1].kind)}
-        table = type(self).EXACT_WINDOW
-        return max(table.get(k, max(table.values())) for k in kinds)
-
-    def _exact_pass(self, arr, sp, bbox, max_area, method, group, Template, scale, params, angles, kwargs, windows,
-                    window=None):
-        """One search with its near-ties flagged and settled (``window``: the near-tie window of both paths instead of
-        the defaults).  True when the device settled it (exact_stats holds its counters and the audit)."""
+    def _exact_pass(self, arr, sp, method, s, window=None):
+        """One search of ``s`` (a _Search) with its near-ties flagged and settled (``window``: the near-tie window of
+        both paths instead of the defaults).  True when the device settled it (exact_stats holds its counters and the
+        audit)."""
         import warnings
-        n_par = len(params)
-        n_twin = self.end_twins(arr, n_par, angles)
-        fft = sp.method == _plan.METHOD_FFT
-        win_fft = (self.exact_window_for(arr, sp) if window is None else window) if fft else 0.0
-        win_direct = self.EXACT_WINDOW_DIRECT if window is None else window
-        try:
-            if fft:
-                route = self.exact_route(arr, sp, bbox, max_area, n_par)
-                if route == "float32":
-                    self.ctx.set_option("near_window", 0.0)
-                    self.ctx.match(arr, sp, sync=True)
-                    self.method_used = "fft"
-                    self._warn_exact_skipped()
-                    self.exact_stats["skipped"] = True
-                    return False
-                fft = route == "fft"
-                if fft:
-                    self.ctx.set_option("near_window", win_fft)
-                    self.ctx.match(arr, sp, sync=True)
-                if fft and method == "auto":
-                    wins, near = self.ctx.resolution_stats()
-                    self.unresolved_frac = near / wins if wins else 0.0
-                    if self.unresolved_frac > self.UNRESOLVED_MAX:
-                        note = ("the FFT path cannot resolve %.1f %% of this surface's cells in float32 (no noise floor "
-                                "of its own)" % (100 * self.unresolved_frac))
-                        if not self._direct_affordable(bbox, max_area, n_par):
-                            warnings.warn(note + "; method='direct' is exact but much slower here - not taken automatically")
-                        else:
-                            warnings.warn(note + ": searched again on the exact real-space path")
-                            fft = False
-                elif fft and method == "fft":
-                    self._warn_if_unresolved()
-                if not fft:
-                    self.plan, sp = self.plan_for(bbox, max_area, "direct", group, n_params=n_par)
-                    self.ctx.reset_best()
-            if not fft:
-                self.ctx.set_option("near_window", win_direct)
+        n_par = len(s.params)
+        n_twin = self.end_twins(arr, n_par, s.angles)
+        planned_fft = sp.method == _plan.METHOD_FFT
+        route, sp = self.exact_plan(arr, sp, s.bbox, s.max_area, s.group, n_par)
+        if route == "float32":
+            with _near_window(self.ctx, 0.0):
                 self.ctx.match(arr, sp, sync=True)
-        finally:
-            self.ctx.set_option("near_window", 0.0)
-        self.method_used = "fft" if fft else "direct"
-        self._exact_sp = sp
-        self._exact_window = win_fft if fft else win_direct
+            self.method_used = "fft"
+            self.exact_stats.update(self._exact_skipped())
+            return False
+        if route == "direct" and planned_fft:
+            self.ctx.reset_best()
+        win = self.exact_window_for(arr, sp) if window is None else window
+        with _near_window(self.ctx, win) as set_window:
+            self.ctx.match(arr, sp, sync=True)
+            if route == "fft" and method in ("auto", "fft") and self._unresolved(method, s.bbox, s.max_area, n_par):
+                self.plan, sp = self.plan_for(s.bbox, s.max_area, "direct", s.group, n_params=n_par)
+                self.ctx.reset_best()
+                route, win = "direct", self.exact_window_for(arr, sp) if window is None else window
+                set_window(win)
+                self.ctx.match(arr, sp, sync=True)
+        self.method_used = route
+        self._exact_sp, self._exact_window = sp, win
         if self.EXACT_USE_EVENTS:
             try:
                 st = self.ctx.settle_exact(n_twin, self.EXACT_MAX_F64)
-                self.exact_stats.update(st, route="device", window=self._exact_window)
+                self.exact_stats.update(st, route="device", window=win)
                 return True
             except _lib.ScarpletHipError as e:
-                msg = str(e)
-                if "overflowed" not in msg and "too much float64 work" not in msg:
+                if not _lib.is_settle_limit(e):
                     raise
-                self.exact_stats["settle"] = msg
+                self.exact_stats["settle"] = str(e)
         # the longer routes (round 5): host lists
         if not self.whole:
             warnings.warn("exact=True: the near-ties of this block were not settled (%s)" % self.exact_stats.get("settle", "host route off"))
             self.exact_stats["skipped"] = True
             return False
-        if fft:
-            self._rescore_near_ties(Template, scale, params, angles, kwargs)
+        if route == "fft":
+            self._rescore_near_ties(s.Template, s.scale, s.params, s.angles, s.kwargs)
         else:
             last = [tuple(c) for c in np.argwhere(self.ctx.near_ties())]
             self.exact_stats["flagged_cells"] = len(last)
-            self._score_float64([(i + self.core[0], j + self.core[2]) for i, j in last], arr, bbox)
+            self._score_float64([(i + self.core[0], j + self.core[2]) for i, j in last], arr, s.bbox)
         return False
+
+    # -- the exact mode's decisions, for Matcher.search and the sharded drivers (dist.py) --------------------------
+    @staticmethod
+    def exact_by_default(arr):
+        """Whether exact=None means on for the descriptors ``arr``: built-in templates at both ends, none whose window
+        the host uploads (each driver adds its own condition)."""
+        return all(int(arr[k].kind) != _WT.KIND_WINDOW for k in (0, len(arr) - 1))
+
+    def exact_plan(self, arr, sp, bbox, max_area, group, n_par):
+        """(route, plan struct) of an exact search of the planned search ``sp``: a search planned on the real-space path
+        stays there ("direct"); an FFT search goes where exact_route says - "fft" as planned, "direct" re-planned onto
+        the real-space path (``self.plan`` too), or "float32": the FFT search without the settle (_exact_skipped)."""
+        if sp.method != _plan.METHOD_FFT:
+            return "direct", sp
+        route = self.exact_route(arr, sp, bbox, max_area, n_par)
+        if route == "direct":
+            self.plan, sp = self.plan_for(bbox, max_area, "direct", group, n_params=n_par)
+        return route, sp
 
     def can_flag_near_ties(self, arr, sp):
         """Whether an FFT search of the descriptors ``arr`` with the plan ``sp`` can flag its near-ties: only the fast row
@@ -636,11 +628,13 @@ class Matcher(object):
         return "float32" if windows and not self._direct_affordable(bbox, max_area, n_par) else "direct"
 
     @staticmethod
-    def _warn_exact_skipped():
+    def _exact_skipped():
+        """exact_plan's "float32": said, and the exact_stats entry that marks it."""
         import warnings
         warnings.warn("exact=True: this plugin's templates carry per-cell masks, which only the real-space path flags, "
                       "and a real-space search would take beyond a hundred times the FFT search here - the float32 FFT "
                       "result stands")
+        return {"skipped": True}
 
     def _direct_affordable(self, bbox, max_area, n_par):
         """The guard of the real-space re-plans: the window fits the real-space kernel's slab and its search costs at
@@ -672,13 +666,10 @@ class Matcher(object):
     def _direct_exact(self, arr, sp):
         """exact=True on the real-space path: the search with its own near-tie flags on (EXACT_WINDOW_DIRECT: the cells
         it decides inside its float32 rounding); returns those cells for _score_float64."""
-        self.ctx.set_option("near_window", self.EXACT_WINDOW_DIRECT)
-        try:
+        with _near_window(self.ctx, self.EXACT_WINDOW_DIRECT):
             self.ctx.reset_best()
             self.ctx.match(arr, sp, sync=True)
             return [tuple(c) for c in np.argwhere(self.ctx.near_ties())]
-        finally:
-            self.ctx.set_option("near_window", 0.0)
 
     def _rescore_near_ties(self, Template, scale, params, angles, kwargs):
         """exact=True, second and third step: the cells the FFT row pass flagged are searched again on the
@@ -733,25 +724,24 @@ class Matcher(object):
             arr, _, _ = aux.describe(Template, scale, params, angles, **kwargs)
             arr = self._without_end_twin(arr, len(params), angles)
             halo = _dist.halo_for_search(bbox, ny, nx)
-            aux.ctx.set_option("near_window", self.EXACT_WINDOW_DIRECT)
             try:
-                for (bi, bj) in todo:
-                    i0, j0 = bi * ph, bj * pw
-                    i1, j1 = min(i0 + ph, ny), min(j0 + pw, nx)
-                    gi = np.arange(i0 - halo[0], i1 + halo[1]) % ny      # the DEM is a torus (the reference's circular convolution)
-                    gj = np.arange(j0 - halo[2], j1 + halo[3]) % nx
-                    blk = np.ascontiguousarray(z[np.ix_(gi, gj)], dtype=np.float64)
-                    aux.set_block(blk, (i0 - halo[0], j0 - halo[2]), (ny, nx), (i0, i1, j0, j1), self.dx, self.dy)
-                    _, sp = aux.plan_for(bbox, max_area, "direct", None, n_params=len(params))
-                    aux.ctx.reset_best()
-                    aux.ctx.match(arr, sp, sync=True)
-                    amp, snr, idx = aux.ctx.get_best()
-                    sel = flags[i0:i1, j0:j1] != 0
-                    self._patches.append((i0, j0, sel, amp, snr, idx))
-                    self.exact_stats["patches"] += 1
-                    last += [(i0 + int(a), j0 + int(b)) for a, b in np.argwhere(sel & (aux.ctx.near_ties() != 0))]
+                with _near_window(aux.ctx, self.EXACT_WINDOW_DIRECT):
+                    for (bi, bj) in todo:
+                        i0, j0 = bi * ph, bj * pw
+                        i1, j1 = min(i0 + ph, ny), min(j0 + pw, nx)
+                        gi = np.arange(i0 - halo[0], i1 + halo[1]) % ny      # the DEM is a torus (the reference's circular convolution)
+                        gj = np.arange(j0 - halo[2], j1 + halo[3]) % nx
+                        blk = np.ascontiguousarray(z[np.ix_(gi, gj)], dtype=np.float64)
+                        aux.set_block(blk, (i0 - halo[0], j0 - halo[2]), (ny, nx), (i0, i1, j0, j1), self.dx, self.dy)
+                        _, sp = aux.plan_for(bbox, max_area, "direct", None, n_params=len(params))
+                        aux.ctx.reset_best()
+                        aux.ctx.match(arr, sp, sync=True)
+                        amp, snr, idx = aux.ctx.get_best()
+                        sel = flags[i0:i1, j0:j1] != 0
+                        self._patches.append((i0, j0, sel, amp, snr, idx))
+                        self.exact_stats["patches"] += 1
+                        last += [(i0 + int(a), j0 + int(b)) for a, b in np.argwhere(sel & (aux.ctx.near_ties() != 0))]
             finally:
-                aux.ctx.set_option("near_window", 0.0)
                 aux.ctx.clear_windows()
         self._score_float64(last, arr_main, bbox)
 
@@ -819,33 +809,33 @@ class Matcher(object):
     # resolution floor (sc_get_resolution_stats) above which method="auto" takes the exact path
     UNRESOLVED_MAX = 0.01
 
-    def _exact_path_if_unresolved(self, arr, bbox, max_area, group, n_params):
-        """method="auto" on a surface WITHOUT a noise floor (synthetic scarps stored as float32:
-        quantisation noise only away from the feature): a float32 FFT convolution resolves an
-        output only to a fraction of its tile's energy, and where the residual T3 - T1 the SNR
-        divides by sinks to that resolution the argmax over templates is rounding noise (8 % of
-        the cells of such a surface, tests/test_gpu_parity.py).  The device counts those cells
-        while it folds; when more than UNRESOLVED_MAX of the wins are such, the search is run
-        again on the real-space path, which sums locally and has no such limit - unless that
-        would take beyond a hundred times longer, then a warning says so."""
+    def _unresolved(self, method, bbox, max_area, n_par):
+        """After an FFT search by method="auto" or "fft" on a surface WITHOUT a noise floor (synthetic scarps stored as
+        float32: quantisation noise only away from the feature): a float32 FFT convolution resolves an output only to a
+        fraction of its tile's energy, and where the residual T3 - T1 the SNR divides by sinks to that resolution the
+        argmax over templates is rounding noise (8 % of the cells of such a surface, tests/test_gpu_parity.py).  The
+        device counts those cells while it folds (self.unresolved_frac).  Beyond UNRESOLVED_MAX of the wins: the FFT
+        path asked for by name is handed out as it is, with a warning; method="auto" is to run again on the real-space
+        path, which sums locally and has no such limit - True - unless _direct_affordable says no (checked against the
+        FFT plan, self.plan), then a warning says so."""
         wins, near = self.ctx.resolution_stats()
         self.unresolved_frac = near / wins if wins else 0.0
         if self.unresolved_frac <= self.UNRESOLVED_MAX:
-            return
+            return False
         import warnings
+        if method == "fft":
+            warnings.warn("method='fft': %.1f %% of the cells this search won lie within the float32 "
+                          "resolution floor of the FFT convolution (a surface without a noise floor of its "
+                          "own); their argmax is rounding noise - method='auto' or 'direct' gives the exact "
+                          "real-space answer" % (100 * self.unresolved_frac))
+            return False
         note = ("the FFT path cannot resolve %.1f %% of this surface's cells in float32 (no noise floor "
                 "of its own)" % (100 * self.unresolved_frac))
-        ww = bbox[3] - bbox[2] + 1
-        n_cells = (self.core[1] - self.core[0]) * (self.core[3] - self.core[2])
-        if not _plan.direct_window_fits(ww) or \
-                _plan.direct_cost(max_area) > 100 * _plan.fft_cost(self.plan, n_cells, n_params):
+        if not self._direct_affordable(bbox, max_area, n_par):
             warnings.warn(note + "; method='direct' is exact but much slower here - not taken automatically")
-            return
+            return False
         warnings.warn(note + ": searched again on the exact real-space path")
-        self.plan, sp = self.plan_for(bbox, max_area, "direct", group, n_params=n_params)
-        self.ctx.reset_best()
-        self.ctx.match(arr, sp, sync=True)
-        self.method_used = "direct"
+        return True
 
     def result(self):
         """(amp, age, angle, snr) float64 maps of the core region."""

@@ -39,9 +39,12 @@ The RCCL path needs ``broadcast_bytes`` only (the 128-byte communicator id);
 tools/torch_transport.py implements all three over torch.distributed.
 """
 
+import contextlib
+
 import numpy as np
 
 from scarplet_amd import _lib, _plan
+from scarplet_amd.core import Matcher, _near_window
 
 
 def grid_dims(nranks, ny, nx):
@@ -281,7 +284,6 @@ class DistMatcher(object):
 
     def __init__(self, rank, nranks, shape, dx, dy, device=0, backend="rccl",
                  broadcast_bytes=None, transport=None, matcher=None):
-        from scarplet_amd.core import Matcher
         self.rank, self.nranks = rank, nranks
         self.ny, self.nx = shape
         self.dx, self.dy = dx, dy
@@ -357,7 +359,7 @@ class DistMatcher(object):
         gather (sc_settle_exact: the halo covers the templates' reach and the curvature stencil) - the record that
         travels carries the float64 argmax, its amplitude and SNR rounded to float32.  ``exact=True`` settles plugins
         whose windows the host uploads as well (every rank uploads its own windows and settles its own block; the near-tie
-        flags need the real-space path for templates with per-cell masks: Matcher.exact_route, as in Matcher.search);
+        flags need the real-space path for templates with per-cell masks: Matcher.exact_plan, as in Matcher.search);
         exact_stats["max_f32_err"] is the settle's audit.  A settle this rank cannot finish (an overflowed event list, more
         float64 work than EXACT_MAX_F64) leaves its float32 record, with a warning and exact_stats["skipped"] - the
         other ranks are not kept waiting in the gather.  Untested on more than one rank for plugins."""
@@ -369,31 +371,25 @@ class DistMatcher(object):
         self.load(z_core, bbox)
         m.plan, sp = m.plan_for(bbox, max_area, method, group, n_params=len(params))
         if exact is None:
-            exact = all(int(arr[k].kind) != 2 for k in (0, len(arr) - 1))         # (2: SC_KIND_WINDOW, a host-uploaded plugin)
-        route = "fft" if sp.method == _plan.METHOD_FFT else "direct"
-        if exact and route == "fft":
-            # (per rank: the blocks - and their tile plans and real-space costs - may differ, and so may the routes; each
-            #  rank settles its own block, so a rank on the real-space path next to one on the FFT tiles is fine)
-            route = m.exact_route(arr, sp, bbox, max_area, len(params))
-            if route == "direct":
-                m.plan, sp = m.plan_for(bbox, max_area, "direct", group, n_params=len(params))
-        self.method_used = m.method_used = "direct" if route == "direct" else "fft"
+            exact = m.exact_by_default(arr)
+        # (per rank: the blocks - and their tile plans and real-space costs - may differ, and so may the routes; each
+        #  rank settles its own block, so a rank on the real-space path next to one on the FFT tiles is fine)
+        route, sp = m.exact_plan(arr, sp, bbox, max_area, group, len(params)) if exact else (None, sp)
+        self.method_used = m.method_used = "direct" if sp.method == _plan.METHOD_DIRECT else "fft"
         m.params, m.angles = params, angles
         if route == "float32":
             m.run_described(arr, sp)
-            m._warn_exact_skipped()
-            self.exact_stats = {"skipped": True}
+            self.exact_stats = m._exact_skipped()
             return self
         try:
             self.exact_stats = m.run_described(arr, sp, m.exact_window_for(arr, sp) if exact else 0.0,
                                                m.end_twins(arr, len(params), angles))
         except _lib.ScarpletHipError as e:
-            msg = str(e)
-            if "overflowed" not in msg and "too much float64 work" not in msg:
+            if not _lib.is_settle_limit(e):
                 raise
             # (the match ran, the settle did not touch the record: this rank's float32 answer stands)
-            warnings.warn("exact=True: rank %d did not settle the near-ties of its block (%s)" % (self.rank, msg))
-            self.exact_stats = {"skipped": True, "settle": msg}
+            warnings.warn("exact=True: rank %d did not settle the near-ties of its block (%s)" % (self.rank, e))
+            self.exact_stats = {"skipped": True, "settle": str(e)}
         return self
 
     def result(self):
@@ -497,7 +493,6 @@ class OrientationMatcher(object):
 
     def __init__(self, rank, nranks, data, device=0, backend="rccl", broadcast_bytes=None,
                  transport=None, matcher=None):
-        from scarplet_amd.core import Matcher
         self.rank, self.nranks = rank, nranks
         self.backend = "host" if backend == "gloo" else backend
         self.transport = transport
@@ -555,14 +550,9 @@ class OrientationMatcher(object):
         if exact and self.nranks > 1 and self.backend == "host" and self.transport is None:
             raise ValueError("exact mode over %d ranks needs transport= (the ranks exchange their candidate lists)" % self.nranks)
         ctx.reset_best()
-        if exact:
-            ctx.set_option("near_window", float(exact_window))
-        try:
+        with _near_window(ctx, exact_window) if exact else contextlib.nullcontext():
             if mine is not None:
                 ctx.match(mine, sp)
-        finally:
-            if exact:
-                ctx.set_option("near_window", 0.0)
         if exact:
             ctx.snapshot_best()
         self._folded = None
@@ -626,7 +616,7 @@ class OrientationMatcher(object):
         """``exact`` (default: on for the built-in template classes wherever the ranks can exchange their candidate
         lists - one rank, RCCL, or a transport): the float64 argmax of the whole search, as ``scarplet_amd.match`` delivers.
         Where the FFT row pass cannot flag the near-ties (UpperBreak's error masks, a plugin's masks, tiles 4096 wide) the
-        search runs on the real-space path instead, as in Matcher.search (Matcher.exact_route: every rank plans from the
+        search runs on the real-space path instead, as in Matcher.search (Matcher.exact_plan: every rank plans from the
         whole grid, so every rank decides alike)."""
         if getattr(self.m, "nan_dem", False):      # the reference's all-NaN maps, on every rank
             self.m.search(Template, scale, params, angles, method=method, **kwargs)
@@ -634,21 +624,14 @@ class OrientationMatcher(object):
             return self
         self._nan = False
         mine, sp = self.describe(Template, scale, params, angles, method, group, **kwargs)
-        arr = self._keep
-        m = self.m
+        arr, m = self._keep, self.m
         if exact is None:
-            exact = all(int(arr[k].kind) != 2 for k in (0, len(arr) - 1)) and \
-                (self.nranks == 1 or self.backend == "rccl" or self.transport is not None)
-        route = "fft" if sp.method == _plan.METHOD_FFT else "direct"
-        if exact and route == "fft":
-            route = m.exact_route(arr, sp, self._bbox, self._area, len(m.params))
-            if route == "direct":
-                m.plan, sp = m.plan_for(self._bbox, self._area, "direct", self._group, n_params=len(m.params))
-        self.method_used = m.method_used = "direct" if route == "direct" else "fft"
+            exact = m.exact_by_default(arr) and (self.nranks == 1 or self.backend == "rccl" or self.transport is not None)
+        route, sp = m.exact_plan(arr, sp, self._bbox, self._area, self._group, len(m.params)) if exact else (None, sp)
+        self.method_used = m.method_used = "direct" if sp.method == _plan.METHOD_DIRECT else "fft"
         if route == "float32":
             self.run(mine, sp)
-            m._warn_exact_skipped()
-            self.exact_stats = {"skipped": True}
+            self.exact_stats = m._exact_skipped()
             return self
         self.run(mine, sp, m.exact_window_for(arr, sp) if exact else 0.0,
                  m.end_twins(arr, len(m.params), m.angles))
