@@ -196,6 +196,10 @@ int sc_clear_windows(sc_ctx* ctx);
  *   "batch_fill"  column-pass workgroups a batched launch sequence aims at (0: the default, 4096):
  *              orientations per launch = batch_fill / (tile pairs x Tx / 8), at most 64 and what the
  *              row pass's tables hold.  Results are bit-identical whatever the batch.
+ *   "fuse_fwd" 1 (default): the wave-per-column inverse pass (column length 1024 / 2048, symmetric
+ *              templates) runs the curvature's forward column transform on the columns it parks,
+ *              instead of a k_fwd_cols launch per orientation; 0: the two-launch form.  Off by itself
+ *              while curvature spectra are kept ("spectra_mb").  Results are bit-identical.
  *   "i1_pairs" tile pairs per launch of the wave-per-column inverse pass (default 2; 1: one pair per
  *              launch), interleaved so that the workgroups which stream the same template
  *              coefficients run on one XCD at the same time.  Results are bit-identical.

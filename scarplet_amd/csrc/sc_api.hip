@@ -44,7 +44,7 @@ size_t sc_total_bytes(sc_ctx* c) {
     DevBuf* arr[] = {&c->z, &c->xaxis, &c->yaxis, &c->A, &c->B, &c->C, &c->curv,
                      &c->best_snr, &c->best_amp, &c->best_id, &c->map_amp,
                      &c->map_snr, &c->templ, &c->sums, &c->wl1, &c->norms, &c->norm_part, &c->win_w, &c->win_m,
-                     &c->tw_y, &c->tw_x, &c->blk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
+                     &c->tw_y, &c->tw_x, &c->blk, &c->cblk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg};
@@ -187,6 +187,8 @@ extern "C" int sc_set_option(sc_ctx* ctx, const char* name, double value) {
         if (!(value >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "spectra_mb must be >= 0");
         ctx->spec_mb = value;
         fft_spectra_forget(ctx);
+    } else if (!strcmp(name, "fuse_fwd")) {
+        ctx->fuse_fwd = value != 0.0;
     } else if (!strcmp(name, "y_gb")) {
         if (!(value >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "y_gb must be >= 0");
         ctx->y_gb = value;
@@ -224,7 +226,7 @@ extern "C" void sc_destroy(sc_ctx* c) {
     DevBuf* arr[] = {&c->z, &c->xaxis, &c->yaxis, &c->A, &c->B, &c->C, &c->curv,
                      &c->best_snr, &c->best_amp, &c->best_id, &c->map_amp,
                      &c->map_snr, &c->templ, &c->sums, &c->wl1, &c->norms, &c->norm_part, &c->win_w, &c->win_m,
-                     &c->tw_y, &c->tw_x, &c->blk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
+                     &c->tw_y, &c->tw_x, &c->blk, &c->cblk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg};

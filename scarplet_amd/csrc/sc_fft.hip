@@ -3,7 +3,8 @@
 // Data flow for one orientation (all templates of the orientation share it):
 //
 //   F1c  k_fwd_rows_curv    curvature of TWO tiles packed as re/im  -> row FFT
-//   F2   k_fwd_cols         column FFT -> uc, uc2 (spectra of curv, curv^2)
+//   F2   k_fwd_cols         column FFT -> uc, uc2 (spectra of curv, curv^2); option "fuse_fwd":
+//                           not launched - k_inv_cols_w8 / _w4 transform the columns they park
 //   F1t  k_fwd_rows_templ   template tile v = alpha*W + iM          -> row FFT
 //   F2   k_fwd_cols         column FFT -> vh
 //   S    k_split_templ_sym  Scarp / Ricker: FFT(W) = {i} a P, FFT(M) = b P with a, b
@@ -1600,7 +1601,7 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
                  int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
                  int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
                  float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
-                 const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl) {
+                 const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl, const bool fwd) {
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     constexpr int S = TY / 16;                 // 16-point sets per line
     static_assert(S % 64 == 0 && S / 64 <= 2, "one wave per line: 64 or 128 sets");
@@ -1697,21 +1698,121 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
         const float2* xcol = (pl ? uc2 : uc) + (size_t)pair * plane + (size_t)ft * TY;
         const float* hsrc = (pl ? mb : wa) + (size_t)vfirst * hplane + (size_t)fs * TY;
         const bool rot = pl == 0 && parity == 1;          // odd W: factor i (own columns) / -i (mirrors)
-        // ---- park X P {i} of the lane's cells (the arithmetic of k_inv_cols_sym, cell for cell)
         float2 xp[NK];
+        // ---- park X P {i} of the lane's cells, cell k from get(k) (the arithmetic of k_inv_cols_sym, cell for cell)
+        auto park = [&](auto get) {
 #pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int fy = lane + 64 * k;
-            float2 pv;
-            if (!MIRROR) {
-                pv = phase_tab(tw + TY, phx, fy, ft);
-            } else {
-                pv = phase_tab(tw + TY, phx, (TY - fy) & (TY - 1), (Tx - ft) & (Tx - 1));
-                pv.y = -pv.y;
+            for (int k = 0; k < NK; ++k) {
+                const int fy = lane + 64 * k;
+                float2 pv;
+                if (!MIRROR) {
+                    pv = phase_tab(tw + TY, phx, fy, ft);
+                } else {
+                    pv = phase_tab(tw + TY, phx, (TY - fy) & (TY - 1), (Tx - ft) & (Tx - 1));
+                    pv.y = -pv.y;
+                }
+                float2 v = cmul(get(k), pv);
+                if (rot) v = MIRROR ? make_float2(v.y, -v.x) : make_float2(-v.y, v.x);
+                xp[k] = v;
             }
-            float2 v = cmul(xcol[fy], pv);
-            if (rot) v = MIRROR ? make_float2(v.y, -v.x) : make_float2(-v.y, v.x);
-            xp[k] = v;
+        };
+        if (fwd) {
+            // ---- F2 here (option "fuse_fwd"): `uc` is the forward row pass's output - blocked, plane 2 pair + {curv,
+            // curv^2} - and the column transform k_fwd_cols would have run on it is run on the eight (four) columns this
+            // workgroup is about to park: one launch and one pass over memory less per orientation.  The workgroup's
+            // columns are whole 128-byte lines of every row block (two side by side, or one): all lanes fill the eight
+            // lines, then every wave transforms its own in place - stage 1 from the line, stages 2 -> 3 across lanes as
+            // in the template loop.  Butterflies, twiddle bases and operand order are those of fft4_lines<TY, false>,
+            // which k_fwd_cols runs: the parked cells have the bits uc / uc2 would have held.
+            constexpr int CH = 4 * NC;                           // cells of a row block that are this workgroup's
+            constexpr int EP = TY / 128;                         // 16-byte loads per lane: NC TY cells over 64 NC lanes
+            {
+                // lane t takes the cells 2 t, 2 t + 1 of every 128 NC: the same two columns of row block t / (2 NC) + 32 u
+                // (addresses from a thread id the compiler cannot trace: traced, the sixteen of them are formed once for
+                //  both planes and kept - spilled - across the template loop, a scratch reload in front of every load)
+                int tid = threadIdx.x;
+                asm volatile("" : "+v"(tid));
+                const int i = (2 * tid) % CH, rb = (2 * tid) / CH;
+                const float2* src = uc + (size_t)(2 * pair + pl) * plane + (size_t)B * CH + (size_t)rb * (Tx >> 2) * 16 + i;
+                const size_t step = (size_t)32 * (Tx >> 2) * 16;
+                float2* dst = sm + (4 * (i >> 4) + (i & 3)) * LINE + ph(4 * rb + ((i >> 2) & 3));
+                float4 x[EP];
+#pragma unroll
+                for (int u = 0; u < EP; ++u) x[u] = *reinterpret_cast<const float4*>(src + u * step);
+#pragma unroll
+                for (int u = 0; u < EP; ++u) {                   // (128 rows on: 136 padded cells)
+                    dst[u * 136] = make_float2(x[u].x, x[u].y);
+                    dst[u * 136 + LINE] = make_float2(x[u].z, x[u].w);
+                }
+            }
+            lds_barrier();                                       // the lines are filled (and the twiddle tables written)
+            int lt = lane;
+            asm volatile("" : "+v"(lt));
+            float2 wq[4];
+            float2 a[U][16];
+#pragma unroll
+            for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
+            asm volatile("" ::: "memory");                       // (the whole line is in registers before stage 1 writes to it)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#if SC_I1_TWTAB
+                set_compute_store<TY, 16, 0, false, true>(line, lt + 64 * u, a[u], wq, t1 + lt + 64 * u, S);
+#else
+                tw_of(t1, S, lt + 64 * u, wq);
+                set_compute_store<TY, 16, 0, false, false, true>(line, lt + 64 * u, a[u], wq);
+#endif
+            }
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
+            if constexpr (SC_I1_XLANE) {
+                float2 o2[U][16];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#if SC_I1_TWTAB
+                    set_compute_regs<false, true>(a[u], wq, o2[u], t2 + ((lt + 64 * u) >> 4), S / 16);
+#else
+                    tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
+                    set_compute_regs<false>(a[u], wq, o2[u]);
+#endif
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+#pragma unroll
+                    for (int mh = 0; mh < 4; ++mh) {
+                        xlane_transpose4(o2[u][4 * mh].x, o2[u][4 * mh + 1].x, o2[u][4 * mh + 2].x, o2[u][4 * mh + 3].x);
+                        xlane_transpose4(o2[u][4 * mh].y, o2[u][4 * mh + 1].y, o2[u][4 * mh + 2].y, o2[u][4 * mh + 3].y);
+                    }
+                constexpr int R3x = TY / 256, NB3 = 16 / R3x;
+#pragma unroll
+                for (int u3 = 0; u3 < U; ++u3)
+#pragma unroll
+                    for (int b = 0; b < NB3; ++b)
+#pragma unroll
+                        for (int j = 0; j < R3x; ++j) a[u3][b + NB3 * j] = o2[j >> 2][4 * (u3 + U * b) + (j & 3)];
+            } else {
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#if SC_I1_TWTAB
+                    set_compute_store<TY, 16, 4, false, true>(line, lt + 64 * u, a[u], wq, t2 + ((lt + 64 * u) >> 4), S / 16);
+#else
+                    tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
+                    set_compute_store<TY, 16, 4, false, false, true>(line, lt + 64 * u, a[u], wq);
+#endif
+                }
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
+                asm volatile("" ::: "memory");
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) set_compute_store<TY, TY / 256, 8, false, false, true>(line, lt + 64 * u, a[u], wq);
+            asm volatile("" ::: "memory");
+            // natural order out: the lane's cells fy = lane + 64 k, as the spectrum layout gave them
+            park([&](int k) { return lds_cell<true>(line + ph(lt + 64 * k)); });
+        } else {
+            park([&](int k) { return xcol[lane + 64 * k]; });
         }
         // coefficient of cell fy: a[fs][fy], mirrors a[fs][-fy mod TY] = a[fs][TY - lane - 64 k] but for
         // fy = 0 - one base per lane and compile-time offsets either way
@@ -1870,7 +1971,7 @@ k_inv_cols_w8(const float2* __restrict__ uc, const float2* __restrict__ uc2,
               int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
               int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
               float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
-              const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl, int jil) {
+              const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl, int jil, int fwd) {
     // jil jobs (tile pairs of one orientation) interleaved along x: the 16 workgroups of eight column blocks and their
     // mirrors are followed by the same 16 of the next job, so that the workgroups which stream the SAME coefficient
     // lines - they do not depend on the tile pair - run on one XCD at the same time, 2 jil of them per column block
@@ -1880,10 +1981,10 @@ k_inv_cols_w8(const float2* __restrict__ uc, const float2* __restrict__ uc2,
     TAKE_TEMPLATE_SHARE(PT, (size_t)TY * Tx)
     if ((j >> 3) & 1)
         inv_cols_w8_body<TY, true, PT, 8>((Tx >> 3) - 1 - i, jobx, uc, uc2, wa, mb, Tx, pair, vfirst, G, rp_lo,
-                                   rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl);
+                                   rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl, fwd != 0);
     else
         inv_cols_w8_body<TY, false, PT, 8>(i, jobx, uc, uc2, wa, mb, Tx, pair, vfirst, G, rp_lo,
-                                    rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl);
+                                    rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl, fwd != 0);
 }
 
 // The same with FOUR columns and four waves per workgroup, one wave per SIMD: a wave may then use
@@ -1898,14 +1999,14 @@ k_inv_cols_w4(const float2* __restrict__ uc, const float2* __restrict__ uc2,
               int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
               int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
               float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
-              const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl) {
+              const TileDev* __restrict__ tiles, int py_valid, const TemplDev* __restrict__ tl, int fwd) {
     const int j = blockIdx.x, i = ((j >> 4) << 3) | (j & 7);
     if ((j >> 3) & 1)
         inv_cols_w8_body<TY, true, PT, 4>((Tx >> 2) - 1 - i, (int)blockIdx.y, uc, uc2, wa, mb, Tx, pair, vfirst, G, rp_lo,
-                                          rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl);
+                                          rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl, fwd != 0);
     else
         inv_cols_w8_body<TY, false, PT, 4>(i, (int)blockIdx.y, uc, uc2, wa, mb, Tx, pair, vfirst, G, rp_lo,
-                                           rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl);
+                                           rp_hi, phx, parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid, tl, fwd != 0);
 }
 
 // ---- I1 at column length 512: HALF a wave per column (round 5) --------------------------------------
@@ -3190,6 +3291,15 @@ static int upload_twiddles(sc_ctx* ctx, DevBuf& buf, int& have, int T, int kph) 
 
 static int npairs_of(const FftGeom& fg) { return (fg.ntiles + 1) / 2; }
 
+// Option "fuse_fwd": may the curvature's forward column transform be left to the inverse column pass?  Where that
+// pass is the wave-per-column one (fft_inverse_fold's `w8`, but for the templates' parity, which is not known yet)
+// and no spectra are kept across searches (kept spectra are uc / uc2).  A chunk that takes another column kernel
+// after all - generic templates, single-template maps - has fft_inverse_fold run k_fwd_cols first.
+static bool fft_fuse_curv(const sc_ctx* ctx, const FftGeom& fg, int slots) {
+    return ctx->fuse_fwd && slots == 0 && (fg.Ty == 2048 || fg.Ty == 1024) && (fg.Tx / 16) % 8 == 0 &&
+           ctx->variant != 1 && ctx->variant != 2 && ctx->variant != 6 && ctx->variant != 8;
+}
+
 void fft_spectra_forget(sc_ctx* ctx) {
     std::fill(ctx->spec_key.begin(), ctx->spec_key.end(), NAN);
 }
@@ -3262,8 +3372,14 @@ int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, in
         }
         const void *p0 = ctx->uc.p, *p1 = ctx->uc2.p, *p2 = ctx->norms.p;
         if ((rc = sc_ensure(ctx, ctx->norms, sizeof(double) * 2 * np * have))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->uc, plane * np * have))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->uc2, plane * np * have))) return rc;
+        if (fft_fuse_curv(ctx, fg, slots)) {
+            // (uc / uc2 are allocated by the chunk that needs them, if one does: fft_inverse_fold)
+            if ((rc = sc_ensure(ctx, ctx->cblk, plane * 2 * np * nb))) return rc;
+        } else {
+            if ((rc = sc_ensure(ctx, ctx->uc, plane * np * have))) return rc;
+            if ((rc = sc_ensure(ctx, ctx->uc2, plane * np * have))) return rc;
+        }
+        ctx->curv_rows = 0;
         if (!keep || slots != ctx->spec_slots || memcmp(sig, ctx->spec_sig, sizeof(sig)) != 0 ||
             p0 != ctx->uc.p || p1 != ctx->uc2.p || p2 != ctx->norms.p) {
             ctx->spec_key.assign((size_t)3 * slots, NAN);
@@ -3359,7 +3475,7 @@ static int set_lds(sc_ctx* ctx, K kernel, size_t bytes) {
         default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "tile size %d", T);  \
     }
 
-static int launch_fwd_cols(sc_ctx* ctx, const FftGeom& fg, int nplanes,
+static int launch_fwd_cols(sc_ctx* ctx, const FftGeom& fg, const float2* in, int nplanes,
                            float2* out0, float2* out1, int split2,
                            const TemplDev* templ = nullptr) {
     size_t lds = fft_lds_bytes(fg.Ty);
@@ -3370,7 +3486,7 @@ static int launch_fwd_cols(sc_ctx* ctx, const FftGeom& fg, int nplanes,
         int rc = set_lds(ctx, k_fwd_cols<T>, lds);                             \
         if (rc) return rc;                                                     \
         hipLaunchKernelGGL(k_fwd_cols<T>, grid, dim3(fft_threads(T)), lds,     \
-                           ctx->stream, (const float2*)ctx->blk.p, fg.Tx,      \
+                           ctx->stream, in, fg.Tx,                             \
                            (const float2*)ctx->tw_y.p, out0, out1, split2,     \
                            templ);                                             \
     }
@@ -3387,6 +3503,9 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
     int np = npairs_of(fg);
     size_t lds = fft_lds_bytes(fg.Tx);
     dim3 grid(fg.Ty / 4 / FWD_ROWS_RBW, np * nb);
+    // fused form: the row spectra go to cblk and stay there for the orientations' column-pass launches
+    const bool fuse = fft_fuse_curv(ctx, fg, ctx->spec_slots);
+    float2* rows_out = (float2*)(fuse ? ctx->cblk.p : ctx->blk.p);
     CurvMix mixc;
     memset(&mixc, 0, sizeof(mixc));
     if (coef) {
@@ -3403,7 +3522,7 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
                            lds, ctx->stream, (const float*)(MIXV ? ctx->A.p : ctx->curv.p), \
                            (const float*)ctx->B.p, (const float*)ctx->C.p, mixc, \
                            ctx->g, (const TileDev*)ctx->tiles.p, fg.Ty,        \
-                           (const float2*)ctx->tw_x.p, (float2*)ctx->blk.p,    \
+                           (const float2*)ctx->tw_x.p, rows_out,               \
                            (double*)ctx->norm_part.p, ctx->dbg, np,            \
                            (size_t)ctx->g.ly * ctx->g.lx);                     \
     }
@@ -3415,7 +3534,9 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
                        (const double*)ctx->norm_part.p, fg.Ty / 4, (double*)ctx->norms.p + ctx->norms_off);
     sc_prof_end(ctx);
     SC_HIP(ctx, hipGetLastError());
-    return launch_fwd_cols(ctx, fg, 2 * np * nb, (float2*)ctx->uc.p + ctx->uc_off, (float2*)ctx->uc2.p + ctx->uc_off, 1);
+    ctx->curv_rows = fuse ? 2 * np * nb : 0;
+    if (fuse) return SC_OK;
+    return launch_fwd_cols(ctx, fg, rows_out, 2 * np * nb, (float2*)ctx->uc.p + ctx->uc_off, (float2*)ctx->uc2.p + ctx->uc_off, 1);
 }
 
 // Symmetric fast path (k_split_templ_sym / k_inv_cols_sym): all templates of the
@@ -3470,7 +3591,7 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
         SC_HIP(ctx, hipGetLastError());
         return SC_OK;
     }
-    int rc = launch_fwd_cols(ctx, fg, n, (float2*)ctx->vh.p, nullptr, 0,
+    int rc = launch_fwd_cols(ctx, fg, (const float2*)ctx->blk.p, n, (float2*)ctx->vh.p, nullptr, 0,
                              (const TemplDev*)ctx->templ.p + first);
     if (rc) return rc;
     size_t cells = half_plane(fg.Ty, fg.Tx);
@@ -3520,6 +3641,22 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
     const bool w8 = symx && ctx->variant != 2 && (fg.Ty == 2048 || fg.Ty == 1024) && (fg.Tx / 16) % 8 == 0;
     if (nb > 1 && (!fast || n > group || nb * n > SC_MAX_BATCH || n > SC_MAX_GROUP))
         return sc_fail(ctx, SC_ERR_INVALID, "orientation batching outside its conditions");
+    // The curvature's row spectra wait in cblk (fft_forward_curv, option "fuse_fwd"): the wave-per-column kernels
+    // transform the columns they park themselves.  Any other column kernel reads uc / uc2: k_fwd_cols after all,
+    // once, for this and every later chunk of the same orientations.
+    const bool fwd = ctx->curv_rows > 0 && w8 && ctx->variant != 1 && !to_maps;
+    if (ctx->curv_rows > 0 && !fwd) {
+        const size_t half = (size_t)fg.Ty * fg.Tx * sizeof(float2) * (ctx->curv_rows / 2);
+        int rc;
+        if ((rc = sc_ensure(ctx, ctx->uc, half))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->uc2, half))) return rc;
+        if ((rc = launch_fwd_cols(ctx, fg, (const float2*)ctx->cblk.p, ctx->curv_rows, (float2*)ctx->uc.p + ctx->uc_off,
+                                  (float2*)ctx->uc2.p + ctx->uc_off, 1)))
+            return rc;
+        ctx->curv_rows = 0;
+    }
+    const float2* const xc = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc.p + ctx->uc_off;
+    const float2* const xc2 = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc2.p + ctx->uc_off;
     // One chunk = pc tile pairs through I1 and I2, group by group.  PTV: the chunk is a
     // single pair whose second tile is empty; templates ride in pairs instead (see
     // k_inv_cols_sym) - the symmetric I1 and the fast I2 know that mode.
@@ -3610,11 +3747,11 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
         if (rc) return rc;                                                     \
         const int nz_ = parts_for((long long)(fg.Tx / 8) * nb * pcc, 256LL * ((T == 1024 && !PTV) ? 2 : 1), NGl); \
         hipLaunchKernelGGL((k_inv_cols_w8<T, PTV>), dim3(fg.Tx / 8 * jilc, nb * pcc / jilc, nz_), dim3(512),  \
-                           w8_lds<T>(), ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, \
+                           w8_lds<T>(), ctx->stream, xc, xc2, \
                            (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
                            (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
                            np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py, \
-                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr, jilc); \
+                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr, jilc, fwd ? 1 : 0); \
     }
 #define FN_W4(T)                                                               \
     {                                                                          \
@@ -3623,11 +3760,11 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
         int rc = set_lds(ctx, k_inv_cols_w4<T, PTV>, lds4);                    \
         if (rc) return rc;                                                     \
         hipLaunchKernelGGL((k_inv_cols_w4<T, PTV>), dim3(fg.Tx / 4, nb * pcc), dim3(256),  \
-                           lds4, ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, \
+                           lds4, ctx->stream, xc, xc2, \
                            (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
                            (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
                            np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py, \
-                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr); \
+                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr, fwd ? 1 : 0); \
     }
 #define FN_SYM(T)                                                              \
     {                                                                          \

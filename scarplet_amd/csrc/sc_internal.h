@@ -115,6 +115,12 @@ struct sc_ctx {
     int tw_Ty = 0, tw_Tx = 0;
     int fft_pb = 1;            // tile pairs per inverse launch (fft_prepare)
     DevBuf blk, uc, uc2, vh, wh, mh, yw, ym, tiles;
+    // sc_set_option "fuse_fwd": the wave-per-column pass (k_inv_cols_w8 / w4) runs the curvature's forward column
+    // transform on the columns it parks; the forward row pass then writes to cblk - a region of its own, blk is
+    // overwritten by the templates' row pass - and k_fwd_cols, uc and uc2 are not needed (sc_fft.hip, fft_forward_curv)
+    int fuse_fwd = 1;
+    DevBuf cblk;
+    int curv_rows = 0;         // planes of cblk that hold the current orientations' row spectra and are not in uc / uc2 (0: uc / uc2 hold them)
     std::vector<WindowSlot> windows;
     // host copies of what a search uploads asynchronously (descriptors, sums, tile list): they must outlive
     // the copy, so they live here - no stream synchronisation between the upload and the launches
