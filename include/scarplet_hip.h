@@ -372,6 +372,55 @@ int sc_trace_result(sc_ctx* ctx, const double* param_of_id, const double* angle_
 /* the first n rows (n <= K) of the last trace's table */
 int sc_trace_segments(sc_ctx* ctx, sc_segment* out, long long n);
 
+/*
+ * Scarp-profile dating across a trace (docs/profiles.md): for each of K cells an elevation profile is cut across the
+ * strike, z(s) = c0 + b s + a erf(s / (2 sqrt(kt))) is fitted to it for every age of a grid, and the best age, its
+ * coefficients and the interval of ages the data do not tell apart come back as one sc_profile_fit.  The window of
+ * the Scarp template is the second derivative of that erf, so `a` estimates what the amp plane of a search estimates.
+ *   cells   K linear indices r * nx + c;  sa, ca: sin and cos of the cell's orientation (as sc_get_result's angle
+ *           plane gives it), evaluated by the caller: the profile runs along (row, col) = (-sa, ca), the strike
+ *           along (ca, sa)
+ *   samples for j = -h..h, k = -w..w: rr = r + (k ca - j sa), cc = c + (j ca + k sa); inside when 0 <= rr <= ny - 1
+ *           and 0 <= cc <= nx - 1; bilinear between the four cells around it (r0 = min(floor rr, ny - 2), likewise
+ *           c0); valid when inside and finite.  p_j = mean of the valid samples in ascending k, s_j = j de; j is a
+ *           valid point when one k is
+ *   fit     the cell is fitted when at least min_samples valid points lie on either side of j = 0; else status 1,
+ *           kt_index -1 and NaN in every float field.  For every age least squares of p on (1, s, erf(s / (2
+ *           sqrt(kt_i)))) over the valid points (columns orthogonalised, never normal equations on raw s);
+ *           sse_i = sum of the squared explicit residuals; kt_index = argmin, ties to the smallest index
+ *   interval thr = sse_min (1 + delta / (n - 3)); lo_index walks down from kt_index while sse[lo_index - 1] <= thr,
+ *           hi_index up likewise; status gains 2 where lo_index == 0 and 4 where hi_index == A - 1
+ * out_rows: K rows in the order of the cells (repeats allowed); out_sse: K x A float64 or NULL.  Every sum runs in a
+ * fixed order: the same bytes on every run.  SC_ERR_INVALID: a cell outside the grid, sa / ca not finite, ages not
+ * finite, not positive or not strictly increasing, A < 1, h < 1, w < 0, min_samples < 2 or > h, delta < 0 or not
+ * finite, de not finite or <= 0, ny or nx < 2.  SC_ERR_UNSUPPORTED: A > SC_PROFILE_MAX_AGES, h > SC_PROFILE_MAX_HALF,
+ * w > SC_PROFILE_MAX_SWATH, K > 2^31 - 1, a context that holds a block of a larger grid.  The buffers are the call's
+ * own: the record, the result planes, the kept spectra, the trace and fill buffers are not touched.  Timed as
+ * SC_K_PROFILE.
+ */
+#define SC_PROFILE_MAX_AGES  64
+#define SC_PROFILE_MAX_HALF  1024
+#define SC_PROFILE_MAX_SWATH 32
+typedef struct sc_profile_fit {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  n;               /* valid points of the profile                     */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;   /* the interval, as indices of the age grid   */
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) */
+    double   kt, kt_lo, kt_hi;
+    double   a, b, c0;        /* of the best age: the scarp's offset is 2 a      */
+    double   sse, rmse;       /* rmse = sqrt(sse / (n - 3))                      */
+} sc_profile_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_profiles(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                    const double* ages, int A, int h, int w, double de, double delta, int min_samples,
+                    sc_profile_fit* out_rows, double* out_sse);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own: the context's DEM, if it has
+ * one, stays as it is */
+int sc_fit_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                        const double* ca, long long K, const double* ages, int A, int h, int w, double de,
+                        double delta, int min_samples, sc_profile_fit* out_rows, double* out_sse);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -501,7 +550,8 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_COUNT       10
+#define SC_K_PROFILE     10     /* sc_fit_profiles / sc_fit_profiles_dem: the table and the fit of every chunk of cells */
+#define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);
 int sc_profile_get(sc_ctx* ctx, int kernel, long long* launches,

@@ -23,8 +23,9 @@ COMM_ID_BYTES = 128
 KIND_WINDOW = 2             # SC_KIND_WINDOW: a template whose window the host uploaded (sc_upload_window)
 
 K_NAMES = ("k_curv", "k_windows", "k_direct", "k_fwd_rows", "k_fwd_cols",
-           "k_inv_cols", "k_inv_rows", "k_settle", "k_noise", "k_trace")
-K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE, K_NOISE, K_TRACE = range(10)
+           "k_inv_cols", "k_inv_rows", "k_settle", "k_noise", "k_trace", "k_profile")
+(K_CURV, K_WINDOWS, K_DIRECT, K_FWD_ROWS, K_FWD_COLS, K_INV_COLS, K_INV_ROWS, K_SETTLE, K_NOISE, K_TRACE,
+ K_PROFILE) = range(11)
 NOISE_MAX_RADIUS = 1048576  # SC_NOISE_MAX_RADIUS: the largest filter radius sc_curvature_noise takes
 
 XFER_RECV, XFER_SEND, XFER_LOCAL = 0, 1, 2
@@ -78,6 +79,21 @@ SEGMENT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment._fields_],
                           + [np.float64] * 10,
                           "offsets": [getattr(sc_segment, f).offset for f, _ in sc_segment._fields_],
                           "itemsize": C.sizeof(sc_segment)})
+
+
+class sc_profile_fit(C.Structure):
+    """One row of sc_fit_profiles / sc_fit_profiles_dem (docs/profiles.md)."""
+    _fields_ = [("cell", C.c_int64), ("n", C.c_int32), ("kt_index", C.c_int32), ("lo_index", C.c_int32),
+                ("hi_index", C.c_int32), ("status", C.c_int32),
+                ("kt", C.c_double), ("kt_lo", C.c_double), ("kt_hi", C.c_double),
+                ("a", C.c_double), ("b", C.c_double), ("c0", C.c_double), ("sse", C.c_double), ("rmse", C.c_double)]
+
+
+PROFILE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fit._fields_],
+                          "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8,
+                          "offsets": [getattr(sc_profile_fit, f).offset for f, _ in sc_profile_fit._fields_],
+                          "itemsize": C.sizeof(sc_profile_fit)})
+PROFILE_MAX_AGES, PROFILE_MAX_HALF, PROFILE_MAX_SWATH = 64, 1024, 32   # SC_PROFILE_MAX_*
 
 
 class sc_xfer(C.Structure):
@@ -146,6 +162,10 @@ SIGNATURES = {
     "sc_trace_result": (C.c_int, [_P, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_longlong, _bp,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_longlong)]),
     "sc_trace_segments": (C.c_int, [_P, C.c_void_p, C.c_longlong]),
+    "sc_fit_profiles": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
+                                  C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    "sc_fit_profiles_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
+                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -454,6 +474,27 @@ class Context(object):
         return self._trace_out(self.core_shape(), lambda t, l, k: self.lib.sc_trace_result(
             self._h, _as(par, _dp), _as(ang, _dp), len(par), float(snr_low), float(snr_high), int(min_cells), t, l, k),
             "sc_trace_result")
+
+    # -- scarp-profile dating (docs/profiles.md) ------------------------------------
+    def fit_profiles(self, cells, sa, ca, ages, h, w, de, delta, min_samples, curve=False, z=None):
+        """sc_fit_profiles on the context's DEM, or sc_fit_profiles_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A = len(cells), len(ages)
+        assert len(sa) == K and len(ca) == K
+        rows = np.zeros(K, dtype=PROFILE_DTYPE)
+        sse = np.empty((K, A), dtype=np.float64) if curve else None
+        tail = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h),
+                int(w), float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p),
+                _as(sse, _dp) if curve else None]
+        if z is None:
+            self._check(self.lib.sc_fit_profiles(self._h, *tail), "sc_fit_profiles")
+        else:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            self._check(self.lib.sc_fit_profiles_dem(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail),
+                        "sc_fit_profiles_dem")
+        return rows, sse
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

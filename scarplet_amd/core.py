@@ -876,6 +876,30 @@ class Matcher(object):
             par, ang = self._id_par, self._id_ang
         return traces._traces(*self.ctx.trace_result(par, ang, lo, hi, mc))
 
+    def fit_profiles(self, traces_or_cells, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
+                     return_curve=False, angle=None):
+        """``sl.fit_profiles`` on the DEM this matcher holds on the device (docs/profiles.md) - no upload.  Given
+        the ``Traces`` of ``extract_traces`` it fits the cells of the segments (``labels > 0``, row-major order) with
+        the angle plane of this matcher's result and adds a ``label`` column; given cells (as ``sl.fit_profiles``
+        takes them) it reads that plane at the cells unless ``angle`` says otherwise.  The bytes are those of
+        ``sl.fit_profiles`` on the same data."""
+        from scarplet_amd import profiles, traces
+        if not getattr(self, "whole", False):
+            raise ValueError("fit_profiles needs the whole DEM on the device, not a block of it")
+        label = None
+        cells = traces_or_cells
+        if isinstance(traces_or_cells, traces.Traces):
+            labels = np.asarray(traces_or_cells.labels)
+            if labels.shape != (self.ny, self.nx):
+                raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
+            cells = np.flatnonzero(labels.ravel() > 0)
+            label = labels.ravel()[cells]
+        if angle is None:
+            angle = self.result_array()[2]
+        args = profiles.check_args((self.ny, self.nx), self.de, cells, angle, half_length, swath, ages, delta,
+                                   min_samples)
+        return profiles._run(self.ctx, args, self.nx, return_curve, label=label)
+
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one
         sl.match per scale on the same data, docs/source/examples/channels.ipynb - its 4-plane result has no scale

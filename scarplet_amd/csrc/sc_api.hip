@@ -47,7 +47,8 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->tw_y, &c->tw_x, &c->blk, &c->cblk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
-                     &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg};
+                     &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse};
     size_t s = 0;
     for (DevBuf* b : arr) s += b->cap;
     for (auto& w : c->windows) s += (size_t)w.h * w.wd * 13;
@@ -229,7 +230,8 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->tw_y, &c->tw_x, &c->blk, &c->cblk, &c->uc, &c->uc2, &c->vh, &c->wh, &c->mh,
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
-                     &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg};
+                     &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse};
     for (DevBuf* b : arr) buf_free(*b);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp[k]);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp_in[k]);
@@ -1166,7 +1168,7 @@ extern "C" int sc_profile_get(sc_ctx* ctx, int kernel, long long* launches, doub
 
 extern "C" const char* sc_kernel_name(int kernel) {
     static const char* names[SC_K_COUNT] = {"k_curv", "k_windows", "k_direct", "k_fwd_rows",
-                                            "k_fwd_cols", "k_inv_cols", "k_inv_rows", "k_settle", "k_noise", "k_trace"};
+                                            "k_fwd_cols", "k_inv_cols", "k_inv_rows", "k_settle", "k_noise", "k_trace", "k_profile"};
     return (kernel >= 0 && kernel < SC_K_COUNT) ? names[kernel] : "?";
 }
 

@@ -189,6 +189,9 @@ struct sc_ctx {
     // sums and totals, the radix sort's keys / values (two of each) and histograms, the segment table
     DevBuf tr_planes, tr_thin, tr_par, tr_lab, tr_cnt, tr_bsum, tr_tot, tr_sort, tr_hist, tr_rbsum, tr_seg;
     long long tr_k = 0;        // segments of the last trace
+    // sc_fit_profiles*: the call's own buffers - an uploaded DEM (the _dem call), cells, (sa, ca), ages, the erf
+    // table, the rows and the sse curves of one chunk of cells
+    DevBuf pf_z, pf_cells, pf_dir, pf_ages, pf_tab, pf_rows, pf_sse;
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);

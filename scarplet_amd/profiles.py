@@ -1,0 +1,192 @@
+"""Scarp-profile dating across a trace, on the device (docs/profiles.md).
+
+``sl.match`` finds per cell the curvature template that fits best, ``sl.extract_traces`` turns that into lines.
+``fit_profiles`` is the classical check of morphologic dating on such a line: an elevation profile is cut across
+the trace at each cell, the diffusion scarp ``z(s) = c0 + b s + a erf(s / (2 sqrt(kt)))`` is fitted to it for every
+age of a grid, and the best age, the offset ``2 a``, the far-field slope ``b`` and the interval of ages the profile
+does not tell apart come back as one row per cell (sc_fit_profiles, include/scarplet_hip.h) - instead of a Python
+loop of ``map_coordinates`` and ``lstsq`` over the cells.
+"""
+import math
+import operator
+
+import numpy as np
+
+from scarplet_amd import _lib, _plan
+
+MAX_CELLS = 2 ** 31 - 1
+
+# the table as Python returns it: where the cell lies, the library's row, the scarp's offset
+FIT_FIELDS = [("row", np.int64), ("col", np.int64)] + \
+    [(f, _lib.PROFILE_DTYPE.fields[f][0]) for f in _lib.PROFILE_DTYPE.names] + [("height", np.float64)]
+FIT_DTYPE = np.dtype(FIT_FIELDS)
+
+
+def _number(x, name):
+    if isinstance(x, (bool, np.bool_)):
+        raise ValueError("%s must be a number" % name)
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number" % name)
+    if not math.isfinite(v):
+        raise ValueError("%s must be finite, got %r" % (name, x))
+    return v
+
+
+def _cells_of(cells, ny, nx):
+    """Linear indices (int64, 1-D) of ``cells``: linear indices, a (rows, cols) pair, or a bool plane."""
+    if isinstance(cells, tuple):
+        if len(cells) != 2:
+            raise ValueError("cells as a tuple must be (rows, cols)")
+        r, c = (np.asarray(v) for v in cells)
+        if r.shape != c.shape or r.ndim > 1:
+            raise ValueError("rows and cols of cells must be 1-D and of one length")
+        r, c = np.atleast_1d(r), np.atleast_1d(c)
+        for v in (r, c):
+            if v.size and v.dtype.kind not in "iu":
+                raise ValueError("rows and cols of cells must be integers")
+        if r.size and (r.min() < 0 or r.max() >= ny or c.min() < 0 or c.max() >= nx):
+            raise ValueError("cells outside the %d x %d grid" % (ny, nx))
+        return r.astype(np.int64) * nx + c.astype(np.int64)
+    arr = np.asarray(cells)
+    if arr.dtype == np.bool_:
+        if arr.shape != (ny, nx):
+            raise ValueError("a bool plane of cells must have the grid's shape %r, got %r" % ((ny, nx), arr.shape))
+        return np.flatnonzero(arr.ravel()).astype(np.int64)
+    if arr.ndim > 1:
+        raise ValueError("cells must be 1-D linear indices, a (rows, cols) tuple or a bool plane")
+    arr = np.atleast_1d(arr)
+    if arr.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if arr.dtype.kind not in "iu":
+        raise ValueError("cells must be integers, got %s" % arr.dtype)
+    if arr.min() < 0 or arr.max() >= ny * nx:
+        raise ValueError("cells outside the %d x %d grid" % (ny, nx))
+    return np.ascontiguousarray(arr, dtype=np.int64)
+
+
+def _angles_of(angle, idx, ny, nx):
+    """One orientation per cell (float64): a scalar, one per cell, or an (ny, nx) plane read at the cells."""
+    try:
+        a = np.asarray(angle, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("angle must be a number, one number per cell or an (ny, nx) plane")
+    if a.ndim == 0:
+        a = np.full(len(idx), float(a))
+    elif a.ndim == 2:
+        if a.shape != (ny, nx):
+            raise ValueError("an angle plane must have the grid's shape %r, got %r" % ((ny, nx), a.shape))
+        a = a.ravel()[idx]
+    elif a.ndim != 1 or len(a) != len(idx):
+        raise ValueError("angle must be a number, one number per cell (%d) or an (ny, nx) plane" % len(idx))
+    if not np.all(np.isfinite(a)):
+        raise ValueError("angle must be finite at every cell")
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def check_args(shape, de, cells, angle, half_length, swath, ages, delta, min_samples):
+    """(cells, sa, ca, ages, h, w, delta, min_samples) validated and normalised for the library; ValueError
+    otherwise.  ``half_length`` and ``swath`` are in data units: h = floor(half_length / de), w = floor(swath / de)."""
+    ny, nx = (int(v) for v in shape)
+    if ny < 2 or nx < 2:
+        raise ValueError("the grid must be at least 2 x 2, got %d x %d" % (ny, nx))
+    de = _number(de, "the cell size")
+    if de <= 0:
+        raise ValueError("the cell size must be > 0")
+    idx = _cells_of(cells, ny, nx)
+    if len(idx) > MAX_CELLS:
+        raise ValueError("%d cells: more than 2^31 - 1" % len(idx))
+    a = _angles_of(angle, idx, ny, nx)
+    hl, sw = _number(half_length, "half_length"), _number(swath, "swath")
+    if hl < 0 or sw < 0:
+        raise ValueError("half_length and swath must be >= 0")
+    h, w = int(math.floor(hl / de)), int(math.floor(sw / de))
+    if h < 2:
+        raise ValueError("half_length %r is %d cells of %r: at least 2 are needed" % (half_length, h, de))
+    if h > _lib.PROFILE_MAX_HALF:
+        raise ValueError("half_length %r is %d cells: more than %d" % (half_length, h, _lib.PROFILE_MAX_HALF))
+    if w > _lib.PROFILE_MAX_SWATH:
+        raise ValueError("swath %r is %d cells: more than %d" % (swath, w, _lib.PROFILE_MAX_SWATH))
+    if ages is None:
+        ages = _plan.age_grid()
+    try:
+        kt = np.atleast_1d(np.asarray(ages, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("ages must be numbers")
+    if kt.ndim != 1 or kt.size < 1:
+        raise ValueError("ages must be a non-empty 1-D sequence")
+    if kt.size > _lib.PROFILE_MAX_AGES:
+        raise ValueError("%d ages: more than %d" % (kt.size, _lib.PROFILE_MAX_AGES))
+    if not (np.all(np.isfinite(kt)) and np.all(kt > 0) and np.all(np.diff(kt) > 0)):
+        raise ValueError("ages must be finite, positive and strictly increasing")
+    d = _number(delta, "delta")
+    if d < 0:
+        raise ValueError("delta must be >= 0, got %r" % (delta,))
+    if isinstance(min_samples, (bool, np.bool_)):
+        raise ValueError("min_samples must be an integer")
+    try:
+        ms = operator.index(min_samples)
+    except TypeError:
+        raise ValueError("min_samples must be an integer, got %r" % (min_samples,))
+    if ms < 2 or ms > h:
+        raise ValueError("min_samples must lie in 2..%d (the half-length in cells), got %r" % (h, min_samples))
+    return idx, np.sin(a), np.cos(a), np.ascontiguousarray(kt), h, w, de, d, ms
+
+
+def _table(rows, nx, label=None):
+    """The library's rows -> the Python table (row, col, the row's fields, height = 2 a; ``label`` when given)."""
+    dt = FIT_DTYPE if label is None else np.dtype(FIT_FIELDS + [("label", np.int32)])
+    out = np.zeros(len(rows), dtype=dt)
+    for f in rows.dtype.names:
+        out[f] = rows[f]
+    out["row"] = rows["cell"] // nx
+    out["col"] = rows["cell"] % nx
+    out["height"] = 2.0 * rows["a"]
+    if label is not None:
+        out["label"] = label
+    return out
+
+
+def _dem_of(data):
+    """(z, de) of a DEMGrid or of anything with its two attributes - shapes checked before anything is copied."""
+    try:
+        z = np.asarray(data._griddata)
+        gi = data._georef_info
+        de = float(gi.dx)
+    except AttributeError:
+        raise ValueError("data must be a DEMGrid")
+    if z.ndim != 2:
+        raise ValueError("data._griddata must be a 2-D array")
+    return z, de
+
+
+def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4, return_curve=False,
+                 device=0):
+    """Fit the diffusion scarp to elevation profiles cut across the strike at ``cells`` (docs/profiles.md).
+
+    ``data``: the DEMGrid.  ``cells``: linear indices ``r * nx + c``, a ``(rows, cols)`` tuple, or a bool plane (its
+    true cells in row-major order).  ``angle``: the orientation as ``sl.match`` returns it - a scalar, one per cell,
+    or an (ny, nx) plane read at the cells; the profile runs along (row, col) = (-sin a, cos a).  ``half_length``
+    and ``swath`` (half-width of the band averaged along the strike) are in data units.  ``ages``: the kt grid,
+    strictly increasing (default: the search's, 10**0 .. 10**3.4).  For every cell and every age the profile is
+    fitted by ``c0 + b s + a erf(s / (2 sqrt(kt)))`` in float64; the age with the smallest sum of squared residuals
+    wins, and ``lo_index .. hi_index`` is the run of ages around it whose sse stays within
+    ``sse_min (1 + delta / (n - 3))``.  A cell with fewer than ``min_samples`` valid points on either side has
+    ``status`` 1 and NaN fields; ``status`` 2 / 4 flag an interval open at the young / old end of the grid.
+
+    Returns a structured array, one row per cell in input order: ``row, col, cell, n, kt_index, lo_index, hi_index,
+    status, kt, kt_lo, kt_hi, a, b, c0, sse, rmse, height`` (= 2 a) - and the (K, A) sse curves when
+    ``return_curve``.  The same bytes on every run."""
+    z, de = _dem_of(data)
+    args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    from scarplet_amd.core import _context
+    return _run(_context(device), args, z.shape[1], return_curve, z=z)
+
+
+def _run(ctx, args, nx, return_curve, z=None, label=None):
+    idx, sa, ca, kt, h, w, de, d, ms = args
+    rows, curve = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z)
+    out = _table(rows, nx, label)
+    return (out, curve) if return_curve else out
