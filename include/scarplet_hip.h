@@ -421,6 +421,67 @@ int sc_fit_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long
                         const double* ca, long long K, const double* ages, int A, int h, int w, double de,
                         double delta, int min_samples, sc_profile_fit* out_rows, double* out_sse);
 
+/*
+ * One scarp age per trace segment, fitted jointly (docs/segments.md): the K cells come grouped into S segments
+ * (seg_start[S + 1], a CSR array from 0 to K; seg_label[S], positive and strictly increasing), each cell's profile is
+ * sampled exactly as sc_fit_profiles samples it, and per segment and age ONE least-squares problem is solved over all
+ * its usable profiles: the amplitude a and the age are the segment's, every profile keeps an intercept c0_c and a
+ * slope b_c of its own (fixed effects).
+ *   usable   a profile with at least min_samples valid points on either side of j = 0 (the rule of sc_fit_profiles);
+ *            other cells count in n_cells only
+ *   per profile c and age i: sbar, pbar, ebar, beta, gamma, See_ci, Sep_ci as passes 0 to 2 of sc_fit_profiles form them
+ *   segment  a_i = (sum_c Sep_ci) / (sum_c See_ci); b_ci = beta_c - a_i gamma_ci; c0_ci = (pbar_c - a_i ebar_ci) -
+ *            b_ci sbar_c; sse_ci = sum_j of the squared explicit residuals; sse_i = sum_c sse_ci.  The sums over c
+ *            run over the usable profiles in input order: blocks of 64 consecutive ones summed in sequence from the
+ *            first, then the block sums in sequence from the first - a shape that depends on n_profiles alone, and
+ *            no addition at all for one profile
+ *   choice   n pooled valid points, dof = n - 2 n_profiles - 1; fitted when n_profiles >= min_profiles and dof >= 1,
+ *            else status 1, indices -1, NaN floats.  kt_index = argmin sse_i (ties to the smallest index), rmse =
+ *            sqrt(sse / dof), thr = sse_min (1 + delta / dof), lo_index / hi_index / status 2 and 4 as sc_fit_profiles
+ * A segment of one usable profile returns the kt_index, lo_index, hi_index, status, a, sse and rmse of sc_fit_profiles
+ * for that cell, bit for bit.  out_rows: S rows; out_cells: K rows in the order of the cells, or NULL; out_sse: S x A
+ * float64, or NULL.  No float atomics, every sum in a fixed order: the same bytes on every run.
+ * The profiles are sampled once and parked on the device between the two passes: with the per-age terms 8 ((2h + 1) +
+ * 4 A) bytes per cell.  A call runs in chunks of whole segments of at most SC_SEGMENT_MAX_PARK such bytes; a single
+ * segment that needs more is SC_ERR_UNSUPPORTED (1.5 million cells at h = 100 and 35 ages, 232 thousand at h = 1024
+ * and 64 ages) - this is the largest supported call, next to the limits of sc_fit_profiles (A, h, w, K <= 2^31 - 1,
+ * the whole grid on the context), which hold here too.  SC_ERR_INVALID: what sc_fit_profiles refuses, and seg_start
+ * not non-decreasing from 0 to K, S < 0, a label <= 0 or not above its predecessor, min_profiles < 1.  The buffers are
+ * the call's own: the record, the result planes, the kept spectra, the trace, fill and profile buffers are not
+ * touched.  Every kernel is timed under SC_K_PROFILE (there is no slot of its own).
+ */
+#define SC_SEGMENT_MAX_PARK (1ll << 32)
+typedef struct sc_segment_fit {
+    int32_t  label;
+    int32_t  n_cells;         /* cells of the segment                            */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n;               /* pooled valid points of the usable profiles      */
+    int32_t  dof;             /* n - 2 n_profiles - 1                            */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) */
+    double   kt, kt_lo, kt_hi;
+    double   a;               /* the segment's amplitude: its offset is 2 a      */
+    double   sse, rmse;       /* rmse = sqrt(sse / dof)                          */
+} sc_segment_fit;
+typedef struct sc_segment_cell {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  used;            /* 1: a usable profile                             */
+    int32_t  n;               /* valid points of the profile                     */
+    double   b, c0, sse;      /* at the segment's best age; NaN where not used or the segment is not fitted */
+} sc_segment_cell;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_segments(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                    const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                    int h, int w, double de, double delta, int min_samples, int min_profiles,
+                    sc_segment_fit* out_rows, sc_segment_cell* out_cells, double* out_sse);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                        const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                        long long S, const double* ages, int A, int h, int w, double de, double delta,
+                        int min_samples, int min_profiles, sc_segment_fit* out_rows, sc_segment_cell* out_cells,
+                        double* out_sse);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -550,7 +611,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles / sc_fit_profiles_dem: the table and the fit of every chunk of cells */
+#define SC_K_PROFILE     10     /* sc_fit_profiles* and sc_fit_segments*: the table and every kernel of every chunk of cells */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

@@ -96,6 +96,32 @@ PROFILE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fit._fields_],
 PROFILE_MAX_AGES, PROFILE_MAX_HALF, PROFILE_MAX_SWATH = 64, 1024, 32   # SC_PROFILE_MAX_*
 
 
+class sc_segment_fit(C.Structure):
+    """One row of sc_fit_segments / sc_fit_segments_dem (docs/segments.md)."""
+    _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n", C.c_int32),
+                ("dof", C.c_int32), ("kt_index", C.c_int32), ("lo_index", C.c_int32), ("hi_index", C.c_int32),
+                ("status", C.c_int32),
+                ("kt", C.c_double), ("kt_lo", C.c_double), ("kt_hi", C.c_double),
+                ("a", C.c_double), ("sse", C.c_double), ("rmse", C.c_double)]
+
+
+class sc_segment_cell(C.Structure):
+    """One cell of the cell table of sc_fit_segments / sc_fit_segments_dem."""
+    _fields_ = [("cell", C.c_int64), ("used", C.c_int32), ("n", C.c_int32),
+                ("b", C.c_double), ("c0", C.c_double), ("sse", C.c_double)]
+
+
+SEGMENT_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fit._fields_],
+                              "formats": [np.int32] * 9 + [np.float64] * 6,
+                              "offsets": [getattr(sc_segment_fit, f).offset for f, _ in sc_segment_fit._fields_],
+                              "itemsize": C.sizeof(sc_segment_fit)})
+SEGMENT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_cell._fields_],
+                               "formats": [np.int64, np.int32, np.int32] + [np.float64] * 3,
+                               "offsets": [getattr(sc_segment_cell, f).offset for f, _ in sc_segment_cell._fields_],
+                               "itemsize": C.sizeof(sc_segment_cell)})
+SEGMENT_MAX_PARK = 1 << 32                                             # SC_SEGMENT_MAX_PARK
+
+
 class sc_xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("kind", C.c_int32),
                 ("sy0", C.c_int32), ("sx0", C.c_int32),
@@ -166,6 +192,12 @@ SIGNATURES = {
                                   C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
     "sc_fit_profiles_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
                                       C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    "sc_fit_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                  C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                  C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_segments_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                      C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int,
+                                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -495,6 +527,33 @@ class Context(object):
             self._check(self.lib.sc_fit_profiles_dem(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail),
                         "sc_fit_profiles_dem")
         return rows, sse
+
+    # -- one age per trace segment (docs/segments.md) -------------------------------
+    def fit_segments(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
+                     cell_table=False, curve=False, z=None):
+        """sc_fit_segments on the context's DEM, or sc_fit_segments_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, cell table or None, curve or None).  cells and seg_start int64, seg_label int32, sa / ca / ages
+        float64, all 1-D and C-contiguous; the cells grouped by segment."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S = len(cells), len(ages), len(seg_label)
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
+        rows = np.zeros(S, dtype=SEGMENT_FIT_DTYPE)
+        tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE) if cell_table else None
+        sse = np.empty((S, A), dtype=np.float64) if curve else None
+        llp = C.POINTER(C.c_longlong)
+        tail = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), float(de),
+                float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
+        if z is None:
+            self._check(self.lib.sc_fit_segments(self._h, *tail), "sc_fit_segments")
+        else:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            self._check(self.lib.sc_fit_segments_dem(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail),
+                        "sc_fit_segments_dem")
+        return rows, tab, sse
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

@@ -900,6 +900,38 @@ class Matcher(object):
                                    min_samples)
         return profiles._run(self.ctx, args, self.nx, return_curve, label=label)
 
+    def fit_segments(self, traces, half_length, swath=0, ages=None, delta=1.0, min_samples=4, min_profiles=1,
+                     return_cells=False, return_curve=False, strike="cell"):
+        """``sl.fit_segments`` on the DEM this matcher holds on the device (docs/segments.md) - no upload: one age,
+        one amplitude and one interval per segment of ``traces`` (the ``Traces`` of ``extract_traces``), fitted
+        jointly to the profiles of all its cells.  One row per row of ``traces.segments``, in that order.
+        ``strike="cell"`` cuts each profile across the orientation this matcher's result has at the cell;
+        ``strike="segment"`` gives every cell of a segment that segment's ``strike`` from the table: parallel
+        profiles, sturdier where single-cell orientations are noisy.  The bytes are those of ``sl.fit_segments`` on
+        the same data."""
+        from scarplet_amd import segments, traces as tr
+        if not getattr(self, "whole", False):
+            raise ValueError("fit_segments needs the whole DEM on the device, not a block of it")
+        if not isinstance(traces, tr.Traces):
+            raise ValueError("traces must be the Traces of extract_traces")
+        if strike not in ("cell", "segment"):
+            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
+        labels = np.asarray(traces.labels)
+        if labels.shape != (self.ny, self.nx):
+            raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
+        cells = np.flatnonzero(labels.ravel() > 0)
+        lab = labels.ravel()[cells]
+        if strike == "segment":
+            seg = traces.segments
+            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
+                raise ValueError("the traces' table does not number the segments of its label plane")
+            angle = np.asarray(seg["strike"], dtype=np.float64)[lab - 1]
+        else:
+            angle = self.result_array()[2]
+        args = segments.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, ages, delta,
+                                   min_samples, min_profiles)
+        return segments._run(self.ctx, args, self.nx, return_cells, return_curve)
+
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one
         sl.match per scale on the same data, docs/source/examples/channels.ipynb - its 4-plane result has no scale

@@ -192,6 +192,13 @@ struct sc_ctx {
     // sc_fit_profiles*: the call's own buffers - an uploaded DEM (the _dem call), cells, (sa, ca), ages, the erf
     // table, the rows and the sse curves of one chunk of cells
     DevBuf pf_z, pf_cells, pf_dir, pf_ages, pf_tab, pf_rows, pf_sse;
+    // sc_fit_segments*: the call's own buffers - an uploaded DEM (the _dem call), ages and the erf table; per chunk of
+    // whole segments the cells, (sa, ca), each cell's segment, the CSR arrays of cells and of 64-profile blocks, the
+    // parked profiles, the per-cell scalars (n, used, sbar, pbar, beta) and per-cell-and-age planes (ebar, gamma,
+    // See - later the cell's sse -, Sep), the ranked list of usable cells, the block partials, the segment totals
+    // (See and Sep; sse), the counts, the rows, the cell table and the curves
+    DevBuf sg_z, sg_ages, sg_tab, sg_cells, sg_dir, sg_cseg, sg_start, sg_blk, sg_label, sg_prof, sg_int, sg_scal,
+        sg_age, sg_list, sg_part, sg_tot, sg_tsse, sg_cnt, sg_rows, sg_out, sg_sse;
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);
@@ -207,6 +214,26 @@ int sc_lds_attr(sc_ctx* ctx, const void* kernel, size_t bytes);
             return sc_fail(ctx, SC_ERR_HIP, "%s: %s (%s:%d)", #call,          \
                            hipGetErrorString(e__), __FILE__, __LINE__);       \
     } while (0)
+
+// sc_profile.hip, shared with sc_segment.hip: the argument checks of a profile call (`who` names the call in the
+// messages) and the launch of the erf table (d_ages on the device; timed as SC_K_PROFILE)
+int sc_pf_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const double* ages, int A, int h, int w, double de, double delta,
+                int min_samples, const void* out_rows);
+int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
+
+#ifdef __HIPCC__
+// one bilinear sample of docs/profiles.md; false where it is outside the grid or not finite
+__device__ __forceinline__ bool pf_sample(const double* __restrict__ z, int ny, int nx, double rr, double cc, double& v) {
+    if (!(rr >= 0.0 && rr <= (double)(ny - 1) && cc >= 0.0 && cc <= (double)(nx - 1))) return false;
+    const int r0 = min((int)floor(rr), ny - 2), c0 = min((int)floor(cc), nx - 2);
+    const double fr = rr - (double)r0, fc = cc - (double)c0;
+    const double* q = z + (size_t)r0 * nx + c0;
+    const double z00 = q[0], z01 = q[1], z10 = q[nx], z11 = q[nx + 1];
+    v = (z00 * (1.0 - fc) + z01 * fc) * (1.0 - fr) + (z10 * (1.0 - fc) + z11 * fc) * fr;
+    return isfinite(v);
+}
+#endif
 
 // profiling brackets around kernel launches
 void sc_prof_begin(sc_ctx* ctx, int kernel);

@@ -36,17 +36,6 @@ __global__ __launch_bounds__(256) void k_pf_table(const double* __restrict__ age
     }
 }
 
-// one bilinear sample of the definition; false where it is outside the grid or not finite
-__device__ __forceinline__ bool pf_sample(const double* __restrict__ z, int ny, int nx, double rr, double cc, double& v) {
-    if (!(rr >= 0.0 && rr <= (double)(ny - 1) && cc >= 0.0 && cc <= (double)(nx - 1))) return false;
-    const int r0 = min((int)floor(rr), ny - 2), c0 = min((int)floor(cc), nx - 2);
-    const double fr = rr - (double)r0, fc = cc - (double)c0;
-    const double* q = z + (size_t)r0 * nx + c0;
-    const double z00 = q[0], z01 = q[1], z10 = q[nx], z11 = q[nx + 1];
-    v = (z00 * (1.0 - fc) + z01 * fc) * (1.0 - fr) + (z10 * (1.0 - fc) + z11 * fc) * fr;
-    return isfinite(v);
-}
-
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict__ z, int ny, int nx,
                                                        const long long* __restrict__ cells,
@@ -196,29 +185,39 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict_
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int pf_check(sc_ctx* ctx, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
-                    long long K, const double* ages, int A, int h, int w, double de, double delta, int min_samples,
-                    const sc_profile_fit* out_rows) {
+// (shared with sc_fit_segments: `who` names the call in the messages)
+int sc_pf_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const double* ages, int A, int h, int w, double de, double delta,
+                int min_samples, const void* out_rows) {
     if (K < 0 || (K > 0 && (!cells || !sa || !ca || !out_rows)) || !ages)
-        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: null argument");
-    if (ny < 2 || nx < 2) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: the grid must be at least 2 x 2");
-    if (A < 1 || h < 1 || w < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: needs A >= 1, h >= 1, w >= 0");
-    if (A > SC_PROFILE_MAX_AGES) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: %d ages, more than %d", A, SC_PROFILE_MAX_AGES);
-    if (h > SC_PROFILE_MAX_HALF) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: half-length %d cells, more than %d", h, SC_PROFILE_MAX_HALF);
-    if (w > SC_PROFILE_MAX_SWATH) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: swath %d cells, more than %d", w, SC_PROFILE_MAX_SWATH);
-    if (K > (long long)INT_MAX) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: %lld cells, more than 2^31 - 1", K);
+        return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
+    if (ny < 2 || nx < 2) return sc_fail(ctx, SC_ERR_INVALID, "%s: the grid must be at least 2 x 2", who);
+    if (A < 1 || h < 1 || w < 0) return sc_fail(ctx, SC_ERR_INVALID, "%s: needs A >= 1, h >= 1, w >= 0", who);
+    if (A > SC_PROFILE_MAX_AGES) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: %d ages, more than %d", who, A, SC_PROFILE_MAX_AGES);
+    if (h > SC_PROFILE_MAX_HALF) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: half-length %d cells, more than %d", who, h, SC_PROFILE_MAX_HALF);
+    if (w > SC_PROFILE_MAX_SWATH) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: swath %d cells, more than %d", who, w, SC_PROFILE_MAX_SWATH);
+    if (K > (long long)INT_MAX) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: %lld cells, more than 2^31 - 1", who, K);
     if (min_samples < 2 || min_samples > h)
-        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: min_samples must lie in 2..h");
-    if (!(isfinite(delta) && delta >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: delta must be finite and >= 0");
-    if (!(isfinite(de) && de > 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: the cell size must be finite and > 0");
+        return sc_fail(ctx, SC_ERR_INVALID, "%s: min_samples must lie in 2..h", who);
+    if (!(isfinite(delta) && delta >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "%s: delta must be finite and >= 0", who);
+    if (!(isfinite(de) && de > 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "%s: the cell size must be finite and > 0", who);
     for (int i = 0; i < A; ++i)
         if (!(isfinite(ages[i]) && ages[i] > 0.0 && (i == 0 || ages[i] > ages[i - 1])))
-            return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: ages must be finite, positive and strictly increasing");
+            return sc_fail(ctx, SC_ERR_INVALID, "%s: ages must be finite, positive and strictly increasing", who);
     const long long nc = ny * nx;
     for (long long k = 0; k < K; ++k) {
-        if (cells[k] < 0 || cells[k] >= nc) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: cell %lld outside the grid", cells[k]);
-        if (!(isfinite(sa[k]) && isfinite(ca[k]))) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_profiles: sa / ca not finite at cell %lld", k);
+        if (cells[k] < 0 || cells[k] >= nc) return sc_fail(ctx, SC_ERR_INVALID, "%s: cell %lld outside the grid", who, cells[k]);
+        if (!(isfinite(sa[k]) && isfinite(ca[k]))) return sc_fail(ctx, SC_ERR_INVALID, "%s: sa / ca not finite at cell %lld", who, k);
     }
+    return SC_OK;
+}
+
+int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab) {
+    const int np = 2 * h + 1;
+    sc_prof_begin(ctx, SC_K_PROFILE);
+    k_pf_table<<<std::max(1, std::min(256, (np * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, h, de, d_tab);
+    SC_HIP(ctx, hipGetLastError());
+    sc_prof_end(ctx, 1);
     return SC_OK;
 }
 
@@ -249,10 +248,7 @@ static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if ((rc = sc_lds_attr(ctx, fn, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    sc_prof_begin(ctx, SC_K_PROFILE);
-    k_pf_table<<<std::max(1, std::min(256, (np * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, h, de, d_tab);
-    SC_HIP(ctx, hipGetLastError());
-    sc_prof_end(ctx, 1);
+    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
 
     std::vector<double> dir;
     for (long long k0 = 0; k0 < K; k0 += chunk) {
@@ -294,7 +290,7 @@ extern "C" int sc_fit_profiles(sc_ctx* ctx, const long long* cells, const double
     const Geom& g = ctx->g;
     if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
         return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: the context holds a block of a larger grid");
-    int rc = pf_check(ctx, g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    int rc = sc_pf_check(ctx, "sc_fit_profiles", g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
     SC_HIP(ctx, hipSetDevice(ctx->device));
     return pf_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows, out_sse);
@@ -304,7 +300,7 @@ extern "C" int sc_fit_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx,
                                    const double* ca, long long K, const double* ages, int A, int h, int w, double de,
                                    double delta, int min_samples, sc_profile_fit* out_rows, double* out_sse) {
     if (!ctx || !z) return SC_ERR_INVALID;
-    int rc = pf_check(ctx, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    int rc = sc_pf_check(ctx, "sc_fit_profiles", ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
     if (K == 0) return SC_OK;
     SC_HIP(ctx, hipSetDevice(ctx->device));

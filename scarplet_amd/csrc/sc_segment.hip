@@ -1,0 +1,586 @@
+// sc_fit_segments / sc_fit_segments_dem: one scarp age per trace segment, fitted jointly (docs/segments.md).
+//
+// The cells arrive grouped by segment (CSR seg_start).  Per segment and age one least-squares problem over all its
+// usable profiles: a shared amplitude a, and an intercept and a slope per profile.  Orthogonalising each profile's erf
+// column and data against its own (1, s) - passes 0 to 2 of k_pf_fit - leaves a one-column problem whose normal
+// equation is a_i = sum_c Sep_ci / sum_c See_ci; the residuals are then explicit.
+//   k_sg_partial  one wave per cell, as k_pf_fit: lanes over the points while sampling (the profile goes to LDS and is
+//                 PARKED in global memory), lanes over the ages for passes 0 to 2; parks sbar, pbar, beta and per age
+//                 ebar, gamma, See, Sep
+//   k_sg_rank     one wave per segment: the usable cells of the segment in input order (ballot and popcount), their
+//                 number and the pooled number of valid points
+//   k_sg_sum1     one wave per block of 64 consecutive usable profiles, lanes over the ages: the block's terms summed
+//                 in sequence from the first
+//   k_sg_sum2     one wave per segment: the block sums in sequence from the first.  The shape of the sum depends on
+//                 n_profiles alone; one profile is no addition at all
+//   k_sg_resid    one wave per cell: the parked profile back into LDS, lanes over the ages, the explicit residuals of
+//                 pass 3 of k_pf_fit with the segment's a_i; the cell's sse_ci takes the place of See_ci
+//   (k_sg_sum1 and k_sg_sum2 again, on sse_ci)
+//   k_sg_choose   one wave per segment: argmin, interval, the row; then lanes over the segment's cells for the cell
+//                 table at the best age
+// No atomics at all.  The erf table is k_pf_table's, the sampling pf_sample: the same bits as sc_fit_profiles.
+#include "sc_internal.h"
+#include <math.h>
+#include <algorithm>
+
+#define SG_WAVES 4                       // cells in flight per workgroup
+#define SG_THREADS (64 * SG_WAVES)
+#define SG_TAB_LDS 65536                 // the table goes to LDS up to this many bytes
+#define SG_BLOCK 64                      // usable profiles per block of the segmented sum
+#define SG_MAX_GRID 2048
+#define SG_MAX_SEGS (1ll << 20)          // segments per chunk: bounds the rows and totals of a call with empty segments
+
+template <bool TAB_LDS>
+__global__ __launch_bounds__(SG_THREADS) void k_sg_partial(const double* __restrict__ z, int ny, int nx,
+                                                           const long long* __restrict__ cells,
+                                                           const double* __restrict__ dir, long long K, int A, int h,
+                                                           int w, double de, int min_samples,
+                                                           const double* __restrict__ tab_g, double* __restrict__ prof_g,
+                                                           int* __restrict__ cn, int* __restrict__ used,
+                                                           double* __restrict__ scal, double* __restrict__ planes) {
+    extern __shared__ double sg_lds[];
+    const int np = 2 * h + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* prof = sg_lds + (size_t)wave * np;
+    const double* tab = tab_g;
+    if (TAB_LDS) {
+        double* t = sg_lds + (size_t)SG_WAVES * np;
+        for (int idx = threadIdx.x; idx < np * A; idx += SG_THREADS) t[idx] = tab_g[idx];
+        tab = t;
+    }
+    __syncthreads();
+    const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
+    const double nan = __builtin_nan("");
+    const size_t stride = (size_t)K * A;                 // one per-cell-and-age plane
+    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * SG_WAVES + wave;
+        const bool act = kc < K;
+        if (act) {
+            const long long cell = cells[kc];
+            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
+            const double r = (double)(cell / nx), c = (double)(cell % nx);
+            for (int jj = lane; jj < np; jj += 64) {
+                const double j = (double)(jj - h);
+                const double jsa = j * sa, jca = j * ca;
+                double acc = 0.0;
+                int cnt = 0;
+                for (int kk = -w; kk <= w; ++kk) {
+                    const double k = (double)kk;
+                    const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
+                    double v;
+                    if (pf_sample(z, ny, nx, rr, cc, v)) {
+                        acc += v;
+                        ++cnt;
+                    }
+                }
+                const double p = cnt ? acc / (double)cnt : nan;
+                prof[jj] = p;
+                prof_g[(size_t)kc * np + jj] = p;
+            }
+        }
+        __syncthreads();
+        if (act) {
+            // pass 0: counts, sums of s, p and this lane's e over the valid points
+            int n = 0, n_neg = 0, n_pos = 0;
+            double Ss = 0.0, Sp = 0.0, Se = 0.0;
+            for (int jj = 0; jj < np; ++jj) {
+                const double p = prof[jj];
+                if (p != p) continue;
+                ++n;
+                n_neg += jj < h ? 1 : 0;
+                n_pos += jj > h ? 1 : 0;
+                Ss += (double)(jj - h) * de;
+                Sp += p;
+                Se += tab[(size_t)jj * A + ia];
+            }
+            const bool ok = n_neg >= min_samples && n_pos >= min_samples;
+            if (lane == 0) {
+                cn[kc] = n;
+                used[kc] = ok ? 1 : 0;
+            }
+            if (ok) {
+                const double dn = (double)n;
+                const double sbar = Ss / dn, pbar = Sp / dn, ebar = Se / dn;
+                // pass 1: the centred s against itself, p and e
+                double Sss = 0.0, Sps = 0.0, Ses = 0.0;
+                for (int jj = 0; jj < np; ++jj) {
+                    const double p = prof[jj];
+                    if (p != p) continue;
+                    const double sc = (double)(jj - h) * de - sbar;
+                    Sss += sc * sc;
+                    Sps += sc * (p - pbar);
+                    Ses += sc * (tab[(size_t)jj * A + ia] - ebar);
+                }
+                const double beta = Sps / Sss, gamma = Ses / Sss;
+                // pass 2: what is left of e after 1 and s, against what is left of p
+                double See = 0.0, Sep = 0.0;
+                for (int jj = 0; jj < np; ++jj) {
+                    const double p = prof[jj];
+                    if (p != p) continue;
+                    const double sc = (double)(jj - h) * de - sbar;
+                    const double e2 = (tab[(size_t)jj * A + ia] - ebar) - gamma * sc;
+                    const double p2 = (p - pbar) - beta * sc;
+                    See += e2 * e2;
+                    Sep += e2 * p2;
+                }
+                if (lane == 0) {
+                    scal[3 * kc] = sbar;
+                    scal[3 * kc + 1] = pbar;
+                    scal[3 * kc + 2] = beta;
+                }
+                if (lane < A) {
+                    const size_t o = (size_t)kc * A + lane;
+                    planes[o] = ebar;
+                    planes[stride + o] = gamma;
+                    planes[2 * stride + o] = See;
+                    planes[3 * stride + o] = Sep;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the usable cells of each segment in input order, their number and the pooled number of valid points
+__global__ __launch_bounds__(64) void k_sg_rank(const int* __restrict__ seg_start, long long S, const int* __restrict__ cn,
+                                                const int* __restrict__ used, int* __restrict__ list,
+                                                int* __restrict__ cnt) {
+    const int lane = threadIdx.x;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int start = seg_start[s], end = seg_start[s + 1];
+        int m = 0, nsum = 0;
+        for (int k0 = start; k0 < end; k0 += 64) {
+            const int k = k0 + lane;
+            const bool u = k < end && used[k] != 0;
+            const unsigned long long mask = __ballot(u);
+            if (u) {
+                list[start + m + __popcll(mask & ((1ull << lane) - 1ull))] = k;
+                nsum += cn[k];
+            }
+            m += __popcll(mask);
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) nsum += __shfl_xor(nsum, o, 64);       // (integers: any order)
+        if (lane == 0) {
+            cnt[2 * s] = m;
+            cnt[2 * s + 1] = nsum;
+        }
+    }
+}
+
+// block g of SG_BLOCK consecutive usable profiles of its segment: P planes summed in sequence from the first term
+template <int P>
+__global__ __launch_bounds__(64) void k_sg_sum1(const double* __restrict__ src, size_t stride, const int* __restrict__ list,
+                                                const int* __restrict__ seg_start, const int* __restrict__ blk_start,
+                                                const int* __restrict__ cnt, long long S, long long G, int A,
+                                                double* __restrict__ part) {
+    const int lane = threadIdx.x;
+    for (long long g = blockIdx.x; g < G; g += gridDim.x) {
+        long long lo = 0, hi = S;                        // the segment with blk_start[s] <= g < blk_start[s + 1]
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if ((long long)blk_start[mid + 1] <= g) lo = mid + 1; else hi = mid;
+        }
+        const long long s = lo;
+        const int m = cnt[2 * s];
+        const int r0 = (int)(g - blk_start[s]) * SG_BLOCK;
+        if (r0 >= m || lane >= A) continue;
+        const int r1 = min(m, r0 + SG_BLOCK);
+        const int* ls = list + seg_start[s];
+        double acc[P];
+        {
+            const size_t o = (size_t)ls[r0] * A + lane;
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] = src[p * stride + o];
+        }
+        for (int r = r0 + 1; r < r1; ++r) {
+            const size_t o = (size_t)ls[r] * A + lane;
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] += src[p * stride + o];
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) part[((size_t)g * P + p) * A + lane] = acc[p];
+    }
+}
+
+// the block sums of each segment in sequence from the first
+template <int P>
+__global__ __launch_bounds__(64) void k_sg_sum2(const double* __restrict__ part, const int* __restrict__ blk_start,
+                                                const int* __restrict__ cnt, long long S, int A, double* __restrict__ tot) {
+    const int lane = threadIdx.x;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int nb = (cnt[2 * s] + SG_BLOCK - 1) / SG_BLOCK;
+        if (nb == 0 || lane >= A) continue;
+        const size_t g0 = (size_t)blk_start[s];
+        double acc[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) acc[p] = part[(g0 * P + p) * A + lane];
+        for (int q = 1; q < nb; ++q) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] += part[((g0 + q) * P + p) * A + lane];
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) tot[((size_t)s * P + p) * A + lane] = acc[p];
+    }
+}
+
+__device__ __forceinline__ bool sg_fitted(int m, int n, int min_profiles) {
+    return m >= min_profiles && n - 2 * m - 1 >= 1;
+}
+
+// the explicit residuals of every usable cell of a fitted segment, with the segment's a_i: sse_ci replaces See_ci
+template <bool TAB_LDS>
+__global__ __launch_bounds__(SG_THREADS) void k_sg_resid(const double* __restrict__ prof_g, const int* __restrict__ cseg,
+                                                         const int* __restrict__ used, const int* __restrict__ cnt,
+                                                         const double* __restrict__ scal, double* __restrict__ planes,
+                                                         const double* __restrict__ tot, long long K, int A, int h,
+                                                         double de, int min_profiles, const double* __restrict__ tab_g) {
+    extern __shared__ double sg_lds[];
+    const int np = 2 * h + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* prof = sg_lds + (size_t)wave * np;
+    const double* tab = tab_g;
+    if (TAB_LDS) {
+        double* t = sg_lds + (size_t)SG_WAVES * np;
+        for (int idx = threadIdx.x; idx < np * A; idx += SG_THREADS) t[idx] = tab_g[idx];
+        tab = t;
+    }
+    __syncthreads();
+    const int ia = min(lane, A - 1);
+    const size_t stride = (size_t)K * A;
+    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * SG_WAVES + wave;
+        bool act = kc < K;
+        int s = 0;
+        if (act) {
+            s = cseg[kc];
+            act = used[kc] != 0 && sg_fitted(cnt[2 * s], cnt[2 * s + 1], min_profiles);
+        }
+        if (act)
+            for (int jj = lane; jj < np; jj += 64) prof[jj] = prof_g[(size_t)kc * np + jj];
+        __syncthreads();
+        if (act) {
+            const size_t o = (size_t)kc * A + ia;
+            const double sbar = scal[3 * kc], pbar = scal[3 * kc + 1], beta = scal[3 * kc + 2];
+            const double ebar = planes[o], gamma = planes[stride + o];
+            const double See = tot[((size_t)s * 2) * A + ia], Sep = tot[((size_t)s * 2 + 1) * A + ia];
+            const double a = Sep / See;
+            const double b = beta - a * gamma;
+            const double c0 = (pbar - a * ebar) - b * sbar;
+            double sse = 0.0;
+            for (int jj = 0; jj < np; ++jj) {
+                const double p = prof[jj];
+                if (p != p) continue;
+                const double sj = (double)(jj - h) * de;
+                const double res = p - ((c0 + b * sj) + a * tab[(size_t)jj * A + ia]);
+                sse += res * res;
+            }
+            if (lane < A) planes[2 * stride + o] = sse;
+        }
+        __syncthreads();
+    }
+}
+
+// the age of each segment, its interval and its row; the cell table at the best age
+__global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_start, const int* __restrict__ label,
+                                                  const int* __restrict__ cnt, long long S, long long K,
+                                                  const double* __restrict__ tot, const double* __restrict__ tsse,
+                                                  const double* __restrict__ ages, int A, double delta, int min_profiles,
+                                                  const long long* __restrict__ cells, const int* __restrict__ cn,
+                                                  const int* __restrict__ used, const double* __restrict__ scal,
+                                                  const double* __restrict__ planes, sc_segment_fit* __restrict__ rows,
+                                                  sc_segment_cell* __restrict__ out_cells, double* __restrict__ curve) {
+    const int lane = threadIdx.x;
+    const int ia = min(lane, A - 1);
+    const double nan = __builtin_nan("");
+    const size_t stride = (size_t)K * A;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int start = seg_start[s], end = seg_start[s + 1];
+        const int m = cnt[2 * s], n = cnt[2 * s + 1];
+        const int dof = n - 2 * m - 1;
+        const bool fitted = sg_fitted(m, n, min_profiles);
+        sc_segment_fit* out = rows + s;
+        int best = -1;
+        double a_best = nan;
+        if (!fitted) {
+            if (lane == 0) {
+                out->label = label[s];
+                out->n_cells = end - start;
+                out->n_profiles = m;
+                out->n = n;
+                out->dof = dof;
+                out->kt_index = -1;
+                out->lo_index = -1;
+                out->hi_index = -1;
+                out->status = 1;
+                out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
+                out->a = nan; out->sse = nan; out->rmse = nan;
+            }
+            if (curve && lane < A) curve[s * A + lane] = nan;
+        } else {
+            const double sse = tsse[(size_t)s * A + ia];
+            const double a = tot[((size_t)s * 2 + 1) * A + ia] / tot[((size_t)s * 2) * A + ia];
+            if (curve && lane < A) curve[s * A + lane] = sse;
+            // argmin over the ages, ties to the smaller index (a NaN never wins)
+            double mn = lane < A ? sse : INFINITY;
+            if (mn != mn) mn = INFINITY;
+            int mi = lane;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const double om = __shfl_xor(mn, o, 64);
+                const int oi = __shfl_xor(mi, o, 64);
+                if (om < mn || (om == mn && oi < mi)) { mn = om; mi = oi; }
+            }
+            best = min(mi, A - 1);
+            const double thr = mn * (1.0 + delta / (double)dof);
+            const unsigned long long ok = __ballot(lane < A && sse <= thr);
+            int lo = best, hi = best;
+            while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
+            while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
+            a_best = __shfl(a, best, 64);
+            if (lane == best) {
+                out->label = label[s];
+                out->n_cells = end - start;
+                out->n_profiles = m;
+                out->n = n;
+                out->dof = dof;
+                out->kt_index = best;
+                out->lo_index = lo;
+                out->hi_index = hi;
+                out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0);
+                out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
+                out->a = a;
+                out->sse = sse; out->rmse = sqrt(sse / (double)dof);
+            }
+        }
+        if (!out_cells) continue;
+        for (int k = start + lane; k < end; k += 64) {
+            sc_segment_cell c;
+            c.cell = cells[k];
+            c.used = used[k];
+            c.n = cn[k];
+            c.b = nan; c.c0 = nan; c.sse = nan;
+            if (fitted && c.used) {
+                const size_t o = (size_t)k * A + best;
+                c.b = scal[3 * k + 2] - a_best * planes[stride + o];
+                c.c0 = (scal[3 * k + 1] - a_best * planes[o]) - c.b * scal[3 * k];
+                c.sse = planes[2 * stride + o];
+            }
+            out_cells[k] = c;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+static long long sg_cap_cells(int A, int h) {
+    return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) + 4ll * A));
+}
+
+static int sg_check(sc_ctx* ctx, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
+                    long long K, const long long* seg_start, const int32_t* seg_label, long long S, const double* ages,
+                    int A, int h, int w, double de, double delta, int min_samples, int min_profiles,
+                    const sc_segment_fit* out_rows) {
+    int rc = sc_pf_check(ctx, "sc_fit_segments", ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    if (rc) return rc;
+    if (S < 0 || !seg_start || (S > 0 && (!seg_label || !out_rows)))
+        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: null argument");
+    if (min_profiles < 1) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: min_profiles must be >= 1");
+    if (seg_start[0] != 0 || seg_start[S] != K)
+        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: seg_start must run from 0 to K");
+    const long long cap = sg_cap_cells(A, h);
+    for (long long s = 0; s < S; ++s) {
+        if (seg_start[s + 1] < seg_start[s])
+            return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: seg_start decreases at segment %lld", s);
+        if (seg_label[s] <= 0 || (s > 0 && seg_label[s] <= seg_label[s - 1]))
+            return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: labels must be positive and strictly increasing");
+    }
+    for (long long s = 0; s < S; ++s)
+        if (seg_start[s + 1] - seg_start[s] > cap)
+            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments: a segment of %lld cells, more than %lld at this h and A",
+                           seg_start[s + 1] - seg_start[s], cap);
+    return SC_OK;
+}
+
+static unsigned sg_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
+
+static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
+                  const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
+                  int w, double de, double delta, int min_samples, int min_profiles, sc_segment_fit* out_rows,
+                  sc_segment_cell* out_cells, double* out_sse) {
+    if (S == 0) return SC_OK;
+    const int np = 2 * h + 1;
+    const size_t tab_bytes = sizeof(double) * (size_t)np * A;
+    const long long cap = sg_cap_cells(A, h);
+    int rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_tab, tab_bytes))) return rc;
+    double* d_ages = (double*)ctx->sg_ages.p;
+    double* d_tab = (double*)ctx->sg_tab.p;
+
+    const bool tab_lds = tab_bytes <= SG_TAB_LDS;
+    const size_t lds = sizeof(double) * (size_t)SG_WAVES * np + (tab_lds ? tab_bytes : 0);
+    const void* fn1 = tab_lds ? (const void*)k_sg_partial<true> : (const void*)k_sg_partial<false>;
+    const void* fn2 = tab_lds ? (const void*)k_sg_resid<true> : (const void*)k_sg_resid<false>;
+    if ((rc = sc_lds_attr(ctx, fn1, lds))) return rc;
+    if ((rc = sc_lds_attr(ctx, fn2, lds))) return rc;
+
+    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
+
+    std::vector<double> dir;
+    std::vector<int> cseg, start, blk;
+    for (long long s0 = 0; s0 < S;) {
+        // a chunk of whole segments: as many as fit the parked bytes
+        long long s1 = s0 + 1;
+        while (s1 < S && s1 - s0 < SG_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) ++s1;
+        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
+        start.resize((size_t)Sc + 1);
+        blk.resize((size_t)Sc + 1);
+        cseg.resize((size_t)m);
+        dir.resize(2 * (size_t)m);
+        blk[0] = 0;
+        for (long long s = 0; s < Sc; ++s) {
+            const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
+            start[s] = (int)a0;
+            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
+            for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
+        }
+        start[Sc] = (int)m;
+        const long long G = blk[Sc];
+        for (long long k = 0; k < m; ++k) {
+            dir[2 * k] = sa[k0 + k];
+            dir[2 * k + 1] = ca[k0 + k];
+        }
+        const size_t mA = (size_t)m * A;
+        if ((rc = sc_ensure(ctx, ctx->sg_cells, sizeof(long long) * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_dir, sizeof(double) * 2 * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_start, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_label, sizeof(int) * (size_t)Sc))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * np))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_int, sizeof(int) * 2 * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_scal, sizeof(double) * 3 * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * 4 * mA))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_list, sizeof(int) * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * A))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * A))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * (size_t)Sc * A))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_cnt, sizeof(int) * 2 * (size_t)Sc))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_fit) * (size_t)Sc))) return rc;
+        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, sizeof(sc_segment_cell) * (size_t)m))) return rc;
+        if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
+        long long* d_cells = (long long*)ctx->sg_cells.p;
+        double* d_dir = (double*)ctx->sg_dir.p;
+        int* d_cseg = (int*)ctx->sg_cseg.p;
+        int* d_start = (int*)ctx->sg_start.p;
+        int* d_blk = (int*)ctx->sg_blk.p;
+        int* d_label = (int*)ctx->sg_label.p;
+        double* d_prof = (double*)ctx->sg_prof.p;
+        int* d_cn = (int*)ctx->sg_int.p;
+        int* d_used = d_cn + m;
+        double* d_scal = (double*)ctx->sg_scal.p;
+        double* d_planes = (double*)ctx->sg_age.p;
+        int* d_list = (int*)ctx->sg_list.p;
+        double* d_part = (double*)ctx->sg_part.p;
+        double* d_tot = (double*)ctx->sg_tot.p;
+        double* d_tsse = (double*)ctx->sg_tsse.p;
+        int* d_cnt = (int*)ctx->sg_cnt.p;
+        sc_segment_fit* d_rows = (sc_segment_fit*)ctx->sg_rows.p;
+        sc_segment_cell* d_out = out_cells ? (sc_segment_cell*)ctx->sg_out.p : nullptr;
+        double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
+
+        if (m) {
+            SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        }
+        SC_HIP(ctx, hipMemcpyAsync(d_start, start.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(d_label, seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
+        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
+        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_fit) * (size_t)Sc, ctx->stream));
+
+        const unsigned gcell = (unsigned)std::max<long long>(1, std::min<long long>((m + SG_WAVES - 1) / SG_WAVES, SG_MAX_GRID));
+        int launches = 0;
+        sc_prof_begin(ctx, SC_K_PROFILE);
+        if (m) {
+            if (tab_lds)
+                k_sg_partial<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples,
+                                                                           d_tab, d_prof, d_cn, d_used, d_scal, d_planes);
+            else
+                k_sg_partial<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples,
+                                                                            d_tab, d_prof, d_cn, d_used, d_scal, d_planes);
+            ++launches;
+        }
+        k_sg_rank<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, Sc, d_cn, d_used, d_list, d_cnt);
+        ++launches;
+        if (G) {
+            k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
+            k_sg_sum2<2><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tot);
+            if (tab_lds)
+                k_sg_resid<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_tot, m,
+                                                                         A, h, de, min_profiles, d_tab);
+            else
+                k_sg_resid<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_tot, m,
+                                                                          A, h, de, min_profiles, d_tab);
+            k_sg_sum1<1><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
+            k_sg_sum2<1><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tsse);
+            launches += 5;
+        }
+        k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, delta,
+                                                        min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_rows, d_out, d_sse);
+        ++launches;
+        SC_HIP(ctx, hipGetLastError());
+        sc_prof_end(ctx, launches);
+        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_cells && m)
+            SC_HIP(ctx, hipMemcpyAsync(out_cells + k0, d_out, sizeof(sc_segment_cell) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sse)
+            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)s0 * A, d_sse, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s0 = s1;
+    }
+    return SC_OK;
+}
+
+extern "C" int sc_fit_segments(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                               const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                               int h, int w, double de, double delta, int min_samples, int min_profiles,
+                               sc_segment_fit* out_rows, sc_segment_cell* out_cells, double* out_sse) {
+    if (!ctx) return SC_ERR_INVALID;
+    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
+    const Geom& g = ctx->g;
+    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
+        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments: the context holds a block of a larger grid");
+    int rc = sg_check(ctx, g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
+                      min_profiles, out_rows);
+    if (rc) return rc;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
+                  min_profiles, out_rows, out_cells, out_sse);
+}
+
+extern "C" int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                                   const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                                   long long S, const double* ages, int A, int h, int w, double de, double delta,
+                                   int min_samples, int min_profiles, sc_segment_fit* out_rows, sc_segment_cell* out_cells,
+                                   double* out_sse) {
+    if (!ctx || !z) return SC_ERR_INVALID;
+    int rc = sg_check(ctx, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
+                      min_profiles, out_rows);
+    if (rc) return rc;
+    if (S == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
+    if ((rc = sc_ensure(ctx, ctx->sg_z, bytes))) return rc;
+    SC_HIP(ctx, hipMemcpyAsync(ctx->sg_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, de, delta,
+                  min_samples, min_profiles, out_rows, out_cells, out_sse);
+}

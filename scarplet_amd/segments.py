@@ -1,0 +1,117 @@
+"""One scarp age per trace segment, fitted jointly on the device (docs/segments.md).
+
+``fit_profiles`` dates every cell of a trace on its own; a mapped scarp gets ONE age with ONE interval.
+``fit_segments`` cuts the same profiles (the same samples, bit for bit) and solves, per segment and age, one
+least-squares problem over all of them: the amplitude ``a`` and the age are the segment's, every profile keeps an
+intercept and a far-field slope of its own, since elevation and slope vary along the strike (sc_fit_segments,
+include/scarplet_hip.h).
+"""
+import operator
+
+import numpy as np
+
+from scarplet_amd import _lib, profiles
+
+# the tables as Python returns them
+FIT_FIELDS = [(f, _lib.SEGMENT_FIT_DTYPE.fields[f][0]) for f in _lib.SEGMENT_FIT_DTYPE.names] + [("height", np.float64)]
+FIT_DTYPE = np.dtype(FIT_FIELDS)
+CELL_FIELDS = [("row", np.int64), ("col", np.int64)] + \
+    [(f, _lib.SEGMENT_CELL_DTYPE.fields[f][0]) for f in _lib.SEGMENT_CELL_DTYPE.names] + [("label", np.int32)]
+CELL_DTYPE = np.dtype(CELL_FIELDS)
+
+
+def _labels_of(labels, idx, ny, nx):
+    """One int64 label per cell: one per cell, or an (ny, nx) int plane read at the cells."""
+    lab = np.asarray(labels)
+    if lab.size and lab.dtype.kind not in "iu":
+        raise ValueError("labels must be integers, got %s" % lab.dtype)
+    if lab.ndim == 2:
+        if lab.shape != (ny, nx):
+            raise ValueError("a label plane must have the grid's shape %r, got %r" % ((ny, nx), lab.shape))
+        lab = lab.ravel()[idx]
+    elif lab.ndim != 1 or len(lab) != len(idx):
+        raise ValueError("labels must be one integer per cell (%d) or an (ny, nx) plane" % len(idx))
+    lab = lab.astype(np.int64)
+    if lab.size and lab.max() > 2 ** 31 - 1:
+        raise ValueError("labels must fit 32 bits")
+    return lab
+
+
+def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles):
+    """What the library takes, validated and normalised; ValueError otherwise.  The shared arguments go through
+    ``profiles.check_args``; cells of label <= 0 are dropped, the rest grouped by label with a stable sort (input
+    order is kept within a label).  Returns (cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples,
+    min_profiles, order, kept): the first three sorted, ``kept`` the input positions of the cells that stay and
+    ``order`` the sort's permutation of them."""
+    idx, sa, ca, kt, h, w, de, d, ms = profiles.check_args(shape, de, cells, angle, half_length, swath, ages, delta,
+                                                           min_samples)
+    ny, nx = (int(v) for v in shape)
+    lab = _labels_of(labels, idx, ny, nx)
+    if isinstance(min_profiles, (bool, np.bool_)):
+        raise ValueError("min_profiles must be an integer >= 1")
+    try:
+        mp = operator.index(min_profiles)
+    except TypeError:
+        raise ValueError("min_profiles must be an integer >= 1, got %r" % (min_profiles,))
+    if mp < 1:
+        raise ValueError("min_profiles must be an integer >= 1, got %r" % (min_profiles,))
+    kept = np.flatnonzero(lab > 0)
+    order = np.argsort(lab[kept], kind="stable")
+    pick = kept[order]
+    seg_label, counts = np.unique(lab[kept], return_counts=True)
+    seg_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt)))
+    if len(counts) and counts.max() > cap:
+        raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages"
+                         % (counts.max(), cap))
+    return (np.ascontiguousarray(idx[pick]), np.ascontiguousarray(sa[pick]), np.ascontiguousarray(ca[pick]), seg_start,
+            np.ascontiguousarray(seg_label, dtype=np.int32), kt, h, w, de, d, ms, mp, order, kept)
+
+
+def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
+                 min_profiles=1, return_cells=False, return_curve=False, device=0):
+    """Fit ONE diffusion scarp per segment to the profiles cut across the strike at its cells (docs/segments.md).
+
+    ``data``, ``cells``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta`` and ``min_samples`` are those of
+    ``sl.fit_profiles``.  ``labels``: one int per cell, or an (ny, nx) int plane read at the cells (the ``labels`` of
+    ``extract_traces``); the cells of one label are one segment, cells of label <= 0 are dropped.  Per segment and
+    age the usable profiles (at least ``min_samples`` valid points on either side) are fitted together by
+    ``c0_c + b_c s + a erf(s / (2 sqrt(kt)))``: ``a`` and ``kt`` shared, an intercept and a slope per profile.  The
+    age with the smallest pooled sum of squared residuals wins; ``lo_index .. hi_index`` is the run of ages around it
+    whose sse stays within ``sse_min (1 + delta / dof)``, ``dof = n - 2 n_profiles - 1``.  A segment with fewer than
+    ``min_profiles`` usable profiles has ``status`` 1 and NaN fields.
+
+    Returns a structured array, one row per distinct label in ascending order: ``label, n_cells, n_profiles, n, dof,
+    kt_index, lo_index, hi_index, status, kt, kt_lo, kt_hi, a, sse, rmse, height`` (= 2 a).  ``return_cells`` adds
+    the per-cell table in input order (``row, col, cell, used, n, b, c0, sse, label``: each profile's slope,
+    intercept and sse at the segment's best age) and ``return_curve`` the (S, A) sse curves, in that order.  The
+    same bytes on every run."""
+    z, de = profiles._dem_of(data)
+    args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    from scarplet_amd.core import _context
+    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z)
+
+
+def _run(ctx, args, nx, return_cells, return_curve, z=None):
+    idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
+    rows, tab, curve = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
+                                        cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+    out = np.zeros(len(rows), dtype=FIT_DTYPE)
+    for f in rows.dtype.names:
+        out[f] = rows[f]
+    out["height"] = 2.0 * rows["a"]
+    res = [out]
+    if return_cells:
+        ct = np.zeros(len(tab), dtype=CELL_DTYPE)
+        back = np.empty(len(order), dtype=np.int64)                    # sorted position of each kept cell
+        back[order] = np.arange(len(order))
+        for f in tab.dtype.names:
+            ct[f] = tab[f][back]
+        ct["row"] = ct["cell"] // nx
+        ct["col"] = ct["cell"] % nx
+        ct["label"] = np.repeat(seg_label, np.diff(seg_start))[back]
+        res.append(ct)
+    if return_curve:
+        res.append(curve)
+    return res[0] if len(res) == 1 else tuple(res)
