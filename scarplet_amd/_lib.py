@@ -11,9 +11,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SCARPLET_HIP_LIB is the ONE environment variable this package reads: a developer hook of the
-# tools/ scripts to load another build of the same library (the -DSC_ABLATE timing build,
-# tools/ablate.sh).  The engine itself - libscarplet_hip.so - reads no environment at all; its
-# options go through sc_set_option.
+# tools/ scripts to load another build of the same library (tools/build_alt.sh).  The engine
+# itself - libscarplet_hip.so - reads no environment at all; its options go through
+# sc_set_option.
 LIB_PATH = os.environ.get("SCARPLET_HIP_LIB") or os.path.join(_HERE, "libscarplet_hip.so")
 
 SC_OK = 0

@@ -142,9 +142,6 @@ extern "C" int sc_create(int device, sc_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
     sc_ctx* c = new sc_ctx();
     c->device = device;
-#ifdef SC_ABLATE
-    if (const char* d = getenv("SC_DBG")) c->dbg = atoi(d);
-#endif
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return SC_ERR_HIP;
@@ -160,10 +157,6 @@ extern "C" int sc_set_option(sc_ctx* ctx, const char* name, double value) {
         ctx->kappa = (float)value;
     } else if (!strcmp(name, "variant")) {
         ctx->variant = (int)value;
-#ifdef SC_ABLATE
-    } else if (!strcmp(name, "dbg")) {
-        ctx->dbg = (int)value;
-#endif
     } else if (!strcmp(name, "batch")) {
         ctx->batch_off = value == 0.0;
     } else if (!strcmp(name, "batch_fill")) {

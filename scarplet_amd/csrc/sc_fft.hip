@@ -47,32 +47,6 @@ struct TileDev {
     int i0, j0, vy, vx, gi0, gj0;
 };
 
-#ifndef SC_I1_XLANE
-#define SC_I1_XLANE 1      // k_inv_cols_w8 / w4: stage 2 -> 3 exchanged across lanes (v_permlane swaps), not through the LDS
-#endif
-#ifndef SC_I2_RD1
-#define SC_I2_RD1 1        // the row pass's stage-2 and stage-3 cells read singly too
-#endif
-#ifndef SC_LDS_WR1
-#define SC_LDS_WR1 0      // ... and written one ds_write_b64 each (wave-per-column kernels)
-#endif
-#ifndef SC_LDS_RD1
-#define SC_LDS_RD1 1      // LDS cells read one ds_read_b64 each (0: the compiler's ds_read2_b64 pairs)
-#endif
-#ifndef SC_H2_XLANE
-#define SC_H2_XLANE 1      // k_inv_cols_h2: the last stage (radix 2) across lanes with v_permlane16_swap instead of through the LDS
-#endif
-#ifndef SC_F1C_HOLD
-#define SC_F1C_HOLD 1      // k_fwd_rows_curv<.., MIX>: the mixed curvature held in registers for the second plane
-#endif
-#ifndef SC_I1_TWTAB
-#ifndef SC_Y_ROWMAJOR
-#define SC_Y_ROWMAJOR 0    // lab (k_inv_cols_w8 + k_inv_rows_fast only): the I1 -> I2 hand-off row-major instead of rows2 blocks
-#endif
-#define SC_I1_TWTAB 0      // 1: the wave-per-column kernels read all fifteen twiddles of a set from LDS tables
-#endif
-
-
 // ---------------------------------------------------------------------------
 // In-LDS FFT of 4 lines of length T (complex float32).
 //
@@ -157,18 +131,6 @@ __device__ __forceinline__ bool sib_wait(const uint32_t* theirs, uint32_t target
 }
 constexpr uint32_t SIB_DONE = 0xFFu;
 
-#ifdef SC_ABLATE
-// store flavours for the ablation build (tools/ablate.sh): 0 non-temporal (production),
-// 1 plain, 2 sc1 (write-through, line dropped from L2), 3 sc0 sc1
-__device__ __forceinline__ void store_flavour(float2* dst, float2 a, float2 b, int mode) {
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const f4 v = {a.x, a.y, b.x, b.y};
-    if (mode == 1) { *reinterpret_cast<f4*>(dst) = v; return; }
-    if (mode == 2) { asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(dst), "v"(v) : "memory"); return; }
-    if (mode == 3) { asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(dst), "v"(v) : "memory"); return; }
-    __builtin_nontemporal_store(v, reinterpret_cast<f4*>(dst));
-}
-#endif
 template <int T>
 __device__ __forceinline__ int lidx(int line, int i) { return line * fft_line(T) + ph(i); }
 
@@ -419,14 +381,14 @@ struct FftTw {
 // ds_read/ds_write with immediate offsets instead of 32 address registers.
 
 // a[j] = line[tt + j*S]
-// (SC_LDS_RD1: every cell with a ds_read_b64 of its own.  Left to itself the compiler pairs the reads of one base
+// (RD1: every cell with a ds_read_b64 of its own.  Left to itself the compiler pairs the reads of one base
 //  into ds_read2_b64 - 8 LDS cycles per wave instruction for 16 bytes per lane, against 2 x 2 cycles for two
 //  ds_read_b64 (MI355X_MICROARCH.md, LDS table: 128 against 256 B/clk/CU).  The wave-per-column pass issues 39 of
 //  them per transform and plane, eight waves at a time: a sixth of its LDS cycles.  RD1: that kernel only - the
 //  forward row pass is 13 % slower with single reads.)
 template <bool RD1, typename V2>
 __device__ __forceinline__ V2 lds_cell2(const V2* p) {            // the same for the packed two-float vector type
-    if constexpr (!RD1 || !SC_LDS_RD1) return *p;
+    if constexpr (!RD1) return *p;
     typedef const volatile __attribute__((address_space(3))) unsigned long long* lds_u64p;
     const unsigned long long v = *(lds_u64p)(p);
     return V2{__uint_as_float((unsigned)v), __uint_as_float((unsigned)(v >> 32))};
@@ -434,13 +396,9 @@ __device__ __forceinline__ V2 lds_cell2(const V2* p) {            // the same fo
 template <bool RD1>
 __device__ __forceinline__ float2 lds_cell(const float2* p) {
     if constexpr (!RD1) return *p;
-#if SC_LDS_RD1
     typedef const volatile __attribute__((address_space(3))) unsigned long long* lds_u64p;    // (volatile keeps the reads single; the LDS address space keeps them ds_ loads)
     const unsigned long long v = *(lds_u64p)(p);
     return make_float2(__uint_as_float((unsigned)v), __uint_as_float((unsigned)(v >> 32)));
-#else
-    return *p;
-#endif
 }
 template <int T, bool RD1 = false>
 __device__ __forceinline__ void set_load(const float2* line, int tt, float2 (&a)[16]) {
@@ -479,41 +437,7 @@ __device__ __forceinline__ void twiddle16(const pk::v2 (&v)[16], const float2 (&
     }
 }
 
-// The fifteen twiddles w^k, k = 1 .. 15, of a radix-16 set as twiddle16 forms them from the four bases -
-// the same products in the same order, so that a table of them gives the same bits as forming them in place.
-__device__ __forceinline__ void twiddle16_expand(const float2 (&w)[4], pk::v2 (&wk)[16]) {
-    using pk::v2;
-    const v2 w1 = v2{w[0].x, w[0].y}, w2 = v2{w[1].x, w[1].y}, w4 = v2{w[2].x, w[2].y}, w8 = v2{w[3].x, w[3].y};
-    wk[0] = v2{1.f, 0.f};
-    wk[8] = w8;
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        v2 x = (k & 1) ? w1 : v2{1.f, 0.f};
-        if (k == 2 || k == 6) x = w2;
-        if (k == 3 || k == 7) x = pk::cmul(w1, w2);
-        if (k == 4) x = w4;
-        if (k >= 5) x = pk::cmul(x, w4);
-        wk[k] = x;
-        wk[k + 8] = pk::cmul(x, w8);
-    }
-}
-// twiddle16 with the fifteen twiddles read from a table (get(k), k = 1 .. 15) instead of formed from four bases
-template <bool INV, typename GET, typename PUT>
-__device__ __forceinline__ void twiddle16_tab(const pk::v2 (&v)[16], GET get, PUT put) {
-    using pk::v2;
-    auto tw = [](v2 a, v2 wk) { return INV ? pk::cmulc(a, wk) : pk::cmul(a, wk); };
-    put(0, v[pk::B<16, INV>::pos(0)]);
-    put(8, tw(v[pk::B<16, INV>::pos(8)], get(8)));
-#pragma unroll
-    for (int k = 1; k < 8; ++k) {
-        put(k, tw(v[pk::B<16, INV>::pos(k)], get(k)));
-        put(k + 8, tw(v[pk::B<16, INV>::pos(k + 8)], get(k + 8)));
-    }
-}
-
-// butterflies of the set (tt) in the stage (R, LST) and store to `line`; TAB: the twiddles of a radix-16 stage
-// come from a table of all fifteen (wtab[k * wstride], k = 1 .. 15) instead of the four bases w
-// ---- stage 2 -> stage 3 of a length-2048 (1024) line WITHOUT the LDS (k_inv_cols_w8, SC_I1_XLANE) --------------------------
+// ---- stage 2 -> stage 3 of a length-2048 (1024) line WITHOUT the LDS (k_inv_cols_w8) --------------------------
 // (written for 2048 = 16 x 16 x 8, two sets per lane; 1024 = 16 x 16 x 4 is the same exchange with one set and four butterflies)
 // Stage 2 (radix 16, stride 16) of the wave's line leaves output m of lane L's set u at element
 //   (L & 15) + 16 m + 256 ((L >> 4) + 4 u);
@@ -538,24 +462,20 @@ __device__ __forceinline__ void xlane_transpose4(float& r0, float& r1, float& r2
     xlane_swap16(r2, r3);
 }
 // a radix-16 stage's butterfly and twiddles with the outputs kept: out[m] = output m (set_compute_store's arithmetic)
-template <bool INV, bool TAB = false>
-__device__ __forceinline__ void set_compute_regs(const float2 (&a)[16], const float2 (&w)[4], float2 (&out)[16],
-                                                 const float2* wtab = nullptr, int wstride = 0) {
+template <bool INV>
+__device__ __forceinline__ void set_compute_regs(const float2 (&a)[16], const float2 (&w)[4], float2 (&out)[16]) {
     using pk::v2;
     v2 v[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) v[k] = v2{a[k].x, a[k].y};
     pk::B<16, INV>::run(v);
     auto put = [&](int m, v2 val) { out[m] = make_float2(val.x, val.y); };
-    if constexpr (TAB)
-        twiddle16_tab<INV>(v, [&](int k) { const float2 x = lds_cell<true>(wtab + k * wstride); return v2{x.x, x.y}; }, put);
-    else
-        twiddle16<INV>(v, w, put);
+    twiddle16<INV>(v, w, put);
 }
 
-template <int T, int R, int LST, bool INV, bool TAB = false, bool WR1 = false>
-__device__ __forceinline__ void set_compute_store(float2* line_, int tt, float2 (&a)[16],
-                                                  const float2 (&w)[4], const float2* wtab = nullptr, int wstride = 0) {
+// butterflies of the set (tt) in the stage (R, LST) and store to `line`
+template <int T, int R, int LST, bool INV>
+__device__ __forceinline__ void set_compute_store(float2* line_, int tt, float2 (&a)[16], const float2 (&w)[4]) {
     using pk::v2;
     constexpr int S = T / 16;
     constexpr int NB = 16 / R;
@@ -581,18 +501,11 @@ __device__ __forceinline__ void set_compute_store(float2* line_, int tt, float2 
         constexpr int wstep = STRIDED ? ST + ST / 16 : 1;      // padded distance of ST elements
         auto put = [&](int m, v2 val) {
             v2* dst = (STRIDED || UNIT) ? wb + m * wstep : line + ph(o + (m << LST));
-            if constexpr (WR1 && SC_LDS_WR1) {       // (one ds_write_b64 per cell, see lds_cell)
-                typedef volatile __attribute__((address_space(3))) unsigned long long* lds_u64w;
-                *(lds_u64w)(dst) = (unsigned long long)__float_as_uint(val.x) | ((unsigned long long)__float_as_uint(val.y) << 32);
-            } else {
-                *dst = val;
-            }
+            *dst = val;
         };
         if constexpr (LAST) {
 #pragma unroll
             for (int m = 0; m < R; ++m) put(m, v[pk::B<R, INV>::pos(m)]);
-        } else if constexpr (TAB) {
-            twiddle16_tab<INV>(v, [&](int k) { const float2 x = wtab[k * wstride]; return v2{x.x, x.y}; }, put);
         } else {
             twiddle16<INV>(v, w, put);
         }
@@ -666,7 +579,7 @@ k_fwd_rows_curv(const float* __restrict__ curv, const float* __restrict__ pB, co
                 CurvMix mixc, Geom g,
                 const TileDev* __restrict__ tiles, int Ty,
                 const float2* __restrict__ tw, float2* __restrict__ blk,
-                double* __restrict__ norm_part, int dbg, int np, size_t curv_stride) {
+                double* __restrict__ norm_part, int np, size_t curv_stride) {
     // blockIdx.y = b * np + p: tile pair p of the b-th orientation of the launch (its
     // curvature plane lies curv_stride floats further on; MIX: its coefficients are mixc.c[b],
     // `curv` is plane A); small searches batch several orientations per launch (sc_api.hip,
@@ -756,11 +669,8 @@ k_fwd_rows_curv(const float* __restrict__ curv, const float* __restrict__ pB, co
     auto fetch = [&](int rbk) {
         int tid = threadIdx.x;                  // (opaque: addresses are rebuilt per step, see fft_stage)
         asm volatile("" : "+v"(tid));
-        if (!SC_DBGBIT(dbg, 8)) { load_tile(ta, va, tid, rbk); load_tile(tb, vb, tid, rbk); }
-        else {
-#pragma unroll
-            for (int u = 0; u < E; ++u) va[u] = vb[u] = 1.f + u;
-        }
+        load_tile(ta, va, tid, rbk);
+        load_tile(tb, vb, tid, rbk);
     };
     fetch(rb0);
     for (int step = 0; step < 2 * RBW; ++step) {
@@ -768,7 +678,7 @@ k_fwd_rows_curv(const float* __restrict__ curv, const float* __restrict__ pB, co
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
         __builtin_assume(tid >= 0 && tid < NT);
-        if (pl == 0 && !SC_DBGBIT(dbg, 1)) {  // |curv|_2^2 and |curv^2|_2^2 of the tile pair (resolution floor, sc_epi_floor)
+        if (pl == 0) {  // |curv|_2^2 and |curv^2|_2^2 of the tile pair (resolution floor, sc_epi_floor)
             // a thread's 2E cells in float32 (the norms only scale the resolution floor, a
             // 1e-7 relative error there moves nothing), float64 from the wave upwards
             float f2 = 0.f, f4 = 0.f;
@@ -809,17 +719,12 @@ k_fwd_rows_curv(const float* __restrict__ curv, const float* __restrict__ pB, co
                                               : make_float2(va[u], vb[u]);
         }
         lds_barrier();
-        if (!SC_DBGBIT(dbg, 2)) fft4_lines<TX, false, true>(sm, twr);
-#if SC_F1C_HOLD
+        fft4_lines<TX, false, true>(sm, twr);
         // MIX: the second plane (curv^2) is filled from the SAME values - held across the first plane's transform - instead
         // of mixing the three stencil planes again: fetched twice, the 12 B per cell came from memory twice (the workgroups
         // of an XCD have more rows in flight than its L2 holds: FETCH_SIZE 3.5 GB per launch for 1.8 GB of planes)
         if (step + 1 < 2 * RBW && (!MIX || ((step + 1) & 1) == 0)) fetch(rb0 + ((step + 1) >> 1));
-#else
-        if (step + 1 < 2 * RBW) fetch(rb0 + ((step + 1) >> 1));
-#endif
         float2* out = blk + (size_t)(pair * 2 + pl) * plane + (size_t)rb * 4 * TX;
-        if (!SC_DBGBIT(dbg, 4))
 #pragma unroll 4
         for (int e = 2 * tid; e < 4 * TX; e += 2 * NT) {
             int cb = e >> 4, rr = (e >> 2) & 3, cc = e & 3;
@@ -1190,7 +1095,7 @@ template <int TY, bool MIRROR>
 __global__ void __launch_bounds__(fft_threads(TY), 2)
 k_inv_cols(const float2* __restrict__ uc, const float2* __restrict__ uc2,
            const float2* __restrict__ wh, const float2* __restrict__ mh, int Tx,
-           int cb0, int pair, int vfirst, int G, int rp_lo, int rp_hi, int dbg,
+           int cb0, int pair, int vfirst, int G, int rp_lo, int rp_hi,
            const float2* __restrict__ tw, float2* __restrict__ yw,
            float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
            const TileDev* __restrict__ tiles, int py_valid) {
@@ -1242,13 +1147,11 @@ k_inv_cols(const float2* __restrict__ uc, const float2* __restrict__ uc2,
             for (int u = 0; u < EP; ++u)
                 hreg[u] = *reinterpret_cast<const float4*>(p + 2 * (threadIdx.x + u * NT));
         };
-        if (!SC_DBGBIT(dbg, 16)) {
-            if (PARK) {
+        if (PARK) {
 #pragma unroll
-                for (int u = 0; u < EP; ++u) xs[threadIdx.x + u * NT] = uu[threadIdx.x + u * NT];
-            }
-            fetch(0);
+            for (int u = 0; u < EP; ++u) xs[threadIdx.x + u * NT] = uu[threadIdx.x + u * NT];
         }
+        fetch(0);
         if (PARK && mirrored) lds_barrier();      // mirrored fills read other threads' cells of xs
         for (int gi_ = 0; gi_ < G; ++gi_) {
             if (!mirrored) {
@@ -1277,13 +1180,12 @@ k_inv_cols(const float2* __restrict__ uc, const float2* __restrict__ uc2,
                 }
             }
             lds_barrier();
-            if (gi_ + 1 < G && !SC_DBGBIT(dbg, 16)) fetch(gi_ + 1);
-            if (!SC_DBGBIT(dbg, 32)) fft4_lines<TY, true>(sm, twr);
+            if (gi_ + 1 < G) fetch(gi_ + 1);
+            fft4_lines<TY, true>(sm, twr);
             // rows2 layout: this block's 4 columns x 2 rows of a row pair are 64
             // contiguous bytes; a thread stores (row 2rp, row 2rp+1) of one column
             float2* o = (pl ? ym : yw) + (size_t)gi_ * plane + (size_t)(cb >> 1) * 16 + (cb & 1) * 8;
             const int e_lo = 4 * rp_lo, e_hi = 4 * (rp_hi + 1);
-            if (!SC_DBGBIT(dbg, 64))
 #pragma unroll 2
             for (int e = e_lo + threadIdx.x; e < e_hi; e += NT) {
                 int rp = e >> 2, k = e & 3;
@@ -1343,12 +1245,8 @@ inv_cols_sym_body(const int cbx, const float2* __restrict__ uc, const float2* __
                const float* __restrict__ wa, const float* __restrict__ mb, int Tx,
                int cb0, int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
                int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
-               float2* __restrict__ ym, int ystride, int dbg, int np, int pcj, int tstride,
+               float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
                const TileDev* __restrict__ tiles, int py_valid) {
-    // dbg: timing-only ablation bits of an SC_ABLATE build (tools/ablate.sh), folded away otherwise:
-    //   1 no coefficient fetch in mirrored launches   2 no coefficient fetch at all   4 no stores
-    //   8 no transform   16 stores paired into whole 128-byte lines (a bijection onto the same plane)
-    //   32 plain stores   64 sc1 stores   128 one contiguous run per workgroup and template   256 sc0 sc1 stores
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     static_assert(inv_cols_park<TY>(), "symmetric I1 parks the spectrum");
     FftTw<TY> twr;
@@ -1464,10 +1362,6 @@ inv_cols_sym_body(const int cbx, const float2* __restrict__ uc, const float2* __
 #pragma unroll
             for (int u = 0; u < EP; ++u) park(xallB[u], pvv[u], xsB, u);
         }
-        if (SC_DBGBIT(dbg, 2) || (mirrored && SC_DBGBIT(dbg, 1))) {
-#pragma unroll
-            for (int u = 0; u < EP; ++u) hreg[u] = make_float2(1.f + u, 2.f);
-        } else
         fetch(0);
         if (mirrored) lds_barrier();      // mirrored fills read other threads' cells of xs
         for (int gi_ = 0; gi_ < NG; ++gi_) {
@@ -1497,27 +1391,14 @@ inv_cols_sym_body(const int cbx, const float2* __restrict__ uc, const float2* __
                 }
             }
             lds_barrier();
-            if (gi_ + 1 < NG && !SC_DBGBIT(dbg, 2) && !(mirrored && SC_DBGBIT(dbg, 1))) fetch(gi_ + 1);
-            if (!SC_DBGBIT(dbg, 8)) fft4_lines<TY, true>(sm, twr);
+            if (gi_ + 1 < NG) fetch(gi_ + 1);
+            fft4_lines<TY, true>(sm, twr);
             float2* o = (pl ? ym : yw) + (size_t)gi_ * plane + (size_t)(cb >> 1) * 16 + (cb & 1) * 8;
             const int e_lo = 4 * rp_lo, e_hi = 4 * (rp_hi + 1);
-            if (!SC_DBGBIT(dbg, 4))
 #pragma unroll 2
             for (int e = e_lo + threadIdx.x; e < e_hi; e += NT) {
                 int rp = e >> 2, k = e & 3;
                 float2 x0 = sm[lidx<TY>(k, 2 * rp)], x1 = sm[lidx<TY>(k, 2 * rp + 1)];
-#ifdef SC_ABLATE
-                if (dbg & (16 | 32 | 64 | 128 | 256)) {
-                    float2* dst = o + (size_t)rp * (Tx >> 3) * 16 + 2 * k;
-                    if (dbg & 16)        // row pairs (2q, 2q+1) of this block -> one whole line in row pair 2q + (cb & 1)
-                        dst = (pl ? ym : yw) + (size_t)gi_ * plane + (size_t)(cb >> 1) * 16 +
-                              (size_t)((rp & ~1) + (cb & 1)) * (Tx >> 3) * 16 + (rp & 1) * 8 + 2 * k;
-                    if (dbg & 128)       // the workgroup's cells of this template as one contiguous run
-                        dst = (pl ? ym : yw) + (size_t)gi_ * plane + (size_t)cb * (TY * 4) + 2 * (size_t)e;
-                    store_flavour(dst, x0, x1, (dbg & 32) ? 1 : (dbg & 64) ? 2 : (dbg & 256) ? 3 : 0);
-                    continue;
-                }
-#endif
                 store_stream(o + (size_t)rp * (Tx >> 3) * 16 + 2 * k, x0, x1);
             }
             lds_barrier();
@@ -1532,10 +1413,10 @@ k_inv_cols_sym(const float2* __restrict__ uc, const float2* __restrict__ uc2,
                const float* __restrict__ wa, const float* __restrict__ mb, int Tx,
                int cb0, int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
                int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
-               float2* __restrict__ ym, int ystride, int dbg, int np, int pcj, int tstride,
+               float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
                const TileDev* __restrict__ tiles, int py_valid) {
     inv_cols_sym_body<TY, MIRROR, PT>((int)blockIdx.x, uc, uc2, wa, mb, Tx, cb0, pair, vfirst, G, rp_lo, rp_hi, phx,
-                                      parity, tw, yw, ym, ystride, dbg, np, pcj, tstride, tiles, py_valid);
+                                      parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid);
 }
 
 // Both halves in ONE launch, a column block and the mirror block that streams (three of four
@@ -1555,16 +1436,16 @@ k_inv_cols_symx(const float2* __restrict__ uc, const float2* __restrict__ uc2,
                 const float* __restrict__ wa, const float* __restrict__ mb, int Tx,
                 int pair, int vfirst, int G, int rp_lo, int rp_hi, const float2* __restrict__ phx,
                 int parity, const float2* __restrict__ tw, float2* __restrict__ yw,
-                float2* __restrict__ ym, int ystride, int dbg, int np, int pcj, int tstride,
+                float2* __restrict__ ym, int ystride, int np, int pcj, int tstride,
                 const TileDev* __restrict__ tiles, int py_valid) {
     const int j = blockIdx.x, i = ((j >> 4) << 3) | (j & 7);
     if constexpr (!XP) TAKE_TEMPLATE_SHARE(PT, (size_t)TY * Tx)
     if ((j >> 3) & 1)
         inv_cols_sym_body<TY, true, PT, XP>((Tx >> 2) - 1 - i, uc, uc2, wa, mb, Tx, 0, pair, vfirst, G, rp_lo, rp_hi, phx,
-                                            parity, tw, yw, ym, ystride, dbg, np, pcj, tstride, tiles, py_valid);
+                                            parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid);
     else
         inv_cols_sym_body<TY, false, PT, XP>(i, uc, uc2, wa, mb, Tx, 0, pair, vfirst, G, rp_lo, rp_hi, phx,
-                                             parity, tw, yw, ym, ystride, dbg, np, pcj, tstride, tiles, py_valid);
+                                             parity, tw, yw, ym, ystride, np, pcj, tstride, tiles, py_valid);
 }
 
 // ---- I1 for symmetric templates, one WAVE per column ----------------------------------
@@ -1591,7 +1472,7 @@ template <int TY>
 __host__ __device__ constexpr int w8_line() { return TY + TY / 16 + 4; }   // lines 8 banks apart: the store pass reads 8 lines x 2 cells
 template <int TY>
 __host__ __device__ constexpr size_t w8_lds() {          // eight lines + the twiddle bases of stages 1 and 2
-    return ((size_t)8 * w8_line<TY>() + (SC_I1_TWTAB ? 16 : 4) * (TY / 16 + TY / 256) + SC_MAX_GROUP) * sizeof(float2);   // + the stored row range per transform
+    return ((size_t)8 * w8_line<TY>() + 4 * (TY / 16 + TY / 256) + SC_MAX_GROUP) * sizeof(float2);   // + the stored row range per transform
 }
 
 template <int TY, bool MIRROR, bool PT, int NC>
@@ -1634,7 +1515,7 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
     // compiler lose count of the coefficient prefetch in flight - every use of a prefetched value
     // then waited for ALL outstanding loads (s_waitcnt vmcnt(0): 70 of them in the four-wave
     // paired-template kernel instead of 8, 1 416 us per C2 launch instead of 878).
-    int2* const rng = reinterpret_cast<int2*>(sm + NC * LINE + (SC_I1_TWTAB ? 16 : 4) * (S + S / 16));
+    int2* const rng = reinterpret_cast<int2*>(sm + NC * LINE + 4 * (S + S / 16));
     {
         const int NGt = PT ? (G + 1) / 2 : G;
         const int gi_ = threadIdx.x;
@@ -1668,26 +1549,9 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
     // 1, 2, 4, 8) in an LDS table behind the lines, [m][tt] and [m][tt >> 4]: 64 registers of
     // parked spectrum leave no room for them
     float2* t1 = sm + NC * LINE;
-#if SC_I1_TWTAB
-    // all fifteen twiddles per set, [k][tt] and [k][tt >> 4] (entry k = 0 unused): forming w^3, w^5 .. w^15 from the
-    // four bases in every transform was 88 of its 640 packed instructions.  The same products in the same order
-    // (twiddle16_expand): the same bits.
-    float2* t2 = t1 + 16 * S;
-    for (int i = threadIdx.x; i < S + S / 16; i += 64 * NC) {
-        const bool st2 = i >= S;
-        const int e = st2 ? (i - S) << 4 : i, n = st2 ? S / 16 : S;
-        float2* t = st2 ? t2 + (i - S) : t1 + i;
-        const float2 wb[4] = {tw[e], tw[2 * e], tw[4 * e], tw[8 * e]};
-        pk::v2 wk[16];
-        twiddle16_expand(wb, wk);
-#pragma unroll
-        for (int k = 1; k < 16; ++k) t[k * n] = make_float2(wk[k].x, wk[k].y);
-    }
-#else
     float2* t2 = t1 + 4 * S;
     for (int i = threadIdx.x; i < 4 * S; i += 64 * NC) t1[i] = tw[(i % S) << (i / S)];
     for (int i = threadIdx.x; i < 4 * (S / 16); i += 64 * NC) t2[i] = tw[((i % (S / 16)) << 4) << (i / (S / 16))];
-#endif
     auto tw_of = [&](const float2* t, int n, int idx, float2 (&wq)[4]) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) wq[m] = lds_cell<true>(t + m * n + idx);
@@ -1755,59 +1619,34 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
             asm volatile("" ::: "memory");                       // (the whole line is in registers before stage 1 writes to it)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-#if SC_I1_TWTAB
-                set_compute_store<TY, 16, 0, false, true>(line, lt + 64 * u, a[u], wq, t1 + lt + 64 * u, S);
-#else
                 tw_of(t1, S, lt + 64 * u, wq);
-                set_compute_store<TY, 16, 0, false, false, true>(line, lt + 64 * u, a[u], wq);
-#endif
+                set_compute_store<TY, 16, 0, false>(line, lt + 64 * u, a[u], wq);
             }
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
-            if constexpr (SC_I1_XLANE) {
-                float2 o2[U][16];
+            float2 o2[U][16];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-#if SC_I1_TWTAB
-                    set_compute_regs<false, true>(a[u], wq, o2[u], t2 + ((lt + 64 * u) >> 4), S / 16);
-#else
-                    tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
-                    set_compute_regs<false>(a[u], wq, o2[u]);
-#endif
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int mh = 0; mh < 4; ++mh) {
-                        xlane_transpose4(o2[u][4 * mh].x, o2[u][4 * mh + 1].x, o2[u][4 * mh + 2].x, o2[u][4 * mh + 3].x);
-                        xlane_transpose4(o2[u][4 * mh].y, o2[u][4 * mh + 1].y, o2[u][4 * mh + 2].y, o2[u][4 * mh + 3].y);
-                    }
-                constexpr int R3x = TY / 256, NB3 = 16 / R3x;
-#pragma unroll
-                for (int u3 = 0; u3 < U; ++u3)
-#pragma unroll
-                    for (int b = 0; b < NB3; ++b)
-#pragma unroll
-                        for (int j = 0; j < R3x; ++j) a[u3][b + NB3 * j] = o2[j >> 2][4 * (u3 + U * b) + (j & 3)];
-            } else {
-                asm volatile("" ::: "memory");
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-#if SC_I1_TWTAB
-                    set_compute_store<TY, 16, 4, false, true>(line, lt + 64 * u, a[u], wq, t2 + ((lt + 64 * u) >> 4), S / 16);
-#else
-                    tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
-                    set_compute_store<TY, 16, 4, false, false, true>(line, lt + 64 * u, a[u], wq);
-#endif
-                }
-                asm volatile("" ::: "memory");
-#pragma unroll
-                for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
-                asm volatile("" ::: "memory");
+            for (int u = 0; u < U; ++u) {
+                tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
+                set_compute_regs<false>(a[u], wq, o2[u]);
             }
 #pragma unroll
-            for (int u = 0; u < U; ++u) set_compute_store<TY, TY / 256, 8, false, false, true>(line, lt + 64 * u, a[u], wq);
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int mh = 0; mh < 4; ++mh) {
+                    xlane_transpose4(o2[u][4 * mh].x, o2[u][4 * mh + 1].x, o2[u][4 * mh + 2].x, o2[u][4 * mh + 3].x);
+                    xlane_transpose4(o2[u][4 * mh].y, o2[u][4 * mh + 1].y, o2[u][4 * mh + 2].y, o2[u][4 * mh + 3].y);
+                }
+            constexpr int R3x = TY / 256, NB3 = 16 / R3x;
+#pragma unroll
+            for (int u3 = 0; u3 < U; ++u3)
+#pragma unroll
+                for (int b = 0; b < NB3; ++b)
+#pragma unroll
+                    for (int j = 0; j < R3x; ++j) a[u3][b + NB3 * j] = o2[j >> 2][4 * (u3 + U * b) + (j & 3)];
+#pragma unroll
+            for (int u = 0; u < U; ++u) set_compute_store<TY, TY / 256, 8, false>(line, lt + 64 * u, a[u], wq);
             asm volatile("" ::: "memory");
             // natural order out: the lane's cells fy = lane + 64 k, as the spectrum layout gave them
             park([&](int k) { return lds_cell<true>(line + ph(lt + 64 * k)); });
@@ -1850,12 +1689,8 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
                     a1[j] = PT ? make_float2(xp[k].x * c[k] - xp[k].y * c2[k], xp[k].x * c2[k] + xp[k].y * c[k])
                                : make_float2(c[k] * xp[k].x, c[k] * xp[k].y);
                 }
-#if SC_I1_TWTAB
-                set_compute_store<TY, 16, 0, true, true>(line, lt + 64 * u, a1, wq, t1 + lt + 64 * u, S);
-#else
                 tw_of(t1, S, lt + 64 * u, wq);
-                set_compute_store<TY, 16, 0, true, false, true>(line, lt + 64 * u, a1, wq);
-#endif
+                set_compute_store<TY, 16, 0, true>(line, lt + 64 * u, a1, wq);
             }
             // next coefficients: all of them now - or, two planes of them (PT) and two sets per lane,
             // the second set's only once the transform's registers are free again
@@ -1865,57 +1700,32 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
             float2 a[U][16];
 #pragma unroll
             for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
-            constexpr bool XLANE = SC_I1_XLANE && (TY == 2048 || TY == 1024);
-            if constexpr (XLANE) {
-                // stage 2 into registers, the exchange across lanes, stage 3 from registers (see xlane_transpose4)
-                float2 o2[U][16];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-#if SC_I1_TWTAB
-                    set_compute_regs<true, true>(a[u], wq, o2[u], t2 + ((lt + 64 * u) >> 4), S / 16);
-#else
-                    tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
-                    set_compute_regs<true>(a[u], wq, o2[u]);
-#endif
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int mh = 0; mh < 4; ++mh) {
-                        xlane_transpose4(o2[u][4 * mh].x, o2[u][4 * mh + 1].x, o2[u][4 * mh + 2].x, o2[u][4 * mh + 3].x);
-                        xlane_transpose4(o2[u][4 * mh].y, o2[u][4 * mh + 1].y, o2[u][4 * mh + 2].y, o2[u][4 * mh + 3].y);
-                    }
-                constexpr int R3x = TY / 256, NB3 = 16 / R3x;      // stage 3: radix 8 / 4, two / four butterflies per set
-#pragma unroll
-                for (int u3 = 0; u3 < U; ++u3) {
-                    // butterfly b of set u3 takes a[b + NB3 j] = element (lt + 64 u3 + S b) + 256 j: set j >> 2, output
-                    // 4 (u3 + U b) + (lane row), of the lane in row j & 3
-#pragma unroll
-                    for (int b = 0; b < NB3; ++b)
-#pragma unroll
-                        for (int j = 0; j < R3x; ++j) a[u3][b + NB3 * j] = o2[j >> 2][4 * (u3 + U * b) + (j & 3)];
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) set_compute_store<TY, TY / 256, 8, true, false, true>(line, lt + 64 * u, a[u], wq);
-            } else {
+            // stage 2 into registers, the exchange across lanes, stage 3 from registers (see xlane_transpose4)
+            float2 o2[U][16];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-#if SC_I1_TWTAB
-                set_compute_store<TY, 16, 4, true, true>(line, lt + 64 * u, a[u], wq, t2 + ((lt + 64 * u) >> 4), S / 16);
-#else
                 tw_of(t2, S / 16, (lt + 64 * u) >> 4, wq);
-                set_compute_store<TY, 16, 4, true, false, true>(line, lt + 64 * u, a[u], wq);
-#endif
+                set_compute_regs<true>(a[u], wq, o2[u]);
             }
-            asm volatile("" ::: "memory");
-            }
-            if constexpr (TY > 256 && !XLANE) {
-                constexpr int R3 = TY / 256;
 #pragma unroll
-                for (int u = 0; u < U; ++u) set_load<TY, true>(line, lt + 64 * u, a[u]);
+            for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int u = 0; u < U; ++u) set_compute_store<TY, R3, 8, true, false, true>(line, lt + 64 * u, a[u], wq);
+                for (int mh = 0; mh < 4; ++mh) {
+                    xlane_transpose4(o2[u][4 * mh].x, o2[u][4 * mh + 1].x, o2[u][4 * mh + 2].x, o2[u][4 * mh + 3].x);
+                    xlane_transpose4(o2[u][4 * mh].y, o2[u][4 * mh + 1].y, o2[u][4 * mh + 2].y, o2[u][4 * mh + 3].y);
+                }
+            constexpr int R3x = TY / 256, NB3 = 16 / R3x;      // stage 3: radix 8 / 4, two / four butterflies per set
+#pragma unroll
+            for (int u3 = 0; u3 < U; ++u3) {
+                // butterfly b of set u3 takes a[b + NB3 j] = element (lt + 64 u3 + S b) + 256 j: set j >> 2, output
+                // 4 (u3 + U b) + (lane row), of the lane in row j & 3
+#pragma unroll
+                for (int b = 0; b < NB3; ++b)
+#pragma unroll
+                    for (int j = 0; j < R3x; ++j) a[u3][b + NB3 * j] = o2[j >> 2][4 * (u3 + U * b) + (j & 3)];
             }
+#pragma unroll
+            for (int u = 0; u < U; ++u) set_compute_store<TY, TY / 256, 8, true>(line, lt + 64 * u, a[u], wq);
             lds_barrier();                                   // all eight lines are complete
             if (SPLIT && gi_ + 1 < NG) fetch(gi_ + 1, 1);
             // ---- store: lane (q, c) of wave w takes column c of row pair rp_lo + 8 w + 64 it + q:
@@ -1931,28 +1741,9 @@ inv_cols_w8_body(const int B, const int jobx, const float2* __restrict__ uc, con
             constexpr int RQ = 64 / NC;                      // row pairs per store instruction
             const int2 sr = rng[gi_];                        // (one LDS word pair, the same for every lane)
             const int s_lo = __builtin_amdgcn_readfirstlane(sr.x), s_hi = __builtin_amdgcn_readfirstlane(sr.y);
-#ifdef SC_I1_PRIO
-            __builtin_amdgcn_s_setprio(3);                   // (experiment: the store pass ahead of other waves' butterflies)
-#endif
-#if SC_Y_ROWMAJOR
-            if constexpr (NC == 8) {                         // (lab: the eight-column kernel only)
-                float2* orow = (pl ? ym : yw) + (size_t)gi_ * plane + (size_t)B * 8 + (ln & 7);
-#pragma unroll 2
-                for (int rp = s_lo + RQ * w + ln / NC; rp <= s_hi; rp += RQ * NC) {
-                    typedef float f2 __attribute__((ext_vector_type(2)));
-                    const float2 c0 = lds_cell<true>(lc + ph(2 * rp)), c1 = lds_cell<true>(lc + ph(2 * rp + 1));
-                    float2* p = orow + (size_t)(2 * rp) * Tx;
-                    __builtin_nontemporal_store(f2{c0.x, c0.y}, reinterpret_cast<f2*>(p));
-                    __builtin_nontemporal_store(f2{c1.x, c1.y}, reinterpret_cast<f2*>(p + Tx));
-                }
-            } else
-#endif
 #pragma unroll 2
             for (int rp = s_lo + RQ * w + ln / NC; rp <= s_hi; rp += RQ * NC)
                 store_stream(o + (size_t)rp * (Tx >> 3) * 16, lds_cell<true>(lc + ph(2 * rp)), lds_cell<true>(lc + ph(2 * rp + 1)));
-#ifdef SC_I1_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
         }
         lds_barrier();                                       // (the next plane's first barrier would do; kept simple)
     }
@@ -2174,14 +1965,13 @@ inv_cols_h2_body(const int B, const int jobx, const float2* __restrict__ uc, con
                                     : make_float2(c[j] * x.x, c[j] * x.y);
                 }
                 tw_of(t1, S, lt, wq);
-                set_compute_store<TY, 16, 0, true, false, true>(line, lt, a1, wq);
+                set_compute_store<TY, 16, 0, true>(line, lt, a1, wq);
             }
             if (gi_ + 1 < NG) fetch(gi_ + 1);
             asm volatile("" ::: "memory");
             float2 a[16];
             set_load<TY, true>(line, lt, a);
             tw_of(t2, S / 16, lt >> 4, wq);
-#if SC_H2_XLANE
             // Stage 2 into registers; stage 3 - radix 2 at stride 256 - across lanes.  Output m of lane hl's stage-2 set
             // is element (hl & 15) + 16 m + 256 (hl >> 4) of its column: the butterfly partner of every one of them sits
             // in the lane 16 further on (the other 16-lane row of the half-wave), same m.  v_permlane16_swap of a value
@@ -2202,12 +1992,6 @@ inv_cols_h2_body(const int B, const int jobx, const float2* __restrict__ uc, con
                     wb[17 * m] = make_float2(fmaf(sgn, hi_x, lo_x), fmaf(sgn, hi_y, lo_y));
                 }
             }
-#else
-            set_compute_store<TY, 16, 4, true, false, true>(line, lt, a, wq);
-            asm volatile("" ::: "memory");
-            set_load<TY, true>(line, lt, a);
-            set_compute_store<TY, 2, 8, true, false, true>(line, lt, a, wq);
-#endif
             lds_barrier();                                   // all sixteen lines are complete
             // ---- store: lane (q, c) of wave w takes column c of row pair s_lo + 4 w + 32 it + q: sixteen lanes write
             // the two 128-byte rows2 blocks of a row pair
@@ -2263,7 +2047,6 @@ struct RowArgs {
     int cy0, cx0, cw;                   // core origin and width
     int pair, first, G;
     int rp_lo, rp_n;                    // valid row pairs of the tile: [rp_lo, rp_lo + rp_n)
-    int dbg;                            // diagnostic ablation bits (SC_DBG), 0 in production
     int ystride;                        // planes between the Y blocks of consecutive jobs
     // orientation batching (fast kernel): the launch folds nb orientations of G templates each
     // (templates first + b*G + g, consecutive); the Y block of (orientation b, pair q of the
@@ -2355,11 +2138,11 @@ k_inv_rows(const float2* __restrict__ yw, const float2* __restrict__ ym,
             bool okB = ri >= 0 && ri < tB.vy && cj >= 0 && cj < tB.vx;
             if (okA) valid |= 1u << (2 * u);
             if (okB) valid |= 2u << (2 * u);
-            const bool rd = !map_amp && !SC_DBGBIT(ra.dbg, 8);
+            const bool rd = !map_amp;
             b_snr[2 * u] = (okA && rd) ? best_snr[(size_t)(tA.i0 + ri - ra.cy0) * ra.cw + (tA.j0 + cj - ra.cx0)] : 0.f;
             b_snr[2 * u + 1] = (okB && rd) ? best_snr[(size_t)(tB.i0 + ri - ra.cy0) * ra.cw + (tB.j0 + cj - ra.cx0)] : 0.f;
         }
-        if (!SC_DBGBIT(ra.dbg, 1)) fetch(0);
+        fetch(0);
         for (int gi_ = 0; gi_ < ra.G; ++gi_) {
             const TemplDev* tp = templ + ra.first + gi_;
             EpiScal es = sc_epi_scalars(sums, ra.first + gi_);
@@ -2380,79 +2163,77 @@ k_inv_rows(const float2* __restrict__ yw, const float2* __restrict__ ym,
                 sm[lidx<TX>(3, c)] = make_float2(yreg[u].z, yreg[u].w);
             }
             lds_barrier();
-            if (gi_ + 1 < ra.G && !SC_DBGBIT(ra.dbg, 1)) fetch(gi_ + 1);
-            if (!SC_DBGBIT(ra.dbg, 2)) fft4_lines<TX, true>(sm, twr);
-            if (!SC_DBGBIT(ra.dbg, 4)) {
-                // branch-free scoring of the 2E slots, then the (rare) stores
-                float t_amp[2 * E], t_snr[2 * E];
+            if (gi_ + 1 < ra.G) fetch(gi_ + 1);
+            fft4_lines<TX, true>(sm, twr);
+            // branch-free scoring of the 2E slots, then the (rare) stores
+            float t_amp[2 * E], t_snr[2 * E];
+#pragma unroll
+            for (int u = 0; u < E; ++u) {
+                int e = threadIdx.x + u * NT;
+                int r2 = e / TX, s = e - r2 * TX;
+                float2 xc = sm[lidx<TX>(r2, s)];
+                float2 t3 = sm[lidx<TX>(2 + r2, s)];
+                int ri, cj;
+                locate(u, ri, cj);
+#pragma unroll
+                for (int part = 0; part < 2; ++part) {
+                    const int c = 2 * u + part;
+                    float amp, snr;
+                    sc_epilogue((part ? xc.y : xc.x) * scale_w,
+                                (part ? t3.y : t3.x) * scale, es, amp, snr);
+                    bool keep = (valid >> c) & 1u;
+                    if (FULL) {
+                        if (keep)
+                            sc_apply_masks(*tp, g, xaxis, yaxis, (part ? tB.i0 : tA.i0) + ri,
+                                           (part ? tB.j0 : tA.j0) + cj, amp, snr);
+                    } else {
+                        keep = keep && (part ? (ri >= rloB && ri <= rhiB && cj >= cloB && cj <= chiB)
+                                             : (ri >= rloA && ri <= rhiA && cj >= cloA && cj <= chiA));
+                    }
+                    t_amp[c] = keep ? amp : 0.f;
+                    t_snr[c] = keep ? snr : 0.f;
+                }
+            }
+            unsigned won = 0;
+            if (map_amp) {
+                won = valid;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 2 * E; ++c) {
+                    // sc_fold on the SNR alone: take if greater; a NaN score
+                    // poisons the cell once (core.py:230-240, see sc_fold)
+                    float bs = b_snr[c], ts = t_snr[c];
+                    bool take = bs < ts;
+                    bool poison = (ts != ts) && (bs == bs);
+                    b_snr[c] = (take || poison) ? ts : bs;
+                    if (take || poison) won |= 1u << c;
+                }
+            }
+            if (won) {
 #pragma unroll
                 for (int u = 0; u < E; ++u) {
-                    int e = threadIdx.x + u * NT;
-                    int r2 = e / TX, s = e - r2 * TX;
-                    float2 xc = sm[lidx<TX>(r2, s)];
-                    float2 t3 = sm[lidx<TX>(2 + r2, s)];
                     int ri, cj;
                     locate(u, ri, cj);
 #pragma unroll
                     for (int part = 0; part < 2; ++part) {
                         const int c = 2 * u + part;
-                        float amp, snr;
-                        sc_epilogue((part ? xc.y : xc.x) * scale_w,
-                                    (part ? t3.y : t3.x) * scale, es, amp, snr);
-                        bool keep = (valid >> c) & 1u;
-                        if (FULL) {
-                            if (keep)
-                                sc_apply_masks(*tp, g, xaxis, yaxis, (part ? tB.i0 : tA.i0) + ri,
-                                               (part ? tB.j0 : tA.j0) + cj, amp, snr);
+                        if (!((won >> c) & 1u)) continue;
+                        size_t o = (size_t)((part ? tB.i0 : tA.i0) + ri - ra.cy0) * ra.cw +
+                                   ((part ? tB.j0 : tA.j0) + cj - ra.cx0);
+                        if (map_amp) {
+                            map_amp[o] = t_amp[c];
+                            map_snr[o] = t_snr[c];
                         } else {
-                            keep = keep && (part ? (ri >= rloB && ri <= rhiB && cj >= cloB && cj <= chiB)
-                                                 : (ri >= rloA && ri <= rhiA && cj >= cloA && cj <= chiA));
-                        }
-                        t_amp[c] = keep ? amp : 0.f;
-                        t_snr[c] = keep ? snr : 0.f;
-                    }
-                }
-                unsigned won = 0;
-                if (map_amp) {
-                    won = valid;
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 2 * E; ++c) {
-                        // sc_fold on the SNR alone: take if greater; a NaN score
-                        // poisons the cell once (core.py:230-240, see sc_fold)
-                        float bs = b_snr[c], ts = t_snr[c];
-                        bool take = bs < ts;
-                        bool poison = (ts != ts) && (bs == bs);
-                        b_snr[c] = (take || poison) ? ts : bs;
-                        if (take || poison) won |= 1u << c;
-                    }
-                }
-                if (won && !SC_DBGBIT(ra.dbg, 8)) {
-#pragma unroll
-                    for (int u = 0; u < E; ++u) {
-                        int ri, cj;
-                        locate(u, ri, cj);
-#pragma unroll
-                        for (int part = 0; part < 2; ++part) {
-                            const int c = 2 * u + part;
-                            if (!((won >> c) & 1u)) continue;
-                            size_t o = (size_t)((part ? tB.i0 : tA.i0) + ri - ra.cy0) * ra.cw +
-                                       ((part ? tB.j0 : tA.j0) + cj - ra.cx0);
-                            if (map_amp) {
-                                map_amp[o] = t_amp[c];
-                                map_snr[o] = t_snr[c];
-                            } else {
-                                bool nan = t_snr[c] != t_snr[c];
-                                best_snr[o] = t_snr[c];
-                                best_amp[o] = nan ? 0.f : t_amp[c];
-                                best_id[o] = nan ? SC_ID_NONE : tid_;
-                                if (ra.stats) {       // a win; near the resolution floor? (see k_inv_rows_fast)
-                                    const float xr_ = t_amp[c] / es.inv_ts, T1 = xr_ * t_amp[c];
-                                    const float fl = es.d3 + fabsf(xr_) * es.dx2 + es.dxx;
-                                    const float d = (T1 / t_snr[c] - (float)SC_EPS) / es.inv_n;
-                                    atomicAdd(ra.stats, 1ull);
-                                    if (fl > 0.f && d < 256.f * fl) atomicAdd(ra.stats + 1, 1ull);
-                                }
+                            bool nan = t_snr[c] != t_snr[c];
+                            best_snr[o] = t_snr[c];
+                            best_amp[o] = nan ? 0.f : t_amp[c];
+                            best_id[o] = nan ? SC_ID_NONE : tid_;
+                            if (ra.stats) {       // a win; near the resolution floor? (see k_inv_rows_fast)
+                                const float xr_ = t_amp[c] / es.inv_ts, T1 = xr_ * t_amp[c];
+                                const float fl = es.d3 + fabsf(xr_) * es.dx2 + es.dxx;
+                                const float d = (T1 / t_snr[c] - (float)SC_EPS) / es.inv_n;
+                                atomicAdd(ra.stats, 1ull);
+                                if (fl > 0.f && d < 256.f * fl) atomicAdd(ra.stats + 1, 1ull);
                             }
                         }
                     }
@@ -2483,43 +2264,6 @@ k_inv_rows(const float2* __restrict__ yw, const float2* __restrict__ ym,
 // small LDS tables.  The two rows of a rows2 pair share their 128-byte lines:
 // their workgroups are given block ids 8 apart, i.e. the same XCD at the same
 // time, so the second reader hits in that XCD's L2.
-#ifndef SC_I2_WAVES
-#define SC_I2_WAVES 4      // waves per SIMD the fast row kernel is compiled for (LDS fits 4 workgroups per CU)
-#endif
-#ifndef SC_I2_FETCH_AT
-#define SC_I2_FETCH_AT 0
-#endif
-#ifndef SC_I2_GRP
-#define SC_I2_GRP 8         // output pairs per record branch of the row pass (SC_I2_RAREWIN); 4, 2, 1: the 2048 kernel spills 44 - 92 B
-#endif
-#ifndef SC_I2_RAREWIN
-#ifndef SC_I2_NEAR_WAVES
-#define SC_I2_NEAR_WAVES 4  // waves per SIMD the near-tie variant is compiled for (round 6: four, like the plain kernel - event loop, amplitude stored at a win)
-#endif
-#ifndef SC_I2_SITE
-#define SC_I2_SITE 0        // lab (round 6): the record's update under a branch per output inside the record branch - measured, not kept
-#endif
-#ifndef SC_I2_AMPW_PLAIN
-#define SC_I2_AMPW_PLAIN 0  // lab (round 6): the plain row kernel stores a winner's amplitude at the win as well
-#endif
-#ifndef SC_I2_NEAR_AMPW
-#define SC_I2_NEAR_AMPW 1
-#endif
-#ifndef SC_I2_NEAR_LOOP
-#define SC_I2_NEAR_LOOP 1   // (round 6) the near-tie events of a record branch from a loop over a mask instead of one site per output
-#endif
-#ifndef SC_I2_NEAR_RARE
-#define SC_I2_NEAR_RARE 1   // the near-tie variant of the row pass on the deferred record update too (0: selects and a test per output)
-#endif
-#ifndef SC_I2_RARE512
-#define SC_I2_RARE512 1     // the deferred record update in the 512-cell row kernels too (round 5, end: row pass of the small grids -4.5 %; 0: selects)
-#endif
-#define SC_I2_RAREWIN 1     // the row pass records a winner's output and index under a rarely taken branch (0: selects per output)
-#endif
-#ifndef SC_I2_STATIC
-#define SC_I2_STATIC 0     // 1: templates whose window limits cover a whole tile row skip the range test per output (stage 3); measured, see DESIGN.md
-#endif
-
 template <int TX>
 __host__ __device__ constexpr bool inv_rows_fast_ok() { return TX == 512 || TX == 1024 || TX == 2048; }
 
@@ -2548,13 +2292,12 @@ __host__ __device__ constexpr size_t inv_rows_fast_lds_split() {
     return inv_rows_fast_lds<TX>() + (size_t)SC_MAX_GROUP * EPI_FLOATS * sizeof(float);
 }
 
-// (FULL - error masks, per-cell masks of generic plugins - carries the mask test's float64 coordinates: at four
-//  waves per SIMD it spilled 76 - 92 B per lane inside the template loop; SC_I2_WAVES_FULL waves, 168 registers)
-#ifndef SC_I2_WAVES_FULL
-#define SC_I2_WAVES_FULL 3
-#endif
+// Waves per SIMD: four (128 registers) - the LDS fits four workgroups per CU - for the plain kernel and for the
+// near-tie variant (event loop, amplitude stored at a win).  Three (168 registers) for FULL - error masks, per-cell
+// masks of generic plugins: it carries the mask test's float64 coordinates and spilled 76 - 92 B per lane inside the
+// template loop at four - and for the near-tie variant with paired templates.
 template <int TX, bool FULL, bool MAPS, bool PT, bool SPLITK = false, bool NEAR = false>
-__global__ void __launch_bounds__(inv_rows_fast_threads<TX>(), NEAR ? (PT ? 3 : SC_I2_NEAR_WAVES) : (FULL && !MAPS) ? SC_I2_WAVES_FULL : SC_I2_WAVES)
+__global__ void __launch_bounds__(inv_rows_fast_threads<TX>(), NEAR ? (PT ? 3 : 4) : (FULL && !MAPS) ? 3 : 4)
 k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
                 RowArgs ra, Geom g, const TileDev* __restrict__ tiles,
                 const TemplDev* __restrict__ templ, const double* __restrict__ sums,
@@ -2573,7 +2316,6 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
     constexpr int NU = NB3 / 2;                // butterflies per plane per thread in stage 3
     constexpr int NC = NU * R3;                // cells per thread (= 8)
     constexpr int LINE = fft_line(TX);
-    constexpr int FETCH_AT = SC_I2_FETCH_AT;   // next template's points: 0 after stage 1, 1 after stage 2
     static_assert(inv_rows_fast_threads<TX>() == NT && NC == 8, "fast I2 geometry");
     const int id = threadIdx.x;
     // blocks b and b + 8 take the two rows of one pair (same XCD, same time)
@@ -2651,16 +2393,9 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
     const int pl1 = (S % 64 == 0) ? __builtin_amdgcn_readfirstlane(id / S) : id / S;
     const int tt1 = id % S;
     v2* line1 = sm + pl1 * LINE + 17 * tt1;
-#if SC_Y_ROWMAJOR
-    // lab: the hand-off row-major, Y[row][column] - the row reads whole 128-byte lines of its own
-    const char* src1 = reinterpret_cast<const char*>((pl1 ? ym : yw) + (size_t)(2 * rp + rh) * TX);
-    const uint32_t voff1 = (uint32_t)(tt1 * sizeof(float2));
-    constexpr size_t JSTRIDE1 = (size_t)S * sizeof(float2);
-#else
     const char* src1 = reinterpret_cast<const char*>((pl1 ? ym : yw) + (size_t)rp * 2 * TX);
     const uint32_t voff1 = (uint32_t)(((tt1 >> 3) * 16 + (tt1 & 7) * 2 + rh) * sizeof(float2));
     constexpr size_t JSTRIDE1 = (size_t)2 * S * sizeof(float2);
-#endif
     // stage-2 mapping (standard): line id / S, set tt2
     const int tt2 = id % S;
     v2* line2 = sm + (id / S) * LINE;
@@ -2724,12 +2459,10 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
     // write-back (the kernel is VALU-bound: every instruction per cell counts).
     constexpr int NBEST = PT ? NC : 2 * NC;
     constexpr uint32_t NONE = 0xFFFFFFFFu;
-    // NEAR (round 6): a winner's amplitude is STORED when it wins (the record branch) instead of its transform output
+    // NEAR: a winner's amplitude is STORED when it wins (the record branch) instead of its transform output
     // being carried in sixteen registers to the write-back - the same product of the same two floats; with the event
     // loop's temporaries the near-tie variant then fits the plain kernel's four waves per SIMD
-    constexpr bool AMPW = (NEAR && !PT && SC_I2_NEAR_LOOP && SC_I2_NEAR_AMPW) ||
-                          (SC_I2_AMPW_PLAIN && !NEAR && !PT && !MAPS && !FULL && !SPLITK);      // (lab: the plain kernel too)
-    static_assert(!(AMPW && SPLITK && !NEAR), "a later share's amplitudes go to its own plane");
+    constexpr bool AMPW = NEAR && !PT;
     auto best_of = [](int c, int part) { return PT ? c : 2 * c + part; };
     float b_snr[NBEST], b_xr[NBEST];
     uint32_t b_ix[NBEST / 4];                  // one byte per cell (0xFF: unchanged)
@@ -2754,11 +2487,7 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
 #pragma unroll
         for (int part = 0; part < (PT ? 1 : 2); ++part) {
             const bool ok = !MAPS && row_of(part) && cj >= 0 && cj < tile_of(part).vx && !(SPLITK && !NEAR && blockIdx.z > 0);
-            // (a cell outside the tile's valid extent holds +inf: nothing compares greater, so the
-            //  templates whose window-limit rectangle covers the whole tile row need no range test
-            //  per output - STATIC below; such a cell is never written back, its winner byte stays NONE)
-            b_snr[best_of(c, part)] = ok ? at_bytes(best_snr + off_of(part), 4u * (uint32_t)cj)
-                                         : ((SC_I2_STATIC && !MAPS && !FULL) ? __builtin_inff() : 0.f);
+            b_snr[best_of(c, part)] = ok ? at_bytes(best_snr + off_of(part), 4u * (uint32_t)cj) : 0.f;
             b_xr[best_of(c, part)] = 0.f;
         }
     }
@@ -2846,7 +2575,7 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
             sib_on = sib_wait(sib_theirs, ra.sib.base + gi_ + 1);
         lds_barrier();
         if (more) fp += (size_t)(nxt - cur - 1) * plane * sizeof(float2);      // (planes of skipped transforms)
-        if (FETCH_AT == 0 && more) {
+        if (more) {
             fetch();                                             // in flight through stages 2-3
             if (sib_mine && id == 0) sib_publish(sib_mine, ra.sib.base + gi_ + 2);
         }
@@ -2854,14 +2583,13 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
         {
             v2 b[16];
 #pragma unroll
-            for (int j = 0; j < 16; ++j) b[j] = lds_cell2<SC_I2_RD1 != 0>(rd2 + j * (S + S / 16));
+            for (int j = 0; j < 16; ++j) b[j] = lds_cell2<true>(rd2 + j * (S + S / 16));
             lds_barrier();
             pk::B<16, true>::run(b);
             wr2[0] = b[pk::B<16, true>::pos(0)];
 #pragma unroll
             for (int m = 1; m < 16; ++m) wr2[17 * m] = pk::cmul(b[pk::B<16, true>::pos(m)], twp2[m]);
         }
-        if (FETCH_AT == 1 && more) fetch();                      // in flight through stage 3
         lds_barrier();
         // ---- stage 3 (radix R3, stride 256) fused with the epilogue: every
         // output is scored as soon as its two butterflies have produced it.
@@ -2874,7 +2602,6 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
         unsigned span[2];
         int base[2];
         uint32_t tix[2];
-        bool covers[2];
 #pragma unroll
         for (int part = 0; part < 2; ++part) {
             const int tgo = PT ? 2 * ok_ + part : ok_;            // template within its orientation
@@ -2895,33 +2622,25 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
             }
             span[part] = (r && hi >= lo) ? (unsigned)(hi - lo) : 0u;
             base[part] = (r && hi >= lo) ? lo : 0x40000000;      // no column reaches it
-            // STATIC: every cell of the part's valid extent may score (the rectangle covers columns
-            // 0 .. vx-1 of this row), or none can whatever the test says (the row lies outside the tile:
-            // its cells hold +inf)
-            covers[part] = !row_of(part) || (r && lo == 0 && hi == t.vx - 1);
         }
-        const bool all_in = SC_I2_STATIC && !FULL && !MAPS && covers[0] && covers[1];     // workgroup-uniform
         const float near_lo = NEAR ? 1.f - 1.0001f * ra.near_w - 2e-7f : 1.f;             // (NEAR, deferred form: candidates score above the record times this)
         const float near_up = 1.f - ra.near_w;                                            // (a winner times this at or below the record it beat: a near-tie)
-        auto stage3 = [&](auto static_tag) {
-        constexpr bool STATIC = decltype(static_tag)::value;
+        // (a lambda called once: written in line, the compiler schedules the row kernels differently)
+        auto stage3 = [&]() {
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             v2 vw[R3], vm[R3];
 #pragma unroll
             for (int k = 0; k < R3; ++k) {
-                vw[k] = lds_cell2<SC_I2_RD1 != 0>(lineW + u * (2 * S + 2 * S / 16) + k * 272);
-                vm[k] = lds_cell2<SC_I2_RD1 != 0>(lineM + u * (2 * S + 2 * S / 16) + k * 272);
+                vw[k] = lds_cell2<true>(lineW + u * (2 * S + 2 * S / 16) + k * 272);
+                vm[k] = lds_cell2<true>(lineM + u * (2 * S + 2 * S / 16) + k * 272);
             }
             pk::B<R3, true>::run(vw);
             pk::B<R3, true>::run(vm);
-            // (RARE: every row length since the end of round 5.  The 512-cell kernels kept the selects while the deferred form
-            //  cost them a scratch reload inside the template loop; it no longer does - 16 B outside the loop in the dealt-out
-            //  form - and their row pass is 4.5 % faster with it: C1F 35.2 -> 34.9 ms, profiles/r05_launch_forms.txt)
-            // (NEAR, SC_I2_NEAR_RARE: the branch also stands for the near-ties - a score above the record LESS the window)
-            constexpr bool RARE = SC_I2_RAREWIN && (TX >= 1024 || SC_I2_RARE512) && (!NEAR || SC_I2_NEAR_RARE);
-            // (GRP outputs pairs per branch: the fewer cells a branch stands for, the more rarely it is taken)
-            constexpr int GRP = (RARE && SC_I2_GRP < R3) ? SC_I2_GRP : R3;
+            // (the record's update is deferred to a rarely taken branch, see below, one branch per GRP output pairs: all
+            //  R3 of a butterfly - with 4, 2 or 1 per branch the 2048 kernel spills 44 - 92 B.  At 512 cells the row pass
+            //  is 4.5 % faster than with selects per output, profiles/r05_launch_forms.txt)
+            constexpr int GRP = R3;
 #pragma unroll
             for (int m0 = 0; m0 < R3; m0 += GRP) {
             bool wonm[GRP][2];                 // lane masks (scalar register pairs): which outputs won their cell
@@ -2931,7 +2650,7 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
             for (int m = m0; m < m0 + GRP; ++m) {
                 const int c = u * R3 + m;
                 const v2 xc = vw[pk::B<R3, true>::pos(m)], t3 = vm[pk::B<R3, true>::pos(m)];
-                const int cj = STATIC ? 0 : col_of(c);
+                const int cj = col_of(c);
 #pragma unroll
                 for (int part = 0; part < 2; ++part) {
                     const int k = best_of(c, part);
@@ -2942,7 +2661,7 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
                     const float T1 = xr * xr * kt[part];
                     const float d = fmaxf(fmaf(tr, scale, -T1), fmaf(fabsf(xr), kx2[part], fl0[part]));
                     float snr = fabsf(T1 * __builtin_amdgcn_rcpf(fmaf(d, inv_n[part], (float)SC_EPS)));
-                    const bool in = STATIC || (unsigned)(cj - base[part]) <= span[part];
+                    const bool in = (unsigned)(cj - base[part]) <= span[part];
                     if (MAPS || FULL) {
                         float amp = xr * ka[part];
                         // `in` is the tile's valid extent here; masks per cell
@@ -2966,43 +2685,11 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
                         // sc_fold: take if greater, ties keep the incumbent; a cell outside
                         // the range (lean variant) or masked to 0 never wins
                         const bool won = (FULL || in) && snr > b_snr[k];
-                        if constexpr (NEAR && !RARE) {
-                            // a score within the window of the running best, either side of it - EQUAL scores included since the
-                            // end of round 5: two templates proportional to each other on a degenerate support (a Ricker window two
-                            // cells wide) score the same bits and differ at 1e-8 in float64; the grid's end twins (-pi/2, +pi/2: one
-                            // template) cost the event route two float64 pairs per cell they hold
-                            const float top = fmaxf(snr, b_snr[k]);
-                            const bool nt = in && snr > 0.f && fabsf(snr - b_snr[k]) <= ra.near_w * top;
-                            nearm |= nt ? (1u << k) : 0u;
-                            if (nt && ra.ev) {             // (before the record moves: b_ix still names the holder)
-                                const unsigned long long slot = atomicAdd(ra.ev_count, 1ull);
-                                if (slot < ra.ev_cap) {
-                                    const uint32_t hx = (b_ix[k >> 2] >> (8 * (k & 3))) & 0xFFu;
-                                    uint32_t* e = ra.ev + SC_EVENT_WORDS * slot;
-                                    e[0] = (uint32_t)(off_of(part) + (size_t)cj);
-                                    e[1] = tp->id;
-                                    // a holder from an earlier launch (or none yet: SC_ID_NONE) stands in the record's id plane
-                                    e[2] = hx != 0xFFu ? templ[ra.first + hx].id : at_bytes(best_id + off_of(part), 4u * (uint32_t)cj);
-                                    e[3] = __float_as_uint(top);
-                                }
-                            }
-                        }
-                        if constexpr (RARE) {
-                            // (NEAR: a candidate - a win, or a score inside the window below the record; near_lo = 1 - near_w less a hair)
-#ifdef SC_I2_NEAR_NOMUL                    // timing probe only: the near-tie variant without its window (flags nothing below the record)
-                            const bool cand = won;
-#else
-                            const bool cand = NEAR ? (in && snr > b_snr[k] * near_lo) : won;
-#endif
-                            wonm[m - m0][part] = cand;
-                            snrs[m - m0][part] = snr;
-                            anyw = anyw || cand;
-                        } else {
-                            b_snr[k] = won ? snr : b_snr[k];
-                            b_xr[k] = won ? xr : b_xr[k];
-                            const uint32_t bm = 0xFFu << (8 * (k & 3));
-                            b_ix[k >> 2] = won ? ((b_ix[k >> 2] & ~bm) | (tix[part] & bm)) : b_ix[k >> 2];
-                        }
+                        // (NEAR: a candidate - a win, or a score inside the window below the record; near_lo = 1 - near_w less a hair)
+                        const bool cand = NEAR ? (in && snr > b_snr[k] * near_lo) : won;
+                        wonm[m - m0][part] = cand;
+                        snrs[m - m0][part] = snr;
+                        anyw = anyw || cand;
                     }
                 }
             }
@@ -3012,11 +2699,12 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
             // template (the kernel is bound by vector issue).  The compare against the record is repeated under the
             // branch: where two templates ride one transform (PT) the second meets the first's update there.
             // Same order, same values: the record is identical.
-            if (RARE && !MAPS && __builtin_amdgcn_ballot_w64(anyw) != 0ull) {
-                // NEAR, one template per transform (round 6): the events of a branch's near-ties come from a LOOP over a mask
+            if (!MAPS && __builtin_amdgcn_ballot_w64(anyw) != 0ull) {
+                // NEAR, one template per transform: the events of a branch's near-ties come from a LOOP over a mask
                 // after the record's update (sixteen unrolled emission sites, each with its atomic and its addresses, cost the
                 // kernel 41 registers and its fourth wave per SIMD: 168 -> 128).
-                constexpr bool NEAR_LOOP = NEAR && !PT && SC_I2_NEAR_LOOP;
+                constexpr bool NEAR_LOOP = NEAR && !PT;      // (AMPW: such a winner's amplitude is stored right here)
+                static_assert(NEAR_LOOP == AMPW, "the event loop and the amplitude stored at a win go together");
                 // NEAR_LOOP: which of the branch's outputs are near-ties costs no vector instruction of its own - a candidate
                 // that does NOT win lies inside the window below the record (that is what made it a candidate); one that
                 // wins is tested against the window's upper side under the branch its amplitude's store takes anyway.
@@ -3057,48 +2745,25 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
                             }
                         }
                         const bool won = wonm[m - m0][part] && snr > b_snr[k];
-                        // (SC_I2_SITE, lab: the record moves under a branch of its own per output.  A cell is won nine times in a
-                        //  search of 6335 templates - ln 6335: the float32 SNRs come in no particular order, whatever order
-                        //  the orientations are searched in - 0.14 % of all (cell, template) pairs; the branch above stands
-                        //  for 1024 cells of the wave and is taken three times in four, one output's 64 cells hold a win one
-                        //  time in twelve.  Skipping the update's 80 vector instructions eleven times in twelve is worth
-                        //  nothing: C3 3.16 -> 3.16 .. 3.22 s with it, five record entries in scratch -
-                        //  profiles/r06_row_pass_probes.txt: the row pass is not bound by its vector instruction count)
-                        const bool any_won = !SC_I2_SITE || PT || __builtin_amdgcn_ballot_w64(won) != 0ull;
                         if constexpr (NEAR_LOOP) {
                             bool nt = wonm[m - m0][part] && !won;                 // below the record, inside the window (equal scores too)
-                            if (any_won) {
-                                nt = nt || (won && snr * near_up <= b_snr[k]);    // won, and the record it beat lies inside the window
-                                if constexpr (AMPW) {
-                                    if (won)
-                                        at_bytes(amp_dst + off_of(part), 4u * (uint32_t)col_of(u * R3 + m)) = (part ? xc.y : xc.x) * ka[part];
-                                } else {
-                                    b_xr[k] = won ? (part ? xc.y : xc.x) : b_xr[k];
-                                }
-                            }
+                            nt = nt || (won && snr * near_up <= b_snr[k]);        // won, and the record it beat lies inside the window
+                            if (won)
+                                at_bytes(amp_dst + off_of(part), 4u * (uint32_t)col_of(u * R3 + m)) = (part ? xc.y : xc.x) * ka[part];
                             if (__builtin_amdgcn_ballot_w64(nt) != 0ull) {
                                 top1 = (nt && ntm == 0u) ? fmaxf(snr, b_snr[k]) : top1;     // (b_snr[k]: still the record the output met)
                                 ntm |= nt ? (1u << (2 * (m - m0) + part)) : 0u;
                             }
                         }
-                        if (any_won) {
-                            b_snr[k] = won ? snr : b_snr[k];
-                            if constexpr (!NEAR_LOOP) {
-                                if constexpr (AMPW) {
-                                    if (won)
-                                        at_bytes(amp_dst + off_of(part), 4u * (uint32_t)col_of(u * R3 + m)) = (part ? xc.y : xc.x) * ka[part];
-                                } else {
-                                    b_xr[k] = won ? (part ? xc.y : xc.x) : b_xr[k];
-                                }
-                            }
-                            const uint32_t bm = 0xFFu << (8 * (k & 3));
-                            b_ix[k >> 2] = won ? ((b_ix[k >> 2] & ~bm) | (tix[part] & bm)) : b_ix[k >> 2];
-                        }
+                        b_snr[k] = won ? snr : b_snr[k];
+                        if constexpr (!NEAR_LOOP) b_xr[k] = won ? (part ? xc.y : xc.x) : b_xr[k];
+                        const uint32_t bm = 0xFFu << (8 * (k & 3));
+                        b_ix[k >> 2] = won ? ((b_ix[k >> 2] & ~bm) | (tix[part] & bm)) : b_ix[k >> 2];
                     }
                 }
                 if constexpr (NEAR_LOOP) {
                     // the events, after the update: the outputs' scores and values are dead by now - the loop's temporaries
-                    // take their registers instead of a fourth wave per SIMD (round 6: 168 registers -> 128)
+                    // take their registers instead of a fourth wave per SIMD (168 registers -> 128)
                     bool first_ev = true;
                     while (ntm) {                          // (per lane; a near-tie is three in a million outputs)
                         const int bit = __builtin_ctz(ntm);
@@ -3129,12 +2794,7 @@ k_inv_rows_fast(const float2* __restrict__ yw, const float2* __restrict__ ym,
             }
         }
         };
-#if SC_I2_STATIC == 2                     // timing probe only: every template on the static path (wrong at the DEM's borders)
-        stage3(std::true_type{});
-#else
-        if (all_in) stage3(std::true_type{});
-        else stage3(std::false_type{});
-#endif
+        stage3();
         lds_barrier();
         if (!more) break;
         cur = nxt;
@@ -3523,7 +3183,7 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
                            (const float*)ctx->B.p, (const float*)ctx->C.p, mixc, \
                            ctx->g, (const TileDev*)ctx->tiles.p, fg.Ty,        \
                            (const float2*)ctx->tw_x.p, rows_out,               \
-                           (double*)ctx->norm_part.p, ctx->dbg, np,            \
+                           (double*)ctx->norm_part.p, np,                      \
                            (size_t)ctx->g.ly * ctx->g.lx);                     \
     }
 #define FN(T) { if (coef) FN2(T, true) else FN2(T, false) }
@@ -3721,13 +3381,13 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
             n_i1 += symx ? 1 : 2;            // one paired launch, or own columns + mirrors
 #define COL_ARGS(CB0)                                                          \
     ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, (const float2*)ctx->wh.p, \
-        (const float2*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi, ctx->dbg,        \
+        (const float2*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi, \
         (const float2*)ctx->tw_y.p, ywp, ymp, group, np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py
 #define SYM_ARGS(CB0)                                                          \
     ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, (const float*)ctx->wh.p, \
-        (const float*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi,                    \
+        (const float*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi, \
         (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group
-#define SYM_ARGS_D(CB0) SYM_ARGS(CB0), ctx->dbg, np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py
+#define SYM_ARGS_D(CB0) SYM_ARGS(CB0), np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py
 #define FN_SYMX(T)                                                             \
     {                                                                          \
         int rc = set_lds(ctx, k_inv_cols_symx<T, PTV>, inv_cols_lds<T>());     \
@@ -3739,7 +3399,7 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                            inv_cols_lds<T>(), ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, \
                            (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
                            (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
-                           ctx->dbg, np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py); \
+                           np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py); \
     }
 #define FN_W8(T)                                                               \
     {                                                                          \
@@ -3822,7 +3482,7 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                                    ldsx, ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off,
                                    (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi,
                                    (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, 1,
-                                   ctx->dbg, np, 1, nb, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py);
+                                   np, 1, nb, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py);
             } else if (w8 && (!PTV || (fg.Ty == 1024 && ctx->variant != 1))) {
                 if (fg.Ty == 2048) FN_W8(2048) else FN_W8(1024)
             } else if (w8 && PTV && fg.Ty == 2048 && ctx->variant != 1) {
@@ -3895,7 +3555,7 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
             const float2* ym_s = (const float2*)ctx->ym.p + yoff;
             const double* norms_s = (const double*)ctx->norms.p + ctx->norms_off + (size_t)2 * np * b0;
             RowArgs ra{fg.Ty, fg.Py, fg.Qx, fg.circ_y, fg.circ_x, ctx->g.cy0, ctx->g.cx0,
-                       ctx->g.cx1 - ctx->g.cx0, pair, first + g0 + b0 * n, G, rp_lo, rp_n, ctx->dbg, group,
+                       ctx->g.cx1 - ctx->g.cx0, pair, first + g0 + b0 * n, G, rp_lo, rp_n, group,
                        nbc, np, pc, SibSync{nullptr, 0}, (unsigned long long*)ctx->res_stats.p, 0, row_skip ? 1 : 0,
                        1, 0, nullptr, nullptr, nullptr, 0.f, nullptr};
             if (xp) {                            // to the row pass: ONE orientation of nb templates, in pairs

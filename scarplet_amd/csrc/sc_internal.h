@@ -13,14 +13,6 @@
 // (round 6: the settle drops an event whose scores the final record has left behind by more than the window)
 #define SC_EVENT_WORDS 4
 
-// Timing-only ablation bits (skip loads / transforms / stores of a kernel; the
-// results are wrong while one is set).  They exist only in a -DSC_ABLATE build
-// (tools/ablate.sh); in the shipped library the tests fold to constants.
-#ifdef SC_ABLATE
-#define SC_DBGBIT(d, b) (((d) & (b)) != 0)
-#else
-#define SC_DBGBIT(d, b) false
-#endif
 #define SC_EXP_UNDERFLOW 745.1332191019412 // exp(-u) != 0  <=>  u < 1075 ln 2
 
 // Device-side view of one template of the current batch.
@@ -165,7 +157,6 @@ struct sc_ctx {
     DevBuf split_s, split_a, split_i;   // scratch records of a split row pass (k_inv_rows_fast SPLITK, k_merge_split)
     DevBuf sib_buf;
     uint32_t sib_epoch = 0;
-    int dbg = 0;               // timing-only ablation bits; only an SC_ABLATE build reads them (tools/ablate.sh)
     // profiling
     int prof = 0;              // 0 off, k: time every k-th launch of a kernel
     int prof_cur = -1;         // kernel being bracketed (-1: not sampled)

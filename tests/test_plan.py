@@ -101,7 +101,7 @@ def test_single_tile_of_column_length_2048_is_replanned():
     assert _plan.Plan(2048, 2048, (0, 2048, 0, 2048), bbox, t_max=1024).Ty == 1024
 
 
-# ---- the wave-per-column pass's stage 2 -> stage 3 exchange across lanes (sc_fft.hip: xlane_transpose4, SC_I1_XLANE) ----------
+# ---- the wave-per-column pass's stage 2 -> stage 3 exchange across lanes (sc_fft.hip: xlane_transpose4) ----------
 def _xlane_model(T):
     """Lanes as numpy arrays: the Stockham placement of stage 2 (radix 16, stride 16) of one wave's line, the 4 x 4
     transposes between the 16-lane row and m & 3 that v_permlane32_swap / v_permlane16_swap perform, and the register

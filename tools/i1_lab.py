@@ -2,10 +2,9 @@
 """Kernel lab: the full C3 search (sustained: a warm-up search, then timed ones) under a list of
 engine option sets, in ONE process (the DEM is synthesised once).  Prints the step time and the
 per-kernel breakdown per option set, and checks every set's best record against the first set's
-(bit for bit) unless an ablation option ("dbg") makes its results meaningless.
+(bit for bit).
 
   python tools/i1_lab.py "variant=0" "variant=8"
-  SCARPLET_HIP_LIB=scarplet_amd/libscarplet_hip_ablate.so python tools/i1_lab.py "dbg=0" "dbg=4" ...
 """
 import argparse, os, sys, time
 import numpy as np
@@ -44,16 +43,11 @@ def apply(spec):
     for kv in spec.split(","):
         if kv:
             k, v = kv.split("=")
-            try:
-                m.ctx.set_option(k, float(v))
-            except Exception as e:          # "dbg" does not exist outside an SC_ABLATE build
-                print("   (option %s ignored: %s)" % (kv, e))
+            m.ctx.set_option(k, float(v))
 
 
 for spec in a.sets:
     apply(a.reset)
-    if "dbg" in a.reset or any("dbg" in s for s in a.sets):
-        apply("dbg=0")
     apply(spec)
     for _ in range(a.warmup):
         m.ctx.reset_best(); m.ctx.match(arr, sp, sync=True)
@@ -66,16 +60,14 @@ for spec in a.sets:
     m.ctx.profile(0)
     line = "  ".join("%s %.0f ms (%.1f us x %d)" % (k.replace("k_", ""), ms / a.steps, 1e3 * ms / max(n, 1), n // a.steps)
                      for k, (n, ms) in prof.items() if n)
-    check = ""
-    if "dbg" not in spec or spec.strip() == "dbg=0":
-        best = m.ctx.get_best()
-        if base is None:
-            base = best
-            check = "reference record"
-        else:
-            same = [bool(np.array_equal(x, y)) for x, y in zip(best, base)]
-            check = "record identical to the first set: amp %s snr %s id %s" % tuple(same)
-            if not all(same):
-                d = np.abs(best[1] - base[1])
-                check += "  (max |d snr| %.3g, cells differing %d)" % (d.max(), int((best[2] != base[2]).sum()))
+    best = m.ctx.get_best()
+    if base is None:
+        base = best
+        check = "reference record"
+    else:
+        same = [bool(np.array_equal(x, y)) for x, y in zip(best, base)]
+        check = "record identical to the first set: amp %s snr %s id %s" % tuple(same)
+        if not all(same):
+            d = np.abs(best[1] - base[1])
+            check += "  (max |d snr| %.3g, cells differing %d)" % (d.max(), int((best[2] != base[2]).sum()))
     print("%-28s step %.3f s  %.0f Mpx.t/s | %s | %s" % (spec, dt, units / dt, line, check), flush=True)
