@@ -482,6 +482,71 @@ int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long
                         int min_samples, int min_profiles, sc_segment_fit* out_rows, sc_segment_cell* out_cells,
                         double* out_sse);
 
+/*
+ * The centre shift (docs/profiles.md, "The centre shift"; docs/segments.md): trace cells do not sit on the scarp's
+ * centre, so the step of the model may move along the profile by a whole number of cells,
+ *   z(s) = c0 + b s + a erf((s - d de) / (2 sqrt(kt))),   d = -D..D.
+ * The profile is sampled exactly as sc_fit_profiles samples it (the same points, the same validity and min_samples
+ * rules about j = 0); the erf column of shift d is row j - d of a table over j = -(h + D)..(h + D) whose rows -h..h are
+ * the bits of the unshifted table, and for each (age i, shift d) the arithmetic is that of sc_fit_profiles.
+ *   single profile  sse*_i = min_d sse_id with d_i its argmin, the candidates taken in the order 0, -1, +1, -2, +2, ...
+ *                   and the first smallest winning; kt_index = argmin_i sse*_i (ties to the smallest index),
+ *                   shift_index = d_kt_index; a, b, c0, sse are those of that pair.  dof = n - 3 - (D > 0): a cell with
+ *                   dof < 1 has status 1 like an unusable one.  rmse = sqrt(sse / dof), thr = sse_min (1 + delta / dof),
+ *                   lo_index / hi_index walk along sse* (a profile likelihood over the shift).  Status 1, 2 and 4 as
+ *                   sc_fit_profiles; 8: |shift_index| == D with D > 0 - the range ended before the fit did
+ *   segment         every usable profile c takes its own d_ci by the single-profile rule at every age; the joint fit
+ *                   of sc_fit_segments at age i then has profile c's erf column shifted by d_ci.
+ *                   dof = n - 2 n_profiles - 1 - (D > 0 ? n_profiles : 0); status 8: a usable profile of the segment
+ *                   has |d_ci| == D at the best age, D > 0.  The parked bytes per cell grow by A (d_ci): 8 ((2h + 1) +
+ *                   4 A) + A, which is what SC_SEGMENT_MAX_PARK bounds here
+ * D = 0 returns the bytes of sc_fit_profiles / sc_fit_segments in every shared field; a segment of one usable profile
+ * returns the kt_index, lo_index, hi_index, status, a, sse and rmse of sc_fit_profiles_shift for that cell and its
+ * shift_index in the cell table, bit for bit.  out_sse holds sse* (K x A; S x A for segments: the pooled curve);
+ * out_shift: K x A int8 in the order of the cells, or NULL.  sc_fit_profiles_shift: d_i of every age, 0 in the rows of
+ * cells with status 1.  sc_fit_segments_shift: d_ci of every age for every USABLE cell - whether or not its segment is
+ * fitted (stage one does not know the segment) - and 0 in the rows of cells that are not usable; the cell table's
+ * shift_index is 0 wherever its b is NaN.  Refused before any device work: what the unshifted calls refuse, and D < 0 or D > h - min_samples
+ * (SC_ERR_INVALID), D > SC_PROFILE_MAX_SHIFT (SC_ERR_UNSUPPORTED).  The same bytes on every run; timed as SC_K_PROFILE.
+ */
+#define SC_PROFILE_MAX_SHIFT 64
+typedef struct sc_profile_shift_fit {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  n;               /* valid points of the profile                     */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;   /* the interval, as indices of the age grid   */
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) + 8 (shift at its limit) */
+    double   kt, kt_lo, kt_hi;
+    double   a, b, c0;        /* of the best (age, shift): the scarp's offset is 2 a */
+    double   sse, rmse;       /* rmse = sqrt(sse / dof)                          */
+    int32_t  shift_index;     /* d of the best age, in cells (0 where not fitted) */
+    double   shift;           /* d de (NaN where not fitted)                     */
+} sc_profile_shift_fit;
+typedef struct sc_segment_shift_cell {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  used;            /* 1: a usable profile                             */
+    int32_t  n;               /* valid points of the profile                     */
+    double   b, c0, sse;      /* at the segment's best age; NaN where not used or the segment is not fitted */
+    int32_t  shift_index;     /* d_ci at the segment's best age (0 where b is NaN) */
+} sc_segment_shift_cell;
+int sc_fit_profiles_shift(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                          const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
+                          sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift);
+int sc_fit_profiles_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                              const double* ca, long long K, const double* ages, int A, int h, int w, int D, double de,
+                              double delta, int min_samples, sc_profile_shift_fit* out_rows, double* out_sse,
+                              int8_t* out_shift);
+int sc_fit_segments_shift(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                          const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                          int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
+                          sc_segment_fit* out_rows, sc_segment_shift_cell* out_cells, double* out_sse,
+                          int8_t* out_shift);
+int sc_fit_segments_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                              const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                              long long S, const double* ages, int A, int h, int w, int D, double de, double delta,
+                              int min_samples, int min_profiles, sc_segment_fit* out_rows,
+                              sc_segment_shift_cell* out_cells, double* out_sse, int8_t* out_shift);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32

@@ -94,6 +94,18 @@ PROFILE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fit._fields_],
                           "offsets": [getattr(sc_profile_fit, f).offset for f, _ in sc_profile_fit._fields_],
                           "itemsize": C.sizeof(sc_profile_fit)})
 PROFILE_MAX_AGES, PROFILE_MAX_HALF, PROFILE_MAX_SWATH = 64, 1024, 32   # SC_PROFILE_MAX_*
+PROFILE_MAX_SHIFT = 64                                                 # SC_PROFILE_MAX_SHIFT
+
+
+class sc_profile_shift_fit(C.Structure):
+    """One row of sc_fit_profiles_shift / sc_fit_profiles_shift_dem: sc_profile_fit and the shift of the best age."""
+    _fields_ = sc_profile_fit._fields_ + [("shift_index", C.c_int32), ("shift", C.c_double)]
+
+
+PROFILE_SHIFT_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_shift_fit._fields_],
+                                "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8 + [np.int32, np.float64],
+                                "offsets": [getattr(sc_profile_shift_fit, f).offset for f, _ in sc_profile_shift_fit._fields_],
+                                "itemsize": C.sizeof(sc_profile_shift_fit)})
 
 
 class sc_segment_fit(C.Structure):
@@ -120,6 +132,18 @@ SEGMENT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_cell._fields_]
                                "offsets": [getattr(sc_segment_cell, f).offset for f, _ in sc_segment_cell._fields_],
                                "itemsize": C.sizeof(sc_segment_cell)})
 SEGMENT_MAX_PARK = 1 << 32                                             # SC_SEGMENT_MAX_PARK
+
+
+class sc_segment_shift_cell(C.Structure):
+    """One cell of the cell table of sc_fit_segments_shift / sc_fit_segments_shift_dem."""
+    _fields_ = sc_segment_cell._fields_ + [("shift_index", C.c_int32)]
+
+
+SEGMENT_SHIFT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_shift_cell._fields_],
+                                     "formats": [np.int64, np.int32, np.int32] + [np.float64] * 3 + [np.int32],
+                                     "offsets": [getattr(sc_segment_shift_cell, f).offset
+                                                 for f, _ in sc_segment_shift_cell._fields_],
+                                     "itemsize": C.sizeof(sc_segment_shift_cell)})
 
 
 class sc_xfer(C.Structure):
@@ -198,6 +222,18 @@ SIGNATURES = {
     "sc_fit_segments_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
                                       C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int,
                                       C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_profiles_shift": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int,
+                                        C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_profiles_shift_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                            _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
+                                            C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_segments_shift": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_segments_shift_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -508,52 +544,66 @@ class Context(object):
             "sc_trace_result")
 
     # -- scarp-profile dating (docs/profiles.md) ------------------------------------
-    def fit_profiles(self, cells, sa, ca, ages, h, w, de, delta, min_samples, curve=False, z=None):
+    def fit_profiles(self, cells, sa, ca, ages, h, w, de, delta, min_samples, curve=False, z=None, shift=None,
+                     shift_plane=False):
         """sc_fit_profiles on the context's DEM, or sc_fit_profiles_dem on ``z`` (float64, C-contiguous, 2-D):
-        (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous."""
+        (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous.  With ``shift`` (D, the
+        range of the centre shift in cells) the _shift calls: (rows, curve or None, (K, A) int8 shifts or None)."""
         for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
             assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A = len(cells), len(ages)
         assert len(sa) == K and len(ca) == K
-        rows = np.zeros(K, dtype=PROFILE_DTYPE)
+        rows = np.zeros(K, dtype=PROFILE_DTYPE if shift is None else PROFILE_SHIFT_DTYPE)
         sse = np.empty((K, A), dtype=np.float64) if curve else None
         tail = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h),
-                int(w), float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p),
-                _as(sse, _dp) if curve else None]
+                int(w)] + ([] if shift is None else [int(shift)]) + \
+               [float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None]
+        name = "sc_fit_profiles"
+        plane = None
+        if shift is not None:
+            name = "sc_fit_profiles_shift"
+            plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
+            tail.append(plane.ctypes.data_as(C.c_void_p) if shift_plane else None)
         if z is None:
-            self._check(self.lib.sc_fit_profiles(self._h, *tail), "sc_fit_profiles")
+            self._check(getattr(self.lib, name)(self._h, *tail), name)
         else:
             assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            self._check(self.lib.sc_fit_profiles_dem(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail),
-                        "sc_fit_profiles_dem")
-        return rows, sse
+            self._check(getattr(self.lib, name + "_dem")(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail), name + "_dem")
+        return (rows, sse) if shift is None else (rows, sse, plane)
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
     def fit_segments(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
-                     cell_table=False, curve=False, z=None):
+                     cell_table=False, curve=False, z=None, shift=None, shift_plane=False):
         """sc_fit_segments on the context's DEM, or sc_fit_segments_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, cell table or None, curve or None).  cells and seg_start int64, seg_label int32, sa / ca / ages
-        float64, all 1-D and C-contiguous; the cells grouped by segment."""
+        float64, all 1-D and C-contiguous; the cells grouped by segment.  With ``shift`` (D, the range of the centre
+        shift in cells) the _shift calls: (rows, cell table or None, curve or None, (K, A) int8 shifts or None)."""
         for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
                      (seg_label, np.int32)):
             assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A, S = len(cells), len(ages), len(seg_label)
         assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
         rows = np.zeros(S, dtype=SEGMENT_FIT_DTYPE)
-        tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE) if cell_table else None
+        tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE if shift is None else SEGMENT_SHIFT_CELL_DTYPE) if cell_table else None
         sse = np.empty((S, A), dtype=np.float64) if curve else None
         llp = C.POINTER(C.c_longlong)
         tail = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), float(de),
-                float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w)] + \
+               ([] if shift is None else [int(shift)]) + \
+               [float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
                 tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
+        name = "sc_fit_segments"
+        plane = None
+        if shift is not None:
+            name = "sc_fit_segments_shift"
+            plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
+            tail.append(plane.ctypes.data_as(C.c_void_p) if shift_plane else None)
         if z is None:
-            self._check(self.lib.sc_fit_segments(self._h, *tail), "sc_fit_segments")
+            self._check(getattr(self.lib, name)(self._h, *tail), name)
         else:
             assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            self._check(self.lib.sc_fit_segments_dem(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail),
-                        "sc_fit_segments_dem")
-        return rows, tab, sse
+            self._check(getattr(self.lib, name + "_dem")(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail), name + "_dem")
+        return (rows, tab, sse) if shift is None else (rows, tab, sse, plane)
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

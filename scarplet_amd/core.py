@@ -877,12 +877,12 @@ class Matcher(object):
         return traces._traces(*self.ctx.trace_result(par, ang, lo, hi, mc))
 
     def fit_profiles(self, traces_or_cells, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
-                     return_curve=False, angle=None):
+                     return_curve=False, angle=None, max_shift=None, return_shift=False):
         """``sl.fit_profiles`` on the DEM this matcher holds on the device (docs/profiles.md) - no upload.  Given
         the ``Traces`` of ``extract_traces`` it fits the cells of the segments (``labels > 0``, row-major order) with
         the angle plane of this matcher's result and adds a ``label`` column; given cells (as ``sl.fit_profiles``
         takes them) it reads that plane at the cells unless ``angle`` says otherwise.  The bytes are those of
-        ``sl.fit_profiles`` on the same data."""
+        ``sl.fit_profiles`` on the same data, ``max_shift`` and ``return_shift`` included."""
         from scarplet_amd import profiles, traces
         if not getattr(self, "whole", False):
             raise ValueError("fit_profiles needs the whole DEM on the device, not a block of it")
@@ -898,18 +898,19 @@ class Matcher(object):
             angle = self.result_array()[2]
         args = profiles.check_args((self.ny, self.nx), self.de, cells, angle, half_length, swath, ages, delta,
                                    min_samples)
-        return profiles._run(self.ctx, args, self.nx, return_curve, label=label)
+        D = profiles.check_shift(max_shift, return_shift, args[6], args[4], args[8])
+        return profiles._run(self.ctx, args, self.nx, return_curve, label=label, shift=D, return_shift=return_shift)
 
     def fit_segments(self, traces, half_length, swath=0, ages=None, delta=1.0, min_samples=4, min_profiles=1,
-                     return_cells=False, return_curve=False, strike="cell"):
+                     return_cells=False, return_curve=False, strike="cell", max_shift=None, return_shift=False):
         """``sl.fit_segments`` on the DEM this matcher holds on the device (docs/segments.md) - no upload: one age,
         one amplitude and one interval per segment of ``traces`` (the ``Traces`` of ``extract_traces``), fitted
         jointly to the profiles of all its cells.  One row per row of ``traces.segments``, in that order.
         ``strike="cell"`` cuts each profile across the orientation this matcher's result has at the cell;
         ``strike="segment"`` gives every cell of a segment that segment's ``strike`` from the table: parallel
         profiles, sturdier where single-cell orientations are noisy.  The bytes are those of ``sl.fit_segments`` on
-        the same data."""
-        from scarplet_amd import segments, traces as tr
+        the same data, ``max_shift`` and ``return_shift`` included."""
+        from scarplet_amd import profiles, segments, traces as tr
         if not getattr(self, "whole", False):
             raise ValueError("fit_segments needs the whole DEM on the device, not a block of it")
         if not isinstance(traces, tr.Traces):
@@ -929,8 +930,9 @@ class Matcher(object):
         else:
             angle = self.result_array()[2]
         args = segments.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, ages, delta,
-                                   min_samples, min_profiles)
-        return segments._run(self.ctx, args, self.nx, return_cells, return_curve)
+                                   min_samples, min_profiles, shift=max_shift is not None)
+        D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
+        return segments._run(self.ctx, args, self.nx, return_cells, return_curve, shift=D, return_shift=return_shift)
 
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one

@@ -48,9 +48,9 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
-                     &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse};
+                     &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift};
     size_t s = 0;
     for (DevBuf* b : arr) s += b->cap;
     for (auto& w : c->windows) s += (size_t)w.h * w.wd * 13;
@@ -226,9 +226,9 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
-                     &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse};
+                     &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift};
     for (DevBuf* b : arr) buf_free(*b);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp[k]);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp_in[k]);

@@ -374,33 +374,298 @@ __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_st
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// host side
+// the centre shift (sc_fit_segments_shift): k_sg_partial, k_sg_resid and k_sg_choose with a shift d_ci per profile
+// and age; the rank and sum kernels above serve both
 // ---------------------------------------------------------------------------------------------------------------
-static long long sg_cap_cells(int A, int h) {
-    return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) + 4ll * A));
+__device__ __forceinline__ int sg_shift_dof(int m, int n, int D) { return n - 2 * m - 1 - (D > 0 ? m : 0); }
+
+// k_sg_partial with the shift search of sc_fit_profiles_shift (sh_search: lanes over the (shift, age) pairs): parks the
+// profile, sbar, pbar, beta and per age ebar, gamma, See, Sep AT d_ci, and d_ci itself
+template <bool TAB_LDS>
+__global__ __launch_bounds__(SG_THREADS) void k_sg_shift(const double* __restrict__ z, int ny, int nx,
+                                                         const long long* __restrict__ cells,
+                                                         const double* __restrict__ dir, long long K, int A, int h, int w,
+                                                         int D, double de, int min_samples,
+                                                         const double* __restrict__ tab_g, double* __restrict__ prof_g,
+                                                         int* __restrict__ cn, int* __restrict__ used,
+                                                         double* __restrict__ scal, double* __restrict__ planes,
+                                                         signed char* __restrict__ shifts) {
+    extern __shared__ double sg_lds[];
+    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* prof = sg_lds + (size_t)wave * np;
+    double* slot = sg_lds + (size_t)SG_WAVES * np + (size_t)wave * sh_slot_doubles(A);
+    const double* tab = tab_g;
+    if (TAB_LDS) {
+        double* t = sg_lds + (size_t)SG_WAVES * (np + sh_slot_doubles(A));
+        for (int idx = threadIdx.x; idx < nt * A; idx += SG_THREADS) t[idx] = tab_g[idx];
+        tab = t;
+    }
+    __syncthreads();
+    const int* srank = (const int*)(slot + (size_t)SH_TERMS * A);
+    const size_t stride = (size_t)K * A;                 // one per-cell-and-age plane
+    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * SG_WAVES + wave;
+        const bool act = kc < K;
+        if (act) {
+            const long long cell = cells[kc];
+            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
+            const double r = (double)(cell / nx), c = (double)(cell % nx);
+            for (int jj = lane; jj < np; jj += 64) {
+                const double p = pf_point(z, ny, nx, r, c, sa, ca, jj, h, w);
+                prof[jj] = p;
+                prof_g[(size_t)kc * np + jj] = p;
+            }
+        }
+        __syncthreads();
+        if (act) {
+            // what depends on neither the age nor the shift, once: pass 0's counts and sums of s and p
+            int n = 0, n_neg = 0, n_pos = 0;
+            double Ss = 0.0, Sp = 0.0;
+            for (int jj = 0; jj < np; ++jj) {
+                const double p = prof[jj];
+                if (p != p) continue;
+                ++n;
+                n_neg += jj < h ? 1 : 0;
+                n_pos += jj > h ? 1 : 0;
+                Ss += (double)(jj - h) * de;
+                Sp += p;
+            }
+            const bool ok = n_neg >= min_samples && n_pos >= min_samples;
+            if (lane == 0) {
+                cn[kc] = n;
+                used[kc] = ok ? 1 : 0;
+            }
+            if (!ok) {
+                if (lane < A) shifts[(size_t)kc * A + lane] = 0;
+            } else {
+                const double dn = (double)n;
+                const double sbar = Ss / dn, pbar = Sp / dn;
+                // ... and pass 1's centred s against itself and p
+                double Sss = 0.0, Sps = 0.0;
+                for (int jj = 0; jj < np; ++jj) {
+                    const double p = prof[jj];
+                    if (p != p) continue;
+                    const double sc = (double)(jj - h) * de - sbar;
+                    Sss += sc * sc;
+                    Sps += sc * (p - pbar);
+                }
+                const double beta = Sps / Sss;
+                sh_search(prof, tab, np, h, A, D, de, lane, dn, sbar, pbar, Sss, beta, slot);
+                if (lane == 0) {
+                    scal[3 * kc] = sbar;
+                    scal[3 * kc + 1] = pbar;
+                    scal[3 * kc + 2] = beta;
+                }
+                if (lane < A) {
+                    const size_t o = (size_t)kc * A + lane;
+                    planes[o] = slot[3 * A + lane];
+                    planes[stride + o] = slot[4 * A + lane];
+                    planes[2 * stride + o] = slot[A + lane];
+                    planes[3 * stride + o] = slot[2 * A + lane];
+                    shifts[o] = (signed char)sh_shift_of(srank[lane]);
+                }
+            }
+        }
+        __syncthreads();
+    }
 }
 
-static int sg_check(sc_ctx* ctx, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
+// k_sg_resid with row j - d_ci of the table over j = -(h + D)..(h + D)
+template <bool TAB_LDS>
+__global__ __launch_bounds__(SG_THREADS) void k_sg_resid_shift(const double* __restrict__ prof_g, const int* __restrict__ cseg,
+                                                               const int* __restrict__ used, const int* __restrict__ cnt,
+                                                               const double* __restrict__ scal, double* __restrict__ planes,
+                                                               const signed char* __restrict__ shifts,
+                                                               const double* __restrict__ tot, long long K, int A, int h,
+                                                               int D, double de, int min_profiles,
+                                                               const double* __restrict__ tab_g) {
+    extern __shared__ double sg_lds[];
+    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* prof = sg_lds + (size_t)wave * np;
+    const double* tab = tab_g;
+    if (TAB_LDS) {
+        double* t = sg_lds + (size_t)SG_WAVES * np;
+        for (int idx = threadIdx.x; idx < nt * A; idx += SG_THREADS) t[idx] = tab_g[idx];
+        tab = t;
+    }
+    __syncthreads();
+    const int ia = min(lane, A - 1);
+    const size_t stride = (size_t)K * A;
+    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * SG_WAVES + wave;
+        bool act = kc < K;
+        int s = 0;
+        if (act) {
+            s = cseg[kc];
+            const int m = cnt[2 * s];
+            act = used[kc] != 0 && m >= min_profiles && sg_shift_dof(m, cnt[2 * s + 1], D) >= 1;
+        }
+        if (act)
+            for (int jj = lane; jj < np; jj += 64) prof[jj] = prof_g[(size_t)kc * np + jj];
+        __syncthreads();
+        if (act) {
+            const size_t o = (size_t)kc * A + ia;
+            const double sbar = scal[3 * kc], pbar = scal[3 * kc + 1], beta = scal[3 * kc + 2];
+            const double ebar = planes[o], gamma = planes[stride + o];
+            const double See = tot[((size_t)s * 2) * A + ia], Sep = tot[((size_t)s * 2 + 1) * A + ia];
+            const double* col = tab + (size_t)(D - (int)shifts[o]) * A + ia;
+            const double a = Sep / See;
+            const double b = beta - a * gamma;
+            const double c0 = (pbar - a * ebar) - b * sbar;
+            double sse = 0.0;
+            for (int jj = 0; jj < np; ++jj) {
+                const double p = prof[jj];
+                if (p != p) continue;
+                const double sj = (double)(jj - h) * de;
+                const double res = p - ((c0 + b * sj) + a * col[(size_t)jj * A]);
+                sse += res * res;
+            }
+            if (lane < A) planes[2 * stride + o] = sse;
+        }
+        __syncthreads();
+    }
+}
+
+// k_sg_choose with the shift's degrees of freedom, status bit 8 and the cells' shift at the best age
+__global__ __launch_bounds__(64) void k_sg_choose_shift(const int* __restrict__ seg_start, const int* __restrict__ label,
+                                                        const int* __restrict__ cnt, long long S, long long K,
+                                                        const double* __restrict__ tot, const double* __restrict__ tsse,
+                                                        const double* __restrict__ ages, int A, int D, double delta,
+                                                        int min_profiles, const long long* __restrict__ cells,
+                                                        const int* __restrict__ cn, const int* __restrict__ used,
+                                                        const double* __restrict__ scal, const double* __restrict__ planes,
+                                                        const signed char* __restrict__ shifts,
+                                                        sc_segment_fit* __restrict__ rows,
+                                                        sc_segment_shift_cell* __restrict__ out_cells,
+                                                        double* __restrict__ curve) {
+    const int lane = threadIdx.x;
+    const int ia = min(lane, A - 1);
+    const double nan = __builtin_nan("");
+    const size_t stride = (size_t)K * A;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int start = seg_start[s], end = seg_start[s + 1];
+        const int m = cnt[2 * s], n = cnt[2 * s + 1];
+        const int dof = sg_shift_dof(m, n, D);
+        const bool fitted = m >= min_profiles && dof >= 1;
+        sc_segment_fit* out = rows + s;
+        int best = -1;
+        double a_best = nan;
+        if (!fitted) {
+            if (lane == 0) {
+                out->label = label[s];
+                out->n_cells = end - start;
+                out->n_profiles = m;
+                out->n = n;
+                out->dof = dof;
+                out->kt_index = -1;
+                out->lo_index = -1;
+                out->hi_index = -1;
+                out->status = 1;
+                out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
+                out->a = nan; out->sse = nan; out->rmse = nan;
+            }
+            if (curve && lane < A) curve[s * A + lane] = nan;
+        } else {
+            const double sse = tsse[(size_t)s * A + ia];
+            const double a = tot[((size_t)s * 2 + 1) * A + ia] / tot[((size_t)s * 2) * A + ia];
+            if (curve && lane < A) curve[s * A + lane] = sse;
+            // argmin over the ages, ties to the smaller index (a NaN never wins)
+            double mn = lane < A ? sse : INFINITY;
+            if (mn != mn) mn = INFINITY;
+            int mi = lane;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) {
+                const double om = __shfl_xor(mn, o, 64);
+                const int oi = __shfl_xor(mi, o, 64);
+                if (om < mn || (om == mn && oi < mi)) { mn = om; mi = oi; }
+            }
+            best = min(mi, A - 1);
+            const double thr = mn * (1.0 + delta / (double)dof);
+            const unsigned long long ok = __ballot(lane < A && sse <= thr);
+            int lo = best, hi = best;
+            while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
+            while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
+            a_best = __shfl(a, best, 64);
+            // a usable profile whose shift at the best age sits at the end of the range
+            bool at_end = false;
+            if (D > 0)
+                for (int k = start + lane; k < end; k += 64) {
+                    const int d = shifts[(size_t)k * A + best];
+                    at_end = at_end || (used[k] != 0 && (d == D || d == -D));
+                }
+            const bool any_end = __ballot(at_end) != 0ull;
+            if (lane == best) {
+                out->label = label[s];
+                out->n_cells = end - start;
+                out->n_profiles = m;
+                out->n = n;
+                out->dof = dof;
+                out->kt_index = best;
+                out->lo_index = lo;
+                out->hi_index = hi;
+                out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0) + (any_end ? 8 : 0);
+                out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
+                out->a = a;
+                out->sse = sse; out->rmse = sqrt(sse / (double)dof);
+            }
+        }
+        if (!out_cells) continue;
+        for (int k = start + lane; k < end; k += 64) {
+            // (field by field: the struct ends in padding, which the host cleared)
+            sc_segment_shift_cell* c = out_cells + k;
+            const int u = used[k];
+            double b = nan, c0 = nan, sse = nan;
+            int d = 0;
+            if (fitted && u) {
+                const size_t o = (size_t)k * A + best;
+                b = scal[3 * k + 2] - a_best * planes[stride + o];
+                c0 = (scal[3 * k + 1] - a_best * planes[o]) - b * scal[3 * k];
+                sse = planes[2 * stride + o];
+                d = shifts[o];
+            }
+            c->cell = cells[k];
+            c->used = u;
+            c->n = cn[k];
+            c->b = b; c->c0 = c0; c->sse = sse;
+            c->shift_index = d;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+// (D < 0 throughout the host side: the call without a shift, its kernels and its bytes)
+static long long sg_cap_cells(int A, int h, int D) {
+    return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) + 4ll * A) + (D >= 0 ? A : 0));
+}
+
+static int sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
                     long long K, const long long* seg_start, const int32_t* seg_label, long long S, const double* ages,
-                    int A, int h, int w, double de, double delta, int min_samples, int min_profiles,
+                    int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
                     const sc_segment_fit* out_rows) {
-    int rc = sc_pf_check(ctx, "sc_fit_segments", ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
+    if (D >= 0 && (rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
     if (S < 0 || !seg_start || (S > 0 && (!seg_label || !out_rows)))
-        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: null argument");
-    if (min_profiles < 1) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: min_profiles must be >= 1");
+        return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
+    if (min_profiles < 1) return sc_fail(ctx, SC_ERR_INVALID, "%s: min_profiles must be >= 1", who);
     if (seg_start[0] != 0 || seg_start[S] != K)
-        return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: seg_start must run from 0 to K");
-    const long long cap = sg_cap_cells(A, h);
+        return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start must run from 0 to K", who);
+    const long long cap = sg_cap_cells(A, h, D);
     for (long long s = 0; s < S; ++s) {
         if (seg_start[s + 1] < seg_start[s])
-            return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: seg_start decreases at segment %lld", s);
+            return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start decreases at segment %lld", who, s);
         if (seg_label[s] <= 0 || (s > 0 && seg_label[s] <= seg_label[s - 1]))
-            return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments: labels must be positive and strictly increasing");
+            return sc_fail(ctx, SC_ERR_INVALID, "%s: labels must be positive and strictly increasing", who);
     }
     for (long long s = 0; s < S; ++s)
         if (seg_start[s + 1] - seg_start[s] > cap)
-            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments: a segment of %lld cells, more than %lld at this h and A",
+            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h and A", who,
                            seg_start[s + 1] - seg_start[s], cap);
     return SC_OK;
 }
@@ -409,12 +674,14 @@ static unsigned sg_grid(long long n) { return (unsigned)std::max<long long>(1, s
 
 static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
-                  int w, double de, double delta, int min_samples, int min_profiles, sc_segment_fit* out_rows,
-                  sc_segment_cell* out_cells, double* out_sse) {
+                  int w, int D, double de, double delta, int min_samples, int min_profiles, sc_segment_fit* out_rows,
+                  void* out_cells, double* out_sse, int8_t* out_shift) {
     if (S == 0) return SC_OK;
-    const int np = 2 * h + 1;
-    const size_t tab_bytes = sizeof(double) * (size_t)np * A;
-    const long long cap = sg_cap_cells(A, h);
+    const bool shift = D >= 0;
+    const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
+    const size_t cell_bytes = shift ? sizeof(sc_segment_shift_cell) : sizeof(sc_segment_cell);
+    const size_t tab_bytes = sizeof(double) * (size_t)nt * A;
+    const long long cap = sg_cap_cells(A, h, D);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_tab, tab_bytes))) return rc;
@@ -423,13 +690,17 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
 
     const bool tab_lds = tab_bytes <= SG_TAB_LDS;
     const size_t lds = sizeof(double) * (size_t)SG_WAVES * np + (tab_lds ? tab_bytes : 0);
-    const void* fn1 = tab_lds ? (const void*)k_sg_partial<true> : (const void*)k_sg_partial<false>;
-    const void* fn2 = tab_lds ? (const void*)k_sg_resid<true> : (const void*)k_sg_resid<false>;
-    if ((rc = sc_lds_attr(ctx, fn1, lds))) return rc;
+    const size_t lds1 = lds + (shift ? sizeof(double) * (size_t)SG_WAVES * sh_slot_doubles(A) : 0);   // (the search's slots)
+    const void* fn1 = shift ? (tab_lds ? (const void*)k_sg_shift<true> : (const void*)k_sg_shift<false>)
+                            : (tab_lds ? (const void*)k_sg_partial<true> : (const void*)k_sg_partial<false>);
+    const void* fn2 = shift ? (tab_lds ? (const void*)k_sg_resid_shift<true> : (const void*)k_sg_resid_shift<false>)
+                            : (tab_lds ? (const void*)k_sg_resid<true> : (const void*)k_sg_resid<false>);
+    if ((rc = sc_lds_attr(ctx, fn1, lds1))) return rc;
     if ((rc = sc_lds_attr(ctx, fn2, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
+    // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
+    if ((rc = sc_pf_table(ctx, d_ages, A, h + (shift ? D : 0), de, d_tab))) return rc;
 
     std::vector<double> dir;
     std::vector<int> cseg, start, blk;
@@ -472,7 +743,8 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * (size_t)Sc * A))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_cnt, sizeof(int) * 2 * (size_t)Sc))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_fit) * (size_t)Sc))) return rc;
-        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, sizeof(sc_segment_cell) * (size_t)m))) return rc;
+        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, cell_bytes * (size_t)m))) return rc;
+        if (shift && (rc = sc_ensure(ctx, ctx->sg_shift, mA))) return rc;
         if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
         long long* d_cells = (long long*)ctx->sg_cells.p;
         double* d_dir = (double*)ctx->sg_dir.p;
@@ -491,7 +763,8 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         double* d_tsse = (double*)ctx->sg_tsse.p;
         int* d_cnt = (int*)ctx->sg_cnt.p;
         sc_segment_fit* d_rows = (sc_segment_fit*)ctx->sg_rows.p;
-        sc_segment_cell* d_out = out_cells ? (sc_segment_cell*)ctx->sg_out.p : nullptr;
+        void* d_out = out_cells ? ctx->sg_out.p : nullptr;
+        signed char* d_shift = shift ? (signed char*)ctx->sg_shift.p : nullptr;
         double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
 
         if (m) {
@@ -504,11 +777,21 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         SC_HIP(ctx, hipMemcpyAsync(d_label, seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
         // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
         SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_fit) * (size_t)Sc, ctx->stream));
+        // (so is the padding at the end of the shifted call's cell table)
+        if (shift && d_out && m) SC_HIP(ctx, hipMemsetAsync(d_out, 0, cell_bytes * (size_t)m, ctx->stream));
 
         const unsigned gcell = (unsigned)std::max<long long>(1, std::min<long long>((m + SG_WAVES - 1) / SG_WAVES, SG_MAX_GRID));
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
-        if (m) {
+        if (m && shift) {
+            if (tab_lds)
+                k_sg_shift<true><<<gcell, SG_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples,
+                                                                          d_tab, d_prof, d_cn, d_used, d_scal, d_planes, d_shift);
+            else
+                k_sg_shift<false><<<gcell, SG_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples,
+                                                                           d_tab, d_prof, d_cn, d_used, d_scal, d_planes, d_shift);
+            ++launches;
+        } else if (m) {
             if (tab_lds)
                 k_sg_partial<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples,
                                                                            d_tab, d_prof, d_cn, d_used, d_scal, d_planes);
@@ -522,7 +805,13 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         if (G) {
             k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
             k_sg_sum2<2><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tot);
-            if (tab_lds)
+            if (shift && tab_lds)
+                k_sg_resid_shift<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift,
+                                                                               d_tot, m, A, h, D, de, min_profiles, d_tab);
+            else if (shift)
+                k_sg_resid_shift<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift,
+                                                                                d_tot, m, A, h, D, de, min_profiles, d_tab);
+            else if (tab_lds)
                 k_sg_resid<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_tot, m,
                                                                          A, h, de, min_profiles, d_tab);
             else
@@ -532,14 +821,23 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
             k_sg_sum2<1><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tsse);
             launches += 5;
         }
-        k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, delta,
-                                                        min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_rows, d_out, d_sse);
+        if (shift)
+            k_sg_choose_shift<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, D, delta,
+                                                                  min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift,
+                                                                  d_rows, (sc_segment_shift_cell*)d_out, d_sse);
+        else
+            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, delta,
+                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_rows,
+                                                            (sc_segment_cell*)d_out, d_sse);
         ++launches;
         SC_HIP(ctx, hipGetLastError());
         sc_prof_end(ctx, launches);
         SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
         if (out_cells && m)
-            SC_HIP(ctx, hipMemcpyAsync(out_cells + k0, d_out, sizeof(sc_segment_cell) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+            SC_HIP(ctx, hipMemcpyAsync((char*)out_cells + cell_bytes * (size_t)k0, d_out, cell_bytes * (size_t)m,
+                                       hipMemcpyDeviceToHost, ctx->stream));
+        if (out_shift && m)
+            SC_HIP(ctx, hipMemcpyAsync(out_shift + (size_t)k0 * A, d_shift, mA, hipMemcpyDeviceToHost, ctx->stream));
         if (out_sse)
             SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)s0 * A, d_sse, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
                                        ctx->stream));
@@ -559,12 +857,12 @@ extern "C" int sc_fit_segments(sc_ctx* ctx, const long long* cells, const double
     const Geom& g = ctx->g;
     if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
         return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments: the context holds a block of a larger grid");
-    int rc = sg_check(ctx, g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
+    int rc = sg_check(ctx, "sc_fit_segments", g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
                       min_profiles, out_rows);
     if (rc) return rc;
     SC_HIP(ctx, hipSetDevice(ctx->device));
-    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
-                  min_profiles, out_rows, out_cells, out_sse);
+    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
+                  min_profiles, out_rows, out_cells, out_sse, nullptr);
 }
 
 extern "C" int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
@@ -573,7 +871,7 @@ extern "C" int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx,
                                    int min_samples, int min_profiles, sc_segment_fit* out_rows, sc_segment_cell* out_cells,
                                    double* out_sse) {
     if (!ctx || !z) return SC_ERR_INVALID;
-    int rc = sg_check(ctx, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, de, delta, min_samples,
+    int rc = sg_check(ctx, "sc_fit_segments", ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
                       min_profiles, out_rows);
     if (rc) return rc;
     if (S == 0) return SC_OK;
@@ -581,6 +879,45 @@ extern "C" int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx,
     const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
     if ((rc = sc_ensure(ctx, ctx->sg_z, bytes))) return rc;
     SC_HIP(ctx, hipMemcpyAsync(ctx->sg_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, de, delta,
-                  min_samples, min_profiles, out_rows, out_cells, out_sse);
+    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, -1, de, delta,
+                  min_samples, min_profiles, out_rows, out_cells, out_sse, nullptr);
+}
+
+extern "C" int sc_fit_segments_shift(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                                     const long long* seg_start, const int32_t* seg_label, long long S, const double* ages,
+                                     int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
+                                     sc_segment_fit* out_rows, sc_segment_shift_cell* out_cells, double* out_sse,
+                                     int8_t* out_shift) {
+    if (!ctx) return SC_ERR_INVALID;
+    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
+    const Geom& g = ctx->g;
+    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
+        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments_shift: the context holds a block of a larger grid");
+    if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments_shift: the shift range must be >= 0 cells");
+    int rc = sg_check(ctx, "sc_fit_segments_shift", g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+                      min_profiles, out_rows);
+    if (rc) return rc;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+                  min_profiles, out_rows, out_cells, out_sse, out_shift);
+}
+
+extern "C" int sc_fit_segments_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells,
+                                         const double* sa, const double* ca, long long K, const long long* seg_start,
+                                         const int32_t* seg_label, long long S, const double* ages, int A, int h, int w,
+                                         int D, double de, double delta, int min_samples, int min_profiles,
+                                         sc_segment_fit* out_rows, sc_segment_shift_cell* out_cells, double* out_sse,
+                                         int8_t* out_shift) {
+    if (!ctx || !z) return SC_ERR_INVALID;
+    if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments_shift_dem: the shift range must be >= 0 cells");
+    int rc = sg_check(ctx, "sc_fit_segments_shift_dem", ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+                      min_profiles, out_rows);
+    if (rc) return rc;
+    if (S == 0) return SC_OK;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
+    if ((rc = sc_ensure(ctx, ctx->sg_z, bytes))) return rc;
+    SC_HIP(ctx, hipMemcpyAsync(ctx->sg_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta,
+                  min_samples, min_profiles, out_rows, out_cells, out_sse, out_shift);
 }

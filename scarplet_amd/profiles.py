@@ -20,6 +20,9 @@ MAX_CELLS = 2 ** 31 - 1
 FIT_FIELDS = [("row", np.int64), ("col", np.int64)] + \
     [(f, _lib.PROFILE_DTYPE.fields[f][0]) for f in _lib.PROFILE_DTYPE.names] + [("height", np.float64)]
 FIT_DTYPE = np.dtype(FIT_FIELDS)
+# ... and with max_shift: the best age's shift, in cells and in data units
+SHIFT_FIT_FIELDS = FIT_FIELDS + [("shift_index", np.int32), ("shift", np.float64)]
+SHIFT_FIT_DTYPE = np.dtype(SHIFT_FIT_FIELDS)
 
 
 def _number(x, name):
@@ -134,9 +137,28 @@ def check_args(shape, de, cells, angle, half_length, swath, ages, delta, min_sam
     return idx, np.sin(a), np.cos(a), np.ascontiguousarray(kt), h, w, de, d, ms
 
 
+def check_shift(max_shift, return_shift, de, h, min_samples):
+    """D = floor(max_shift / de), the range of the centre shift in cells, or None for ``max_shift=None``; ValueError
+    otherwise.  ``de``, ``h`` and ``min_samples`` as check_args returns them."""
+    if max_shift is None:
+        if return_shift:
+            raise ValueError("return_shift needs max_shift")
+        return None
+    ms = _number(max_shift, "max_shift")
+    if ms < 0:
+        raise ValueError("max_shift must be >= 0, got %r" % (max_shift,))
+    D = int(math.floor(ms / de))
+    top = min(_lib.PROFILE_MAX_SHIFT, h - min_samples)
+    if D > top:
+        raise ValueError("max_shift %r is %d cells: more than %d (at most %d, and half_length less min_samples)"
+                         % (max_shift, D, top, _lib.PROFILE_MAX_SHIFT))
+    return D
+
+
 def _table(rows, nx, label=None):
     """The library's rows -> the Python table (row, col, the row's fields, height = 2 a; ``label`` when given)."""
-    dt = FIT_DTYPE if label is None else np.dtype(FIT_FIELDS + [("label", np.int32)])
+    fields = SHIFT_FIT_FIELDS if "shift" in rows.dtype.names else FIT_FIELDS
+    dt = np.dtype(fields + ([] if label is None else [("label", np.int32)]))
     out = np.zeros(len(rows), dtype=dt)
     for f in rows.dtype.names:
         out[f] = rows[f]
@@ -162,7 +184,7 @@ def _dem_of(data):
 
 
 def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4, return_curve=False,
-                 device=0):
+                 device=0, max_shift=None, return_shift=False):
     """Fit the diffusion scarp to elevation profiles cut across the strike at ``cells`` (docs/profiles.md).
 
     ``data``: the DEMGrid.  ``cells``: linear indices ``r * nx + c``, a ``(rows, cols)`` tuple, or a bool plane (its
@@ -177,16 +199,29 @@ def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0,
 
     Returns a structured array, one row per cell in input order: ``row, col, cell, n, kt_index, lo_index, hi_index,
     status, kt, kt_lo, kt_hi, a, b, c0, sse, rmse, height`` (= 2 a) - and the (K, A) sse curves when
-    ``return_curve``.  The same bytes on every run."""
+    ``return_curve``.  The same bytes on every run.
+
+    ``max_shift`` (data units; None: the step stays at the cell) lets the step sit ``d`` cells along the profile,
+    ``|d| <= floor(max_shift / de)``: ``a erf((s - d de) / (2 sqrt(kt)))``, the best ``d`` chosen for every age (tried
+    in the order 0, -1, +1, ...).  The table gains ``shift_index`` (d of the best age) and ``shift`` (d de), the
+    curves are the minima over d, one degree of freedom goes to the shift (``n - 4`` for ``n - 3`` when the range is
+    not 0), and ``status`` gains 8 where ``|shift_index|`` is the end of the range.  ``return_shift`` adds the
+    (K, A) int8 plane of every age's d, after the curves."""
     z, de = _dem_of(data)
     args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
+    D = check_shift(max_shift, return_shift, args[6], args[4], args[8])
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_curve, z=z)
+    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift)
 
 
-def _run(ctx, args, nx, return_curve, z=None, label=None):
+def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False):
     idx, sa, ca, kt, h, w, de, d, ms = args
-    rows, curve = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z)
-    out = _table(rows, nx, label)
-    return (out, curve) if return_curve else out
+    if shift is None:
+        rows, curve = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z)
+        out = _table(rows, nx, label)
+        return (out, curve) if return_curve else out
+    rows, curve, plane = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z, shift=shift,
+                                          shift_plane=bool(return_shift))
+    res = [_table(rows, nx, label)] + ([curve] if return_curve else []) + ([plane] if return_shift else [])
+    return res[0] if len(res) == 1 else tuple(res)

@@ -18,6 +18,9 @@ FIT_DTYPE = np.dtype(FIT_FIELDS)
 CELL_FIELDS = [("row", np.int64), ("col", np.int64)] + \
     [(f, _lib.SEGMENT_CELL_DTYPE.fields[f][0]) for f in _lib.SEGMENT_CELL_DTYPE.names] + [("label", np.int32)]
 CELL_DTYPE = np.dtype(CELL_FIELDS)
+# ... and with max_shift: each profile's shift at the segment's best age, in cells and in data units
+SHIFT_CELL_FIELDS = CELL_FIELDS[:-1] + [("shift_index", np.int32), ("shift", np.float64), ("label", np.int32)]
+SHIFT_CELL_DTYPE = np.dtype(SHIFT_CELL_FIELDS)
 
 
 def _labels_of(labels, idx, ny, nx):
@@ -37,12 +40,12 @@ def _labels_of(labels, idx, ny, nx):
     return lab
 
 
-def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles):
+def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=False):
     """What the library takes, validated and normalised; ValueError otherwise.  The shared arguments go through
     ``profiles.check_args``; cells of label <= 0 are dropped, the rest grouped by label with a stable sort (input
     order is kept within a label).  Returns (cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples,
     min_profiles, order, kept): the first three sorted, ``kept`` the input positions of the cells that stay and
-    ``order`` the sort's permutation of them."""
+    ``order`` the sort's permutation of them.  ``shift``: the call parks each cell's shifts too (max_shift is given)."""
     idx, sa, ca, kt, h, w, de, d, ms = profiles.check_args(shape, de, cells, angle, half_length, swath, ages, delta,
                                                            min_samples)
     ny, nx = (int(v) for v in shape)
@@ -60,7 +63,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta,
     pick = kept[order]
     seg_label, counts = np.unique(lab[kept], return_counts=True)
     seg_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt)))
+    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt)) + (len(kt) if shift else 0))
     if len(counts) and counts.max() > cap:
         raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages"
                          % (counts.max(), cap))
@@ -69,7 +72,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta,
 
 
 def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
-                 min_profiles=1, return_cells=False, return_curve=False, device=0):
+                 min_profiles=1, return_cells=False, return_curve=False, device=0, max_shift=None, return_shift=False):
     """Fit ONE diffusion scarp per segment to the profiles cut across the strike at its cells (docs/segments.md).
 
     ``data``, ``cells``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta`` and ``min_samples`` are those of
@@ -85,25 +88,39 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     kt_index, lo_index, hi_index, status, kt, kt_lo, kt_hi, a, sse, rmse, height`` (= 2 a).  ``return_cells`` adds
     the per-cell table in input order (``row, col, cell, used, n, b, c0, sse, label``: each profile's slope,
     intercept and sse at the segment's best age) and ``return_curve`` the (S, A) sse curves, in that order.  The
-    same bytes on every run."""
+    same bytes on every run.
+
+    ``max_shift`` (data units; None: every step stays at its cell) gives every profile a shift of its own, chosen at
+    every age as ``sl.fit_profiles(..., max_shift=...)`` chooses it; the joint fit then has each profile's erf moved by
+    its shift.  ``dof`` loses one more per profile when the range is not 0, ``status`` gains 8 where a usable profile's
+    shift at the best age is the end of the range, the cell table gains ``shift_index`` and ``shift``, and
+    ``return_shift`` adds the (K, A) int8 plane of every cell's shift at every age, in input order, last."""
     z, de = profiles._dem_of(data)
-    args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles)
+    args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles,
+                      shift=max_shift is not None)
+    D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z)
+    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift)
 
 
-def _run(ctx, args, nx, return_cells, return_curve, z=None):
+def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False):
     idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
-    rows, tab, curve = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
-                                        cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+    plane = None
+    if shift is None:
+        rows, tab, curve = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
+                                            cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+    else:
+        rows, tab, curve, plane = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
+                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z,
+                                                   shift=shift, shift_plane=bool(return_shift))
     out = np.zeros(len(rows), dtype=FIT_DTYPE)
     for f in rows.dtype.names:
         out[f] = rows[f]
     out["height"] = 2.0 * rows["a"]
     res = [out]
     if return_cells:
-        ct = np.zeros(len(tab), dtype=CELL_DTYPE)
+        ct = np.zeros(len(tab), dtype=CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE)
         back = np.empty(len(order), dtype=np.int64)                    # sorted position of each kept cell
         back[order] = np.arange(len(order))
         for f in tab.dtype.names:
@@ -111,7 +128,13 @@ def _run(ctx, args, nx, return_cells, return_curve, z=None):
         ct["row"] = ct["cell"] // nx
         ct["col"] = ct["cell"] % nx
         ct["label"] = np.repeat(seg_label, np.diff(seg_start))[back]
+        if shift is not None:
+            ct["shift"] = np.where(np.isnan(ct["b"]), np.nan, ct["shift_index"] * de)
         res.append(ct)
     if return_curve:
         res.append(curve)
+    if return_shift:
+        back = np.empty(len(order), dtype=np.int64)
+        back[order] = np.arange(len(order))
+        res.append(np.ascontiguousarray(plane[back]))
     return res[0] if len(res) == 1 else tuple(res)
