@@ -3244,7 +3244,8 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
             case 256: FN(256); break;
             case 512: FN(512); break;
             case 1024: FN(1024); break;
-            default: FN(2048); break;
+            case 2048: FN(2048); break;
+            default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "symmetric template transform: column length %d", fg.Ty);
         }
 #undef FN
         sc_prof_end(ctx);
@@ -3491,7 +3492,8 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 switch (fg.Ty) {
                     case 512: FN_SYMX(512); break;
                     case 1024: FN_SYMX(1024); break;
-                    default: FN_SYMX(2048); break;
+                    case 2048: FN_SYMX(2048); break;
+                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "paired column pass: column length %d", fg.Ty);
                 }
             } else if (sym) {
                 switch (fg.Ty) {
@@ -3500,7 +3502,8 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                     case 256: FN_SYM(256); break;
                     case 512: FN_SYM(512); break;
                     case 1024: FN_SYM(1024); break;
-                    default: FN_SYM(2048); break;
+                    case 2048: FN_SYM(2048); break;
+                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "symmetric column pass: column length %d", fg.Ty);
                 }
             } else {
                 DISPATCH_T(fg.Ty, FN)
@@ -3658,13 +3661,15 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 switch (fg.Tx) {
                     case 512: LAUNCH_NEAR(512) break;
                     case 1024: LAUNCH_NEAR(1024) break;
-                    default: LAUNCH_NEAR(2048) break;
+                    case 2048: LAUNCH_NEAR(2048) break;
+                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "fast row pass: row length %d", fg.Tx);
                 }
             } else if (fast) {
                 switch (fg.Tx) {
                     case 512: if (full_masks) LAUNCH_FAST(512, true) else LAUNCH_FAST(512, false) break;
                     case 1024: if (full_masks) LAUNCH_FAST(1024, true) else LAUNCH_FAST(1024, false) break;
-                    default: if (full_masks) LAUNCH_FAST(2048, true) else LAUNCH_FAST(2048, false) break;
+                    case 2048: if (full_masks) LAUNCH_FAST(2048, true) else LAUNCH_FAST(2048, false) break;
+                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "fast row pass: row length %d", fg.Tx);
                 }
             } else {
 #define FN(T) { if (full_masks) LAUNCH_ROWS(T, true) else LAUNCH_ROWS(T, false) }

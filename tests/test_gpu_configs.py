@@ -16,7 +16,8 @@ from scarplet_amd import _plan, synthetic
 from scarplet_amd import WindowedTemplate as WT
 from conftest import golden
 from test_gpu_parity import (AMP_RTOL, AMP_ATOL, SNR_RTOL, SNR_ATOL, TIE_RTOL, EXACT_MIN,
-                             fold_check, grid, report, CLS)
+                             fold_check, grid, CLS)
+from parity_report import report
 
 pytestmark = pytest.mark.gpu
 
