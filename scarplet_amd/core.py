@@ -605,8 +605,8 @@ class Matcher(object):
     def can_flag_near_ties(self, arr, sp):
         """Whether an FFT search of the descriptors ``arr`` with the plan ``sp`` can flag its near-ties: only the fast row
         kernel does (tiles 512, 1024 or 2048 wide, not turned off by option "variant" 9), and only for templates without
-        per-cell masks - no UpperBreak error masks (FLAG_ERR_XR_*), no plugin window with masks (sc_fft.hip's condition
-        for the near-tie flags; SC_ERR_UNSUPPORTED otherwise)."""
+        per-cell masks - no UpperBreak error masks (FLAG_ERR_XR_*), no plugin window with masks (the condition of the
+        library's route, csrc/sc_fft_route.h, for the near-tie flags; SC_ERR_UNSUPPORTED otherwise)."""
         if sp.method != _plan.METHOD_FFT or sp.Tx not in (512, 1024, 2048) or not len(arr) or \
                 getattr(self.ctx, "variant", 0) == 9:
             return False

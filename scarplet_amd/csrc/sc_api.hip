@@ -762,7 +762,7 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
         i = j;
     }
     // Chunks: one run, or - small FFT searches - nb consecutive runs of equal length, parity
-    // and mask kind sent through every launch together (sc_fft.hip, "Orientation batching")
+    // and mask kind sent through every launch together (sc_fft.hip, "Orientation batching"; how many: fft_route_batch)
     struct Chunk { int first, n, nb, wh, ww, parity; bool full, long_runs; size_t cells; int run0; };
     std::vector<Chunk> chunks;
     size_t max_cells = 0, max_dcells = 0, max_spans = 0;

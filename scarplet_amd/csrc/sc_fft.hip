@@ -38,6 +38,9 @@
 //
 // The in-LDS FFT is a Stockham autosort with radices 16,16,..,r (see below);
 // complex arithmetic is packed (namespace pk).
+//
+// Which of these kernels a chunk of templates takes is decided in one place, fft_route (sc_fft_route.h: a pure
+// function, checked on the host); the host side below asks it and tests no tile size or "variant" for itself.
 #include "sc_internal.h"
 #include <math.h>
 #include <type_traits>
@@ -137,91 +140,6 @@ __device__ __forceinline__ int lidx(int line, int i) { return line * fft_line(T)
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) {
-    return make_float2(a.x + b.x, a.y + b.y);
-}
-__device__ __forceinline__ float2 csub(float2 a, float2 b) {
-    return make_float2(a.x - b.x, a.y - b.y);
-}
-// multiply by -j (forward) / +j (inverse)
-template <bool INV>
-__device__ __forceinline__ float2 mulj(float2 a) {
-    return INV ? make_float2(-a.y, a.x) : make_float2(a.y, -a.x);
-}
-template <bool INV>
-__device__ __forceinline__ float2 cw(float c, float s) {      // exp(-/+ i*angle)
-    return make_float2(c, INV ? s : -s);
-}
-template <bool INV>
-__device__ __forceinline__ void dft4(float2& a0, float2& a1, float2& a2, float2& a3) {
-    float2 apc = cadd(a0, a2), amc = csub(a0, a2);
-    float2 bpd = cadd(a1, a3), bmd = mulj<INV>(csub(a1, a3));
-    a0 = cadd(apc, bpd);
-    a1 = cadd(amc, bmd);
-    a2 = csub(apc, bpd);
-    a3 = csub(amc, bmd);
-}
-
-// radix-R butterfly on v[0..R-1] (natural order in); result X[m] is returned
-// through out(m).  All indices are compile-time after unrolling.
-template <int R, bool INV>
-struct Bfly;
-
-template <bool INV>
-struct Bfly<2, INV> {
-    static __device__ __forceinline__ void run(float2* v) {
-        float2 a = v[0], b = v[1];
-        v[0] = cadd(a, b);
-        v[1] = csub(a, b);
-    }
-    static __device__ __forceinline__ constexpr int pos(int m) { return m; }
-};
-template <bool INV>
-struct Bfly<4, INV> {
-    static __device__ __forceinline__ void run(float2* v) { dft4<INV>(v[0], v[1], v[2], v[3]); }
-    static __device__ __forceinline__ constexpr int pos(int m) { return m; }
-};
-template <bool INV>
-struct Bfly<8, INV> {
-    // j = c + 2d, m = r + 4s: DFT4 over d, twiddle w8^(c r), DFT2 over c
-    static __device__ __forceinline__ void run(float2* v) {
-        dft4<INV>(v[0], v[2], v[4], v[6]);
-        dft4<INV>(v[1], v[3], v[5], v[7]);
-        const float h = 0.70710678118654752f;
-        v[3] = cmul(v[3], cw<INV>(h, h));
-        v[5] = mulj<INV>(v[5]);
-        v[7] = cmul(v[7], cw<INV>(-h, h));
-        Bfly<2, INV>::run(v + 0);
-        Bfly<2, INV>::run(v + 2);
-        Bfly<2, INV>::run(v + 4);
-        Bfly<2, INV>::run(v + 6);
-    }
-    // X[r + 4s] sits at v[2r + s]
-    static __device__ __forceinline__ constexpr int pos(int m) { return 2 * (m & 3) + (m >> 2); }
-};
-template <bool INV>
-struct Bfly<16, INV> {
-    // j = c + 4d, m = r + 4s: DFT4 over d, twiddle w16^(c r), DFT4 over c
-    static __device__ __forceinline__ void run(float2* v) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) dft4<INV>(v[c], v[c + 4], v[c + 8], v[c + 12]);
-        const float c1 = 0.92387953251128674f, s1 = 0.38268343236508977f;
-        const float h = 0.70710678118654752f;
-        v[1 + 4] = cmul(v[1 + 4], cw<INV>(c1, s1));       // w^1
-        v[1 + 8] = cmul(v[1 + 8], cw<INV>(h, h));         // w^2
-        v[1 + 12] = cmul(v[1 + 12], cw<INV>(s1, c1));     // w^3
-        v[2 + 4] = cmul(v[2 + 4], cw<INV>(h, h));         // w^2
-        v[2 + 8] = mulj<INV>(v[2 + 8]);                   // w^4
-        v[2 + 12] = cmul(v[2 + 12], cw<INV>(-h, h));      // w^6
-        v[3 + 4] = cmul(v[3 + 4], cw<INV>(s1, c1));       // w^3
-        v[3 + 8] = cmul(v[3 + 8], cw<INV>(-h, h));        // w^6
-        v[3 + 12] = cmul(v[3 + 12], cw<INV>(-c1, -s1));   // w^9
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dft4<INV>(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
-    }
-    // X[r + 4s] sits at v[4r + s]
-    static __device__ __forceinline__ constexpr int pos(int m) { return 4 * (m & 3) + (m >> 2); }
-};
 
 // ---------------------------------------------------------------------------
 // Packed complex arithmetic: a complex value is a native 2-vector, so a complex
@@ -2924,7 +2842,7 @@ k_merge_split(float* __restrict__ best_snr, float* __restrict__ best_amp, uint32
 // host side
 // ---------------------------------------------------------------------------
 bool fft_size_supported(int T) {
-    return T >= 64 && T <= 4096 && (T & (T - 1)) == 0;
+    return fft_route_size_ok(T);
 }
 
 // Entries 0 .. T-1: the forward twiddles exp(-2 pi i k / T).  Entries T .. 2T-1: the phase
@@ -2951,13 +2869,25 @@ static int upload_twiddles(sc_ctx* ctx, DevBuf& buf, int& have, int T, int kph) 
 
 static int npairs_of(const FftGeom& fg) { return (fg.ntiles + 1) / 2; }
 
-// Option "fuse_fwd": may the curvature's forward column transform be left to the inverse column pass?  Where that
-// pass is the wave-per-column one (fft_inverse_fold's `w8`, but for the templates' parity, which is not known yet)
-// and no spectra are kept across searches (kept spectra are uc / uc2).  A chunk that takes another column kernel
-// after all - generic templates, single-template maps - has fft_inverse_fold run k_fwd_cols first.
+static FftRouteIn fft_route_in(const sc_ctx* ctx, const FftGeom& fg, int parity) {
+    FftRouteIn in{};
+    in.Ty = fg.Ty; in.Tx = fg.Tx; in.ntiles = fg.ntiles; in.parity = parity;
+    in.near = ctx->near_w > 0.f; in.kept = ctx->spec_slots > 0;
+    in.nb = in.n = in.group = 1;
+    in.variant = ctx->variant; in.sib = ctx->sib; in.i1_pairs = ctx->i1_pairs; in.split_i1 = ctx->split_i1;
+    in.split_fill = ctx->split_fill; in.fuse_fwd = ctx->fuse_fwd; in.batch_off = ctx->batch_off;
+    in.batch_templ = ctx->batch_templ; in.batch_fill = ctx->batch_fill;
+    return in;
+}
+
+// Option "fuse_fwd": may the curvature's forward column transform be left to the inverse column pass?  A question to
+// the route (FftRoute::fused), put for the parity that gives the most - the templates' parity is not known yet when
+// the search is prepared and the curvature transformed.  A chunk that takes another column kernel after all -
+// generic templates, single-template maps - has fft_inverse_fold run k_fwd_cols first.
 static bool fft_fuse_curv(const sc_ctx* ctx, const FftGeom& fg, int slots) {
-    return ctx->fuse_fwd && slots == 0 && (fg.Ty == 2048 || fg.Ty == 1024) && (fg.Tx / 16) % 8 == 0 &&
-           ctx->variant != 1 && ctx->variant != 2 && ctx->variant != 6 && ctx->variant != 8;
+    FftRouteIn in = fft_route_in(ctx, fg, 1);
+    in.kept = slots > 0;
+    return fft_route(in).fused;
 }
 
 void fft_spectra_forget(sc_ctx* ctx) {
@@ -2968,7 +2898,7 @@ void fft_spectra_forget(sc_ctx* ctx) {
 int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, int nb, int n_slots) {
     // nb: orientations batched per launch (fft_batch_orientations); 1 for the large searches
     if (!fft_size_supported(fg.Ty) || !fft_size_supported(fg.Tx))
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "FFT tile %dx%d not supported", fg.Ty, fg.Tx);
+        return sc_fail(ctx, SC_ERR_UNSUPPORTED, FFT_REFUSE_SIZE, fg.Ty, fg.Tx);
     int rc;
     if ((rc = upload_twiddles(ctx, ctx->tw_y, ctx->tw_Ty, fg.Ty, 1 - ctx->g.oy))) return rc;
     if ((rc = upload_twiddles(ctx, ctx->tw_x, ctx->tw_Tx, fg.Tx, 1 - ctx->g.ox))) return rc;
@@ -3080,26 +3010,11 @@ int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, in
 // launch: nb curvature planes and spectra, the templates of all of them in one forward pass,
 // the inverse column pass with one job per (orientation, tile pair), and the row pass folding
 // nb * n templates in the order the orientations come - the same cells in the same order as
-// orientation by orientation, so the result is bit-identical.  Conditions: the fast row
-// kernel (its scalar table and winner byte hold SC_MAX_GROUP templates), all templates of an
-// orientation in one inverse launch (group >= n), and at most ~4096 column workgroups.
+// orientation by orientation, so the result is bit-identical.  How many: fft_route_batch.
 int fft_batch_orientations(const sc_ctx* ctx, const FftGeom& fg, int n_per, int group) {
-    if (ctx->batch_off || n_per < 1 || n_per > group) return 1;
-    const bool fast = (fg.Tx == 512 || fg.Tx == 1024 || fg.Tx == 2048) && ctx->variant != 9;
-    if (!fast) return 1;
-    const int np = (fg.ntiles + 1) / 2;
-    // What one launch sequence may carry.  The row pass folds at most SC_MAX_GROUP templates per launch: where three
-    // or more orientations fit that (C2: six of ten templates), the batch stops there and the row pass takes it in ONE
-    // launch (more, sliced over two row-pass launches, cost C2's row pass 14 %); where they do not (C1F: 35 ages, one
-    // orientation per row-pass launch either way) the forward passes and the column pass batch up to SC_MAX_BATCH
-    // templates - 181 five-kernel launch sequences of a few microseconds each were 15 of C1F's 52 ms, now 6
-    const int cap = ctx->batch_templ > 0 ? ctx->batch_templ : SC_MAX_BATCH;
-    const int by_table = (SC_MAX_GROUP / n_per >= 3 || cap <= SC_MAX_GROUP) ? std::min(cap, SC_MAX_GROUP) / n_per : cap / n_per;
-    // (round 4: 4096 workgroups and up to SC_MAX_ORIENT orientations - BASELINE config C5, one template per
-    //  orientation on a 512 x 512 tile, runs 64 orientations per launch sequence instead of 32: 5.95 -> 5.2 ms;
-    //  C1 and C2 are where they were with either)
-    const int by_fill = (ctx->batch_fill > 0 ? ctx->batch_fill : 4096) / std::max(1, np * (fg.Tx / 8));
-    return std::max(1, std::min(std::min(by_table, by_fill), SC_MAX_ORIENT));
+    FftRouteIn in = fft_route_in(ctx, fg, 1);
+    in.n = n_per; in.group = group;
+    return fft_route_batch(in);
 }
 
 // Rendezvous words for a launch of n workgroups (SibSync): one buffer per context, a new epoch per
@@ -3123,17 +3038,15 @@ static int set_lds(sc_ctx* ctx, K kernel, size_t bytes) {
     return sc_lds_attr(ctx, (const void*)kernel, bytes);
 }
 
-#define DISPATCH_T(T, FN)                                                     \
-    switch (T) {                                                              \
-        case 64: FN(64); break;                                               \
-        case 128: FN(128); break;                                             \
-        case 256: FN(256); break;                                             \
-        case 512: FN(512); break;                                             \
-        case 1024: FN(1024); break;                                           \
-        case 2048: FN(2048); break;                                           \
-        case 4096: FN(4096); break;                                           \
-        default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "tile size %d", T);  \
-    }
+// A runtime size as a template argument: f(std::integral_constant<int, T>) for the T of the list that equals `size`;
+// a size the list does not name is SC_ERR_UNSUPPORTED with `fmt` (one %d: the size), never another size's kernel
+template <int... Ts, typename F>
+static int fft_for_size(sc_ctx* ctx, int size, const char* fmt, F f) {
+    int rc = SC_OK;
+    const bool matched = ((size == Ts && ((rc = f(std::integral_constant<int, Ts>{})), true)) || ...);
+    return matched ? rc : sc_fail(ctx, SC_ERR_UNSUPPORTED, fmt, size);
+}
+#define FFT_SIZES 64, 128, 256, 512, 1024, 2048, 4096
 
 static int launch_fwd_cols(sc_ctx* ctx, const FftGeom& fg, const float2* in, int nplanes,
                            float2* out0, float2* out1, int split2,
@@ -3141,17 +3054,14 @@ static int launch_fwd_cols(sc_ctx* ctx, const FftGeom& fg, const float2* in, int
     size_t lds = fft_lds_bytes(fg.Ty);
     dim3 grid(fg.Tx / 4, nplanes);
     sc_prof_begin(ctx, SC_K_FWD_COLS);
-#define FN(T)                                                                  \
-    {                                                                          \
-        int rc = set_lds(ctx, k_fwd_cols<T>, lds);                             \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL(k_fwd_cols<T>, grid, dim3(fft_threads(T)), lds,     \
-                           ctx->stream, in, fg.Tx,                             \
-                           (const float2*)ctx->tw_y.p, out0, out1, split2,     \
-                           templ);                                             \
-    }
-    DISPATCH_T(fg.Ty, FN)
-#undef FN
+    int rc = fft_for_size<FFT_SIZES>(ctx, fg.Ty, "tile size %d", [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if (int rc = set_lds(ctx, k_fwd_cols<T>, lds)) return rc;
+        hipLaunchKernelGGL(k_fwd_cols<T>, grid, dim3(fft_threads(T)), lds, ctx->stream, in, fg.Tx,
+                           (const float2*)ctx->tw_y.p, out0, out1, split2, templ);
+        return SC_OK;
+    });
+    if (rc) return rc;
     sc_prof_end(ctx);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
@@ -3174,22 +3084,19 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
             for (int j = 0; j < 3; ++j) mixc.c[b][j] = coef[b][j];
     }
     sc_prof_begin(ctx, SC_K_FWD_ROWS);
-#define FN2(T, MIXV)                                                           \
-    {                                                                          \
-        int rc = set_lds(ctx, k_fwd_rows_curv<T, MIXV>, lds);                  \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_fwd_rows_curv<T, MIXV>), grid, dim3(fft_threads(T)), \
-                           lds, ctx->stream, (const float*)(MIXV ? ctx->A.p : ctx->curv.p), \
-                           (const float*)ctx->B.p, (const float*)ctx->C.p, mixc, \
-                           ctx->g, (const TileDev*)ctx->tiles.p, fg.Ty,        \
-                           (const float2*)ctx->tw_x.p, rows_out,               \
-                           (double*)ctx->norm_part.p, np,                      \
-                           (size_t)ctx->g.ly * ctx->g.lx);                     \
-    }
-#define FN(T) { if (coef) FN2(T, true) else FN2(T, false) }
-    DISPATCH_T(fg.Tx, FN)
-#undef FN
-#undef FN2
+    int rc = fft_for_size<FFT_SIZES>(ctx, fg.Tx, "tile size %d", [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        auto launch = [&](auto kernel, const void* plane) {
+            if (int rc = set_lds(ctx, kernel, lds)) return rc;
+            hipLaunchKernelGGL(kernel, grid, dim3(fft_threads(T)), lds, ctx->stream, (const float*)plane,
+                               (const float*)ctx->B.p, (const float*)ctx->C.p, mixc, ctx->g,
+                               (const TileDev*)ctx->tiles.p, fg.Ty, (const float2*)ctx->tw_x.p, rows_out,
+                               (double*)ctx->norm_part.p, np, (size_t)ctx->g.ly * ctx->g.lx);
+            return SC_OK;
+        };
+        return coef ? launch(k_fwd_rows_curv<T, true>, ctx->A.p) : launch(k_fwd_rows_curv<T, false>, ctx->curv.p);
+    });
+    if (rc) return rc;
     hipLaunchKernelGGL(k_tile_norms, dim3(np * nb), dim3(64), 0, ctx->stream,
                        (const double*)ctx->norm_part.p, fg.Ty / 4, (double*)ctx->norms.p + ctx->norms_off);
     sc_prof_end(ctx);
@@ -3199,66 +3106,49 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
     return launch_fwd_cols(ctx, fg, rows_out, 2 * np * nb, (float2*)ctx->uc.p + ctx->uc_off, (float2*)ctx->uc2.p + ctx->uc_off, 1);
 }
 
-// Symmetric fast path (k_split_templ_sym / k_inv_cols_sym): all templates of the
-// chunk share one parity and the tile is small enough for the parked spectrum.
-static bool fft_use_sym(const sc_ctx* ctx, const FftGeom& fg, int parity) {
-    return parity != 0 && fg.Ty <= 2048 && ctx->variant != 8;
-}
-
 int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int parity) {
     size_t lds = fft_lds_bytes(fg.Tx);
     dim3 grid(fg.Ty / 4, n);
     sc_prof_begin(ctx, SC_K_FWD_ROWS);
-#define FN(T)                                                                  \
-    {                                                                          \
-        int rc = set_lds(ctx, k_fwd_rows_templ<T>, lds);                       \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL(k_fwd_rows_templ<T>, grid, dim3(fft_threads(T)),    \
-                           lds, ctx->stream, (const TemplDev*)ctx->templ.p,    \
-                           first, (const float*)ctx->win_w.p,                  \
-                           (const uint8_t*)ctx->win_m.p,                       \
-                           (const double*)ctx->sums.p, fg.Ty,                  \
-                           (const float2*)ctx->tw_x.p, (float2*)ctx->blk.p);   \
-    }
-    DISPATCH_T(fg.Tx, FN)
-#undef FN
+    int rc = fft_for_size<FFT_SIZES>(ctx, fg.Tx, "tile size %d", [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        if (int rc = set_lds(ctx, k_fwd_rows_templ<T>, lds)) return rc;
+        hipLaunchKernelGGL(k_fwd_rows_templ<T>, grid, dim3(fft_threads(T)), lds, ctx->stream,
+                           (const TemplDev*)ctx->templ.p, first, (const float*)ctx->win_w.p,
+                           (const uint8_t*)ctx->win_m.p, (const double*)ctx->sums.p, fg.Ty,
+                           (const float2*)ctx->tw_x.p, (float2*)ctx->blk.p);
+        return SC_OK;
+    });
+    if (rc) return rc;
     sc_prof_end(ctx);
     SC_HIP(ctx, hipGetLastError());
-    if (fft_use_sym(ctx, fg, parity) && ctx->variant != 7) {
+    const FftTemplFwd how = fft_route(fft_route_in(ctx, fg, parity)).templ;
+    if (how == FFT_TEMPL_COLS_SYM) {
         // symmetric templates: column transform and split in one kernel (k_fwd_cols_tsym)
         size_t ldsc = fft_lds_bytes(fg.Ty);
         dim3 gridc(fg.Tx / 8 + 1, n);
         sc_prof_begin(ctx, SC_K_FWD_COLS);
-#define FN(T)                                                                  \
-    {                                                                          \
-        int rc = set_lds(ctx, k_fwd_cols_tsym<T>, ldsc);                       \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL(k_fwd_cols_tsym<T>, gridc, dim3(fft_threads(T)), ldsc, ctx->stream, \
-                           (const float2*)ctx->blk.p, fg.Tx, (const float2*)ctx->tw_y.p, \
-                           (const TemplDev*)ctx->templ.p + first, (const float2*)ctx->tw_x.p + fg.Tx, \
-                           parity, (float*)ctx->wh.p, (float*)ctx->mh.p);      \
-    }
-        switch (fg.Ty) {
-            case 64: FN(64); break;
-            case 128: FN(128); break;
-            case 256: FN(256); break;
-            case 512: FN(512); break;
-            case 1024: FN(1024); break;
-            case 2048: FN(2048); break;
-            default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "symmetric template transform: column length %d", fg.Ty);
-        }
-#undef FN
+        rc = fft_for_size<64, 128, 256, 512, 1024, 2048>(ctx, fg.Ty, "symmetric template transform: column length %d", [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            if (int rc = set_lds(ctx, k_fwd_cols_tsym<T>, ldsc)) return rc;
+            hipLaunchKernelGGL(k_fwd_cols_tsym<T>, gridc, dim3(fft_threads(T)), ldsc, ctx->stream,
+                               (const float2*)ctx->blk.p, fg.Tx, (const float2*)ctx->tw_y.p,
+                               (const TemplDev*)ctx->templ.p + first, (const float2*)ctx->tw_x.p + fg.Tx,
+                               parity, (float*)ctx->wh.p, (float*)ctx->mh.p);
+            return SC_OK;
+        });
+        if (rc) return rc;
         sc_prof_end(ctx);
         SC_HIP(ctx, hipGetLastError());
         return SC_OK;
     }
-    int rc = launch_fwd_cols(ctx, fg, (const float2*)ctx->blk.p, n, (float2*)ctx->vh.p, nullptr, 0,
-                             (const TemplDev*)ctx->templ.p + first);
+    rc = launch_fwd_cols(ctx, fg, (const float2*)ctx->blk.p, n, (float2*)ctx->vh.p, nullptr, 0,
+                         (const TemplDev*)ctx->templ.p + first);
     if (rc) return rc;
     size_t cells = half_plane(fg.Ty, fg.Tx);
     dim3 grid_s((unsigned)((cells / 2 + 255) / 256), n);
     sc_prof_begin(ctx, SC_K_FWD_COLS);
-    if (fft_use_sym(ctx, fg, parity))
+    if (how == FFT_TEMPL_SPLIT_SYM)
         hipLaunchKernelGGL(k_split_templ_sym, grid_s, dim3(256), 0, ctx->stream,
                            (const float2*)ctx->vh.p, fg.Ty, fg.Tx, (const float2*)ctx->tw_y.p + fg.Ty,
                            (const float2*)ctx->tw_x.p + fg.Tx,
@@ -3271,6 +3161,213 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
     return SC_OK;
 }
 
+// ---- the column pass's launchers, one per family ----
+// One launch of the inverse column pass: the kernels' arguments by name (k_inv_cols,
+// inv_cols_sym_body, k_inv_cols_w8 say what they mean) and what shapes the grid
+struct ColLaunch {
+    int Ty, Tx;
+    bool pt;                       // paired templates (the kernels' PT)
+    int jobs;                      // grid.y: tile pairs x batched orientations; paired orientations: pairs of them
+    int ng;                        // transforms of the launch (what its parts along grid.z share out)
+    int split_i1;                  // ... and the option that steers them (FftRoute::split_i1)
+    const float2 *uc, *uc2;        // curvature spectra; `fwd`: the row spectra in cblk
+    const void *wh, *mh;           // template spectra: float2 (generic) or the real coefficients (symmetric)
+    int pair, vfirst, G, rp_lo, rp_hi;
+    const float2* phx;
+    int parity;
+    const float2* tw;
+    float2 *yw, *ym;
+    int ystride, np, pcj, tstride;
+    const TileDev* tiles;
+    int py_valid;
+    const TemplDev* tl;            // w8, w4, h2: the templates whose window limits bound the rows stored, or nullptr
+    int jil, fwd;                  // w8: interleaved tile pairs; w8, w4: transform the curvature columns first
+};
+// the kernels of symmetric templates but k_inv_cols_sym share their arguments up to py_valid
+template <typename K, typename... Tail>
+static int launch_cols_kernel(sc_ctx* ctx, K kernel, dim3 grid, int threads, size_t lds, const ColLaunch& a, Tail... tail) {
+    if (int rc = set_lds(ctx, kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, ctx->stream, a.uc, a.uc2, (const float*)a.wh, (const float*)a.mh,
+                       a.Tx, a.pair, a.vfirst, a.G, a.rp_lo, a.rp_hi, a.phx, a.parity, a.tw, a.yw, a.ym, a.ystride,
+                       a.np, a.pcj, a.tstride, a.tiles, a.py_valid, tail...);
+    return SC_OK;
+}
+// own columns, then mirrors: two launches
+template <int T>
+static int launch_cols_generic(sc_ctx* ctx, const ColLaunch& a) {
+    const size_t lds = inv_cols_lds<T>();
+    int rc = set_lds(ctx, k_inv_cols<T, false>, lds);
+    if (!rc) rc = set_lds(ctx, k_inv_cols<T, true>, lds);
+    if (rc) return rc;
+    auto launch = [&](auto kernel, int nblocks, int cb0) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks, a.jobs), dim3(fft_threads(T)), lds, ctx->stream, a.uc, a.uc2,
+                           (const float2*)a.wh, (const float2*)a.mh, a.Tx, cb0, a.pair, a.vfirst, a.G, a.rp_lo, a.rp_hi,
+                           a.tw, a.yw, a.ym, a.ystride, a.np, a.pcj, a.tstride, a.tiles, a.py_valid);
+    };
+    const int nlo = a.Tx / 8, nhi = a.Tx / 4 - nlo;
+    launch(k_inv_cols<T, false>, nlo, 0);
+    if (nhi > 0) launch(k_inv_cols<T, true>, nhi, nlo);
+    return SC_OK;
+}
+template <int T, bool PT>
+static int launch_cols_sym(sc_ctx* ctx, const ColLaunch& a) {
+    const size_t lds = inv_cols_lds<T>();
+    int rc = set_lds(ctx, k_inv_cols_sym<T, false, PT>, lds);
+    if (!rc) rc = set_lds(ctx, k_inv_cols_sym<T, true, PT>, lds);
+    if (rc) return rc;
+    auto launch = [&](auto kernel, int nblocks, int cb0) {
+        hipLaunchKernelGGL(kernel, dim3(nblocks, a.jobs), dim3(fft_threads(T)), lds, ctx->stream, a.uc, a.uc2,
+                           (const float*)a.wh, (const float*)a.mh, a.Tx, cb0, a.pair, a.vfirst, a.G, a.rp_lo, a.rp_hi,
+                           a.phx, a.parity, a.tw, a.yw, a.ym, a.ystride, a.np, a.pcj, a.tstride, a.tiles, a.py_valid);
+    };
+    const int nlo = a.Tx / 8, nhi = a.Tx / 4 - nlo;
+    launch(k_inv_cols_sym<T, false, PT>, nlo, 0);
+    if (nhi > 0) launch(k_inv_cols_sym<T, true, PT>, nhi, nlo);
+    return SC_OK;
+}
+// the parts along grid.z: up to the chip's resident capacity for the kernel - the four-column kernels: 256 CUs x
+// what LDS and 256 registers allow; wave-per-column: one or two 512-thread workgroups per CU
+template <int T, bool PT>
+static int launch_cols_symx(sc_ctx* ctx, const ColLaunch& a) {
+    const long long cap = 256LL * std::max<size_t>(1, std::min<size_t>((160 * 1024) / inv_cols_lds<T>(), 2048 / fft_threads(T) / 2));
+    const int nz = fft_route_parts(a.split_i1, (long long)(a.Tx / 4) * a.jobs, cap, a.ng);
+    return launch_cols_kernel(ctx, k_inv_cols_symx<T, PT>, dim3(a.Tx / 4, a.jobs, nz), fft_threads(T), inv_cols_lds<T>(), a);
+}
+// paired orientations: two spectra parked
+static int launch_cols_symx_xp(sc_ctx* ctx, const ColLaunch& a) {
+    const size_t lds = inv_cols_lds<512>() + (size_t)4 * 512 * sizeof(float2);
+    return launch_cols_kernel(ctx, k_inv_cols_symx<512, true, true>, dim3(a.Tx / 4, a.jobs), fft_threads(512), lds, a);
+}
+template <int T, bool PT>
+static int launch_cols_w8(sc_ctx* ctx, const ColLaunch& a) {
+    const int nz = fft_route_parts(a.split_i1, (long long)(a.Tx / 8) * a.jobs, 256LL * ((T == 1024 && !PT) ? 2 : 1), a.ng);
+    return launch_cols_kernel(ctx, k_inv_cols_w8<T, PT>, dim3(a.Tx / 8 * a.jil, a.jobs / a.jil, nz), 512, w8_lds<T>(), a,
+                              a.tl, a.jil, a.fwd);
+}
+template <bool PT>
+static int launch_cols_w4(sc_ctx* ctx, const ColLaunch& a) {
+    const size_t lds = (size_t)88 * 1024;      // (more LDS than it uses: one workgroup per CU, one wave per SIMD)
+    return launch_cols_kernel(ctx, k_inv_cols_w4<2048, PT>, dim3(a.Tx / 4, a.jobs), 256, lds, a, a.tl, a.fwd);
+}
+template <bool PT, bool XP>
+static int launch_cols_h2(sc_ctx* ctx, const ColLaunch& a) {
+    const int nz = XP ? 1 : fft_route_parts(a.split_i1, (long long)(a.Tx / 16) * a.jobs, 512, a.ng);
+    return launch_cols_kernel(ctx, k_inv_cols_h2<PT, XP>, dim3(a.Tx / 16, a.jobs, nz), 512, h2_lds(), a, a.tl);
+}
+
+// (the forms of paired orientations exist with paired templates only; h2 at 512, w4 at 2048)
+static int launch_inv_cols(sc_ctx* ctx, FftColKernel k, const ColLaunch& a) {
+    switch (k) {
+        case FFT_COL_GENERIC:
+            return fft_for_size<FFT_SIZES>(ctx, a.Ty, "tile size %d", [&](auto t) {
+                return launch_cols_generic<decltype(t)::value>(ctx, a);
+            });
+        case FFT_COL_SYM:
+            return fft_for_size<64, 128, 256, 512, 1024, 2048>(ctx, a.Ty, "symmetric column pass: column length %d", [&](auto t) {
+                constexpr int T = decltype(t)::value;
+                return a.pt ? launch_cols_sym<T, true>(ctx, a) : launch_cols_sym<T, false>(ctx, a);
+            });
+        case FFT_COL_SYMX:
+            return fft_for_size<512, 1024, 2048>(ctx, a.Ty, "paired column pass: column length %d", [&](auto t) {
+                constexpr int T = decltype(t)::value;
+                return a.pt ? launch_cols_symx<T, true>(ctx, a) : launch_cols_symx<T, false>(ctx, a);
+            });
+        case FFT_COL_W8:
+            return fft_for_size<1024, 2048>(ctx, a.Ty, "wave-per-column pass: column length %d", [&](auto t) {
+                constexpr int T = decltype(t)::value;
+                return a.pt ? launch_cols_w8<T, true>(ctx, a) : launch_cols_w8<T, false>(ctx, a);
+            });
+        case FFT_COL_W4:
+            if (a.Ty == 2048) return a.pt ? launch_cols_w4<true>(ctx, a) : launch_cols_w4<false>(ctx, a);
+            break;
+        case FFT_COL_H2:
+            if (a.Ty == H2_TY) return a.pt ? launch_cols_h2<true, false>(ctx, a) : launch_cols_h2<false, false>(ctx, a);
+            break;
+        case FFT_COL_SYMX_XP:
+            if (a.Ty == 512 && a.pt) return launch_cols_symx_xp(ctx, a);
+            break;
+        case FFT_COL_H2_XP:
+            if (a.Ty == H2_TY && a.pt) return launch_cols_h2<true, true>(ctx, a);
+            break;
+    }
+    return sc_fail(ctx, SC_ERR_UNSUPPORTED, "column pass: kernel %d at column length %d", (int)k, a.Ty);
+}
+
+// ---- the row pass's launchers, one per family ----
+// One launch of the row pass.  k: FFT_ROW_SPLIT is the dealt-out form (ra.nsplit > 1) and its merge
+struct RowLaunch {
+    FftRowKernel k;
+    int Tx;
+    bool pt, full_masks, to_maps, near;
+    dim3 grid;
+    const float2 *yw, *ym;
+    const double* norms;
+    RowArgs ra;
+};
+// every row kernel takes the same arguments
+template <typename K>
+static int launch_row_kernel(sc_ctx* ctx, K kernel, const RowLaunch& a, int threads, size_t lds) {
+    if (int rc = set_lds(ctx, kernel, lds)) return rc;
+    hipLaunchKernelGGL(kernel, a.grid, dim3(threads), lds, ctx->stream, a.yw, a.ym, a.ra, ctx->g,
+                       (const TileDev*)ctx->tiles.p, (const TemplDev*)ctx->templ.p, (const double*)ctx->sums.p,
+                       (const double*)ctx->wl1.p, a.norms, ctx->kappa, (const double*)ctx->xaxis.p,
+                       (const double*)ctx->yaxis.p, (const float2*)ctx->tw_x.p, (float*)ctx->best_snr.p,
+                       (float*)ctx->best_amp.p, (uint32_t*)ctx->best_id.p,
+                       a.to_maps ? (float*)ctx->map_amp.p : nullptr, a.to_maps ? (float*)ctx->map_snr.p : nullptr);
+    return SC_OK;
+}
+template <int T, bool FULL>
+static int launch_rows_generic(sc_ctx* ctx, const RowLaunch& a) {
+    return launch_row_kernel(ctx, k_inv_rows<T, FULL>, a, fft_threads(T), fft_lds_bytes(T));
+}
+// the plain fast kernel (FULL, MAPS as the search asks) and its near-tie form
+template <int T, bool FULL, bool MAPS, bool PT, bool NEAR = false>
+static int launch_rows_fast(sc_ctx* ctx, const RowLaunch& a) {
+    return launch_row_kernel(ctx, k_inv_rows_fast<T, FULL, MAPS, PT, false, NEAR>, a, inv_rows_fast_threads<T>(),
+                             inv_rows_fast_lds<T>());
+}
+// the dealt-out form and the merge of its shares: T in {512, 1024}, no masks, no maps
+template <int T, bool PT, bool NEAR>
+static int launch_rows_split(sc_ctx* ctx, const RowLaunch& a) {
+    if (int rc = launch_row_kernel(ctx, k_inv_rows_fast<T, false, false, PT, true, NEAR>, a, inv_rows_fast_threads<T>(),
+                                   inv_rows_fast_lds_split<T>()))
+        return rc;
+    const RowArgs& ra = a.ra;
+    const unsigned mb = (unsigned)std::min<size_t>((ra.nc + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_merge_split<NEAR>, dim3(mb), dim3(256), 0, ctx->stream, (float*)ctx->best_snr.p,
+                       (float*)ctx->best_amp.p, (uint32_t*)ctx->best_id.p, ra.s2, (const float*)ra.a2,
+                       (const uint32_t*)ra.i2, ra.nc, NEAR ? ra.nsplit : ra.nsplit - 1, ra.near_w, ra.near,
+                       ra.ev_count, ra.ev, ra.ev_cap);
+    return SC_OK;
+}
+
+template <int T, bool PT>
+static int launch_rows_fast_family(sc_ctx* ctx, const RowLaunch& a) {
+    switch (a.k) {
+        case FFT_ROW_SPLIT:
+            if constexpr (T <= 1024) return a.near ? launch_rows_split<T, PT, true>(ctx, a) : launch_rows_split<T, PT, false>(ctx, a);
+            break;
+        case FFT_ROW_NEAR: return launch_rows_fast<T, false, false, PT, true>(ctx, a);
+        case FFT_ROW_FAST:
+            if (a.full_masks) return a.to_maps ? launch_rows_fast<T, true, true, PT>(ctx, a) : launch_rows_fast<T, true, false, PT>(ctx, a);
+            return a.to_maps ? launch_rows_fast<T, false, true, PT>(ctx, a) : launch_rows_fast<T, false, false, PT>(ctx, a);
+        default: break;
+    }
+    return sc_fail(ctx, SC_ERR_UNSUPPORTED, "fast row pass: kernel %d at row length %d", (int)a.k, T);
+}
+
+static int launch_inv_rows(sc_ctx* ctx, const RowLaunch& a) {
+    if (a.k == FFT_ROW_GENERIC)
+        return fft_for_size<FFT_SIZES>(ctx, a.Tx, "tile size %d", [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            return a.full_masks ? launch_rows_generic<T, true>(ctx, a) : launch_rows_generic<T, false>(ctx, a);
+        });
+    return fft_for_size<512, 1024, 2048>(ctx, a.Tx, "fast row pass: row length %d", [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        return a.pt ? launch_rows_fast_family<T, true>(ctx, a) : launch_rows_fast_family<T, false>(ctx, a);
+    });
+}
+
 // Templates [first, first+n) of the current batch have their spectra in vh
 // planes [0, n).  For every tile pair: inverse transforms in groups of `group`
 // templates, folded in template order.
@@ -3278,9 +3375,14 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                      int group, bool to_maps, bool full_masks, int parity, int nb) {
     // nb > 1: templates [first, first + nb*n) are nb orientations of n templates each
     // (fft_batch_orientations); n <= group then, and the row kernel is the fast one
-    const bool sym = fft_use_sym(ctx, fg, parity);
+    if (group > SC_MAX_GROUP)
+        return sc_fail(ctx, SC_ERR_INVALID, "group %d exceeds %d", group, SC_MAX_GROUP);
+    FftRouteIn rin = fft_route_in(ctx, fg, parity);
+    rin.full_masks = full_masks; rin.to_maps = to_maps; rin.nb = nb; rin.n = n; rin.group = group;
+    const FftRoute r = fft_route(rin);
+    // (the near-tie refusal is answered where the parent answered it: at the chunk's first row-pass launch)
+    if (r.err && r.msg != FFT_REFUSE_NEAR) return sc_fail(ctx, r.err, r.msg, fg.Ty, fg.Tx);
     int np = npairs_of(fg);
-    size_t lds_r = fft_lds_bytes(fg.Tx);
     // row pairs of a tile that hold valid outputs: r' in [Py, Py + Vy)
     int rp_lo = 0, rp_hi = fg.Ty / 2 - 1;
     if (!fg.circ_y) {
@@ -3288,24 +3390,12 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
         rp_hi = std::min(fg.Ty - 1, fg.Py + fg.Vy - 1) / 2;
     }
     const int rp_n = rp_hi - rp_lo + 1;
-    if (group > SC_MAX_GROUP)
-        return sc_fail(ctx, SC_ERR_INVALID, "group %d exceeds %d", group, SC_MAX_GROUP);
     const int pb = std::max(1, ctx->fft_pb);
     const size_t yblock = (size_t)fg.Ty * fg.Tx * group;          // cells per pair in yw / ym
-    const bool fast = (fg.Tx == 512 || fg.Tx == 1024 || fg.Tx == 2048) && ctx->variant != 9;
-    // block and mirror workgroups of the two-launch form in one launch, paired per XCD (k_inv_cols_symx)
-    const bool symx = sym && ctx->variant != 6 && fg.Ty >= 512 && fg.Ty <= 2048 && (fg.Tx / 8) % 8 == 0;
-    // one wave per column (k_inv_cols_w8): column length 1024 / 2048.  Paired-template chunks at 2048 take
-    // the four-wave form k_inv_cols_w4 (one wave per SIMD, 512 registers): with eight waves the second
-    // coefficient plane does not fit - 32 spilled values reloaded per transform wait for the stores in
-    // flight, 1 455 us at C2 against k_inv_cols_symx's 1 000; k_inv_cols_w4: 915
-    const bool w8 = symx && ctx->variant != 2 && (fg.Ty == 2048 || fg.Ty == 1024) && (fg.Tx / 16) % 8 == 0;
-    if (nb > 1 && (!fast || n > group || nb * n > SC_MAX_BATCH || n > SC_MAX_GROUP))
-        return sc_fail(ctx, SC_ERR_INVALID, "orientation batching outside its conditions");
     // The curvature's row spectra wait in cblk (fft_forward_curv, option "fuse_fwd"): the wave-per-column kernels
     // transform the columns they park themselves.  Any other column kernel reads uc / uc2: k_fwd_cols after all,
     // once, for this and every later chunk of the same orientations.
-    const bool fwd = ctx->curv_rows > 0 && w8 && ctx->variant != 1 && !to_maps;
+    const bool fwd = ctx->curv_rows > 0 && r.fwd;
     if (ctx->curv_rows > 0 && !fwd) {
         const size_t half = (size_t)fg.Ty * fg.Tx * sizeof(float2) * (ctx->curv_rows / 2);
         int rc;
@@ -3316,20 +3406,15 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
             return rc;
         ctx->curv_rows = 0;
     }
-    const float2* const xc = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc.p + ctx->uc_off;
-    const float2* const xc2 = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc2.p + ctx->uc_off;
-    // One chunk = pc tile pairs through I1 and I2, group by group.  PTV: the chunk is a
+    // One chunk = pc tile pairs through I1 and I2, group by group.  pt: the chunk is a
     // single pair whose second tile is empty; templates ride in pairs instead (see
     // k_inv_cols_sym) - the symmetric I1 and the fast I2 know that mode.
-    auto chunk = [&](int pair0, int pc, auto ptc) -> int {
-        constexpr bool PTV = decltype(ptc)::value;
+    auto chunk = [&](int pair0, int pc, bool pt) -> int {
+        const FftChunkRoute& c = pt ? r.ptc : r.main;
+        const bool xp = fft_route_xp(c.col), fast = c.row != FFT_ROW_GENERIC;
         for (int g0 = 0; g0 < n; g0 += group) {
             int G = std::min(group, n - g0);
-            // Paired orientations (inv_cols_sym_body, XP): a paired-template chunk with ONE template per
-            // orientation and a batch of orientations would run every transform half empty
-            // (option "variant" 12: off, for the cross-check of the two forms)
-            const bool xp = PTV && n == 1 && nb >= 2 && pc == 1 && sym && symx && fg.Ty == 512 &&
-                            ctx->variant != 12 && !to_maps;
+            const int ng = pt ? (G + 1) / 2 : G;               // transforms of the group: templates ride in pairs
             // I1: as many tile pairs per launch as it takes to fill the chip once
             // (one 2048-tile pair does; longer launches lost 6 % on the sustained C3 run)
             const size_t lds_c = (size_t)4 * fft_line(fg.Ty) * sizeof(float2) +
@@ -3342,361 +3427,136 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
             // jil) - a launch of several pairs one after the other along y lost 6 % (the pairs' workgroups drift apart);
             // interleaved, the 2 x i1_pairs workgroups that stream the same coefficient lines run together on one XCD
             int jil = 1;
-            if (nb == 1 && w8 && (!PTV || fg.Ty == 1024) && ctx->variant != 1 && !xp && ctx->i1_pairs > 1) {
-                jil = std::min(pc, ctx->i1_pairs);
-                pi1 = jil;
-            }
-            // rows masked by the templates' window limits are neither stored by the wave-per-column
-            // kernels nor scored by the row pass (not with explicit per-cell masks or single-template
-            // maps: those write every cell; option "variant" 13 switches it off for the cross-check)
-            const bool row_skip = !full_masks && !to_maps && ctx->variant != 13;
-            // An under-filled column pass deals its transforms out along grid.z (take_template_share): nz parts
-            // so that the launch's workgroups come up to the chip's resident capacity for the kernel (the
-            // four-column kernels: 256 CUs x what LDS and 256 registers allow; wave-per-column: one or two
-            // 512-thread workgroups per CU), every part at least four transforms.  Option "split_i1" 0: off.
-            auto parts_for = [&](long long workgroups, long long capacity, int transforms) {
-                if (!ctx->split_i1 || workgroups <= 0) return 1;
-                if (ctx->split_i1 > 1) return std::max(1, std::min(ctx->split_i1, transforms));   // (lab: a given number of parts)
-                // the number of parts (1 .. 8, every part at least four transforms) that fills the launch's rounds of
-                // resident workgroups best: 672 workgroups on 512 slots are 1.31 rounds - a third of the chip idles through
-                // the second -, in three parts 2 016 workgroups are 3.94 rounds of a third the length (C1F: seven batched
-                // orientations x three tile pairs x 32 column blocks).  Fewer parts win ties: every part parks the spectrum.
-                int best = 1;
-                double best_u = 0.0;
-                for (int nz = 1; nz <= 8 && transforms / nz >= 4; ++nz) {
-                    const long long w = workgroups * nz, rounds = (w + capacity - 1) / capacity;
-                    const double u = (double)w / (double)(rounds * capacity);
-                    if (u > best_u + 0.03) { best_u = u; best = nz; }
-                }
-                return best;
-            };
-            const int NGl = PTV ? (G + 1) / 2 : G;
+            if (c.jil > 1) pi1 = jil = std::min(pc, c.jil);
             sc_prof_begin(ctx, SC_K_INV_COLS);
             int n_i1 = 0;
             for (int pl0 = 0; pl0 < pc; pl0 += pi1) {
-            const int pcc = std::min(pi1, pc - pl0);
-            const int jilc = jil > 1 ? pcc : 1;                 // (the last launch of a chunk may hold fewer pairs)
-            const int pair = pair0 + pl0;
-            float2* ywp = (float2*)ctx->yw.p + (size_t)pl0 * yblock;
-            float2* ymp = (float2*)ctx->ym.p + (size_t)pl0 * yblock;
-            n_i1 += symx ? 1 : 2;            // one paired launch, or own columns + mirrors
-#define COL_ARGS(CB0)                                                          \
-    ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, (const float2*)ctx->wh.p, \
-        (const float2*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi, \
-        (const float2*)ctx->tw_y.p, ywp, ymp, group, np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py
-#define SYM_ARGS(CB0)                                                          \
-    ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, (const float*)ctx->wh.p, \
-        (const float*)ctx->mh.p, fg.Tx, CB0, pair, g0, G, rp_lo, rp_hi, \
-        (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group
-#define SYM_ARGS_D(CB0) SYM_ARGS(CB0), np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py
-#define FN_SYMX(T)                                                             \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_cols_symx<T, PTV>, inv_cols_lds<T>());     \
-        if (rc) return rc;                                                     \
-        const int nz_ = parts_for((long long)(fg.Tx / 4) * nb * pcc,                                \
-                                  256LL * std::max<size_t>(1, std::min<size_t>((160 * 1024) / inv_cols_lds<T>(), \
-                                                                               2048 / fft_threads(T) / 2)), NGl); \
-        hipLaunchKernelGGL((k_inv_cols_symx<T, PTV>), dim3(fg.Tx / 4, nb * pcc, nz_), dim3(fft_threads(T)), \
-                           inv_cols_lds<T>(), ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, \
-                           (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
-                           (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
-                           np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py); \
-    }
-#define FN_W8(T)                                                               \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_cols_w8<T, PTV>, w8_lds<T>());             \
-        if (rc) return rc;                                                     \
-        const int nz_ = parts_for((long long)(fg.Tx / 8) * nb * pcc, 256LL * ((T == 1024 && !PTV) ? 2 : 1), NGl); \
-        hipLaunchKernelGGL((k_inv_cols_w8<T, PTV>), dim3(fg.Tx / 8 * jilc, nb * pcc / jilc, nz_), dim3(512),  \
-                           w8_lds<T>(), ctx->stream, xc, xc2, \
-                           (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
-                           (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
-                           np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py, \
-                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr, jilc, fwd ? 1 : 0); \
-    }
-#define FN_W4(T)                                                               \
-    {                                                                          \
-        /* (more LDS than it uses: one workgroup per CU, one wave per SIMD) */ \
-        const size_t lds4 = (size_t)88 * 1024;                                 \
-        int rc = set_lds(ctx, k_inv_cols_w4<T, PTV>, lds4);                    \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_inv_cols_w4<T, PTV>), dim3(fg.Tx / 4, nb * pcc), dim3(256),  \
-                           lds4, ctx->stream, xc, xc2, \
-                           (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
-                           (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, group, \
-                           np, pcc, n, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py, \
-                           row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr, fwd ? 1 : 0); \
-    }
-#define FN_SYM(T)                                                              \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_cols_sym<T, false, PTV>, inv_cols_lds<T>());    \
-        if (rc) return rc;                                                     \
-        rc = set_lds(ctx, k_inv_cols_sym<T, true, PTV>, inv_cols_lds<T>());         \
-        if (rc) return rc;                                                     \
-        const int nlo = fg.Tx / 8, nhi = fg.Tx / 4 - nlo;                      \
-        hipLaunchKernelGGL((k_inv_cols_sym<T, false, PTV>), dim3(nlo, nb * pcc), dim3(fft_threads(T)), \
-                           inv_cols_lds<T>(), SYM_ARGS_D(0));                  \
-        if (nhi > 0)                                                           \
-            hipLaunchKernelGGL((k_inv_cols_sym<T, true, PTV>), dim3(nhi, nb * pcc), dim3(fft_threads(T)), \
-                               inv_cols_lds<T>(), SYM_ARGS_D(nlo));            \
-    }
-#define FN(T)                                                                  \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_cols<T, false>, inv_cols_lds<T>());        \
-        if (rc) return rc;                                                     \
-        rc = set_lds(ctx, k_inv_cols<T, true>, inv_cols_lds<T>());             \
-        if (rc) return rc;                                                     \
-        const int nlo = fg.Tx / 8, nhi = fg.Tx / 4 - nlo;                      \
-        hipLaunchKernelGGL((k_inv_cols<T, false>), dim3(nlo, nb * pcc), dim3(fft_threads(T)), \
-                           inv_cols_lds<T>(), COL_ARGS(0));                    \
-        if (nhi > 0)                                                           \
-            hipLaunchKernelGGL((k_inv_cols<T, true>), dim3(nhi, nb * pcc), dim3(fft_threads(T)), \
-                               inv_cols_lds<T>(), COL_ARGS(nlo));              \
-    }
-            // column length 512: half a wave per column (k_inv_cols_h2), where the grid pairs up per XCD - sixteen
-            // workgroup ids = eight column blocks and their mirrors: (Tx / 32) % 8 == 0; "variant" 18: the four-column kernels
-            const bool h2 = sym && symx && fg.Ty == 512 && (fg.Tx / 32) % 8 == 0 && ctx->variant != 18 && ctx->variant != 1 &&
-                            ctx->variant != 2;
-#define FN_H2(XPV, GY, YSTR, PCJ, TSTR, TLP)                                   \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_cols_h2<PTV, XPV>, h2_lds());              \
-        if (rc) return rc;                                                     \
-        const int nz_ = XPV ? 1 : parts_for((long long)(fg.Tx / 16) * (GY), 512, NGl); \
-        hipLaunchKernelGGL((k_inv_cols_h2<PTV, XPV>), dim3(fg.Tx / 16, (GY), nz_), dim3(512), h2_lds(), ctx->stream, \
-                           (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off, \
-                           (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi, \
-                           (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, (YSTR), \
-                           np, (PCJ), (TSTR), (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py, (TLP)); \
-    }
-            // (paired orientations - ONE transform per plane and job, all prologue - stay on the four-column kernel: on the
-            //  sixteen-column workgroups C5's column pass took 2.07 ms against 1.62; option "variant" 19 takes them anyway)
-            if (xp && h2 && ctx->variant == 19) {
-                if constexpr (PTV) FN_H2(true, (nb + 1) / 2, 1, 1, nb, (const TemplDev*)nullptr)
-            } else if (h2 && !xp) {
-                FN_H2(false, nb * pcc, group, pcc, n, row_skip ? (const TemplDev*)ctx->templ.p + first : (const TemplDev*)nullptr)
-            } else if (xp) {
-                // paired orientations: job j = orientations 2j, 2j+1; plane j of Y; tstride carries nb
-                const size_t ldsx = inv_cols_lds<512>() + (size_t)4 * 512 * sizeof(float2);
-                int rc = set_lds(ctx, k_inv_cols_symx<512, PTV, PTV>, ldsx);
-                if (rc) return rc;
-                hipLaunchKernelGGL((k_inv_cols_symx<512, PTV, PTV>), dim3(fg.Tx / 4, (nb + 1) / 2), dim3(fft_threads(512)),
-                                   ldsx, ctx->stream, (const float2*)ctx->uc.p + ctx->uc_off, (const float2*)ctx->uc2.p + ctx->uc_off,
-                                   (const float*)ctx->wh.p, (const float*)ctx->mh.p, fg.Tx, pair, g0, G, rp_lo, rp_hi,
-                                   (const float2*)ctx->tw_x.p + fg.Tx, parity, (const float2*)ctx->tw_y.p, ywp, ymp, 1,
-                                   np, 1, nb, (const TileDev*)ctx->tiles.p, fg.circ_y ? -1 : fg.Py);
-            } else if (w8 && (!PTV || (fg.Ty == 1024 && ctx->variant != 1))) {
-                if (fg.Ty == 2048) FN_W8(2048) else FN_W8(1024)
-            } else if (w8 && PTV && fg.Ty == 2048 && ctx->variant != 1) {
-                FN_W4(2048)
-            } else if (sym && symx) {
-                switch (fg.Ty) {
-                    case 512: FN_SYMX(512); break;
-                    case 1024: FN_SYMX(1024); break;
-                    case 2048: FN_SYMX(2048); break;
-                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "paired column pass: column length %d", fg.Ty);
+                const int pcc = std::min(pi1, pc - pl0);
+                ColLaunch a{};
+                a.Ty = fg.Ty; a.Tx = fg.Tx; a.pt = pt; a.jobs = nb * pcc; a.ng = ng; a.split_i1 = r.split_i1;
+                a.uc = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc.p + ctx->uc_off;
+                a.uc2 = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc2.p + ctx->uc_off;
+                a.wh = ctx->wh.p; a.mh = ctx->mh.p;
+                a.pair = pair0 + pl0; a.vfirst = g0; a.G = G; a.rp_lo = rp_lo; a.rp_hi = rp_hi;
+                a.phx = (const float2*)ctx->tw_x.p + fg.Tx; a.parity = parity; a.tw = (const float2*)ctx->tw_y.p;
+                a.yw = (float2*)ctx->yw.p + (size_t)pl0 * yblock;
+                a.ym = (float2*)ctx->ym.p + (size_t)pl0 * yblock;
+                a.ystride = group; a.np = np; a.pcj = pcc; a.tstride = n;
+                a.tiles = (const TileDev*)ctx->tiles.p; a.py_valid = fg.circ_y ? -1 : fg.Py;
+                a.tl = r.row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr;
+                a.jil = jil > 1 ? pcc : 1;                      // (the last launch of a chunk may hold fewer pairs)
+                a.fwd = fwd ? 1 : 0;
+                if (xp) {                        // job j = orientations 2j, 2j+1; plane j of Y; tstride carries nb
+                    a.jobs = (nb + 1) / 2; a.ystride = 1; a.pcj = 1; a.tstride = nb; a.tl = nullptr;
                 }
-            } else if (sym) {
-                switch (fg.Ty) {
-                    case 64: FN_SYM(64); break;
-                    case 128: FN_SYM(128); break;
-                    case 256: FN_SYM(256); break;
-                    case 512: FN_SYM(512); break;
-                    case 1024: FN_SYM(1024); break;
-                    case 2048: FN_SYM(2048); break;
-                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "symmetric column pass: column length %d", fg.Ty);
-                }
-            } else {
-                DISPATCH_T(fg.Ty, FN)
-            }
-#undef FN
-#undef FN_SYM
-#undef FN_SYMX
-#undef FN_W8
-#undef FN_W4
-#undef FN_H2
-#undef SYM_ARGS_D
-#undef SYM_ARGS
-#undef COL_ARGS
+                if (int rc = launch_inv_cols(ctx, c.col, a)) return rc;
+                // one paired launch, or own columns + mirrors
+                n_i1 += (c.col == FFT_COL_GENERIC || c.col == FFT_COL_SYM) ? 2 : 1;
             }
             sc_prof_end(ctx, n_i1);
-            const int pair = pair0;
             // The row pass folds at most SC_MAX_GROUP templates per launch (its scalar table, its 64-bit mask of
-            // transforms, the winner's byte): a batch of more - nb orientations of G templates each, round 5 -
+            // transforms, the winner's byte): a batch of more - nb orientations of G templates each -
             // goes through it in slices of whole orientations, in order; the running best lives in the record
             // between launches, so the fold is the one of a single launch (and of no batching at all).
             // (slices of equal size: 8 orientations of 10 templates go 4 + 4, not 6 + 2 - a short last launch leaves the
             //  chip part empty)
-            // Round 5, second step: where the dealt-out row pass applies (small grids: SPLITK) a launch carries up to
+            // Where the dealt-out row pass applies (small grids: FFT_ROW_SPLIT) a launch carries up to
             // 255 templates - the winner's byte - in shares of at most SC_MAX_GROUP transforms each; C1F's 7 batched
             // orientations of 35 ages are then ONE row-pass launch of four shares at four waves per SIMD instead of
-            // seven launches of two
-            // (with near-tie flags on - the exact mode - only for searches of several templates per orientation: a share meets the
-            //  record as the launch found it, not what the shares before it have reached, and lists near-ties against that floor
-            //  that the sequential fold would not; a Ricker's SNR varies slowly with the orientation - on C5, one template per
-            //  orientation, the split cost more in float64 pairs than it saved in the pass: 14.0 -> 17.3 ms; C1F 51.7 -> 46.6)
-            const bool near_split_ok = !(ctx->near_w > 0.f) || (!xp && G >= 4);
-            const bool can_split = fast && near_split_ok && !to_maps && !full_masks && fg.Tx <= 1024 && ctx->variant != 15 &&
-                                   !(ctx->sib & 1) && ctx->variant != 20;
+            // seven launches of two.  (With near-tie flags on the route allows it from four templates per orientation
+            //  only: on C5, one template per orientation, the split cost more in float64 pairs than it saved in the
+            //  pass: 14.0 -> 17.3 ms; C1F 51.7 -> 46.6)
             // How many shares: up to four (any number, not only powers of two) while the launch stays within ~4 300 waves -
             // the four per SIMD the kernel's 128 registers allow and 5 % (measured at C1F, 1 044 single-wave rows: two
             // shares 19.0 ms, three 13.8, four 13.5; option "split_fill" sets another bound)
-            const int wpw = inv_rows_fast_threads<512>() * (fg.Tx / 512) / 64;          // waves per row workgroup
-            const long long row_wgs = (long long)rp_n * 2 * pc;
-            const long long cap_wg = (ctx->split_fill > 0 ? ctx->split_fill : 4300) / wpw;
-            const int nsplit_max = can_split ? (int)std::max<long long>(1, std::min<long long>(4, cap_wg / std::max<long long>(1, row_wgs))) : 1;
-            const int tper = PTV ? 2 : 1;                      // templates per transform
+            const bool split = c.row == FFT_ROW_SPLIT && G >= c.split_min_g;
+            int nsplit_max = 1;
+            if (split) {
+                const int wpw = inv_rows_fast_threads<512>() * (fg.Tx / 512) / 64;          // waves per row workgroup
+                const long long row_wgs = (long long)rp_n * 2 * pc, cap_wg = c.split_waves / wpw;
+                nsplit_max = (int)std::max<long long>(1, std::min<long long>(c.split_max, cap_wg / std::max<long long>(1, row_wgs)));
+            }
             int nbs = nb;
             if (nb > 1 && !xp) {
-                const int cap_t = nsplit_max > 1 ? std::min(255, SC_MAX_GROUP * nsplit_max * tper) : SC_MAX_GROUP;
+                const int cap_t = nsplit_max > 1 ? std::min(255, SC_MAX_GROUP * nsplit_max * (pt ? 2 : 1)) : SC_MAX_GROUP;
                 const int cap = std::max(1, cap_t / std::max(1, G)), nsl = (nb + cap - 1) / cap;
                 nbs = (nb + nsl - 1) / nsl;
             }
             for (int b0 = 0; b0 < nb; b0 += nbs) {
-            const int nbc = std::min(nbs, nb - b0);
-            const size_t yoff = (size_t)b0 * pc * group * (size_t)fg.Ty * fg.Tx;        // job (b0, 0) of yw / ym
-            const float2* yw_s = (const float2*)ctx->yw.p + yoff;
-            const float2* ym_s = (const float2*)ctx->ym.p + yoff;
-            const double* norms_s = (const double*)ctx->norms.p + ctx->norms_off + (size_t)2 * np * b0;
-            RowArgs ra{fg.Ty, fg.Py, fg.Qx, fg.circ_y, fg.circ_x, ctx->g.cy0, ctx->g.cx0,
-                       ctx->g.cx1 - ctx->g.cx0, pair, first + g0 + b0 * n, G, rp_lo, rp_n, group,
-                       nbc, np, pc, SibSync{nullptr, 0}, (unsigned long long*)ctx->res_stats.p, 0, row_skip ? 1 : 0,
-                       1, 0, nullptr, nullptr, nullptr, 0.f, nullptr};
-            if (xp) {                            // to the row pass: ONE orientation of nb templates, in pairs
-                ra.G = nb; ra.nb = 1; ra.ystride = 1; ra.xp = 1;
-            }
-            dim3 gridr(fast ? ((rp_n + 7) / 8) * 16 : (rp_n + 1) / 2, pc);
-            // Small grids: a row workgroup folds the launch's transforms one after the other, and a 512 x 512
-            // search has 512 rows of ONE wave each for 1 024 SIMDs (BASELINE config C5: the row pass was a
-            // third of the search, a chain of single-wave transforms at half the issue rate).  There the
-            // transforms are dealt out over nsplit workgroups per row, each folding its share in order into a
-            // record of its own; k_merge_split folds the shares into the record in order.  Same winners, same
-            // ties (option "variant" 15: off).
-            // Near-tie flags (option "near_window" > 0: the host layer's exact mode): the plain fast kernel only
-            const bool near = ctx->near_w > 0.f && !to_maps;
-            if (near) {
-                if (!fast || full_masks)
-                    return sc_fail(ctx, SC_ERR_UNSUPPORTED, "near-tie flags need the fast row kernel without per-cell masks");
-                int rc = sc_near_buffers(ctx, &ra.ev_count, &ra.ev, &ra.ev_cap);
-                if (rc) return rc;
-                ra.near_w = ctx->near_w;
-                ra.near = (uint8_t*)ctx->near.p;
-            }
-            int nsplit = 1;
-            if (fast && near_split_ok && !to_maps && !full_masks && fg.Tx <= 1024 && ctx->variant != 15 && !(ctx->sib & 1)) {
-                const int ngl = nbc * (PTV ? (G + 1) / 2 : G);
-                // (option "split_fill": the waves the dealt-out row pass may come to instead of the chip's resident
-                //  capacity for the kernel; every share at least four transforms, at most SC_MAX_GROUP - its 64-bit mask)
-                nsplit = std::max(1, std::min(nsplit_max, ngl / 4));
-                nsplit = std::max(nsplit, (ngl + SC_MAX_GROUP - 1) / SC_MAX_GROUP);
-                if (nsplit > 4 || (ngl + nsplit - 1) / nsplit > SC_MAX_GROUP)
-                    return sc_fail(ctx, SC_ERR_INVALID, "row pass: %d transforms in %d shares", ngl, nsplit);
-            }
-            if (nsplit > 1) {
-                const size_t nc = (size_t)(ctx->g.cy1 - ctx->g.cy0) * (ctx->g.cx1 - ctx->g.cx0);
-                const size_t need = (size_t)4 * nc * sizeof(float);          // up to four shares: three scratch records (four with near-tie flags on)
-                const bool fresh = ctx->split_s.cap < need;
-                int rc;
-                if ((rc = sc_ensure(ctx, ctx->split_s, need))) return rc;
-                if ((rc = sc_ensure(ctx, ctx->split_a, need))) return rc;
-                if ((rc = sc_ensure(ctx, ctx->split_i, need))) return rc;
-                if (fresh) SC_HIP(ctx, hipMemsetAsync(ctx->split_s.p, 0, need, ctx->stream));   // (sc_reset_best clears it from then on)
-                ra.nsplit = nsplit;
-                ra.nc = nc;
-                ra.s2 = (float*)ctx->split_s.p;
-                ra.a2 = (float*)ctx->split_a.p;
-                ra.i2 = (uint32_t*)ctx->split_i.p;
-                gridr.z = nsplit;
-            }
-            if (fast && (ctx->sib & 1)) {
-                int rc = sib_slots(ctx, (size_t)gridr.x * gridr.y, ra.sib);
-                if (rc) return rc;
-            }
-            sc_prof_begin(ctx, SC_K_INV_ROWS);
-#define ROW_ARGS lds_r, FAST_ARGS
-#define FAST_ARGS                                                              \
-    ctx->stream, yw_s, ym_s, ra, ctx->g,                                       \
-        (const TileDev*)ctx->tiles.p, (const TemplDev*)ctx->templ.p, (const double*)ctx->sums.p, \
-        (const double*)ctx->wl1.p, norms_s, ctx->kappa,                        \
-        (const double*)ctx->xaxis.p, (const double*)ctx->yaxis.p, (const float2*)ctx->tw_x.p, \
-        (float*)ctx->best_snr.p, (float*)ctx->best_amp.p, (uint32_t*)ctx->best_id.p,        \
-        to_maps ? (float*)ctx->map_amp.p : nullptr, to_maps ? (float*)ctx->map_snr.p : nullptr
-#define LAUNCH_ROWS(T, FULLV)                                                  \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_rows<T, FULLV>, lds_r);                    \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_inv_rows<T, FULLV>), gridr, dim3(fft_threads(T)), ROW_ARGS); \
-    }
-#define LAUNCH_FAST2(T, FULLV, MAPSV)                                          \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_rows_fast<T, FULLV, MAPSV, PTV>, inv_rows_fast_lds<T>()); \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_inv_rows_fast<T, FULLV, MAPSV, PTV>), gridr,          \
-                           dim3(inv_rows_fast_threads<T>()), inv_rows_fast_lds<T>(), FAST_ARGS); \
-    }
-#define LAUNCH_FAST(T, FULLV)                                                  \
-    { if (to_maps) LAUNCH_FAST2(T, FULLV, true) else LAUNCH_FAST2(T, FULLV, false) }
-#define LAUNCH_SPLIT2(T, NEARV)                                                \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_rows_fast<T, false, false, PTV, true, NEARV>, inv_rows_fast_lds_split<T>()); \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_inv_rows_fast<T, false, false, PTV, true, NEARV>), gridr,   \
-                           dim3(inv_rows_fast_threads<T>()), inv_rows_fast_lds_split<T>(), FAST_ARGS); \
-        const unsigned mb_ = (unsigned)std::min<size_t>((ra.nc + 255) / 256, 2048); \
-        hipLaunchKernelGGL(k_merge_split<NEARV>, dim3(mb_), dim3(256), 0, ctx->stream, (float*)ctx->best_snr.p, \
-                           (float*)ctx->best_amp.p, (uint32_t*)ctx->best_id.p, ra.s2,                \
-                           (const float*)ra.a2, (const uint32_t*)ra.i2, ra.nc, (NEARV) ? nsplit : nsplit - 1, ra.near_w, ra.near, \
-                           ra.ev_count, ra.ev, ra.ev_cap);                                           \
-    }
-#define LAUNCH_SPLIT(T) { if (near) LAUNCH_SPLIT2(T, true) else LAUNCH_SPLIT2(T, false) }
-#define LAUNCH_NEAR(T)                                                         \
-    {                                                                          \
-        int rc = set_lds(ctx, k_inv_rows_fast<T, false, false, PTV, false, true>, inv_rows_fast_lds<T>()); \
-        if (rc) return rc;                                                     \
-        hipLaunchKernelGGL((k_inv_rows_fast<T, false, false, PTV, false, true>), gridr,   \
-                           dim3(inv_rows_fast_threads<T>()), inv_rows_fast_lds<T>(), FAST_ARGS); \
-    }
-            if (nsplit > 1) {
-                if (fg.Tx == 512) LAUNCH_SPLIT(512) else LAUNCH_SPLIT(1024)
-            } else if (near) {
-                switch (fg.Tx) {
-                    case 512: LAUNCH_NEAR(512) break;
-                    case 1024: LAUNCH_NEAR(1024) break;
-                    case 2048: LAUNCH_NEAR(2048) break;
-                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "fast row pass: row length %d", fg.Tx);
+                const int nbc = std::min(nbs, nb - b0);
+                const size_t yoff = (size_t)b0 * pc * group * (size_t)fg.Ty * fg.Tx;        // job (b0, 0) of yw / ym
+                RowLaunch rl{};
+                rl.Tx = fg.Tx; rl.pt = pt; rl.full_masks = full_masks; rl.to_maps = to_maps; rl.near = r.near;
+                rl.yw = (const float2*)ctx->yw.p + yoff;
+                rl.ym = (const float2*)ctx->ym.p + yoff;
+                rl.norms = (const double*)ctx->norms.p + ctx->norms_off + (size_t)2 * np * b0;
+                RowArgs& ra = rl.ra;
+                ra = RowArgs{fg.Ty, fg.Py, fg.Qx, fg.circ_y, fg.circ_x, ctx->g.cy0, ctx->g.cx0,
+                             ctx->g.cx1 - ctx->g.cx0, pair0, first + g0 + b0 * n, G, rp_lo, rp_n, group,
+                             nbc, np, pc, SibSync{nullptr, 0}, (unsigned long long*)ctx->res_stats.p, 0, r.row_skip ? 1 : 0,
+                             1, 0, nullptr, nullptr, nullptr, 0.f, nullptr};
+                if (xp) {                            // to the row pass: ONE orientation of nb templates, in pairs
+                    ra.G = nb; ra.nb = 1; ra.ystride = 1; ra.xp = 1;
                 }
-            } else if (fast) {
-                switch (fg.Tx) {
-                    case 512: if (full_masks) LAUNCH_FAST(512, true) else LAUNCH_FAST(512, false) break;
-                    case 1024: if (full_masks) LAUNCH_FAST(1024, true) else LAUNCH_FAST(1024, false) break;
-                    case 2048: if (full_masks) LAUNCH_FAST(2048, true) else LAUNCH_FAST(2048, false) break;
-                    default: return sc_fail(ctx, SC_ERR_UNSUPPORTED, "fast row pass: row length %d", fg.Tx);
+                rl.grid = dim3(fast ? ((rp_n + 7) / 8) * 16 : (rp_n + 1) / 2, pc);
+                // Near-tie flags (option "near_window" > 0: the host layer's exact mode)
+                if (r.err) return sc_fail(ctx, r.err, r.msg, fg.Ty, fg.Tx);
+                if (r.near) {
+                    int rc = sc_near_buffers(ctx, &ra.ev_count, &ra.ev, &ra.ev_cap);
+                    if (rc) return rc;
+                    ra.near_w = ctx->near_w;
+                    ra.near = (uint8_t*)ctx->near.p;
                 }
-            } else {
-#define FN(T) { if (full_masks) LAUNCH_ROWS(T, true) else LAUNCH_ROWS(T, false) }
-                DISPATCH_T(fg.Tx, FN)
-#undef FN
+                // Small grids: a row workgroup folds the launch's transforms one after the other, and a 512 x 512
+                // search has 512 rows of ONE wave each for 1 024 SIMDs (BASELINE config C5: the row pass was a
+                // third of the search, a chain of single-wave transforms at half the issue rate).  There the
+                // transforms are dealt out over nsplit workgroups per row, each folding its share in order into a
+                // record of its own; k_merge_split folds the shares into the record in order.  Same winners, same ties.
+                int nsplit = 1;
+                if (split) {
+                    const int ngl = nbc * ng;
+                    // (every share at least four transforms, at most SC_MAX_GROUP - its 64-bit mask)
+                    nsplit = std::max(1, std::min(nsplit_max, ngl / 4));
+                    nsplit = std::max(nsplit, (ngl + SC_MAX_GROUP - 1) / SC_MAX_GROUP);
+                    if (nsplit > 4 || (ngl + nsplit - 1) / nsplit > SC_MAX_GROUP)
+                        return sc_fail(ctx, SC_ERR_INVALID, "row pass: %d transforms in %d shares", ngl, nsplit);
+                }
+                if (nsplit > 1) {
+                    const size_t nc = (size_t)(ctx->g.cy1 - ctx->g.cy0) * (ctx->g.cx1 - ctx->g.cx0);
+                    const size_t need = (size_t)4 * nc * sizeof(float);          // up to four shares: three scratch records (four with near-tie flags on)
+                    const bool fresh = ctx->split_s.cap < need;
+                    int rc;
+                    if ((rc = sc_ensure(ctx, ctx->split_s, need))) return rc;
+                    if ((rc = sc_ensure(ctx, ctx->split_a, need))) return rc;
+                    if ((rc = sc_ensure(ctx, ctx->split_i, need))) return rc;
+                    if (fresh) SC_HIP(ctx, hipMemsetAsync(ctx->split_s.p, 0, need, ctx->stream));   // (sc_reset_best clears it from then on)
+                    ra.nsplit = nsplit;
+                    ra.nc = nc;
+                    ra.s2 = (float*)ctx->split_s.p;
+                    ra.a2 = (float*)ctx->split_a.p;
+                    ra.i2 = (uint32_t*)ctx->split_i.p;
+                    rl.grid.z = nsplit;
+                }
+                if (r.sib_rows) {
+                    int rc = sib_slots(ctx, (size_t)rl.grid.x * rl.grid.y, ra.sib);
+                    if (rc) return rc;
+                }
+                // a launch of one share is the plain kernel's (or its near-tie form's)
+                rl.k = nsplit > 1 || c.row != FFT_ROW_SPLIT ? c.row : r.near ? FFT_ROW_NEAR : FFT_ROW_FAST;
+                sc_prof_begin(ctx, SC_K_INV_ROWS);
+                if (int rc = launch_inv_rows(ctx, rl)) return rc;
+                sc_prof_end(ctx);
             }
-#undef LAUNCH_ROWS
-#undef LAUNCH_FAST
-#undef LAUNCH_FAST2
-#undef LAUNCH_SPLIT
-#undef LAUNCH_SPLIT2
-#undef LAUNCH_NEAR
-#undef ROW_ARGS
-#undef FAST_ARGS
-            sc_prof_end(ctx);
-            }                                    // (row-pass slices)
         }
         return SC_OK;
     };
-    const bool pt = sym && fast && (fg.ntiles & 1) && ctx->variant != 5;
-    const int np_main = pt ? np - 1 : np;
+    const int np_main = r.pt ? np - 1 : np;
     for (int pair0 = 0; pair0 < np_main; pair0 += pb) {
-        int rc = chunk(pair0, std::min(pb, np_main - pair0), std::false_type{});
+        int rc = chunk(pair0, std::min(pb, np_main - pair0), false);
         if (rc) return rc;
     }
-    if (pt) {
-        int rc = chunk(np - 1, 1, std::true_type{});
+    if (r.pt) {
+        int rc = chunk(np - 1, 1, true);
         if (rc) return rc;
     }
     SC_HIP(ctx, hipGetLastError());

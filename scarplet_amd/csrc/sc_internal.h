@@ -60,12 +60,7 @@ struct WindowSlot {
     uint8_t* mask_err = nullptr;
 };
 
-// templates per inverse launch (sc_match batches an orientation run in chunks)
-#define SC_MAX_GROUP 64
-// templates one batched launch SEQUENCE can carry (forward passes and column pass of nb orientations x n
-// templates each); the row pass folds them in launches of at most SC_MAX_GROUP, orientation slice after slice
-#define SC_MAX_BATCH 256
-#define SC_MAX_ORIENT 64         // orientations (curvature planes) one launch sequence can carry
+#include "sc_fft_route.h"         // SC_MAX_GROUP, SC_MAX_BATCH, SC_MAX_ORIENT; the FFT path's choice of kernels
 
 struct sc_ctx {
     int device = 0;

@@ -1,8 +1,8 @@
 """Every kernel class of the FFT path's dispatch table against the float64 oracle, by forced tile plans.
 
-sc_fft.hip chooses its kernels by the tile's column length Ty (64 .. 256: k_inv_cols_sym or the generic k_inv_cols;
+The route (fft_route, scarplet_amd/csrc/sc_fft_route.h) chooses the kernels by the tile's column length Ty (64 .. 256: k_inv_cols_sym or the generic k_inv_cols;
 512: k_inv_cols_symx / k_inv_cols_h2 / the paired-orientation form; 1024, 2048: the wave-per-column kernels with the
-fused forward column transform; 4096: the generic complex path, fft_use_sym is false there), by the row length Tx (512,
+fused forward column transform; 4096: the generic complex path, no symmetric-template kernel there), by the row length Tx (512,
 1024, 2048: k_inv_rows_fast and its near-tie and dealt-out forms; the rest: k_inv_rows), by the chunk's parity and masks,
 by the parity of the tile count (an odd count sends the last tile through the paired-template chunk) and by whether maps
 or the fold are asked for.  A natural plan on the suite's DEMs reaches a few of these combinations; a hand-built plan

@@ -163,7 +163,7 @@ def test_cross_lane_exchange_feeds_stage_3_what_the_lds_path_reads():
 
 def test_can_flag_near_ties_mirrors_the_row_kernel():
     """Matcher.can_flag_near_ties - how Matcher and the dist drivers choose the exact mode's path before matching - states
-    sc_fft.hip's condition for the near-tie flags: an FFT plan with tiles 512, 1024 or 2048 wide, option "variant" not 9,
+    the route's condition for the near-tie flags (fft_route in sc_fft_route.h, FFT_REFUSE_NEAR): an FFT plan with tiles 512, 1024 or 2048 wide, option "variant" not 9,
     no template with UpperBreak error masks, no host-uploaded window with masks."""
     import types
     from scarplet_amd import _lib

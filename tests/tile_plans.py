@@ -3,7 +3,7 @@
 On the periodic whole-DEM context a tile loads its input modulo the DEM, and sc_match accepts any plan whose tiles
 cover the core: neither V == T - span nor T <= n is required.  So a tile of any supported size - 64 to 4096 on either
 axis, in any number - can be put on a small DEM, and one float64 oracle stack of that DEM can serve every kernel class the
-dispatch table of sc_fft.hip knows.  tests/test_tile_plans_host.py checks these plans on the host.
+route of the FFT path (scarplet_amd/csrc/sc_fft_route.h) knows.  tests/test_tile_plans_host.py checks these plans on the host.
 """
 
 SIZES = (64, 128, 256, 512, 1024, 2048, 4096)
