@@ -544,6 +544,22 @@ class Context(object):
             "sc_trace_result")
 
     # -- scarp-profile dating (docs/profiles.md) ------------------------------------
+    def _fit_call(self, name, head, rest, shift, shift_plane, shape, z):
+        """sc_fit_profiles / sc_fit_segments and their _shift and _dem forms: ``head``, D when shifted, ``rest``, and when
+        shifted the int8 plane of ``shape`` (returned; None unless asked for).  ``z``: the _dem form on that DEM."""
+        plane = None
+        args = head + rest
+        if shift is not None:
+            name += "_shift"
+            plane = np.zeros(shape, dtype=np.int8) if shift_plane else None
+            args = head + [int(shift)] + rest + [plane.ctypes.data_as(C.c_void_p) if shift_plane else None]
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return plane
+
     def fit_profiles(self, cells, sa, ca, ages, h, w, de, delta, min_samples, curve=False, z=None, shift=None,
                      shift_plane=False):
         """sc_fit_profiles on the context's DEM, or sc_fit_profiles_dem on ``z`` (float64, C-contiguous, 2-D):
@@ -555,20 +571,9 @@ class Context(object):
         assert len(sa) == K and len(ca) == K
         rows = np.zeros(K, dtype=PROFILE_DTYPE if shift is None else PROFILE_SHIFT_DTYPE)
         sse = np.empty((K, A), dtype=np.float64) if curve else None
-        tail = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h),
-                int(w)] + ([] if shift is None else [int(shift)]) + \
-               [float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None]
-        name = "sc_fit_profiles"
-        plane = None
-        if shift is not None:
-            name = "sc_fit_profiles_shift"
-            plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
-            tail.append(plane.ctypes.data_as(C.c_void_p) if shift_plane else None)
-        if z is None:
-            self._check(getattr(self.lib, name)(self._h, *tail), name)
-        else:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            self._check(getattr(self.lib, name + "_dem")(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail), name + "_dem")
+        head = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w)]
+        rest = [float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None]
+        plane = self._fit_call("sc_fit_profiles", head, rest, shift, shift_plane, (K, A), z)
         return (rows, sse) if shift is None else (rows, sse, plane)
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
@@ -587,22 +592,11 @@ class Context(object):
         tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE if shift is None else SEGMENT_SHIFT_CELL_DTYPE) if cell_table else None
         sse = np.empty((S, A), dtype=np.float64) if curve else None
         llp = C.POINTER(C.c_longlong)
-        tail = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w)] + \
-               ([] if shift is None else [int(shift)]) + \
-               [float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+        head = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w)]
+        rest = [float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
                 tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
-        name = "sc_fit_segments"
-        plane = None
-        if shift is not None:
-            name = "sc_fit_segments_shift"
-            plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
-            tail.append(plane.ctypes.data_as(C.c_void_p) if shift_plane else None)
-        if z is None:
-            self._check(getattr(self.lib, name)(self._h, *tail), name)
-        else:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            self._check(getattr(self.lib, name + "_dem")(self._h, _as(z, _dp), z.shape[0], z.shape[1], *tail), name + "_dem")
+        plane = self._fit_call("sc_fit_segments", head, rest, shift, shift_plane, (K, A), z)
         return (rows, tab, sse) if shift is None else (rows, tab, sse, plane)
 
     # -- measurement ----------------------------------------------------------

@@ -1,0 +1,303 @@
+// The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
+// included by sc_profile.hip and sc_segment.hip alone.  The library is built with -ffp-contract=off and every helper
+// here is inlined, so a helper does the operations of its text in the order of its text wherever it is called: the
+// four calls return the same bits in every field they share because they call the same helpers.
+#pragma once
+#include "sc_internal.h"
+
+#define PF_WAVES 4                       // cells in flight per workgroup: one wave per cell
+#define PF_THREADS (64 * PF_WAVES)
+#define PF_TAB_LDS 65536                 // the erf table goes to LDS up to this many bytes
+#define PF_MAX_GRID 2048
+
+// ---- sc_profile.hip, shared with sc_segment.hip (`who` names the call in the messages) ----------------------------------
+// the argument checks of a profile call
+int sc_pf_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const double* ages, int A, int h, int w, double de, double delta,
+                int min_samples, const void* out_rows);
+// the rules of the shift range D of sc_fit_profiles_shift / sc_fit_segments_shift
+int sc_pf_check_shift(sc_ctx* ctx, const char* who, int h, int D, int min_samples);
+// the calls on the context's DEM: it must be set and be the whole grid
+int sc_pf_whole_grid(sc_ctx* ctx, const char* who);
+// the _dem calls: z (ny x nx float64 on the host) into the call's own buffer
+int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx);
+// the launch of the erf table over j = -h..h (d_ages on the device; timed as SC_K_PROFILE)
+int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
+
+// ---- the centre shift (docs/profiles.md, "The centre shift") --------------------------------------------------------------
+// candidates in the order 0, -1, +1, -2, +2, ...: rank r -> shift d
+__host__ __device__ __forceinline__ int sh_shift_of(int r) { return (r & 1) ? -((r + 1) >> 1) : (r >> 1); }
+
+#define SH_TERMS 5             // what a wave keeps per age of the best shift: sse, See, Sep, ebar, gamma
+__host__ __device__ __forceinline__ size_t sh_slot_doubles(int A) { return (size_t)SH_TERMS * A + (size_t)((A + 1) / 2); }
+
+// ---- dynamic LDS of a kernel with one wave per cell ------------------------------------------------------------------------
+// PF_WAVES profiles of np points, then PF_WAVES slots of the shift search where the kernel searches, then the erf table
+// (nt rows of A) where it is staged.  The host sizes the launch by the same two functions.
+__host__ __device__ __forceinline__ size_t pf_lds_head(int np, int A, bool slots) {
+    return (size_t)PF_WAVES * ((size_t)np + (slots ? sh_slot_doubles(A) : 0));
+}
+__host__ __device__ __forceinline__ size_t pf_lds_bytes(int np, int nt, int A, bool slots, bool tab_lds) {
+    return sizeof(double) * (pf_lds_head(np, A, slots) + (tab_lds ? (size_t)nt * A : 0));
+}
+
+struct pf_lds {
+    double* prof;              // this wave's profile
+    double* slot;              // this wave's slot of the search (SLOTS)
+    const double* tab;         // the table: in LDS (TAB_LDS) or where it was
+};
+
+// carves the workgroup's LDS and stages the table; ends in a barrier
+template <bool TAB_LDS, bool SLOTS>
+__device__ __forceinline__ pf_lds pf_stage(const double* __restrict__ tab_g, int np, int nt, int A) {
+    extern __shared__ double pf_lds_mem[];
+    const int wave = threadIdx.x >> 6;
+    pf_lds L;
+    L.prof = pf_lds_mem + (size_t)wave * np;
+    L.slot = SLOTS ? pf_lds_mem + (size_t)PF_WAVES * np + (size_t)wave * sh_slot_doubles(A) : nullptr;
+    L.tab = tab_g;
+    if (TAB_LDS) {
+        double* t = pf_lds_mem + pf_lds_head(np, A, SLOTS);
+        for (int idx = threadIdx.x; idx < nt * A; idx += PF_THREADS) t[idx] = tab_g[idx];
+        L.tab = t;
+    }
+    __syncthreads();
+    return L;
+}
+
+// ---- sampling (docs/profiles.md, "Samples") ----------------------------------------------------------------------------------
+// one bilinear sample; false where it is outside the grid or not finite
+__device__ __forceinline__ bool pf_sample(const double* __restrict__ z, int ny, int nx, double rr, double cc, double& v) {
+    if (!(rr >= 0.0 && rr <= (double)(ny - 1) && cc >= 0.0 && cc <= (double)(nx - 1))) return false;
+    const int r0 = min((int)floor(rr), ny - 2), c0 = min((int)floor(cc), nx - 2);
+    const double fr = rr - (double)r0, fc = cc - (double)c0;
+    const double* q = z + (size_t)r0 * nx + c0;
+    const double z00 = q[0], z01 = q[1], z10 = q[nx], z11 = q[nx + 1];
+    v = (z00 * (1.0 - fc) + z01 * fc) * (1.0 - fr) + (z10 * (1.0 - fc) + z11 * fc) * fr;
+    return isfinite(v);
+}
+
+// one point of a profile: the mean of the valid samples across the swath in ascending k, NaN where none is valid
+__device__ __forceinline__ double pf_point(const double* __restrict__ z, int ny, int nx, double r, double c, double sa,
+                                           double ca, int jj, int h, int w) {
+    const double j = (double)(jj - h);
+    const double jsa = j * sa, jca = j * ca;
+    double acc = 0.0;
+    int cnt = 0;
+    for (int kk = -w; kk <= w; ++kk) {
+        const double k = (double)kk;
+        const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
+        double v;
+        if (pf_sample(z, ny, nx, rr, cc, v)) {
+            acc += v;
+            ++cnt;
+        }
+    }
+    return cnt ? acc / (double)cnt : __builtin_nan("");
+}
+
+// the profile of input cell kc, lanes over its points: into the wave's LDS and, where park is given, global memory
+__device__ __forceinline__ void pf_cut(const double* __restrict__ z, int ny, int nx, long long cell,
+                                       const double* __restrict__ dir, long long kc, int h, int w, int lane, double* prof,
+                                       double* __restrict__ park) {
+    const int np = 2 * h + 1;
+    const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
+    const double r = (double)(cell / nx), c = (double)(cell % nx);
+    for (int jj = lane; jj < np; jj += 64) {
+        const double p = pf_point(z, ny, nx, r, c, sa, ca, jj, h, w);
+        prof[jj] = p;
+        if (park) park[(size_t)kc * np + jj] = p;
+    }
+}
+
+// ---- the fit of one erf column to one profile ----------------------------------------------------------------------------------
+// The profile is in LDS, NaN marking a missing point; point jj has s = (jj - h) de and the column's e is col[jj * A].
+// Every sum is a plain loop over ascending jj in one lane.  The lanes-over-ages kernels (k_pf_fit, k_sg_partial) take
+// the column's sums in the sweeps that form the profile's own (COL); the kernels of the shift form the profile's once
+// (no COL) and each (shift, age) pair's by pf_column.  An in-order sum is the same bits in a sweep of its own.
+struct pf_mom { int n, n_neg, n_pos; double Ss, Sp, Se; };      // pass 0: counts (all, j < 0, j > 0) and plain sums
+struct pf_lin { double dn, sbar, pbar, Sss, beta; };            // the profile against (1, s)
+struct pf_col { double ebar, gamma, See, Sep; };                // the column against (1, s), and what is left of both
+
+template <bool COL>
+__device__ __forceinline__ pf_mom pf_moments(const double* prof, int np, int h, double de, const double* col, int A) {
+    pf_mom m = {0, 0, 0, 0.0, 0.0, 0.0};
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        ++m.n;
+        m.n_neg += jj < h ? 1 : 0;
+        m.n_pos += jj > h ? 1 : 0;
+        m.Ss += (double)(jj - h) * de;
+        m.Sp += p;
+        if (COL) m.Se += col[(size_t)jj * A];
+    }
+    return m;
+}
+
+// pass 1: the centred s against itself and p - and against e (COL: t.ebar and t.gamma)
+template <bool COL>
+__device__ __forceinline__ pf_lin pf_line(const double* prof, int np, int h, double de, const pf_mom& m, const double* col,
+                                          int A, pf_col& t) {
+    pf_lin L;
+    L.dn = (double)m.n;
+    L.sbar = m.Ss / L.dn;
+    L.pbar = m.Sp / L.dn;
+    if (COL) t.ebar = m.Se / L.dn;
+    double Sss = 0.0, Sps = 0.0, Ses = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double sc = (double)(jj - h) * de - L.sbar;
+        Sss += sc * sc;
+        Sps += sc * (p - L.pbar);
+        if (COL) Ses += sc * (col[(size_t)jj * A] - t.ebar);
+    }
+    L.Sss = Sss;
+    L.beta = Sps / Sss;
+    if (COL) t.gamma = Ses / Sss;
+    return L;
+}
+
+// pass 2: what is left of e after 1 and s, against what is left of p (t.ebar and t.gamma in, t.See and t.Sep out)
+__device__ __forceinline__ void pf_rest(const double* prof, int np, int h, double de, const pf_lin& L, const double* col,
+                                        int A, pf_col& t) {
+    double See = 0.0, Sep = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double sc = (double)(jj - h) * de - L.sbar;
+        const double e2 = (col[(size_t)jj * A] - t.ebar) - t.gamma * sc;
+        const double p2 = (p - L.pbar) - L.beta * sc;
+        See += e2 * e2;
+        Sep += e2 * p2;
+    }
+    t.See = See;
+    t.Sep = Sep;
+}
+
+// passes 0 to 2 of a column alone, the profile's own terms given
+__device__ __forceinline__ pf_col pf_column(const double* prof, int np, int h, double de, const pf_lin& L, const double* col,
+                                            int A) {
+    pf_col t;
+    double Se = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        Se += col[(size_t)jj * A];
+    }
+    t.ebar = Se / L.dn;
+    double Ses = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double sc = (double)(jj - h) * de - L.sbar;
+        Ses += sc * (col[(size_t)jj * A] - t.ebar);
+    }
+    t.gamma = Ses / L.Sss;
+    pf_rest(prof, np, h, de, L, col, A, t);
+    return t;
+}
+
+// slope and intercept of a profile once the amplitude a is known (its own Sep / See, or the segment's)
+__device__ __forceinline__ void pf_slope(double sbar, double pbar, double beta, double ebar, double gamma, double a,
+                                         double& b, double& c0) {
+    b = beta - a * gamma;
+    c0 = (pbar - a * ebar) - b * sbar;
+}
+
+// pass 3: the explicit residuals
+__device__ __forceinline__ double pf_sse(const double* prof, int np, int h, double de, const double* col, int A, double a,
+                                         double b, double c0) {
+    double sse = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de;
+        const double res = p - ((c0 + b * s) + a * col[(size_t)jj * A]);
+        sse += res * res;
+    }
+    return sse;
+}
+
+// ---- the choice over the ages ---------------------------------------------------------------------------------------------------
+// One wave, lane i holding sse_i (lanes >= A are ignored): argmin with ties to the smaller index (a NaN never wins), thr =
+// sse_min (1 + delta / dof), and the interval walked from the best age while sse <= thr.  The same in every lane.
+struct pf_pick { int best, lo, hi; double sse_min; };
+
+__device__ __forceinline__ pf_pick pf_choose(double sse, int lane, int A, double delta, int dof) {
+    double m = lane < A ? sse : INFINITY;
+    if (m != m) m = INFINITY;
+    int mi = lane;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const double om = __shfl_xor(m, o, 64);
+        const int oi = __shfl_xor(mi, o, 64);
+        if (om < m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    pf_pick k;
+    k.sse_min = m;
+    k.best = min(mi, A - 1);
+    const double thr = m * (1.0 + delta / (double)dof);
+    const unsigned long long ok = __ballot(lane < A && sse <= thr);
+    k.lo = k.hi = k.best;
+    while (k.lo > 0 && ((ok >> (k.lo - 1)) & 1ull)) --k.lo;
+    while (k.hi < A - 1 && ((ok >> (k.hi + 1)) & 1ull)) ++k.hi;
+    return k;
+}
+
+// status bits 2 and 4: the interval is open below, above
+__device__ __forceinline__ int pf_open(const pf_pick& k, int A) { return (k.lo == 0 ? 2 : 0) + (k.hi == A - 1 ? 4 : 0); }
+
+// ---- the shift search --------------------------------------------------------------------------------------------------------------
+// One wave, one profile: for every age i the shift d_i with the smallest sse among d = -D..D.  The LANES RUN OVER THE
+// (shift rank, age) PAIRS, age-minor, 64 pairs a round; each lane runs pf_column, pf_slope and pf_sse for its pair with
+// e_ij taken from row j - d of the table (rows -(h + D)..(h + D), A doubles each).  The lanes of a round that share an
+// age sit A lanes apart: an argmin over them by shuffles (offsets A, 2 A, 4 A, ...) on the key (sse, rank) - a NaN
+// counts as +inf, the smaller rank wins a tie, so the order of the combination does not matter - leaves the round's
+// winner of every age known to its lowest lane; the winning lane merges its terms into the wave's slot, where a later
+// round wins only when strictly smaller (ranks ascend from round to round).  The first smallest in the order 0, -1,
+// +1, ... wins, whatever the round it fell into.  slot: SH_TERMS x A doubles (sse, See, Sep, ebar, gamma of the
+// winner), then A ints (its rank).  No atomics, no float sum across lanes.
+__device__ __forceinline__ void sh_search(const double* prof, const double* tab, int np, int h, int A, int D, double de,
+                                          int lane, const pf_lin& L, double* slot) {
+    int* srank = (int*)(slot + (size_t)SH_TERMS * A);
+    const int P = A * (2 * D + 1);
+    const int low = lane % A;                            // the lowest lane of this lane's age in a round
+    for (int q0 = 0; q0 < P; q0 += 64) {
+        const bool on = q0 + lane < P;
+        const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
+        const int r = q / A, i = q - r * A;
+        const double* col = tab + (size_t)(D - sh_shift_of(r)) * A + i;
+        const pf_col t = pf_column(prof, np, h, de, L, col, A);
+        const double a = t.Sep / t.See;
+        double b, c0;
+        pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
+        const double sse = pf_sse(prof, np, h, de, col, A, a, b, c0);
+        // the round's winner of every age: argmin over the lanes A apart (a lane past the end hands back its own value)
+        const double key = (on && sse == sse) ? sse : INFINITY;
+        double m = key;
+        int mr = on ? r : INT_MAX;
+        for (int off = A; off < 64; off <<= 1) {
+            const double om = __shfl_down(m, off, 64);
+            const int orr = __shfl_down(mr, off, 64);
+            if (om < m || (om == m && orr < mr)) { m = om; mr = orr; }
+        }
+        const int win = __shfl(mr, low, 64);
+        if (on && r == win) {                            // (one lane per age)
+            const double cur = slot[i];
+            if (q0 == 0 || key < ((cur == cur) ? cur : INFINITY)) {       // (every age meets its rank 0 in the first round)
+                slot[i] = sse;
+                slot[A + i] = t.See;
+                slot[2 * A + i] = t.Sep;
+                slot[3 * A + i] = t.ebar;
+                slot[4 * A + i] = t.gamma;
+                srank[i] = r;
+            }
+        }
+        // (one wave: the next round's winners, and the caller, read what these lanes wrote)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}

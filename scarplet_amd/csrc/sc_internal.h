@@ -203,144 +203,6 @@ int sc_lds_attr(sc_ctx* ctx, const void* kernel, size_t bytes);
                            hipGetErrorString(e__), __FILE__, __LINE__);       \
     } while (0)
 
-// sc_profile.hip, shared with sc_segment.hip: the argument checks of a profile call (`who` names the call in the
-// messages) and the launch of the erf table (d_ages on the device; timed as SC_K_PROFILE)
-int sc_pf_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
-                const double* ca, long long K, const double* ages, int A, int h, int w, double de, double delta,
-                int min_samples, const void* out_rows);
-int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
-// the rules of the shift range D of sc_fit_profiles_shift / sc_fit_segments_shift
-int sc_pf_check_shift(sc_ctx* ctx, const char* who, int h, int D, int min_samples);
-
-#ifdef __HIPCC__
-// one bilinear sample of docs/profiles.md; false where it is outside the grid or not finite
-__device__ __forceinline__ bool pf_sample(const double* __restrict__ z, int ny, int nx, double rr, double cc, double& v) {
-    if (!(rr >= 0.0 && rr <= (double)(ny - 1) && cc >= 0.0 && cc <= (double)(nx - 1))) return false;
-    const int r0 = min((int)floor(rr), ny - 2), c0 = min((int)floor(cc), nx - 2);
-    const double fr = rr - (double)r0, fc = cc - (double)c0;
-    const double* q = z + (size_t)r0 * nx + c0;
-    const double z00 = q[0], z01 = q[1], z10 = q[nx], z11 = q[nx + 1];
-    v = (z00 * (1.0 - fc) + z01 * fc) * (1.0 - fr) + (z10 * (1.0 - fc) + z11 * fc) * fr;
-    return isfinite(v);
-}
-
-// ---- the centre shift of sc_fit_profiles_shift / sc_fit_segments_shift (docs/profiles.md, "The centre shift") ----------
-// candidates in the order 0, -1, +1, -2, +2, ...: rank r -> shift d
-__device__ __forceinline__ int sh_shift_of(int r) { return (r & 1) ? -((r + 1) >> 1) : (r >> 1); }
-
-#define SH_TERMS 5             // what a wave keeps per age of the best shift: sse, See, Sep, ebar, gamma
-__host__ __device__ __forceinline__ size_t sh_slot_doubles(int A) { return (size_t)SH_TERMS * A + (size_t)((A + 1) / 2); }
-
-// One point of a profile (docs/profiles.md, "Samples"): the mean of the valid bilinear samples across the swath in
-// ascending k, NaN where none is valid - the loop k_pf_fit and k_sg_partial write out, for the kernels of the shift
-__device__ __forceinline__ double pf_point(const double* __restrict__ z, int ny, int nx, double r, double c, double sa,
-                                           double ca, int jj, int h, int w) {
-    const double j = (double)(jj - h);
-    const double jsa = j * sa, jca = j * ca;
-    double acc = 0.0;
-    int cnt = 0;
-    for (int kk = -w; kk <= w; ++kk) {
-        const double k = (double)kk;
-        const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
-        double v;
-        if (pf_sample(z, ny, nx, rr, cc, v)) {
-            acc += v;
-            ++cnt;
-        }
-    }
-    return cnt ? acc / (double)cnt : __builtin_nan("");
-}
-
-// One wave, one profile (in LDS, NaN marking a missing point): for every age i the shift d_i with the smallest sse among
-// d = -D..D.  The LANES RUN OVER THE (shift rank, age) PAIRS, age-minor, 64 pairs a round; each lane runs the four passes
-// of k_pf_fit for its pair with e_ij taken from row j - d of the table (rows -(h + D)..(h + D), A doubles each).  n, sbar,
-// pbar, Sss and beta depend on neither i nor d: the caller forms them once, by the same sums.  The lanes of a round that
-// share an age sit A lanes apart: an argmin over them by shuffles (offsets A, 2 A, 4 A, ...) on the key (sse, rank) - a
-// NaN counts as +inf, the smaller rank wins a tie, so the order of the combination does not matter - leaves the
-// round's winner of every age known to its lowest lane; the winning lane merges its terms into the wave's slot, where
-// a later round wins only when strictly smaller (ranks ascend from round to round).  The first smallest in the order
-// 0, -1, +1, ... wins, whatever the round it fell into.  slot: SH_TERMS x A doubles (sse, See, Sep, ebar, gamma of the
-// winner), then A ints (its rank).  No atomics, no float sum across lanes.
-__device__ __forceinline__ void sh_search(const double* prof, const double* tab, int np, int h, int A, int D, double de,
-                                          int lane, double dn, double sbar, double pbar, double Sss, double beta,
-                                          double* slot) {
-    int* srank = (int*)(slot + (size_t)SH_TERMS * A);
-    const int P = A * (2 * D + 1);
-    const int low = lane % A;                            // the lowest lane of this lane's age in a round
-    for (int q0 = 0; q0 < P; q0 += 64) {
-        const bool on = q0 + lane < P;
-        const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
-        const int r = q / A, i = q - r * A;
-        const double* col = tab + (size_t)(D - sh_shift_of(r)) * A + i;      // e_ij of point jj: col[jj * A]
-        // pass 0: the sum of this pair's e over the valid points
-        double Se = 0.0;
-        for (int jj = 0; jj < np; ++jj) {
-            const double p = prof[jj];
-            if (p != p) continue;
-            Se += col[(size_t)jj * A];
-        }
-        const double ebar = Se / dn;
-        // pass 1: the centred s against e
-        double Ses = 0.0;
-        for (int jj = 0; jj < np; ++jj) {
-            const double p = prof[jj];
-            if (p != p) continue;
-            const double sc = (double)(jj - h) * de - sbar;
-            Ses += sc * (col[(size_t)jj * A] - ebar);
-        }
-        const double gamma = Ses / Sss;
-        // pass 2: what is left of e after 1 and s, against what is left of p
-        double See = 0.0, Sep = 0.0;
-        for (int jj = 0; jj < np; ++jj) {
-            const double p = prof[jj];
-            if (p != p) continue;
-            const double sc = (double)(jj - h) * de - sbar;
-            const double e2 = (col[(size_t)jj * A] - ebar) - gamma * sc;
-            const double p2 = (p - pbar) - beta * sc;
-            See += e2 * e2;
-            Sep += e2 * p2;
-        }
-        const double a = Sep / See;
-        const double b = beta - a * gamma;
-        const double c0 = (pbar - a * ebar) - b * sbar;
-        // pass 3: the explicit residuals
-        double sse = 0.0;
-        for (int jj = 0; jj < np; ++jj) {
-            const double p = prof[jj];
-            if (p != p) continue;
-            const double s = (double)(jj - h) * de;
-            const double res = p - ((c0 + b * s) + a * col[(size_t)jj * A]);
-            sse += res * res;
-        }
-        // the round's winner of every age: argmin over the lanes A apart (a lane past the end hands back its own value)
-        const double key = (on && sse == sse) ? sse : INFINITY;
-        double m = key;
-        int mr = on ? r : INT_MAX;
-        for (int off = A; off < 64; off <<= 1) {
-            const double om = __shfl_down(m, off, 64);
-            const int orr = __shfl_down(mr, off, 64);
-            if (om < m || (om == m && orr < mr)) { m = om; mr = orr; }
-        }
-        const int win = __shfl(mr, low, 64);
-        if (on && r == win) {                            // (one lane per age)
-            const double cur = slot[i];
-            if (q0 == 0 || key < ((cur == cur) ? cur : INFINITY)) {       // (every age meets its rank 0 in the first round)
-                slot[i] = sse;
-                slot[A + i] = See;
-                slot[2 * A + i] = Sep;
-                slot[3 * A + i] = ebar;
-                slot[4 * A + i] = gamma;
-                srank[i] = r;
-            }
-        }
-        // (one wave: the next round's winners, and the caller, read what these lanes wrote)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
-#endif
-
 // profiling brackets around kernel launches
 void sc_prof_begin(sc_ctx* ctx, int kernel);
 void sc_prof_end(sc_ctx* ctx, int n = 1);

@@ -1,30 +1,31 @@
-// sc_fit_profiles / sc_fit_profiles_dem: scarp-profile dating across a trace (docs/profiles.md).
+// sc_fit_profiles* : scarp-profile dating across a trace (docs/profiles.md).
 //
 // For each cell a profile of 2h + 1 points is cut across the strike (each point the mean of up to 2w + 1 bilinear
-// samples along the strike), and z(s) = c0 + b s + a erf(s / (2 sqrt(kt))) is fitted to it for each of A ages.
+// samples along the strike), and z(s) = c0 + b s + a erf(s / (2 sqrt(kt))) is fitted to it for each of A ages.  The
+// pieces are those of sc_fit.h; a kernel here is the order in which it calls them.
 //   k_pf_table   the erf column of every (point, age): it depends on the cell in no way, so it is a table of
 //                (2h + 1) x A float64, age-minor, built once per call
 //   k_pf_fit     one wave per cell, PF_WAVES cells per workgroup, workgroups striding over the cells so that the
 //                cells in flight are neighbours of the input order (cells of one trace share their samples' lines)
-//     sampling   lanes over the points j, the 2w + 1 samples of a point summed in ascending k; the profile goes to
-//                the wave's slice of LDS, NaN marking a point without a valid sample
-//     fit        lanes over the AGES: lane i walks the whole profile for age i - the profile is an LDS broadcast,
-//                the table row j is A consecutive doubles - in four passes (sums and means; the centred s against
-//                p and e; the residual column e'' against the detrended p; the explicit residuals).  Every sum is a
-//                plain loop over ascending j in one lane: no cross-lane reduction, the same bits every run, and a
-//                profile with missing points is the same code as a complete one.
-//     choice     argmin over the lanes (ties to the smaller age index), a ballot of sse <= thr for the interval
-// The table sits in LDS when it fits PF_TAB_LDS bytes (35 ages at h = 100: 56 KB) and in global memory otherwise.
-// No atomics at all.
-#include "sc_internal.h"
+//     pf_cut       lanes over the points j; the profile goes to the wave's slice of LDS, NaN marking a point without
+//                  a valid sample
+//     the fit      lanes over the AGES: lane i walks the whole profile for age i - the profile is an LDS broadcast,
+//                  the table row j is A consecutive doubles - in four sweeps: pf_moments and pf_line with the lane's
+//                  column in the same sweep, pf_rest, pf_sse.  Every sum is a plain loop over ascending j in one
+//                  lane: no cross-lane reduction, the same bits every run, and a profile with missing points is the
+//                  same code as a complete one.
+//     pf_choose    argmin over the lanes (ties to the smaller age index), a ballot of sse <= thr for the interval
+//   k_pf_shift   sc_fit_profiles_shift: the same wave per cell, pf_cut and LDS profile; the table covers
+//                j = -(h + D)..(h + D).  pf_moments and pf_line without a column, once; then the lanes run over the
+//                (shift, age) pairs (sh_search), whose winners per age come back in the wave's slot of LDS, and
+//                pf_choose runs on sse*.
+// The table sits in LDS when it fits PF_TAB_LDS bytes (35 ages at h = 100: 56 KB) and in global memory otherwise
+// (pf_stage).  No atomics at all.
+#include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
 
-#define PF_WAVES 4                       // cells in flight per workgroup
-#define PF_THREADS (64 * PF_WAVES)
-#define PF_TAB_LDS 65536                 // the table goes to LDS up to this many bytes
 #define PF_CHUNK (1ll << 19)             // cells per launch: bounds the call's buffers (96 B a row, 8 A B a curve)
-#define PF_MAX_GRID 2048
 
 __global__ __launch_bounds__(256) void k_pf_table(const double* __restrict__ ages, int A, int h, double de,
                                                   double* __restrict__ tab) {
@@ -36,6 +37,37 @@ __global__ __launch_bounds__(256) void k_pf_table(const double* __restrict__ age
     }
 }
 
+// the fields sc_profile_fit and sc_profile_shift_fit share, of a cell that is not fitted and of one that is (the rows
+// were cleared: their padding is part of what the caller compares)
+template <class ROW>
+__device__ __forceinline__ void pf_row_unfit(ROW* out, long long cell, int n) {
+    const double nan = __builtin_nan("");
+    out->cell = cell;
+    out->n = n;
+    out->kt_index = -1;
+    out->lo_index = -1;
+    out->hi_index = -1;
+    out->status = 1;
+    out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
+    out->a = nan; out->b = nan; out->c0 = nan;
+    out->sse = nan; out->rmse = nan;
+}
+
+template <class ROW>
+__device__ __forceinline__ void pf_row_fit(ROW* out, long long cell, int n, const pf_pick& k, int status,
+                                           const double* __restrict__ ages, double a, double b, double c0, double sse,
+                                           int dof) {
+    out->cell = cell;
+    out->n = n;
+    out->kt_index = k.best;
+    out->lo_index = k.lo;
+    out->hi_index = k.hi;
+    out->status = status;
+    out->kt = ages[k.best]; out->kt_lo = ages[k.lo]; out->kt_hi = ages[k.hi];
+    out->a = a; out->b = b; out->c0 = c0;
+    out->sse = sse; out->rmse = sqrt(sse / (double)dof);
+}
+
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict__ z, int ny, int nx,
                                                        const long long* __restrict__ cells,
@@ -43,19 +75,11 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict_
                                                        const double* __restrict__ ages, int A, int h, int w, double de,
                                                        double delta, int min_samples, const double* __restrict__ tab_g,
                                                        sc_profile_fit* __restrict__ rows, double* __restrict__ curve) {
-    extern __shared__ double pf_lds[];
     const int np = 2 * h + 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = pf_lds + (size_t)wave * np;
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = pf_lds + (size_t)PF_WAVES * np;
-        for (int idx = threadIdx.x; idx < np * A; idx += PF_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
+    const pf_lds L = pf_stage<TAB_LDS, false>(tab_g, np, np, A);
     const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
-    const double nan = __builtin_nan("");
+    const double* col = L.tab + ia;
     const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
     for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
         const long long kc = g * PF_WAVES + wave;
@@ -63,128 +87,33 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict_
         long long cell = 0;
         if (act) {
             cell = cells[kc];
-            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
-            const double r = (double)(cell / nx), c = (double)(cell % nx);
-            for (int jj = lane; jj < np; jj += 64) {
-                const double j = (double)(jj - h);
-                const double jsa = j * sa, jca = j * ca;
-                double acc = 0.0;
-                int cnt = 0;
-                for (int kk = -w; kk <= w; ++kk) {
-                    const double k = (double)kk;
-                    const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
-                    double v;
-                    if (pf_sample(z, ny, nx, rr, cc, v)) {
-                        acc += v;
-                        ++cnt;
-                    }
-                }
-                prof[jj] = cnt ? acc / (double)cnt : nan;
-            }
+            pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr);
         }
         __syncthreads();
         if (act) {
-            // pass 0: counts, sums of s, p and this lane's e over the valid points
-            int n = 0, n_neg = 0, n_pos = 0;
-            double Ss = 0.0, Sp = 0.0, Se = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                ++n;
-                n_neg += jj < h ? 1 : 0;
-                n_pos += jj > h ? 1 : 0;
-                Ss += (double)(jj - h) * de;
-                Sp += p;
-                Se += tab[(size_t)jj * A + ia];
-            }
+            const pf_mom mo = pf_moments<true>(L.prof, np, h, de, col, A);
             sc_profile_fit* out = rows + kc;
-            if (n_neg < min_samples || n_pos < min_samples) {
-                if (lane == 0) {
-                    out->cell = cell;
-                    out->n = n;
-                    out->kt_index = -1;
-                    out->lo_index = -1;
-                    out->hi_index = -1;
-                    out->status = 1;
-                    out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
-                    out->a = nan; out->b = nan; out->c0 = nan;
-                    out->sse = nan; out->rmse = nan;
-                }
-                if (curve && lane < A) curve[kc * A + lane] = nan;
+            if (mo.n_neg < min_samples || mo.n_pos < min_samples) {
+                if (lane == 0) pf_row_unfit(out, cell, mo.n);
+                if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
             } else {
-                const double dn = (double)n;
-                const double sbar = Ss / dn, pbar = Sp / dn, ebar = Se / dn;
-                // pass 1: the centred s against itself, p and e
-                double Sss = 0.0, Sps = 0.0, Ses = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    Sss += sc * sc;
-                    Sps += sc * (p - pbar);
-                    Ses += sc * (tab[(size_t)jj * A + ia] - ebar);
-                }
-                const double beta = Sps / Sss, gamma = Ses / Sss;
-                // pass 2: what is left of e after 1 and s, against what is left of p
-                double See = 0.0, Sep = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    const double e2 = (tab[(size_t)jj * A + ia] - ebar) - gamma * sc;
-                    const double p2 = (p - pbar) - beta * sc;
-                    See += e2 * e2;
-                    Sep += e2 * p2;
-                }
-                const double a = Sep / See;
-                const double b = beta - a * gamma;
-                const double c0 = (pbar - a * ebar) - b * sbar;
-                // pass 3: the explicit residuals
-                double sse = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double s = (double)(jj - h) * de;
-                    const double res = p - ((c0 + b * s) + a * tab[(size_t)jj * A + ia]);
-                    sse += res * res;
-                }
+                pf_col t;
+                const pf_lin f = pf_line<true>(L.prof, np, h, de, mo, col, A, t);
+                pf_rest(L.prof, np, h, de, f, col, A, t);
+                const double a = t.Sep / t.See;
+                double b, c0;
+                pf_slope(f.sbar, f.pbar, f.beta, t.ebar, t.gamma, a, b, c0);
+                const double sse = pf_sse(L.prof, np, h, de, col, A, a, b, c0);
                 if (curve && lane < A) curve[kc * A + lane] = sse;
-                // argmin over the ages, ties to the smaller index (a NaN never wins)
-                double m = lane < A ? sse : INFINITY;
-                if (m != m) m = INFINITY;
-                int mi = lane;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const double om = __shfl_xor(m, o, 64);
-                    const int oi = __shfl_xor(mi, o, 64);
-                    if (om < m || (om == m && oi < mi)) { m = om; mi = oi; }
-                }
-                const int best = min(mi, A - 1);
-                const double thr = m * (1.0 + delta / (double)(n - 3));
-                const unsigned long long ok = __ballot(lane < A && sse <= thr);
-                int lo = best, hi = best;
-                while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
-                while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
-                if (lane == best) {
-                    out->cell = cell;
-                    out->n = n;
-                    out->kt_index = best;
-                    out->lo_index = lo;
-                    out->hi_index = hi;
-                    out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0);
-                    out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
-                    out->a = a; out->b = b; out->c0 = c0;
-                    out->sse = sse; out->rmse = sqrt(sse / (double)(n - 3));
-                }
+                const int dof = mo.n - 3;
+                const pf_pick k = pf_choose(sse, lane, A, delta, dof);
+                if (lane == k.best) pf_row_fit(out, cell, mo.n, k, pf_open(k, A), ages, a, b, c0, sse, dof);
             }
         }
         __syncthreads();
     }
 }
 
-// sc_fit_profiles_shift: the same wave per cell, sampling and LDS profile; the table covers j = -(h + D)..(h + D) and
-// the lanes run over the (shift, age) pairs (sh_search, sc_internal.h), whose winners per age come back in the wave's
-// slot of LDS.  The choice over the ages is k_pf_fit's, on sse*.
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restrict__ z, int ny, int nx,
                                                          const long long* __restrict__ cells,
@@ -194,21 +123,12 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restric
                                                          const double* __restrict__ tab_g,
                                                          sc_profile_shift_fit* __restrict__ rows,
                                                          double* __restrict__ curve, signed char* __restrict__ shifts) {
-    extern __shared__ double pf_lds[];
-    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
+    const int np = 2 * h + 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = pf_lds + (size_t)wave * np;
-    double* slot = pf_lds + (size_t)PF_WAVES * np + (size_t)wave * sh_slot_doubles(A);
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = pf_lds + (size_t)PF_WAVES * (np + sh_slot_doubles(A));
-        for (int idx = threadIdx.x; idx < nt * A; idx += PF_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
+    const pf_lds L = pf_stage<TAB_LDS, true>(tab_g, np, 2 * (h + D) + 1, A);
+    const double* slot = L.slot;
     const int* srank = (const int*)(slot + (size_t)SH_TERMS * A);
     const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
-    const double nan = __builtin_nan("");
     const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
     for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
         const long long kc = g * PF_WAVES + wave;
@@ -216,91 +136,38 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restric
         long long cell = 0;
         if (act) {
             cell = cells[kc];
-            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
-            const double r = (double)(cell / nx), c = (double)(cell % nx);
-            for (int jj = lane; jj < np; jj += 64) prof[jj] = pf_point(z, ny, nx, r, c, sa, ca, jj, h, w);
+            pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr);
         }
         __syncthreads();
         if (act) {
-            // what depends on neither the age nor the shift, once: pass 0's counts and sums of s and p
-            int n = 0, n_neg = 0, n_pos = 0;
-            double Ss = 0.0, Sp = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                ++n;
-                n_neg += jj < h ? 1 : 0;
-                n_pos += jj > h ? 1 : 0;
-                Ss += (double)(jj - h) * de;
-                Sp += p;
-            }
-            const int dof = n - 3 - (D > 0 ? 1 : 0);
+            // what depends on neither the age nor the shift, once
+            const pf_mom mo = pf_moments<false>(L.prof, np, h, de, nullptr, A);
+            const int dof = mo.n - 3 - (D > 0 ? 1 : 0);
             sc_profile_shift_fit* out = rows + kc;
-            if (n_neg < min_samples || n_pos < min_samples || dof < 1) {
+            if (mo.n_neg < min_samples || mo.n_pos < min_samples || dof < 1) {
                 if (lane == 0) {
-                    out->cell = cell;
-                    out->n = n;
-                    out->kt_index = -1;
-                    out->lo_index = -1;
-                    out->hi_index = -1;
-                    out->status = 1;
-                    out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
-                    out->a = nan; out->b = nan; out->c0 = nan;
-                    out->sse = nan; out->rmse = nan;
+                    pf_row_unfit(out, cell, mo.n);
                     out->shift_index = 0;
-                    out->shift = nan;
+                    out->shift = __builtin_nan("");
                 }
-                if (curve && lane < A) curve[kc * A + lane] = nan;
+                if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
                 if (shifts && lane < A) shifts[kc * A + lane] = 0;
             } else {
-                const double dn = (double)n;
-                const double sbar = Ss / dn, pbar = Sp / dn;
-                // ... and pass 1's centred s against itself and p
-                double Sss = 0.0, Sps = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    Sss += sc * sc;
-                    Sps += sc * (p - pbar);
-                }
-                const double beta = Sps / Sss;
-                sh_search(prof, tab, np, h, A, D, de, lane, dn, sbar, pbar, Sss, beta, slot);
+                pf_col t;
+                const pf_lin f = pf_line<false>(L.prof, np, h, de, mo, nullptr, A, t);
+                sh_search(L.prof, L.tab, np, h, A, D, de, lane, f, L.slot);
                 // lane i takes age i's winner
                 const double sse = slot[ia];
                 const int d = sh_shift_of(srank[ia]);
                 if (curve && lane < A) curve[kc * A + lane] = sse;
                 if (shifts && lane < A) shifts[kc * A + lane] = (signed char)d;
-                // argmin over the ages, ties to the smaller index (a NaN never wins)
-                double m = lane < A ? sse : INFINITY;
-                if (m != m) m = INFINITY;
-                int mi = lane;
-#pragma unroll
-                for (int o = 32; o >= 1; o >>= 1) {
-                    const double om = __shfl_xor(m, o, 64);
-                    const int oi = __shfl_xor(mi, o, 64);
-                    if (om < m || (om == m && oi < mi)) { m = om; mi = oi; }
-                }
-                const int best = min(mi, A - 1);
-                const double thr = m * (1.0 + delta / (double)dof);
-                const unsigned long long ok = __ballot(lane < A && sse <= thr);
-                int lo = best, hi = best;
-                while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
-                while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
-                if (lane == best) {
-                    const double ebar = slot[3 * A + ia], gamma = slot[4 * A + ia];
+                const pf_pick k = pf_choose(sse, lane, A, delta, dof);
+                if (lane == k.best) {
                     const double a = slot[2 * A + ia] / slot[A + ia];
-                    const double b = beta - a * gamma;
-                    const double c0 = (pbar - a * ebar) - b * sbar;
-                    out->cell = cell;
-                    out->n = n;
-                    out->kt_index = best;
-                    out->lo_index = lo;
-                    out->hi_index = hi;
-                    out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0) + (D > 0 && (d == D || d == -D) ? 8 : 0);
-                    out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
-                    out->a = a; out->b = b; out->c0 = c0;
-                    out->sse = sse; out->rmse = sqrt(sse / (double)dof);
+                    double b, c0;
+                    pf_slope(f.sbar, f.pbar, f.beta, slot[3 * A + ia], slot[4 * A + ia], a, b, c0);
+                    pf_row_fit(out, cell, mo.n, k, pf_open(k, A) + (D > 0 && (d == D || d == -D) ? 8 : 0), ages, a, b, c0, sse,
+                               dof);
                     out->shift_index = d;
                     out->shift = (double)d * de;
                 }
@@ -340,108 +207,7 @@ int sc_pf_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const 
     return SC_OK;
 }
 
-int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab) {
-    const int np = 2 * h + 1;
-    sc_prof_begin(ctx, SC_K_PROFILE);
-    k_pf_table<<<std::max(1, std::min(256, (np * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, h, de, d_tab);
-    SC_HIP(ctx, hipGetLastError());
-    sc_prof_end(ctx, 1);
-    return SC_OK;
-}
 
-static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
-                  long long K, const double* ages, int A, int h, int w, double de, double delta, int min_samples,
-                  sc_profile_fit* out_rows, double* out_sse) {
-    if (K == 0) return SC_OK;
-    const int np = 2 * h + 1;
-    const size_t tab_bytes = sizeof(double) * (size_t)np * A;
-    const long long chunk = std::min<long long>(K, PF_CHUNK);
-    int rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_tab, tab_bytes))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, sizeof(sc_profile_fit) * (size_t)chunk))) return rc;
-    if (out_sse && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)A * (size_t)chunk))) return rc;
-    double* d_ages = (double*)ctx->pf_ages.p;
-    double* d_tab = (double*)ctx->pf_tab.p;
-    long long* d_cells = (long long*)ctx->pf_cells.p;
-    double* d_dir = (double*)ctx->pf_dir.p;
-    sc_profile_fit* d_rows = (sc_profile_fit*)ctx->pf_rows.p;
-    double* d_sse = out_sse ? (double*)ctx->pf_sse.p : nullptr;
-
-    const bool tab_lds = tab_bytes <= PF_TAB_LDS;
-    const size_t lds = sizeof(double) * (size_t)PF_WAVES * np + (tab_lds ? tab_bytes : 0);
-    const void* fn = tab_lds ? (const void*)k_pf_fit<true> : (const void*)k_pf_fit<false>;
-    if ((rc = sc_lds_attr(ctx, fn, lds))) return rc;
-
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
-
-    std::vector<double> dir;
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const long long m = std::min(chunk, K - k0);
-        dir.resize(2 * (size_t)m);
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_profile_fit) * (size_t)m, ctx->stream));
-        const unsigned grid = (unsigned)std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID);
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        if (tab_lds)
-            k_pf_fit<true><<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, de, delta,
-                                                                   min_samples, d_tab, d_rows, d_sse);
-        else
-            k_pf_fit<false><<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, de, delta,
-                                                                    min_samples, d_tab, d_rows, d_sse);
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + k0, d_rows, sizeof(sc_profile_fit) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sse)
-            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)k0 * A, d_sse, sizeof(double) * (size_t)A * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        // (dir is reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return SC_OK;
-}
-
-extern "C" int sc_fit_profiles(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
-                               const double* ages, int A, int h, int w, double de, double delta, int min_samples,
-                               sc_profile_fit* out_rows, double* out_sse) {
-    if (!ctx) return SC_ERR_INVALID;
-    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
-    const Geom& g = ctx->g;
-    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles: the context holds a block of a larger grid");
-    int rc = sc_pf_check(ctx, "sc_fit_profiles", g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
-    if (rc) return rc;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    return pf_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows, out_sse);
-}
-
-extern "C" int sc_fit_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
-                                   const double* ca, long long K, const double* ages, int A, int h, int w, double de,
-                                   double delta, int min_samples, sc_profile_fit* out_rows, double* out_sse) {
-    if (!ctx || !z) return SC_ERR_INVALID;
-    int rc = sc_pf_check(ctx, "sc_fit_profiles", ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
-    if (rc) return rc;
-    if (K == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
-    if ((rc = sc_ensure(ctx, ctx->pf_z, bytes))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(ctx->pf_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return pf_run(ctx, (const double*)ctx->pf_z.p, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows,
-                  out_sse);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the centre shift
-// ---------------------------------------------------------------------------------------------------------------
 // (shared with sc_fit_segments_shift)
 int sc_pf_check_shift(sc_ctx* ctx, const char* who, int h, int D, int min_samples) {
     if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "%s: the shift range must be >= 0 cells", who);
@@ -451,11 +217,40 @@ int sc_pf_check_shift(sc_ctx* ctx, const char* who, int h, int D, int min_sample
     return SC_OK;
 }
 
-static int pf_shift_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
-                        const double* ca, long long K, const double* ages, int A, int h, int w, int D, double de,
-                        double delta, int min_samples, sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
+int sc_pf_whole_grid(sc_ctx* ctx, const char* who) {
+    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
+    const Geom& g = ctx->g;
+    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
+        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: the context holds a block of a larger grid", who);
+    return SC_OK;
+}
+
+int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx) {
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
+    int rc = sc_ensure(ctx, buf, bytes);
+    if (rc) return rc;
+    SC_HIP(ctx, hipMemcpyAsync(buf.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return SC_OK;
+}
+
+int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab) {
+    const int np = 2 * h + 1;
+    sc_prof_begin(ctx, SC_K_PROFILE);
+    k_pf_table<<<std::max(1, std::min(256, (np * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, h, de, d_tab);
+    SC_HIP(ctx, hipGetLastError());
+    sc_prof_end(ctx, 1);
+    return SC_OK;
+}
+
+// D < 0: the call without a shift, its kernel and its rows (sc_profile_fit; sc_profile_shift_fit otherwise)
+static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
+                  long long K, const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
+                  void* out_rows, double* out_sse, int8_t* out_shift) {
     if (K == 0) return SC_OK;
-    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
+    const bool shift = D >= 0;
+    const int np = 2 * h + 1, ht = h + (shift ? D : 0), nt = 2 * ht + 1;
+    const size_t row_bytes = shift ? sizeof(sc_profile_shift_fit) : sizeof(sc_profile_fit);
     const size_t tab_bytes = sizeof(double) * (size_t)nt * A;
     const long long chunk = std::min<long long>(K, PF_CHUNK);
     int rc;
@@ -463,25 +258,26 @@ static int pf_shift_run(sc_ctx* ctx, const double* z, int ny, int nx, const long
     if ((rc = sc_ensure(ctx, ctx->pf_tab, tab_bytes))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, sizeof(sc_profile_shift_fit) * (size_t)chunk))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->pf_rows, row_bytes * (size_t)chunk))) return rc;
     if (out_sse && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)A * (size_t)chunk))) return rc;
     if (out_shift && (rc = sc_ensure(ctx, ctx->pf_shift, (size_t)A * (size_t)chunk))) return rc;
     double* d_ages = (double*)ctx->pf_ages.p;
     double* d_tab = (double*)ctx->pf_tab.p;
     long long* d_cells = (long long*)ctx->pf_cells.p;
     double* d_dir = (double*)ctx->pf_dir.p;
-    sc_profile_shift_fit* d_rows = (sc_profile_shift_fit*)ctx->pf_rows.p;
+    void* d_rows = ctx->pf_rows.p;
     double* d_sse = out_sse ? (double*)ctx->pf_sse.p : nullptr;
     signed char* d_shift = out_shift ? (signed char*)ctx->pf_shift.p : nullptr;
 
     const bool tab_lds = tab_bytes <= PF_TAB_LDS;
-    const size_t lds = sizeof(double) * (size_t)PF_WAVES * (np + sh_slot_doubles(A)) + (tab_lds ? tab_bytes : 0);
-    const void* fn = tab_lds ? (const void*)k_pf_shift<true> : (const void*)k_pf_shift<false>;
-    if ((rc = sc_lds_attr(ctx, fn, lds))) return rc;
+    const size_t lds = pf_lds_bytes(np, nt, A, shift, tab_lds);
+    const auto k_fit = tab_lds ? k_pf_fit<true> : k_pf_fit<false>;
+    const auto k_shift = tab_lds ? k_pf_shift<true> : k_pf_shift<false>;
+    if ((rc = sc_lds_attr(ctx, shift ? (const void*)k_shift : (const void*)k_fit, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
     // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
-    if ((rc = sc_pf_table(ctx, d_ages, A, h + D, de, d_tab))) return rc;
+    if ((rc = sc_pf_table(ctx, d_ages, A, ht, de, d_tab))) return rc;
 
     std::vector<double> dir;
     for (long long k0 = 0; k0 < K; k0 += chunk) {
@@ -494,18 +290,19 @@ static int pf_shift_run(sc_ctx* ctx, const double* z, int ny, int nx, const long
         SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
         SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
         // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_profile_shift_fit) * (size_t)m, ctx->stream));
+        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, row_bytes * (size_t)m, ctx->stream));
         const unsigned grid = (unsigned)std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID);
         sc_prof_begin(ctx, SC_K_PROFILE);
-        if (tab_lds)
-            k_pf_shift<true><<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, D, de, delta,
-                                                                     min_samples, d_tab, d_rows, d_sse, d_shift);
+        if (shift)
+            k_shift<<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, D, de, delta, min_samples,
+                                                           d_tab, (sc_profile_shift_fit*)d_rows, d_sse, d_shift);
         else
-            k_pf_shift<false><<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, D, de, delta,
-                                                                      min_samples, d_tab, d_rows, d_sse, d_shift);
+            k_fit<<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, de, delta, min_samples,
+                                                         d_tab, (sc_profile_fit*)d_rows, d_sse);
         SC_HIP(ctx, hipGetLastError());
         sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + k0, d_rows, sizeof(sc_profile_shift_fit) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync((char*)out_rows + row_bytes * (size_t)k0, d_rows, row_bytes * (size_t)m, hipMemcpyDeviceToHost,
+                                   ctx->stream));
         if (out_sse)
             SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)k0 * A, d_sse, sizeof(double) * (size_t)A * (size_t)m,
                                        hipMemcpyDeviceToHost, ctx->stream));
@@ -518,20 +315,53 @@ static int pf_shift_run(sc_ctx* ctx, const double* z, int ny, int nx, const long
     return SC_OK;
 }
 
+// The four calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
+// host, uploaded - or on the context's DEM (z null).  shift: D is the caller's range, checked here.
+static int pf_call(sc_ctx* ctx, const char* who, bool shift, const double* z, int ny, int nx, const long long* cells,
+                   const double* sa, const double* ca, long long K, const double* ages, int A, int h, int w, int D, double de,
+                   double delta, int min_samples, void* out_rows, double* out_sse, int8_t* out_shift) {
+    int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    if (rc) return rc;
+    if (shift && (rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
+    const double* z_dev = ctx->z_dev;
+    if (z) {
+        if (K == 0) return SC_OK;
+        if ((rc = sc_pf_upload(ctx, ctx->pf_z, z, ny, nx))) return rc;
+        z_dev = (const double*)ctx->pf_z.p;
+    } else {
+        SC_HIP(ctx, hipSetDevice(ctx->device));
+    }
+    return pf_run(ctx, z_dev, ny, nx, cells, sa, ca, K, ages, A, h, w, shift ? D : -1, de, delta, min_samples, out_rows, out_sse,
+                  out_shift);
+}
+
+extern "C" int sc_fit_profiles(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                               const double* ages, int A, int h, int w, double de, double delta, int min_samples,
+                               sc_profile_fit* out_rows, double* out_sse) {
+    if (!ctx) return SC_ERR_INVALID;
+    int rc = sc_pf_whole_grid(ctx, "sc_fit_profiles");
+    if (rc) return rc;
+    return pf_call(ctx, "sc_fit_profiles", false, nullptr, ctx->g.ny, ctx->g.nx, cells, sa, ca, K, ages, A, h, w, 0, de, delta,
+                   min_samples, out_rows, out_sse, nullptr);
+}
+
+// (reports as sc_fit_profiles)
+extern "C" int sc_fit_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                                   const double* ca, long long K, const double* ages, int A, int h, int w, double de,
+                                   double delta, int min_samples, sc_profile_fit* out_rows, double* out_sse) {
+    if (!ctx || !z) return SC_ERR_INVALID;
+    return pf_call(ctx, "sc_fit_profiles", false, z, ny, nx, cells, sa, ca, K, ages, A, h, w, 0, de, delta, min_samples, out_rows,
+                   out_sse, nullptr);
+}
+
 extern "C" int sc_fit_profiles_shift(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
                                      const double* ages, int A, int h, int w, int D, double de, double delta,
                                      int min_samples, sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
     if (!ctx) return SC_ERR_INVALID;
-    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
-    const Geom& g = ctx->g;
-    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_profiles_shift: the context holds a block of a larger grid");
-    int rc = sc_pf_check(ctx, "sc_fit_profiles_shift", g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
+    int rc = sc_pf_whole_grid(ctx, "sc_fit_profiles_shift");
     if (rc) return rc;
-    if ((rc = sc_pf_check_shift(ctx, "sc_fit_profiles_shift", h, D, min_samples))) return rc;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    return pf_shift_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, K, ages, A, h, w, D, de, delta, min_samples, out_rows,
-                        out_sse, out_shift);
+    return pf_call(ctx, "sc_fit_profiles_shift", true, nullptr, ctx->g.ny, ctx->g.nx, cells, sa, ca, K, ages, A, h, w, D, de, delta,
+                   min_samples, out_rows, out_sse, out_shift);
 }
 
 extern "C" int sc_fit_profiles_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells,
@@ -539,14 +369,6 @@ extern "C" int sc_fit_profiles_shift_dem(sc_ctx* ctx, const double* z, int ny, i
                                          int w, int D, double de, double delta, int min_samples,
                                          sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
     if (!ctx || !z) return SC_ERR_INVALID;
-    int rc = sc_pf_check(ctx, "sc_fit_profiles_shift_dem", ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
-    if (rc) return rc;
-    if ((rc = sc_pf_check_shift(ctx, "sc_fit_profiles_shift_dem", h, D, min_samples))) return rc;
-    if (K == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
-    if ((rc = sc_ensure(ctx, ctx->pf_z, bytes))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(ctx->pf_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return pf_shift_run(ctx, (const double*)ctx->pf_z.p, ny, nx, cells, sa, ca, K, ages, A, h, w, D, de, delta, min_samples,
-                        out_rows, out_sse, out_shift);
+    return pf_call(ctx, "sc_fit_profiles_shift_dem", true, z, ny, nx, cells, sa, ca, K, ages, A, h, w, D, de, delta, min_samples,
+                   out_rows, out_sse, out_shift);
 }

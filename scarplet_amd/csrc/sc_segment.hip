@@ -1,140 +1,133 @@
-// sc_fit_segments / sc_fit_segments_dem: one scarp age per trace segment, fitted jointly (docs/segments.md).
+// sc_fit_segments*: one scarp age per trace segment, fitted jointly (docs/segments.md).
 //
 // The cells arrive grouped by segment (CSR seg_start).  Per segment and age one least-squares problem over all its
 // usable profiles: a shared amplitude a, and an intercept and a slope per profile.  Orthogonalising each profile's erf
-// column and data against its own (1, s) - passes 0 to 2 of k_pf_fit - leaves a one-column problem whose normal
-// equation is a_i = sum_c Sep_ci / sum_c See_ci; the residuals are then explicit.
-//   k_sg_partial  one wave per cell, as k_pf_fit: lanes over the points while sampling (the profile goes to LDS and is
-//                 PARKED in global memory), lanes over the ages for passes 0 to 2; parks sbar, pbar, beta and per age
-//                 ebar, gamma, See, Sep
+// column and data against its own (1, s) - passes 0 to 2 of the fit, sc_fit.h - leaves a one-column problem whose
+// normal equation is a_i = sum_c Sep_ci / sum_c See_ci; the residuals are then explicit.
+//   k_sg_partial  one wave per cell: pf_cut, lanes over the points (the profile goes to LDS and is PARKED in global
+//                 memory); then lanes over the ages for pf_moments and pf_line with the lane's column in the same
+//                 sweep, and pf_rest.  Parks sbar, pbar, beta and per age ebar, gamma, See, Sep
+//   k_sg_shift    sc_fit_segments_shift's k_sg_partial: pf_moments and pf_line without a column, once, then the
+//                 lanes run over the (shift, age) pairs (sh_search); parks the same terms AT d_ci, and d_ci itself
 //   k_sg_rank     one wave per segment: the usable cells of the segment in input order (ballot and popcount), their
 //                 number and the pooled number of valid points
 //   k_sg_sum1     one wave per block of 64 consecutive usable profiles, lanes over the ages: the block's terms summed
 //                 in sequence from the first
 //   k_sg_sum2     one wave per segment: the block sums in sequence from the first.  The shape of the sum depends on
 //                 n_profiles alone; one profile is no addition at all
-//   k_sg_resid    one wave per cell: the parked profile back into LDS, lanes over the ages, the explicit residuals of
-//                 pass 3 of k_pf_fit with the segment's a_i; the cell's sse_ci takes the place of See_ci
+//   k_sg_resid    one wave per cell: the parked profile back into LDS, lanes over the ages, pf_slope and pf_sse with
+//                 the segment's a_i and the column at d_ci (the unshifted call: no d_ci, D = 0); the cell's sse_ci
+//                 takes the place of See_ci
 //   (k_sg_sum1 and k_sg_sum2 again, on sse_ci)
-//   k_sg_choose   one wave per segment: argmin, interval, the row; then lanes over the segment's cells for the cell
-//                 table at the best age
-// No atomics at all.  The erf table is k_pf_table's, the sampling pf_sample: the same bits as sc_fit_profiles.
-#include "sc_internal.h"
+//   k_sg_choose   one wave per segment: pf_choose, the row; then lanes over the segment's cells for the cell table at
+//                 the best age (sc_segment_cell, or sc_segment_shift_cell with d_ci at that age)
+// No atomics at all.  The erf table is k_pf_table's: the same bits as sc_fit_profiles*.
+#include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
+#include <type_traits>
 
-#define SG_WAVES 4                       // cells in flight per workgroup
-#define SG_THREADS (64 * SG_WAVES)
-#define SG_TAB_LDS 65536                 // the table goes to LDS up to this many bytes
 #define SG_BLOCK 64                      // usable profiles per block of the segmented sum
-#define SG_MAX_GRID 2048
 #define SG_MAX_SEGS (1ll << 20)          // segments per chunk: bounds the rows and totals of a call with empty segments
 
+// what k_sg_partial and k_sg_shift park of a cell apart from the per-age terms
+__device__ __forceinline__ void sg_park_cell(long long kc, int lane, int n, bool ok, int* __restrict__ cn,
+                                             int* __restrict__ used) {
+    if (lane == 0) {
+        cn[kc] = n;
+        used[kc] = ok ? 1 : 0;
+    }
+}
+__device__ __forceinline__ void sg_park_line(long long kc, int lane, const pf_lin& f, double* __restrict__ scal) {
+    if (lane == 0) {
+        scal[3 * kc] = f.sbar;
+        scal[3 * kc + 1] = f.pbar;
+        scal[3 * kc + 2] = f.beta;
+    }
+}
+
 template <bool TAB_LDS>
-__global__ __launch_bounds__(SG_THREADS) void k_sg_partial(const double* __restrict__ z, int ny, int nx,
+__global__ __launch_bounds__(PF_THREADS) void k_sg_partial(const double* __restrict__ z, int ny, int nx,
                                                            const long long* __restrict__ cells,
                                                            const double* __restrict__ dir, long long K, int A, int h,
                                                            int w, double de, int min_samples,
                                                            const double* __restrict__ tab_g, double* __restrict__ prof_g,
                                                            int* __restrict__ cn, int* __restrict__ used,
                                                            double* __restrict__ scal, double* __restrict__ planes) {
-    extern __shared__ double sg_lds[];
     const int np = 2 * h + 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = sg_lds + (size_t)wave * np;
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = sg_lds + (size_t)SG_WAVES * np;
-        for (int idx = threadIdx.x; idx < np * A; idx += SG_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
+    const pf_lds L = pf_stage<TAB_LDS, false>(tab_g, np, np, A);
     const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
-    const double nan = __builtin_nan("");
+    const double* col = L.tab + ia;
     const size_t stride = (size_t)K * A;                 // one per-cell-and-age plane
-    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
     for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * SG_WAVES + wave;
+        const long long kc = g * PF_WAVES + wave;
         const bool act = kc < K;
+        if (act) pf_cut(z, ny, nx, cells[kc], dir, kc, h, w, lane, L.prof, prof_g);
+        __syncthreads();
         if (act) {
-            const long long cell = cells[kc];
-            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
-            const double r = (double)(cell / nx), c = (double)(cell % nx);
-            for (int jj = lane; jj < np; jj += 64) {
-                const double j = (double)(jj - h);
-                const double jsa = j * sa, jca = j * ca;
-                double acc = 0.0;
-                int cnt = 0;
-                for (int kk = -w; kk <= w; ++kk) {
-                    const double k = (double)kk;
-                    const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
-                    double v;
-                    if (pf_sample(z, ny, nx, rr, cc, v)) {
-                        acc += v;
-                        ++cnt;
-                    }
+            const pf_mom mo = pf_moments<true>(L.prof, np, h, de, col, A);
+            const bool ok = mo.n_neg >= min_samples && mo.n_pos >= min_samples;
+            sg_park_cell(kc, lane, mo.n, ok, cn, used);
+            if (ok) {
+                pf_col t;
+                const pf_lin f = pf_line<true>(L.prof, np, h, de, mo, col, A, t);
+                pf_rest(L.prof, np, h, de, f, col, A, t);
+                sg_park_line(kc, lane, f, scal);
+                if (lane < A) {
+                    const size_t o = (size_t)kc * A + lane;
+                    planes[o] = t.ebar;
+                    planes[stride + o] = t.gamma;
+                    planes[2 * stride + o] = t.See;
+                    planes[3 * stride + o] = t.Sep;
                 }
-                const double p = cnt ? acc / (double)cnt : nan;
-                prof[jj] = p;
-                prof_g[(size_t)kc * np + jj] = p;
             }
         }
         __syncthreads();
+    }
+}
+
+template <bool TAB_LDS>
+__global__ __launch_bounds__(PF_THREADS) void k_sg_shift(const double* __restrict__ z, int ny, int nx,
+                                                         const long long* __restrict__ cells,
+                                                         const double* __restrict__ dir, long long K, int A, int h, int w,
+                                                         int D, double de, int min_samples,
+                                                         const double* __restrict__ tab_g, double* __restrict__ prof_g,
+                                                         int* __restrict__ cn, int* __restrict__ used,
+                                                         double* __restrict__ scal, double* __restrict__ planes,
+                                                         signed char* __restrict__ shifts) {
+    const int np = 2 * h + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const pf_lds L = pf_stage<TAB_LDS, true>(tab_g, np, 2 * (h + D) + 1, A);
+    const double* slot = L.slot;
+    const int* srank = (const int*)(slot + (size_t)SH_TERMS * A);
+    const size_t stride = (size_t)K * A;                 // one per-cell-and-age plane
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * PF_WAVES + wave;
+        const bool act = kc < K;
+        if (act) pf_cut(z, ny, nx, cells[kc], dir, kc, h, w, lane, L.prof, prof_g);
+        __syncthreads();
         if (act) {
-            // pass 0: counts, sums of s, p and this lane's e over the valid points
-            int n = 0, n_neg = 0, n_pos = 0;
-            double Ss = 0.0, Sp = 0.0, Se = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                ++n;
-                n_neg += jj < h ? 1 : 0;
-                n_pos += jj > h ? 1 : 0;
-                Ss += (double)(jj - h) * de;
-                Sp += p;
-                Se += tab[(size_t)jj * A + ia];
-            }
-            const bool ok = n_neg >= min_samples && n_pos >= min_samples;
-            if (lane == 0) {
-                cn[kc] = n;
-                used[kc] = ok ? 1 : 0;
-            }
-            if (ok) {
-                const double dn = (double)n;
-                const double sbar = Ss / dn, pbar = Sp / dn, ebar = Se / dn;
-                // pass 1: the centred s against itself, p and e
-                double Sss = 0.0, Sps = 0.0, Ses = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    Sss += sc * sc;
-                    Sps += sc * (p - pbar);
-                    Ses += sc * (tab[(size_t)jj * A + ia] - ebar);
-                }
-                const double beta = Sps / Sss, gamma = Ses / Sss;
-                // pass 2: what is left of e after 1 and s, against what is left of p
-                double See = 0.0, Sep = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    const double e2 = (tab[(size_t)jj * A + ia] - ebar) - gamma * sc;
-                    const double p2 = (p - pbar) - beta * sc;
-                    See += e2 * e2;
-                    Sep += e2 * p2;
-                }
-                if (lane == 0) {
-                    scal[3 * kc] = sbar;
-                    scal[3 * kc + 1] = pbar;
-                    scal[3 * kc + 2] = beta;
-                }
+            // what depends on neither the age nor the shift, once
+            const pf_mom mo = pf_moments<false>(L.prof, np, h, de, nullptr, A);
+            const bool ok = mo.n_neg >= min_samples && mo.n_pos >= min_samples;
+            sg_park_cell(kc, lane, mo.n, ok, cn, used);
+            if (!ok) {
+                if (lane < A) shifts[(size_t)kc * A + lane] = 0;
+            } else {
+                pf_col t;
+                const pf_lin f = pf_line<false>(L.prof, np, h, de, mo, nullptr, A, t);
+                sh_search(L.prof, L.tab, np, h, A, D, de, lane, f, L.slot);
+                sg_park_line(kc, lane, f, scal);
                 if (lane < A) {
                     const size_t o = (size_t)kc * A + lane;
-                    planes[o] = ebar;
-                    planes[stride + o] = gamma;
-                    planes[2 * stride + o] = See;
-                    planes[3 * stride + o] = Sep;
+                    planes[o] = slot[3 * A + lane];
+                    planes[stride + o] = slot[4 * A + lane];
+                    planes[2 * stride + o] = slot[A + lane];
+                    planes[3 * stride + o] = slot[2 * A + lane];
+                    shifts[o] = (signed char)sh_shift_of(srank[lane]);
                 }
             }
         }
@@ -225,323 +218,66 @@ __global__ __launch_bounds__(64) void k_sg_sum2(const double* __restrict__ part,
     }
 }
 
-__device__ __forceinline__ bool sg_fitted(int m, int n, int min_profiles) {
-    return m >= min_profiles && n - 2 * m - 1 >= 1;
-}
+// the degrees of freedom of a segment of m usable profiles and n pooled points (D = 0 in the call without a shift), and
+// whether it is fitted
+__device__ __forceinline__ int sg_dof(int m, int n, int D) { return n - 2 * m - 1 - (D > 0 ? m : 0); }
+__device__ __forceinline__ bool sg_fitted(int m, int dof, int min_profiles) { return m >= min_profiles && dof >= 1; }
 
-// the explicit residuals of every usable cell of a fitted segment, with the segment's a_i: sse_ci replaces See_ci
+// the explicit residuals of every usable cell of a fitted segment, with the segment's a_i: sse_ci replaces See_ci.  The
+// table covers j = -(h + D)..(h + D) and the cell's column at age i is its row j - d_ci; shifts null: d_ci = 0
 template <bool TAB_LDS>
-__global__ __launch_bounds__(SG_THREADS) void k_sg_resid(const double* __restrict__ prof_g, const int* __restrict__ cseg,
+__global__ __launch_bounds__(PF_THREADS) void k_sg_resid(const double* __restrict__ prof_g, const int* __restrict__ cseg,
                                                          const int* __restrict__ used, const int* __restrict__ cnt,
                                                          const double* __restrict__ scal, double* __restrict__ planes,
-                                                         const double* __restrict__ tot, long long K, int A, int h,
+                                                         const signed char* __restrict__ shifts,
+                                                         const double* __restrict__ tot, long long K, int A, int h, int D,
                                                          double de, int min_profiles, const double* __restrict__ tab_g) {
-    extern __shared__ double sg_lds[];
     const int np = 2 * h + 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = sg_lds + (size_t)wave * np;
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = sg_lds + (size_t)SG_WAVES * np;
-        for (int idx = threadIdx.x; idx < np * A; idx += SG_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
+    const pf_lds L = pf_stage<TAB_LDS, false>(tab_g, np, 2 * (h + D) + 1, A);
     const int ia = min(lane, A - 1);
     const size_t stride = (size_t)K * A;
-    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
     for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * SG_WAVES + wave;
-        bool act = kc < K;
-        int s = 0;
-        if (act) {
-            s = cseg[kc];
-            act = used[kc] != 0 && sg_fitted(cnt[2 * s], cnt[2 * s + 1], min_profiles);
-        }
-        if (act)
-            for (int jj = lane; jj < np; jj += 64) prof[jj] = prof_g[(size_t)kc * np + jj];
-        __syncthreads();
-        if (act) {
-            const size_t o = (size_t)kc * A + ia;
-            const double sbar = scal[3 * kc], pbar = scal[3 * kc + 1], beta = scal[3 * kc + 2];
-            const double ebar = planes[o], gamma = planes[stride + o];
-            const double See = tot[((size_t)s * 2) * A + ia], Sep = tot[((size_t)s * 2 + 1) * A + ia];
-            const double a = Sep / See;
-            const double b = beta - a * gamma;
-            const double c0 = (pbar - a * ebar) - b * sbar;
-            double sse = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                const double sj = (double)(jj - h) * de;
-                const double res = p - ((c0 + b * sj) + a * tab[(size_t)jj * A + ia]);
-                sse += res * res;
-            }
-            if (lane < A) planes[2 * stride + o] = sse;
-        }
-        __syncthreads();
-    }
-}
-
-// the age of each segment, its interval and its row; the cell table at the best age
-__global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_start, const int* __restrict__ label,
-                                                  const int* __restrict__ cnt, long long S, long long K,
-                                                  const double* __restrict__ tot, const double* __restrict__ tsse,
-                                                  const double* __restrict__ ages, int A, double delta, int min_profiles,
-                                                  const long long* __restrict__ cells, const int* __restrict__ cn,
-                                                  const int* __restrict__ used, const double* __restrict__ scal,
-                                                  const double* __restrict__ planes, sc_segment_fit* __restrict__ rows,
-                                                  sc_segment_cell* __restrict__ out_cells, double* __restrict__ curve) {
-    const int lane = threadIdx.x;
-    const int ia = min(lane, A - 1);
-    const double nan = __builtin_nan("");
-    const size_t stride = (size_t)K * A;
-    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
-        const int start = seg_start[s], end = seg_start[s + 1];
-        const int m = cnt[2 * s], n = cnt[2 * s + 1];
-        const int dof = n - 2 * m - 1;
-        const bool fitted = sg_fitted(m, n, min_profiles);
-        sc_segment_fit* out = rows + s;
-        int best = -1;
-        double a_best = nan;
-        if (!fitted) {
-            if (lane == 0) {
-                out->label = label[s];
-                out->n_cells = end - start;
-                out->n_profiles = m;
-                out->n = n;
-                out->dof = dof;
-                out->kt_index = -1;
-                out->lo_index = -1;
-                out->hi_index = -1;
-                out->status = 1;
-                out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
-                out->a = nan; out->sse = nan; out->rmse = nan;
-            }
-            if (curve && lane < A) curve[s * A + lane] = nan;
-        } else {
-            const double sse = tsse[(size_t)s * A + ia];
-            const double a = tot[((size_t)s * 2 + 1) * A + ia] / tot[((size_t)s * 2) * A + ia];
-            if (curve && lane < A) curve[s * A + lane] = sse;
-            // argmin over the ages, ties to the smaller index (a NaN never wins)
-            double mn = lane < A ? sse : INFINITY;
-            if (mn != mn) mn = INFINITY;
-            int mi = lane;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const double om = __shfl_xor(mn, o, 64);
-                const int oi = __shfl_xor(mi, o, 64);
-                if (om < mn || (om == mn && oi < mi)) { mn = om; mi = oi; }
-            }
-            best = min(mi, A - 1);
-            const double thr = mn * (1.0 + delta / (double)dof);
-            const unsigned long long ok = __ballot(lane < A && sse <= thr);
-            int lo = best, hi = best;
-            while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
-            while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
-            a_best = __shfl(a, best, 64);
-            if (lane == best) {
-                out->label = label[s];
-                out->n_cells = end - start;
-                out->n_profiles = m;
-                out->n = n;
-                out->dof = dof;
-                out->kt_index = best;
-                out->lo_index = lo;
-                out->hi_index = hi;
-                out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0);
-                out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
-                out->a = a;
-                out->sse = sse; out->rmse = sqrt(sse / (double)dof);
-            }
-        }
-        if (!out_cells) continue;
-        for (int k = start + lane; k < end; k += 64) {
-            sc_segment_cell c;
-            c.cell = cells[k];
-            c.used = used[k];
-            c.n = cn[k];
-            c.b = nan; c.c0 = nan; c.sse = nan;
-            if (fitted && c.used) {
-                const size_t o = (size_t)k * A + best;
-                c.b = scal[3 * k + 2] - a_best * planes[stride + o];
-                c.c0 = (scal[3 * k + 1] - a_best * planes[o]) - c.b * scal[3 * k];
-                c.sse = planes[2 * stride + o];
-            }
-            out_cells[k] = c;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// the centre shift (sc_fit_segments_shift): k_sg_partial, k_sg_resid and k_sg_choose with a shift d_ci per profile
-// and age; the rank and sum kernels above serve both
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int sg_shift_dof(int m, int n, int D) { return n - 2 * m - 1 - (D > 0 ? m : 0); }
-
-// k_sg_partial with the shift search of sc_fit_profiles_shift (sh_search: lanes over the (shift, age) pairs): parks the
-// profile, sbar, pbar, beta and per age ebar, gamma, See, Sep AT d_ci, and d_ci itself
-template <bool TAB_LDS>
-__global__ __launch_bounds__(SG_THREADS) void k_sg_shift(const double* __restrict__ z, int ny, int nx,
-                                                         const long long* __restrict__ cells,
-                                                         const double* __restrict__ dir, long long K, int A, int h, int w,
-                                                         int D, double de, int min_samples,
-                                                         const double* __restrict__ tab_g, double* __restrict__ prof_g,
-                                                         int* __restrict__ cn, int* __restrict__ used,
-                                                         double* __restrict__ scal, double* __restrict__ planes,
-                                                         signed char* __restrict__ shifts) {
-    extern __shared__ double sg_lds[];
-    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = sg_lds + (size_t)wave * np;
-    double* slot = sg_lds + (size_t)SG_WAVES * np + (size_t)wave * sh_slot_doubles(A);
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = sg_lds + (size_t)SG_WAVES * (np + sh_slot_doubles(A));
-        for (int idx = threadIdx.x; idx < nt * A; idx += SG_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
-    const int* srank = (const int*)(slot + (size_t)SH_TERMS * A);
-    const size_t stride = (size_t)K * A;                 // one per-cell-and-age plane
-    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
-    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * SG_WAVES + wave;
-        const bool act = kc < K;
-        if (act) {
-            const long long cell = cells[kc];
-            const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
-            const double r = (double)(cell / nx), c = (double)(cell % nx);
-            for (int jj = lane; jj < np; jj += 64) {
-                const double p = pf_point(z, ny, nx, r, c, sa, ca, jj, h, w);
-                prof[jj] = p;
-                prof_g[(size_t)kc * np + jj] = p;
-            }
-        }
-        __syncthreads();
-        if (act) {
-            // what depends on neither the age nor the shift, once: pass 0's counts and sums of s and p
-            int n = 0, n_neg = 0, n_pos = 0;
-            double Ss = 0.0, Sp = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                ++n;
-                n_neg += jj < h ? 1 : 0;
-                n_pos += jj > h ? 1 : 0;
-                Ss += (double)(jj - h) * de;
-                Sp += p;
-            }
-            const bool ok = n_neg >= min_samples && n_pos >= min_samples;
-            if (lane == 0) {
-                cn[kc] = n;
-                used[kc] = ok ? 1 : 0;
-            }
-            if (!ok) {
-                if (lane < A) shifts[(size_t)kc * A + lane] = 0;
-            } else {
-                const double dn = (double)n;
-                const double sbar = Ss / dn, pbar = Sp / dn;
-                // ... and pass 1's centred s against itself and p
-                double Sss = 0.0, Sps = 0.0;
-                for (int jj = 0; jj < np; ++jj) {
-                    const double p = prof[jj];
-                    if (p != p) continue;
-                    const double sc = (double)(jj - h) * de - sbar;
-                    Sss += sc * sc;
-                    Sps += sc * (p - pbar);
-                }
-                const double beta = Sps / Sss;
-                sh_search(prof, tab, np, h, A, D, de, lane, dn, sbar, pbar, Sss, beta, slot);
-                if (lane == 0) {
-                    scal[3 * kc] = sbar;
-                    scal[3 * kc + 1] = pbar;
-                    scal[3 * kc + 2] = beta;
-                }
-                if (lane < A) {
-                    const size_t o = (size_t)kc * A + lane;
-                    planes[o] = slot[3 * A + lane];
-                    planes[stride + o] = slot[4 * A + lane];
-                    planes[2 * stride + o] = slot[A + lane];
-                    planes[3 * stride + o] = slot[2 * A + lane];
-                    shifts[o] = (signed char)sh_shift_of(srank[lane]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// k_sg_resid with row j - d_ci of the table over j = -(h + D)..(h + D)
-template <bool TAB_LDS>
-__global__ __launch_bounds__(SG_THREADS) void k_sg_resid_shift(const double* __restrict__ prof_g, const int* __restrict__ cseg,
-                                                               const int* __restrict__ used, const int* __restrict__ cnt,
-                                                               const double* __restrict__ scal, double* __restrict__ planes,
-                                                               const signed char* __restrict__ shifts,
-                                                               const double* __restrict__ tot, long long K, int A, int h,
-                                                               int D, double de, int min_profiles,
-                                                               const double* __restrict__ tab_g) {
-    extern __shared__ double sg_lds[];
-    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* prof = sg_lds + (size_t)wave * np;
-    const double* tab = tab_g;
-    if (TAB_LDS) {
-        double* t = sg_lds + (size_t)SG_WAVES * np;
-        for (int idx = threadIdx.x; idx < nt * A; idx += SG_THREADS) t[idx] = tab_g[idx];
-        tab = t;
-    }
-    __syncthreads();
-    const int ia = min(lane, A - 1);
-    const size_t stride = (size_t)K * A;
-    const long long rounds = (K + SG_WAVES - 1) / SG_WAVES;
-    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * SG_WAVES + wave;
+        const long long kc = g * PF_WAVES + wave;
         bool act = kc < K;
         int s = 0;
         if (act) {
             s = cseg[kc];
             const int m = cnt[2 * s];
-            act = used[kc] != 0 && m >= min_profiles && sg_shift_dof(m, cnt[2 * s + 1], D) >= 1;
+            act = used[kc] != 0 && sg_fitted(m, sg_dof(m, cnt[2 * s + 1], D), min_profiles);
         }
         if (act)
-            for (int jj = lane; jj < np; jj += 64) prof[jj] = prof_g[(size_t)kc * np + jj];
+            for (int jj = lane; jj < np; jj += 64) L.prof[jj] = prof_g[(size_t)kc * np + jj];
         __syncthreads();
         if (act) {
             const size_t o = (size_t)kc * A + ia;
-            const double sbar = scal[3 * kc], pbar = scal[3 * kc + 1], beta = scal[3 * kc + 2];
-            const double ebar = planes[o], gamma = planes[stride + o];
             const double See = tot[((size_t)s * 2) * A + ia], Sep = tot[((size_t)s * 2 + 1) * A + ia];
-            const double* col = tab + (size_t)(D - (int)shifts[o]) * A + ia;
+            const double* col = L.tab + (size_t)(D - (shifts ? (int)shifts[o] : 0)) * A + ia;
             const double a = Sep / See;
-            const double b = beta - a * gamma;
-            const double c0 = (pbar - a * ebar) - b * sbar;
-            double sse = 0.0;
-            for (int jj = 0; jj < np; ++jj) {
-                const double p = prof[jj];
-                if (p != p) continue;
-                const double sj = (double)(jj - h) * de;
-                const double res = p - ((c0 + b * sj) + a * col[(size_t)jj * A]);
-                sse += res * res;
-            }
+            double b, c0;
+            pf_slope(scal[3 * kc], scal[3 * kc + 1], scal[3 * kc + 2], planes[o], planes[stride + o], a, b, c0);
+            const double sse = pf_sse(L.prof, np, h, de, col, A, a, b, c0);
             if (lane < A) planes[2 * stride + o] = sse;
         }
         __syncthreads();
     }
 }
 
-// k_sg_choose with the shift's degrees of freedom, status bit 8 and the cells' shift at the best age
-__global__ __launch_bounds__(64) void k_sg_choose_shift(const int* __restrict__ seg_start, const int* __restrict__ label,
-                                                        const int* __restrict__ cnt, long long S, long long K,
-                                                        const double* __restrict__ tot, const double* __restrict__ tsse,
-                                                        const double* __restrict__ ages, int A, int D, double delta,
-                                                        int min_profiles, const long long* __restrict__ cells,
-                                                        const int* __restrict__ cn, const int* __restrict__ used,
-                                                        const double* __restrict__ scal, const double* __restrict__ planes,
-                                                        const signed char* __restrict__ shifts,
-                                                        sc_segment_fit* __restrict__ rows,
-                                                        sc_segment_shift_cell* __restrict__ out_cells,
-                                                        double* __restrict__ curve) {
+// the age of each segment, its interval and its row; the cell table at the best age.  CELL: sc_segment_cell, or
+// sc_segment_shift_cell with the shift's degrees of freedom, status bit 8 and the cells' d_ci at the best age (the
+// call without a shift: D = 0, shifts null)
+template <class CELL>
+__global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_start, const int* __restrict__ label,
+                                                  const int* __restrict__ cnt, long long S, long long K,
+                                                  const double* __restrict__ tot, const double* __restrict__ tsse,
+                                                  const double* __restrict__ ages, int A, int D, double delta,
+                                                  int min_profiles, const long long* __restrict__ cells,
+                                                  const int* __restrict__ cn, const int* __restrict__ used,
+                                                  const double* __restrict__ scal, const double* __restrict__ planes,
+                                                  const signed char* __restrict__ shifts, sc_segment_fit* __restrict__ rows,
+                                                  CELL* __restrict__ out_cells, double* __restrict__ curve) {
+    constexpr bool SHIFT = std::is_same<CELL, sc_segment_shift_cell>::value;
     const int lane = threadIdx.x;
     const int ia = min(lane, A - 1);
     const double nan = __builtin_nan("");
@@ -549,89 +285,66 @@ __global__ __launch_bounds__(64) void k_sg_choose_shift(const int* __restrict__ 
     for (long long s = blockIdx.x; s < S; s += gridDim.x) {
         const int start = seg_start[s], end = seg_start[s + 1];
         const int m = cnt[2 * s], n = cnt[2 * s + 1];
-        const int dof = sg_shift_dof(m, n, D);
-        const bool fitted = m >= min_profiles && dof >= 1;
+        const int dof = sg_dof(m, n, D);
+        const bool fitted = sg_fitted(m, dof, min_profiles);
+        // (the rows were cleared: their padding is part of what the caller compares)
         sc_segment_fit* out = rows + s;
         int best = -1;
         double a_best = nan;
-        if (!fitted) {
-            if (lane == 0) {
-                out->label = label[s];
-                out->n_cells = end - start;
-                out->n_profiles = m;
-                out->n = n;
-                out->dof = dof;
-                out->kt_index = -1;
-                out->lo_index = -1;
-                out->hi_index = -1;
-                out->status = 1;
-                out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
-                out->a = nan; out->sse = nan; out->rmse = nan;
-            }
-            if (curve && lane < A) curve[s * A + lane] = nan;
-        } else {
-            const double sse = tsse[(size_t)s * A + ia];
-            const double a = tot[((size_t)s * 2 + 1) * A + ia] / tot[((size_t)s * 2) * A + ia];
-            if (curve && lane < A) curve[s * A + lane] = sse;
-            // argmin over the ages, ties to the smaller index (a NaN never wins)
-            double mn = lane < A ? sse : INFINITY;
-            if (mn != mn) mn = INFINITY;
-            int mi = lane;
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) {
-                const double om = __shfl_xor(mn, o, 64);
-                const int oi = __shfl_xor(mi, o, 64);
-                if (om < mn || (om == mn && oi < mi)) { mn = om; mi = oi; }
-            }
-            best = min(mi, A - 1);
-            const double thr = mn * (1.0 + delta / (double)dof);
-            const unsigned long long ok = __ballot(lane < A && sse <= thr);
-            int lo = best, hi = best;
-            while (lo > 0 && ((ok >> (lo - 1)) & 1ull)) --lo;
-            while (hi < A - 1 && ((ok >> (hi + 1)) & 1ull)) ++hi;
+        pf_pick k = {-1, -1, -1, nan};
+        int status = 1;
+        double a = nan, sse = nan;
+        if (fitted) {
+            sse = tsse[(size_t)s * A + ia];
+            a = tot[((size_t)s * 2 + 1) * A + ia] / tot[((size_t)s * 2) * A + ia];
+            k = pf_choose(sse, lane, A, delta, dof);
+            best = k.best;
             a_best = __shfl(a, best, 64);
             // a usable profile whose shift at the best age sits at the end of the range
             bool at_end = false;
-            if (D > 0)
-                for (int k = start + lane; k < end; k += 64) {
-                    const int d = shifts[(size_t)k * A + best];
-                    at_end = at_end || (used[k] != 0 && (d == D || d == -D));
+            if (SHIFT && D > 0)
+                for (int c = start + lane; c < end; c += 64) {
+                    const int d = shifts[(size_t)c * A + best];
+                    at_end = at_end || (used[c] != 0 && (d == D || d == -D));
                 }
-            const bool any_end = __ballot(at_end) != 0ull;
-            if (lane == best) {
-                out->label = label[s];
-                out->n_cells = end - start;
-                out->n_profiles = m;
-                out->n = n;
-                out->dof = dof;
-                out->kt_index = best;
-                out->lo_index = lo;
-                out->hi_index = hi;
-                out->status = (lo == 0 ? 2 : 0) + (hi == A - 1 ? 4 : 0) + (any_end ? 8 : 0);
-                out->kt = ages[best]; out->kt_lo = ages[lo]; out->kt_hi = ages[hi];
-                out->a = a;
-                out->sse = sse; out->rmse = sqrt(sse / (double)dof);
-            }
+            status = pf_open(k, A) + (__ballot(at_end) != 0ull ? 8 : 0);
+        }
+        if (curve && lane < A) curve[s * A + lane] = sse;
+        if (lane == (fitted ? best : 0)) {
+            out->label = label[s];
+            out->n_cells = end - start;
+            out->n_profiles = m;
+            out->n = n;
+            out->dof = dof;
+            out->kt_index = k.best;
+            out->lo_index = k.lo;
+            out->hi_index = k.hi;
+            out->status = status;
+            out->kt = fitted ? ages[k.best] : nan;
+            out->kt_lo = fitted ? ages[k.lo] : nan;
+            out->kt_hi = fitted ? ages[k.hi] : nan;
+            out->a = a;
+            out->sse = sse;
+            out->rmse = fitted ? sqrt(sse / (double)dof) : nan;
         }
         if (!out_cells) continue;
-        for (int k = start + lane; k < end; k += 64) {
-            // (field by field: the struct ends in padding, which the host cleared)
-            sc_segment_shift_cell* c = out_cells + k;
-            const int u = used[k];
-            double b = nan, c0 = nan, sse = nan;
+        for (int c = start + lane; c < end; c += 64) {
+            // (field by field: sc_segment_shift_cell ends in padding, which the host cleared)
+            CELL* oc = out_cells + c;
+            const int u = used[c];
+            double b = nan, c0 = nan, csse = nan;
             int d = 0;
             if (fitted && u) {
-                const size_t o = (size_t)k * A + best;
-                b = scal[3 * k + 2] - a_best * planes[stride + o];
-                c0 = (scal[3 * k + 1] - a_best * planes[o]) - b * scal[3 * k];
-                sse = planes[2 * stride + o];
-                d = shifts[o];
+                const size_t o = (size_t)c * A + best;
+                pf_slope(scal[3 * c], scal[3 * c + 1], scal[3 * c + 2], planes[o], planes[stride + o], a_best, b, c0);
+                csse = planes[2 * stride + o];
+                if (SHIFT) d = shifts[o];
             }
-            c->cell = cells[k];
-            c->used = u;
-            c->n = cn[k];
-            c->b = b; c->c0 = c0; c->sse = sse;
-            c->shift_index = d;
+            oc->cell = cells[c];
+            oc->used = u;
+            oc->n = cn[c];
+            oc->b = b; oc->c0 = c0; oc->sse = csse;
+            if constexpr (SHIFT) oc->shift_index = d;
         }
     }
 }
@@ -688,15 +401,14 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     double* d_ages = (double*)ctx->sg_ages.p;
     double* d_tab = (double*)ctx->sg_tab.p;
 
-    const bool tab_lds = tab_bytes <= SG_TAB_LDS;
-    const size_t lds = sizeof(double) * (size_t)SG_WAVES * np + (tab_lds ? tab_bytes : 0);
-    const size_t lds1 = lds + (shift ? sizeof(double) * (size_t)SG_WAVES * sh_slot_doubles(A) : 0);   // (the search's slots)
-    const void* fn1 = shift ? (tab_lds ? (const void*)k_sg_shift<true> : (const void*)k_sg_shift<false>)
-                            : (tab_lds ? (const void*)k_sg_partial<true> : (const void*)k_sg_partial<false>);
-    const void* fn2 = shift ? (tab_lds ? (const void*)k_sg_resid_shift<true> : (const void*)k_sg_resid_shift<false>)
-                            : (tab_lds ? (const void*)k_sg_resid<true> : (const void*)k_sg_resid<false>);
-    if ((rc = sc_lds_attr(ctx, fn1, lds1))) return rc;
-    if ((rc = sc_lds_attr(ctx, fn2, lds))) return rc;
+    const bool tab_lds = tab_bytes <= PF_TAB_LDS;
+    const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds), lds1 = pf_lds_bytes(np, nt, A, shift, tab_lds);
+    const auto k_partial = tab_lds ? k_sg_partial<true> : k_sg_partial<false>;
+    const auto k_shift = tab_lds ? k_sg_shift<true> : k_sg_shift<false>;
+    const auto k_resid = tab_lds ? k_sg_resid<true> : k_sg_resid<false>;
+    const int Dk = shift ? D : 0;                        // what k_sg_resid and k_sg_choose take: no shift is a range of 0
+    if ((rc = sc_lds_attr(ctx, shift ? (const void*)k_shift : (const void*)k_partial, lds1))) return rc;
+    if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
     // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
@@ -780,54 +492,34 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         // (so is the padding at the end of the shifted call's cell table)
         if (shift && d_out && m) SC_HIP(ctx, hipMemsetAsync(d_out, 0, cell_bytes * (size_t)m, ctx->stream));
 
-        const unsigned gcell = (unsigned)std::max<long long>(1, std::min<long long>((m + SG_WAVES - 1) / SG_WAVES, SG_MAX_GRID));
+        const unsigned gcell = (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
-        if (m && shift) {
-            if (tab_lds)
-                k_sg_shift<true><<<gcell, SG_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples,
-                                                                          d_tab, d_prof, d_cn, d_used, d_scal, d_planes, d_shift);
-            else
-                k_sg_shift<false><<<gcell, SG_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples,
-                                                                           d_tab, d_prof, d_cn, d_used, d_scal, d_planes, d_shift);
-            ++launches;
-        } else if (m) {
-            if (tab_lds)
-                k_sg_partial<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples,
-                                                                           d_tab, d_prof, d_cn, d_used, d_scal, d_planes);
-            else
-                k_sg_partial<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples,
-                                                                            d_tab, d_prof, d_cn, d_used, d_scal, d_planes);
-            ++launches;
-        }
+        if (m && shift)
+            k_shift<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples, d_tab, d_prof,
+                                                             d_cn, d_used, d_scal, d_planes, d_shift);
+        else if (m)
+            k_partial<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples, d_tab, d_prof,
+                                                               d_cn, d_used, d_scal, d_planes);
+        if (m) ++launches;
         k_sg_rank<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, Sc, d_cn, d_used, d_list, d_cnt);
         ++launches;
         if (G) {
             k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
             k_sg_sum2<2><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tot);
-            if (shift && tab_lds)
-                k_sg_resid_shift<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift,
-                                                                               d_tot, m, A, h, D, de, min_profiles, d_tab);
-            else if (shift)
-                k_sg_resid_shift<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift,
-                                                                                d_tot, m, A, h, D, de, min_profiles, d_tab);
-            else if (tab_lds)
-                k_sg_resid<true><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_tot, m,
-                                                                         A, h, de, min_profiles, d_tab);
-            else
-                k_sg_resid<false><<<gcell, SG_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_tot, m,
-                                                                          A, h, de, min_profiles, d_tab);
+            k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift, d_tot, m, A, h,
+                                                            Dk, de, min_profiles, d_tab);
             k_sg_sum1<1><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
             k_sg_sum2<1><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tsse);
             launches += 5;
         }
         if (shift)
-            k_sg_choose_shift<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, D, delta,
-                                                                  min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift,
-                                                                  d_rows, (sc_segment_shift_cell*)d_out, d_sse);
+            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, Dk, delta,
+                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift, d_rows,
+                                                            (sc_segment_shift_cell*)d_out, d_sse);
         else
-            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, delta,
-                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_rows,
+            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, Dk, delta,
+                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift, d_rows,
                                                             (sc_segment_cell*)d_out, d_sse);
         ++launches;
         SC_HIP(ctx, hipGetLastError());
@@ -848,39 +540,47 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     return SC_OK;
 }
 
+// The four calls after their null checks and the early check of D: the argument checks under the name `who`, then the
+// fit on z - ny x nx on the host, uploaded - or on the context's DEM (z null).  D < 0: the call without a shift
+static int sg_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                   const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                   const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
+                   sc_segment_fit* out_rows, void* out_cells, double* out_sse, int8_t* out_shift) {
+    int rc = sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+                      min_profiles, out_rows);
+    if (rc) return rc;
+    const double* z_dev = ctx->z_dev;
+    if (z) {
+        if (S == 0) return SC_OK;
+        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
+        z_dev = (const double*)ctx->sg_z.p;
+    } else {
+        SC_HIP(ctx, hipSetDevice(ctx->device));
+    }
+    return sg_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+                  min_profiles, out_rows, out_cells, out_sse, out_shift);
+}
+
 extern "C" int sc_fit_segments(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
                                const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
                                int h, int w, double de, double delta, int min_samples, int min_profiles,
                                sc_segment_fit* out_rows, sc_segment_cell* out_cells, double* out_sse) {
     if (!ctx) return SC_ERR_INVALID;
-    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
-    const Geom& g = ctx->g;
-    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments: the context holds a block of a larger grid");
-    int rc = sg_check(ctx, "sc_fit_segments", g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
-                      min_profiles, out_rows);
+    int rc = sc_pf_whole_grid(ctx, "sc_fit_segments");
     if (rc) return rc;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
-                  min_profiles, out_rows, out_cells, out_sse, nullptr);
+    return sg_call(ctx, "sc_fit_segments", nullptr, ctx->g.ny, ctx->g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w,
+                   -1, de, delta, min_samples, min_profiles, out_rows, out_cells, out_sse, nullptr);
 }
 
+// (reports as sc_fit_segments)
 extern "C" int sc_fit_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
                                    const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
                                    long long S, const double* ages, int A, int h, int w, double de, double delta,
                                    int min_samples, int min_profiles, sc_segment_fit* out_rows, sc_segment_cell* out_cells,
                                    double* out_sse) {
     if (!ctx || !z) return SC_ERR_INVALID;
-    int rc = sg_check(ctx, "sc_fit_segments", ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
-                      min_profiles, out_rows);
-    if (rc) return rc;
-    if (S == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
-    if ((rc = sc_ensure(ctx, ctx->sg_z, bytes))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(ctx->sg_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, -1, de, delta,
-                  min_samples, min_profiles, out_rows, out_cells, out_sse, nullptr);
+    return sg_call(ctx, "sc_fit_segments", z, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta,
+                   min_samples, min_profiles, out_rows, out_cells, out_sse, nullptr);
 }
 
 extern "C" int sc_fit_segments_shift(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
@@ -889,17 +589,11 @@ extern "C" int sc_fit_segments_shift(sc_ctx* ctx, const long long* cells, const 
                                      sc_segment_fit* out_rows, sc_segment_shift_cell* out_cells, double* out_sse,
                                      int8_t* out_shift) {
     if (!ctx) return SC_ERR_INVALID;
-    if (!ctx->have_dem) return sc_fail(ctx, SC_ERR_NO_DEM, "no DEM set");
-    const Geom& g = ctx->g;
-    if (g.ly != g.ny || g.lx != g.nx || g.gy0 != 0 || g.gx0 != 0 || g.cy0 != 0 || g.cx0 != 0 || g.cy1 != g.ny || g.cx1 != g.nx)
-        return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_fit_segments_shift: the context holds a block of a larger grid");
-    if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments_shift: the shift range must be >= 0 cells");
-    int rc = sg_check(ctx, "sc_fit_segments_shift", g.ny, g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
-                      min_profiles, out_rows);
+    int rc = sc_pf_whole_grid(ctx, "sc_fit_segments_shift");
     if (rc) return rc;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    return sg_run(ctx, ctx->z_dev, g.ny, g.nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
-                  min_profiles, out_rows, out_cells, out_sse, out_shift);
+    if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments_shift: the shift range must be >= 0 cells");
+    return sg_call(ctx, "sc_fit_segments_shift", nullptr, ctx->g.ny, ctx->g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A,
+                   h, w, D, de, delta, min_samples, min_profiles, out_rows, out_cells, out_sse, out_shift);
 }
 
 extern "C" int sc_fit_segments_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells,
@@ -910,14 +604,6 @@ extern "C" int sc_fit_segments_shift_dem(sc_ctx* ctx, const double* z, int ny, i
                                          int8_t* out_shift) {
     if (!ctx || !z) return SC_ERR_INVALID;
     if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "sc_fit_segments_shift_dem: the shift range must be >= 0 cells");
-    int rc = sg_check(ctx, "sc_fit_segments_shift_dem", ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
-                      min_profiles, out_rows);
-    if (rc) return rc;
-    if (S == 0) return SC_OK;
-    SC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t bytes = sizeof(double) * (size_t)ny * (size_t)nx;
-    if ((rc = sc_ensure(ctx, ctx->sg_z, bytes))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(ctx->sg_z.p, z, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return sg_run(ctx, (const double*)ctx->sg_z.p, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta,
-                  min_samples, min_profiles, out_rows, out_cells, out_sse, out_shift);
+    return sg_call(ctx, "sc_fit_segments_shift_dem", z, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de,
+                   delta, min_samples, min_profiles, out_rows, out_cells, out_sse, out_shift);
 }

@@ -379,6 +379,12 @@ def segment_cases():
     corners = np.array([0, n - 1, n * (n - 1), n * n - 1, 150 * n + 150, 151 * n + 150])
     add("unusable segment", zb, 1.0, corners, [4, 4, 4, 4, 6, 6], 0.0, 100, 5, 3, ages[:NA["unusable segment"]], ms=20)
     add("no cell", z, 1.0, on[:0], on[:0], 0.2, 100, 5, 8, ages, ms=15)
+    # 217 rows of 64 ages are 111 KB: past the 64 KB up to which the kernels stage the erf table in LDS, so the residual and
+    # choice kernels read it from global memory.  Segments of 1, 64 and 65 cells (a rng of its own: the cases above stay)
+    rng = np.random.default_rng(20261019)
+    lab = np.repeat([2, 3, 1], [1, 64, 65])
+    add("table in global memory", pr.synthetic_z(256), 1.0, pr.scarp_cells(256, len(lab), rng, spread=1.0), lab,
+        0.2 + 0.02 * rng.standard_normal(len(lab)), 100, 1, 4, 10 ** np.linspace(0, NA["64 ages"], 64), ms=15)
     return cases
 
 

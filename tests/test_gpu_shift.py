@@ -64,7 +64,8 @@ def scases():
 
 PNAMES = ["synthetic h100 w0 D8", "synthetic h100 w5 D1", "synthetic h30 w5 D4", "64 ages", "one age", "repeated cells",
           "D = h - min_samples", "no cell", "borders and corners", "NaN cells"]
-SNAMES = ["segments h100 w0 D8", "segments h30 w5 D4", "sizes 1 2 64 65 300", "shuffled order", "unusable segment", "no cell"]
+SNAMES = ["segments h100 w0 D8", "segments h30 w5 D4", "sizes 1 2 64 65 300", "shuffled order", "unusable segment", "no cell",
+          "table in global memory"]
 
 
 def test_the_case_lists_are_the_ones_named_here():

@@ -251,7 +251,7 @@ def test_segment_kernels_have_no_scratch():
     from test_isa_budget import kernel_table
     t = kernel_table("sc_segment.hip")
     for k in ("k_sg_partial<true>", "k_sg_partial<false>", "k_sg_rank", "k_sg_sum1<2>", "k_sg_sum1<1>", "k_sg_sum2<2>",
-              "k_sg_sum2<1>", "k_sg_resid<true>", "k_sg_resid<false>", "k_sg_choose"):
+              "k_sg_sum2<1>", "k_sg_resid<true>", "k_sg_resid<false>", "k_sg_choose<sc_segment_cell>"):
         assert k in t, sorted(t)
     for name, r in t.items():
         assert r["scratch"] == 0, (name, r)

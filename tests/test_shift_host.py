@@ -223,8 +223,9 @@ def test_library_exports_the_shift_calls():
 def test_shift_kernels_have_no_scratch():
     from test_isa_budget import kernel_table
     t = dict(kernel_table("sc_profile.hip"), **kernel_table("sc_segment.hip"))
-    for k in ("k_pf_shift<true>", "k_pf_shift<false>", "k_sg_shift<true>", "k_sg_shift<false>", "k_sg_resid_shift<true>",
-              "k_sg_resid_shift<false>", "k_sg_choose_shift"):
+    # (k_sg_resid and k_sg_choose serve the calls with and without a shift)
+    for k in ("k_pf_shift<true>", "k_pf_shift<false>", "k_sg_shift<true>", "k_sg_shift<false>", "k_sg_resid<true>",
+              "k_sg_resid<false>", "k_sg_choose<sc_segment_shift_cell>"):
         assert k in t, sorted(t)
         assert t[k]["scratch"] == 0, (k, t[k])
         assert t[k]["vgpr"] + t[k]["agpr"] <= 128, (k, t[k])               # four waves per SIMD
