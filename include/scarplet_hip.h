@@ -547,6 +547,63 @@ int sc_fit_segments_shift_dem(sc_ctx* ctx, const double* z, int ny, int nx, cons
                               int min_samples, int min_profiles, sc_segment_fit* out_rows,
                               sc_segment_shift_cell* out_cells, double* out_sse, int8_t* out_shift);
 
+/*
+ * Block-bootstrap intervals of the age of sc_fit_segments (docs/bootstrap.md): a moving-block bootstrap along the strike.
+ * The cells of a segment come cut into blocks of neighbouring profiles (CSR over blocks and cells, below); the blocks are
+ * resampled with replacement and the segment's shared amplitude and age are re-fitted in every replicate.
+ *   stage one   the sampling and parking of sc_fit_segments (D = 0) or sc_fit_segments_shift (D > 0): See_ci, Sep_ci of
+ *               every usable profile and age, at d_ci with a shift
+ *   block       (sum See_ci, sum Sep_ci) over the block's usable profiles in hand-over order: runs of 64 consecutive
+ *               ones summed in sequence from the first, then the run sums in sequence from the first.  A block without a
+ *               usable profile stays in the partition with terms (0, 0)
+ *   draws       segment s of nb blocks and label L; replicate 0 takes blocks 0..nb-1 once each.  Replicate r = 1..R takes
+ *               nb draws k = 0..nb-1: u = mix(mix(seed ^ (L * 0x9E3779B97F4A7C15)) + ((r << 32) | k)) modulo 2^64, mix the
+ *               splitmix64 finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *               z ^= z >> 31), block = ((u >> 32) * nb) >> 32.  Integers only; keyed by the label, not by the position
+ *   replicate   SSee_i, SSep_i: the drawn blocks' terms added in draw order.  Failed when SSee_i is 0 or not finite at
+ *               any age (index -1, a NaN); else kt_index = argmax_i SSep_i^2 / SSee_i (ties to the smallest index; a NaN
+ *               never wins), a = SSep / SSee at that age.  This is the argmin of the pooled sse, with nothing subtracted
+ *   summary     n_ok replicates of 1..R that did not fail, n_failed the others.  q = (1 - level) / 2 in float64; over the
+ *               n_ok indices sorted ascending, lo_index = x[floor(q n_ok)], hi_index = x[ceil((1 - q) n_ok) - 1], taken
+ *               from an A-bin integer histogram; a_lo, a_hi by the same ranks over the sorted a; a_mean and a_sd (n - 1;
+ *               NaN for n_ok = 1) summed in replicate order.  kt_index0, a0: replicate 0
+ *   status      1: not bootstrapped - fewer than min_blocks blocks, fewer than min_profiles usable profiles, or n_ok = 0;
+ *               the indices are -1 and the floats NaN.  Otherwise 2 where lo_index == 0, + 4 where hi_index == A - 1
+ * seg_blk_start[S + 1]: CSR over blocks, 0 to NB; blk_start[NB + 1]: CSR over cells, 0 to K, with segment s's blocks
+ * covering exactly its cells.  R in 1..SC_BOOT_MAX_REPLICATES, 0 < level < 1, min_blocks >= 2.  out_rows: S rows;
+ * out_hist: S x A int32 (the histogram of replicates 1..R), out_index: S x (R + 1) int8 and out_a: S x (R + 1) float64
+ * (replicate 0 first), each or NULL.  Refused before any device work: what sc_fit_segments_shift refuses (a segment above
+ * the park limit included), CSR arrays that do not fit together, R, level or min_blocks out of range.  No float atomics,
+ * every sum in a fixed order: the same bytes on every run.  Timed as SC_K_PROFILE.
+ */
+#define SC_BOOT_MAX_REPLICATES 4096
+typedef struct sc_segment_boot {
+    int32_t  label;
+    int32_t  n_cells;         /* cells of the segment                            */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n_blocks;        /* blocks of the segment, empty ones included      */
+    int32_t  replicates;      /* R                                               */
+    int32_t  n_failed;        /* replicates of 1..R that failed                  */
+    int32_t  kt_index0;       /* replicate 0: every block once                   */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not bootstrapped), or 2 (lo_index == 0) + 4 (hi_index == A - 1) */
+    double   kt0, kt_lo, kt_hi;
+    double   a0;              /* replicate 0's amplitude                         */
+    double   a_mean, a_sd, a_lo, a_hi;
+} sc_segment_boot;
+int sc_bootstrap_segments(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                          const long long* seg_start, const int32_t* seg_label, long long S,
+                          const long long* seg_blk_start, const long long* blk_start, long long NB, const double* ages,
+                          int A, int h, int w, int D, double de, int min_samples, int min_profiles, int min_blocks, int R,
+                          double level, uint64_t seed, sc_segment_boot* out_rows, int32_t* out_hist, int8_t* out_index,
+                          double* out_a);
+int sc_bootstrap_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                              const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                              long long S, const long long* seg_blk_start, const long long* blk_start, long long NB,
+                              const double* ages, int A, int h, int w, int D, double de, int min_samples, int min_profiles,
+                              int min_blocks, int R, double level, uint64_t seed, sc_segment_boot* out_rows,
+                              int32_t* out_hist, int8_t* out_index, double* out_a);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -676,7 +733,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles* and sc_fit_segments*: the table and every kernel of every chunk of cells */
+#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*: the table and every kernel of every chunk */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

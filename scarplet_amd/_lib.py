@@ -146,6 +146,22 @@ SEGMENT_SHIFT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_shift_ce
                                      "itemsize": C.sizeof(sc_segment_shift_cell)})
 
 
+class sc_segment_boot(C.Structure):
+    """One row of sc_bootstrap_segments / sc_bootstrap_segments_dem (docs/bootstrap.md)."""
+    _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n_blocks", C.c_int32),
+                ("replicates", C.c_int32), ("n_failed", C.c_int32), ("kt_index0", C.c_int32), ("lo_index", C.c_int32),
+                ("hi_index", C.c_int32), ("status", C.c_int32),
+                ("kt0", C.c_double), ("kt_lo", C.c_double), ("kt_hi", C.c_double), ("a0", C.c_double),
+                ("a_mean", C.c_double), ("a_sd", C.c_double), ("a_lo", C.c_double), ("a_hi", C.c_double)]
+
+
+SEGMENT_BOOT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_boot._fields_],
+                               "formats": [np.int32] * 10 + [np.float64] * 8,
+                               "offsets": [getattr(sc_segment_boot, f).offset for f, _ in sc_segment_boot._fields_],
+                               "itemsize": C.sizeof(sc_segment_boot)})
+BOOT_MAX_REPLICATES = 4096                                             # SC_BOOT_MAX_REPLICATES
+
+
 class sc_xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("kind", C.c_int32),
                 ("sy0", C.c_int32), ("sx0", C.c_int32),
@@ -234,6 +250,16 @@ SIGNATURES = {
                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
+    "sc_bootstrap_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
+                                        C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, _dp]),
+    "sc_bootstrap_segments_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong,
+                                            C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int,
+                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -598,6 +624,37 @@ class Context(object):
                 tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
         plane = self._fit_call("sc_fit_segments", head, rest, shift, shift_plane, (K, A), z)
         return (rows, tab, sse) if shift is None else (rows, tab, sse, plane)
+
+    # -- block-bootstrap intervals per segment (docs/bootstrap.md) -----------------------
+    def bootstrap_segments(self, cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, ages, h, w, D, de,
+                           min_samples, min_profiles, min_blocks, R, level, seed, hist=False, replicates=False, z=None):
+        """sc_bootstrap_segments on the context's DEM, or sc_bootstrap_segments_dem on ``z`` (float64, C-contiguous,
+        2-D): (rows, (S, A) int32 histograms or None, (S, R + 1) int8 indices or None, (S, R + 1) float64 amplitudes
+        or None).  cells, seg_start, seg_blk_start and blk_start int64, seg_label int32, sa / ca / ages float64, all
+        1-D and C-contiguous; the cells grouped by segment and, within it, by block."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32), (seg_blk_start, np.int64), (blk_start, np.int64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S, NB = len(cells), len(ages), len(seg_label), len(blk_start) - 1
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1 and len(seg_blk_start) == S + 1
+        rows = np.zeros(S, dtype=SEGMENT_BOOT_DTYPE)
+        hg = np.zeros((S, A), dtype=np.int32) if hist else None
+        idx = np.zeros((S, int(R) + 1), dtype=np.int8) if replicates else None
+        amp = np.zeros((S, int(R) + 1), dtype=np.float64) if replicates else None
+        llp = C.POINTER(C.c_longlong)
+        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, seg_blk_start.ctypes.data_as(llp),
+                blk_start.ctypes.data_as(llp), NB, _as(ages, _dp), A, int(h), int(w), int(D), float(de), int(min_samples),
+                int(min_profiles), int(min_blocks), int(R), float(level), int(seed), rows.ctypes.data_as(C.c_void_p),
+                hg.ctypes.data_as(C.c_void_p) if hist else None, idx.ctypes.data_as(C.c_void_p) if replicates else None,
+                _as(amp, _dp) if replicates else None]
+        name = "sc_bootstrap_segments"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, hg, idx, amp
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

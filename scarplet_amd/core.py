@@ -934,6 +934,39 @@ class Matcher(object):
         D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
         return segments._run(self.ctx, args, self.nx, return_cells, return_curve, shift=D, return_shift=return_shift)
 
+    def bootstrap_segments(self, traces, half_length, block_length, swath=0, replicates=1000, level=0.95, seed=0, ages=None,
+                           min_samples=4, min_profiles=1, min_blocks=5, max_shift=None, return_hist=False,
+                           return_replicates=False, strike="cell"):
+        """``sl.bootstrap_segments`` on the DEM this matcher holds on the device (docs/bootstrap.md) - no upload: a
+        block-bootstrap interval of the age and the amplitude of every segment of ``traces``.  ``strike`` chooses the
+        profiles' orientation as in ``fit_segments``; with ``strike="segment"`` the blocks are cut along the table's
+        ``strike`` too.  The bytes are those of ``sl.bootstrap_segments`` on the same data."""
+        from scarplet_amd import bootstrap, traces as tr
+        if not getattr(self, "whole", False):
+            raise ValueError("bootstrap_segments needs the whole DEM on the device, not a block of it")
+        if not isinstance(traces, tr.Traces):
+            raise ValueError("traces must be the Traces of extract_traces")
+        if strike not in ("cell", "segment"):
+            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
+        labels = np.asarray(traces.labels)
+        if labels.shape != (self.ny, self.nx):
+            raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
+        cells = np.flatnonzero(labels.ravel() > 0)
+        lab = labels.ravel()[cells]
+        seg_strike = None
+        if strike == "segment":
+            seg = traces.segments
+            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
+                raise ValueError("the traces' table does not number the segments of its label plane")
+            seg_strike = np.asarray(seg["strike"], dtype=np.float64)
+            angle = seg_strike[lab - 1]
+        else:
+            angle = self.result_array()[2]
+        args = bootstrap.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, block_length,
+                                    replicates, level, seed, ages, min_samples, min_profiles, min_blocks, max_shift,
+                                    seg_strike=seg_strike)
+        return bootstrap._run(self.ctx, args, return_hist, return_replicates)
+
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one
         sl.match per scale on the same data, docs/source/examples/channels.ipynb - its 4-plane result has no scale

@@ -1,9 +1,11 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
-// included by sc_profile.hip and sc_segment.hip alone.  The library is built with -ffp-contract=off and every helper
-// here is inlined, so a helper does the operations of its text in the order of its text wherever it is called: the
-// four calls return the same bits in every field they share because they call the same helpers.
+// included by sc_profile.hip and sc_segment.hip alone - and by sc_bootstrap.hip for the host side of stage one.  The
+// library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
+// in the order of its text wherever it is called: the four calls return the same bits in every field they share because
+// they call the same helpers.
 #pragma once
 #include "sc_internal.h"
+#include <vector>
 
 #define PF_WAVES 4                       // cells in flight per workgroup: one wave per cell
 #define PF_THREADS (64 * PF_WAVES)
@@ -23,6 +25,32 @@ int sc_pf_whole_grid(sc_ctx* ctx, const char* who);
 int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx);
 // the launch of the erf table over j = -h..h (d_ages on the device; timed as SC_K_PROFILE)
 int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
+
+// ---- sc_segment.hip, shared with sc_bootstrap.hip ----------------------------------------------------------------------------
+// the argument checks of a segment call (D < 0: the call without a shift) and the cells of one segment its park holds
+int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
+                const void* out_rows);
+long long sc_sg_cap_cells(int A, int h, int D);
+// Stage one of a chunk of whole segments: the host arrays that go up (kept until the stream is synchronised) and, on the
+// device, the chunk's cells, (sa, ca), CSR array over cells and labels, what k_sg_partial / k_sg_shift park (profiles, n
+// and used, sbar / pbar / beta, the four per-age planes ebar, gamma, See, Sep - at d_ci with a shift - and d_ci) and what
+// k_sg_rank leaves (the usable cells of each segment in order; n_profiles and the pooled n per segment)
+struct sg_stage {
+    std::vector<double> dir;
+    std::vector<int> start;
+    long long Sc = 0, m = 0;
+    long long* cells = nullptr;
+    double *dirs = nullptr, *prof = nullptr, *scal = nullptr, *planes = nullptr;
+    int *seg = nullptr, *label = nullptr, *cn = nullptr, *used = nullptr, *list = nullptr, *cnt = nullptr;
+    signed char* shift = nullptr;
+};
+int sc_sg_stage_attr(sc_ctx* ctx, int A, int h, int D);
+int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, const long long* seg_start,
+                        const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st);
+int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
+                       const double* d_tab, const sg_stage& st, int& launches);
 
 // ---- the centre shift (docs/profiles.md, "The centre shift") --------------------------------------------------------------
 // candidates in the order 0, -1, +1, -2, +2, ...: rank r -> shift d

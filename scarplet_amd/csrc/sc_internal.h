@@ -187,6 +187,10 @@ struct sc_ctx {
     DevBuf sg_z, sg_ages, sg_tab, sg_cells, sg_dir, sg_cseg, sg_start, sg_blk, sg_label, sg_prof, sg_int, sg_scal,
         sg_age, sg_list, sg_part, sg_tot, sg_tsse, sg_cnt, sg_rows, sg_out, sg_sse;
     DevBuf sg_shift;           // sc_fit_segments_shift*: d_ci parked beside the per-age terms, int8
+    // sc_bootstrap_segments*: stage one lives in the sg_ buffers; per chunk the CSR arrays of blocks over cells and of
+    // segments over blocks, the block terms (See, Sep per block and age), every replicate's index and amplitude, the
+    // histograms and the rows
+    DevBuf bs_blk, bs_sblk, bs_terms, bs_index, bs_a, bs_hist, bs_rows;
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);

@@ -353,14 +353,14 @@ __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_st
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 // (D < 0 throughout the host side: the call without a shift, its kernels and its bytes)
-static long long sg_cap_cells(int A, int h, int D) {
+long long sc_sg_cap_cells(int A, int h, int D) {
     return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) + 4ll * A) + (D >= 0 ? A : 0));
 }
 
-static int sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
+int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
                     long long K, const long long* seg_start, const int32_t* seg_label, long long S, const double* ages,
                     int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
-                    const sc_segment_fit* out_rows) {
+                    const void* out_rows) {
     int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
     if (D >= 0 && (rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
@@ -369,7 +369,7 @@ static int sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, co
     if (min_profiles < 1) return sc_fail(ctx, SC_ERR_INVALID, "%s: min_profiles must be >= 1", who);
     if (seg_start[0] != 0 || seg_start[S] != K)
         return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start must run from 0 to K", who);
-    const long long cap = sg_cap_cells(A, h, D);
+    const long long cap = sc_sg_cap_cells(A, h, D);
     for (long long s = 0; s < S; ++s) {
         if (seg_start[s + 1] < seg_start[s])
             return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start decreases at segment %lld", who, s);
@@ -384,6 +384,94 @@ static int sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, co
 }
 
 static unsigned sg_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
+static unsigned sg_grid_cells(long long m) {
+    return (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
+}
+
+// Stage one of a chunk of whole segments s0..s1 (shared with sc_bootstrap.hip): the chunk's cells, (sa, ca), CSR array and
+// labels go up, and the buffers of what k_sg_partial / k_sg_shift park and k_sg_rank lists are sized.  No launch
+int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, const long long* seg_start,
+                        const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st) {
+    const bool shift = D >= 0;
+    const int np = 2 * h + 1;
+    const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
+    int rc;
+    st.Sc = Sc;
+    st.m = m;
+    st.start.resize((size_t)Sc + 1);
+    st.dir.resize(2 * (size_t)m);
+    for (long long s = 0; s <= Sc; ++s) st.start[s] = (int)(seg_start[s0 + s] - k0);
+    for (long long k = 0; k < m; ++k) {
+        st.dir[2 * k] = sa[k0 + k];
+        st.dir[2 * k + 1] = ca[k0 + k];
+    }
+    const size_t mA = (size_t)m * A;
+    if ((rc = sc_ensure(ctx, ctx->sg_cells, sizeof(long long) * (size_t)m))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_dir, sizeof(double) * 2 * (size_t)m))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_start, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_label, sizeof(int) * (size_t)Sc))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * np))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_int, sizeof(int) * 2 * (size_t)m))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_scal, sizeof(double) * 3 * (size_t)m))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * 4 * mA))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_list, sizeof(int) * (size_t)m))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_cnt, sizeof(int) * 2 * (size_t)Sc))) return rc;
+    if (shift && (rc = sc_ensure(ctx, ctx->sg_shift, mA))) return rc;
+    st.cells = (long long*)ctx->sg_cells.p;
+    st.dirs = (double*)ctx->sg_dir.p;
+    st.seg = (int*)ctx->sg_start.p;
+    st.label = (int*)ctx->sg_label.p;
+    st.prof = (double*)ctx->sg_prof.p;
+    st.cn = (int*)ctx->sg_int.p;
+    st.used = st.cn + m;
+    st.scal = (double*)ctx->sg_scal.p;
+    st.planes = (double*)ctx->sg_age.p;
+    st.list = (int*)ctx->sg_list.p;
+    st.cnt = (int*)ctx->sg_cnt.p;
+    st.shift = shift ? (signed char*)ctx->sg_shift.p : nullptr;
+    if (m) {
+        SC_HIP(ctx, hipMemcpyAsync(st.cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(st.dirs, st.dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    }
+    SC_HIP(ctx, hipMemcpyAsync(st.seg, st.start.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(st.label, seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
+    return SC_OK;
+}
+
+// ... and its two launches, inside the caller's timing bracket: the parking kernel (none for a chunk without cells) and
+// k_sg_rank.  d_tab: the erf table over h + D (h without a shift).  Adds the number of launches to `launches`
+int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
+                       const double* d_tab, const sg_stage& st, int& launches) {
+    const bool shift = D >= 0;
+    const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
+    const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
+    const size_t lds1 = pf_lds_bytes(np, nt, A, shift, tab_lds);
+    const auto k_partial = tab_lds ? k_sg_partial<true> : k_sg_partial<false>;
+    const auto k_shift = tab_lds ? k_sg_shift<true> : k_sg_shift<false>;
+    const long long m = st.m;
+    const unsigned gcell = sg_grid_cells(m);
+    if (m && shift)
+        k_shift<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, D, de, min_samples, d_tab, st.prof,
+                                                         st.cn, st.used, st.scal, st.planes, st.shift);
+    else if (m)
+        k_partial<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, de, min_samples, d_tab, st.prof,
+                                                           st.cn, st.used, st.scal, st.planes);
+    if (m) ++launches;
+    k_sg_rank<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.Sc, st.cn, st.used, st.list, st.cnt);
+    ++launches;
+    return SC_OK;
+}
+
+// the dynamic-LDS limit of the parking kernel, raised before the first chunk
+int sc_sg_stage_attr(sc_ctx* ctx, int A, int h, int D) {
+    const bool shift = D >= 0;
+    const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
+    const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
+    const auto k_partial = tab_lds ? k_sg_partial<true> : k_sg_partial<false>;
+    const auto k_shift = tab_lds ? k_sg_shift<true> : k_sg_shift<false>;
+    return sc_lds_attr(ctx, shift ? (const void*)k_shift : (const void*)k_partial, pf_lds_bytes(np, nt, A, shift, tab_lds));
+}
+
 
 static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
@@ -394,7 +482,7 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
     const size_t cell_bytes = shift ? sizeof(sc_segment_shift_cell) : sizeof(sc_segment_cell);
     const size_t tab_bytes = sizeof(double) * (size_t)nt * A;
-    const long long cap = sg_cap_cells(A, h, D);
+    const long long cap = sc_sg_cap_cells(A, h, D);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_tab, tab_bytes))) return rc;
@@ -402,108 +490,73 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     double* d_tab = (double*)ctx->sg_tab.p;
 
     const bool tab_lds = tab_bytes <= PF_TAB_LDS;
-    const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds), lds1 = pf_lds_bytes(np, nt, A, shift, tab_lds);
-    const auto k_partial = tab_lds ? k_sg_partial<true> : k_sg_partial<false>;
-    const auto k_shift = tab_lds ? k_sg_shift<true> : k_sg_shift<false>;
+    const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds);
     const auto k_resid = tab_lds ? k_sg_resid<true> : k_sg_resid<false>;
     const int Dk = shift ? D : 0;                        // what k_sg_resid and k_sg_choose take: no shift is a range of 0
-    if ((rc = sc_lds_attr(ctx, shift ? (const void*)k_shift : (const void*)k_partial, lds1))) return rc;
+    if ((rc = sc_sg_stage_attr(ctx, A, h, D))) return rc;
     if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
     // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
     if ((rc = sc_pf_table(ctx, d_ages, A, h + (shift ? D : 0), de, d_tab))) return rc;
 
-    std::vector<double> dir;
-    std::vector<int> cseg, start, blk;
+    sg_stage st;
+    std::vector<int> cseg, blk;
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes
         long long s1 = s0 + 1;
         while (s1 < S && s1 - s0 < SG_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) ++s1;
         const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        start.resize((size_t)Sc + 1);
         blk.resize((size_t)Sc + 1);
         cseg.resize((size_t)m);
-        dir.resize(2 * (size_t)m);
         blk[0] = 0;
         for (long long s = 0; s < Sc; ++s) {
             const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            start[s] = (int)a0;
             blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
             for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
         }
-        start[Sc] = (int)m;
         const long long G = blk[Sc];
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
         const size_t mA = (size_t)m * A;
-        if ((rc = sc_ensure(ctx, ctx->sg_cells, sizeof(long long) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_dir, sizeof(double) * 2 * (size_t)m))) return rc;
+        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, A, h, D, st))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_start, sizeof(int) * ((size_t)Sc + 1)))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_label, sizeof(int) * (size_t)Sc))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * np))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_int, sizeof(int) * 2 * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_scal, sizeof(double) * 3 * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * 4 * mA))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_list, sizeof(int) * (size_t)m))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * A))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * A))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_cnt, sizeof(int) * 2 * (size_t)Sc))) return rc;
         if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_fit) * (size_t)Sc))) return rc;
         if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, cell_bytes * (size_t)m))) return rc;
-        if (shift && (rc = sc_ensure(ctx, ctx->sg_shift, mA))) return rc;
         if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
-        long long* d_cells = (long long*)ctx->sg_cells.p;
-        double* d_dir = (double*)ctx->sg_dir.p;
+        long long* d_cells = st.cells;
         int* d_cseg = (int*)ctx->sg_cseg.p;
-        int* d_start = (int*)ctx->sg_start.p;
+        int* d_start = st.seg;
         int* d_blk = (int*)ctx->sg_blk.p;
-        int* d_label = (int*)ctx->sg_label.p;
-        double* d_prof = (double*)ctx->sg_prof.p;
-        int* d_cn = (int*)ctx->sg_int.p;
-        int* d_used = d_cn + m;
-        double* d_scal = (double*)ctx->sg_scal.p;
-        double* d_planes = (double*)ctx->sg_age.p;
-        int* d_list = (int*)ctx->sg_list.p;
+        int* d_label = st.label;
+        double* d_prof = st.prof;
+        int* d_cn = st.cn;
+        int* d_used = st.used;
+        double* d_scal = st.scal;
+        double* d_planes = st.planes;
+        int* d_list = st.list;
         double* d_part = (double*)ctx->sg_part.p;
         double* d_tot = (double*)ctx->sg_tot.p;
         double* d_tsse = (double*)ctx->sg_tsse.p;
-        int* d_cnt = (int*)ctx->sg_cnt.p;
+        int* d_cnt = st.cnt;
         sc_segment_fit* d_rows = (sc_segment_fit*)ctx->sg_rows.p;
         void* d_out = out_cells ? ctx->sg_out.p : nullptr;
-        signed char* d_shift = shift ? (signed char*)ctx->sg_shift.p : nullptr;
+        signed char* d_shift = st.shift;
         double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
 
-        if (m) {
-            SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-            SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-            SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_start, start.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+        if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
         SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_label, seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
         // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
         SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_fit) * (size_t)Sc, ctx->stream));
         // (so is the padding at the end of the shifted call's cell table)
         if (shift && d_out && m) SC_HIP(ctx, hipMemsetAsync(d_out, 0, cell_bytes * (size_t)m, ctx->stream));
 
-        const unsigned gcell = (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
+        const unsigned gcell = sg_grid_cells(m);
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
-        if (m && shift)
-            k_shift<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, D, de, min_samples, d_tab, d_prof,
-                                                             d_cn, d_used, d_scal, d_planes, d_shift);
-        else if (m)
-            k_partial<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, A, h, w, de, min_samples, d_tab, d_prof,
-                                                               d_cn, d_used, d_scal, d_planes);
-        if (m) ++launches;
-        k_sg_rank<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, Sc, d_cn, d_used, d_list, d_cnt);
-        ++launches;
+        if ((rc = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, d_tab, st, launches))) return rc;
         if (G) {
             k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
             k_sg_sum2<2><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tot);
@@ -546,7 +599,7 @@ static int sg_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                    const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
                    const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
                    sc_segment_fit* out_rows, void* out_cells, double* out_sse, int8_t* out_shift) {
-    int rc = sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
+    int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
                       min_profiles, out_rows);
     if (rc) return rc;
     const double* z_dev = ctx->z_dev;
