@@ -164,6 +164,33 @@ int sc_set_masks(sc_ctx* ctx, int slot, const uint8_t* limits,
 int sc_clear_windows(sc_ctx* ctx);
 
 /*
+ * The reference's Crater template (WindowedTemplate.py:528-605; docs/craters.md) for every (radius, age) of a grid,
+ * synthesised on the device in float64 straight into window slots - no host array, no upload.  Template
+ * k = i_radius * n_ages + i_age is W = sum over theta_j, j ascending, of sign_j * (-xr / p0) * exp(-(xr * xr) / p1) where
+ * |xr| < 1 and |yr| < d_half, with xm = x - dx, yp = y + dy, xr = xm * cos_a + yp * sin_a, yr = -xm * sin_a + yp * cos_a on
+ * the axes of the last sc_set_dem (SC_ERR_NO_DEM without one), every operation correctly rounded and in this order.
+ * The caller evaluates what decides the two compares with numpy, as the reference does:
+ *   theta_tab  n_theta x 3: cos(alpha_j), sin(alpha_j) of alpha_j = -theta_j, and the sign (-1 where
+ *              pi/2 < theta_j < 3 pi/2, else +1)
+ *   dxy        n_radii x n_theta x 2: dx = R cos(theta_j), dy = R sin(theta_j)
+ *   ring       n_radii x 2: bounds lo <= x^2 + y^2 <= hi outside which no strip keeps a cell - at most
+ *              max(R - 1, 0)^2 and at least (R + 1)^2 + d_half^2, widened beyond rounding; such cells are 0 unevaluated
+ *   age_tab    n_ages x 2: p0 = 2 kt^1.5 sqrt(pi), p1 = 4 kt
+ *   d_half     5 / de
+ *   boxes      n_radii x 4: pmin, pmax, qmin, qmax of the radius's support box in offsets from (ny / 2, nx / 2); a box
+ *              that leaves the grid is SC_ERR_INVALID
+ * slots, count, sumsq: n_radii x n_ages each - the window slot (what sc_upload_window returns: the float64 window, its
+ * float32 copy and the W != 0 bytes, for sc_template.window), count(W != 0) and sum(W * W) (sc_template.p0 / p1 of an
+ * SC_KIND_WINDOW descriptor), summed in a fixed order: the same bits on every run.  w_out: the float64 windows back on
+ * the host, one box after the other in template order, or NULL.  All slots of a call share one allocation, which
+ * sc_clear_windows frees.  SC_ERR_UNSUPPORTED beyond 4096 strips, 65535 templates or 2^31 - 1 window cells.  Timed
+ * under SC_K_WINDOWS.
+ */
+int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const double* theta_tab, const double* dxy,
+                      const double* ring, const double* age_tab, double d_half, const int32_t* boxes, int* slots,
+                      double* count, double* sumsq, double* w_out);
+
+/*
  * Engine options, set explicitly (nothing is read from the environment):
  *   "kappa"    float32 resolution floor of the FFT epilogue in units of eps32
  *              (default 4; 0 switches the floor off; sc_internal.h sc_epi_floor)

@@ -347,6 +347,115 @@ class Channel(Ricker):
     pass
 
 
+# ---- Crater (WT.py:528-605; docs/craters.md) ----------------------------------------------------
+CRATER_STRIPS = 359                                   # WT.py:586
+
+
+def crater_box(R, de):
+    """Support box of a Crater of radius ``R`` (= r / de, WT.py:562) as (pmin, pmax, qmin, qmax), offsets from the
+    cell (ny // 2, nx // 2).  A strip keeps a cell only where |xr| < 1 and |yr| < 5 / de, and (xr + R, yr) is the cell
+    rotated about the centre: every kept cell lies within sqrt((R + 1)^2 + (5 / de)^2) of it in coordinate units.
+    One more cell on every side covers the half cell by which cell n // 2 of an even grid misses the centre."""
+    half = int(np.ceil(np.sqrt((abs(R) + 1.0) ** 2 + (5.0 / de) ** 2) / abs(de))) + 1
+    return (-half, half, -half, half)
+
+
+def crater_limits(box, nx, ny):
+    """(ilo, ihi, jlo, jhi): the cells at which ``box``, centred on the cell, lies inside the grid - the window limits
+    of a Crater.  Empty (lo > hi) where the box is larger than the grid."""
+    pmin, pmax, qmin, qmax = box
+    return (-pmin, ny - 1 - pmax, -qmin, nx - 1 - qmax)
+
+
+def crater_tables(radii, ages, nx, ny, de):
+    """What sc_crater_windows takes (include/scarplet_hip.h) for the radii ``radii`` (as Crater takes them: r, with
+    R = r / de) and the ages ``ages``: every transcendental that decides a compare of Crater.template(), evaluated
+    scalar by scalar with numpy as the reference evaluates it (WT.py:586-596).  A ValueError where a radius's support
+    box (crater_box) leaves the grid."""
+    radii = [float(r) for r in np.atleast_1d(radii)]
+    ages = [float(a) for a in np.atleast_1d(ages)]
+    if not radii or not ages:
+        raise ValueError("crater search: no radii or no ages")
+    if not all(np.isfinite(r) and r > 0 for r in radii) or not all(np.isfinite(a) and a > 0 for a in ages):
+        raise ValueError("crater search: radii and ages must be finite and positive")
+    d_half = 5 / de
+    thetas = np.linspace(0, 2 * np.pi, num=CRATER_STRIPS, endpoint=False)
+    theta_tab = np.empty((len(thetas), 3))
+    for k, theta in enumerate(thetas):
+        alpha = -theta
+        theta_tab[k] = (np.cos(alpha), np.sin(alpha), -1.0 if (theta > np.pi / 2 and theta < 3 * np.pi / 2) else 1.0)
+    dxy = np.empty((len(radii), len(thetas), 2))
+    ring = np.empty((len(radii), 2))
+    boxes = np.empty((len(radii), 4), dtype=np.int32)
+    for i, r in enumerate(radii):
+        R = r / de
+        for k, theta in enumerate(thetas):
+            dxy[i, k] = (R * np.cos(theta), R * np.sin(theta))
+        lo, hi = max(abs(R) - 1.0, 0.0) ** 2, (abs(R) + 1.0) ** 2 + d_half ** 2
+        ring[i] = (max(lo * (1 - 1e-9) - 1e-9, 0.0), hi * (1 + 1e-9) + 1e-9)
+        box = crater_box(R, de)
+        if ny // 2 + box[0] < 0 or ny // 2 + box[1] >= ny or nx // 2 + box[2] < 0 or nx // 2 + box[3] >= nx:
+            raise ValueError("crater search: radius %g needs a support box of %d x %d cells about the centre, which "
+                             "leaves the %d x %d grid" % (r, box[1] - box[0] + 1, box[3] - box[2] + 1, ny, nx))
+        boxes[i] = box
+    age_tab = np.array([(2. * kt ** (3 / 2.) * np.sqrt(np.pi), 4. * kt) for kt in ages], dtype=np.float64)
+    return dict(theta_tab=theta_tab, dxy=dxy, ring=ring, age_tab=age_tab, d_half=float(d_half), boxes=boxes)
+
+
+class Crater(WindowedTemplate):
+    """Radially symmetric crater rim of radius ``r`` and morphologic age ``kt`` (WT.py:528-605): 359 thin Scarp
+    strips tangent to a ring.  ``Crater(r, kt, nx, ny, de)`` - not the (scale, age, angle, ...) signature of the other
+    classes: it is searched with ``scarplet_amd.match_craters`` over a (radius, age) grid, not handed to ``match``.
+    The reference divides the radius by ``de`` and then uses it in coordinate units; that is kept (docs/craters.md)."""
+
+    def __init__(self, r, kt, nx, ny, de):
+        self.r = r / de                               # WT.py:562
+        self.kt = kt
+        self.nx = nx
+        self.ny = ny
+        self.de = de
+
+    def _support_bbox(self):
+        return crater_box(self.r, self.de)
+
+    def template(self):
+        """The reference's loop (WT.py:577-605) with its operations in its order, evaluated on the support box - the
+        cells outside it add +-0 in every strip.  A box larger than the grid is clipped to it."""
+        x, y = self._axes()
+        pmin, pmax, qmin, qmax = self._support_bbox()
+        i0, i1 = max(self.ny // 2 + pmin, 0), min(self.ny // 2 + pmax, self.ny - 1) + 1
+        j0, j1 = max(self.nx // 2 + qmin, 0), min(self.nx // 2 + qmax, self.nx - 1) + 1
+        x, y = np.meshgrid(x[j0:j1], y[i0:i1])
+        W = np.zeros_like(x)
+        thetas = np.linspace(0, 2 * np.pi, num=CRATER_STRIPS, endpoint=False)
+        for theta in thetas:
+            alpha = -theta
+            dx = self.r * np.cos(theta)
+            dy = self.r * np.sin(theta)
+            xr = (x - dx) * np.cos(alpha) + (y + dy) * np.sin(alpha)
+            yr = -(x - dx) * np.sin(alpha) + (y + dy) * np.cos(alpha)
+            mask = (abs(xr) < 1) & (abs(yr) < 5 / self.de)
+            if not mask.any():
+                continue
+            this_W = (-xr / (2. * self.kt ** (3 / 2.) * np.sqrt(np.pi))) * np.exp(-xr ** 2. / (4. * self.kt))
+            this_W *= mask
+            if theta > np.pi / 2 and theta < 3 * np.pi / 2:
+                this_W *= -1
+            W += this_W
+        out = np.zeros((self.ny, self.nx))
+        out[i0:i1, j0:j1] = W
+        return out
+
+    def get_window_limits(self):
+        """Masked unless the support box, centred on the cell, lies inside the grid: a rectangle (the reference's
+        Crater inherits a get_window_limits() that reads attributes it never sets, and cannot be called)."""
+        ilo, ihi, jlo, jhi = crater_limits(self._support_bbox(), self.nx, self.ny)
+        lim = np.ones((self.ny, self.nx), dtype=bool)
+        if ihi >= ilo and jhi >= jlo:
+            lim[max(ilo, 0):ihi + 1, max(jlo, 0):jhi + 1] = False
+        return lim
+
+
 # ---- the reference's own built-in classes ------------------------------------------------------
 _TWIN_CACHE = {}
 # probe grids of builtin_twin: (scale d, second argument, orientation, nx, ny, de) - odd and even

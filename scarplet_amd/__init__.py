@@ -6,11 +6,11 @@ plugin classes, with the work done by hand-written HIP kernels reached through
 a C-ABI shared library (include/scarplet_hip.h).
 """
 
-from scarplet_amd.core import (match, match_scales, match_template, compare, load,  # noqa: F401
+from scarplet_amd.core import (match, match_scales, match_craters, match_template, compare, load,  # noqa: F401
                                calculate_best_fit_parameters,
                                calculate_best_fit_parameters_serial, Matcher)
 from scarplet_amd import WindowedTemplate, dem  # noqa: F401
-from scarplet_amd.WindowedTemplate import (Scarp, Ricker, Channel,  # noqa: F401
+from scarplet_amd.WindowedTemplate import (Scarp, Ricker, Channel, Crater,  # noqa: F401
                                            RightFacingUpperBreakScarp,
                                            LeftFacingUpperBreakScarp)
 from scarplet_amd.dem import DEMGrid  # noqa: F401

@@ -17,6 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SCARPLET_HIP_LIB") or os.path.join(_HERE, "libscarplet_hip.so")
 
 SC_OK = 0
+SC_ERR_INVALID = -1
 ABI_VERSION = 10
 ID_NONE = 0xFFFFFFFF
 COMM_ID_BYTES = 128
@@ -192,6 +193,8 @@ SIGNATURES = {
                                    C.POINTER(C.c_int)]),
     "sc_set_masks": (C.c_int, [_P, C.c_int, _bp, _bp]),
     "sc_clear_windows": (C.c_int, [_P]),
+    "sc_crater_windows": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double,
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int), _dp, _dp, _dp]),
     "sc_reset_best": (C.c_int, [_P]),
     "sc_match": (C.c_int, [_P, C.POINTER(sc_template), C.c_int,
                            C.POINTER(sc_plan)]),
@@ -491,6 +494,37 @@ class Context(object):
     def clear_windows(self):
         self._check(self.lib.sc_clear_windows(self._h), "sc_clear_windows")
         self.masked_slots.clear()
+
+    def crater_windows(self, tables, return_windows=False):
+        """sc_crater_windows for the tables of ``WindowedTemplate.crater_tables``: the Crater windows of every (radius,
+        age), radius-major, synthesised into window slots.  Returns (slots, count(W != 0), sum(W * W)) - and, with
+        ``return_windows``, the list of float64 windows as the device made them.  A support box that leaves the grid
+        is a ValueError."""
+        n_r, n_a = len(tables["boxes"]), len(tables["age_tab"])
+        arrs = {k: np.ascontiguousarray(tables[k], dtype=np.float64) for k in ("theta_tab", "dxy", "ring", "age_tab")}
+        n_th = len(arrs["theta_tab"])
+        assert arrs["theta_tab"].shape == (n_th, 3) and arrs["dxy"].shape == (n_r, n_th, 2) \
+            and arrs["ring"].shape == (n_r, 2) and arrs["age_tab"].shape == (n_a, 2)
+        boxes = np.ascontiguousarray(tables["boxes"], dtype=np.int32)
+        assert boxes.shape == (n_r, 4)
+        slots = np.empty(n_r * n_a, dtype=np.intc)
+        count, sumsq = np.empty(n_r * n_a), np.empty(n_r * n_a)
+        sizes = np.repeat((boxes[:, 1] - boxes[:, 0] + 1).astype(np.int64) * (boxes[:, 3] - boxes[:, 2] + 1), n_a)
+        w = np.empty(int(sizes.sum()) if return_windows and (sizes > 0).all() else 0)
+        rc = self.lib.sc_crater_windows(self._h, n_r, n_a, n_th, _as(arrs["theta_tab"], _dp), _as(arrs["dxy"], _dp),
+                                        _as(arrs["ring"], _dp), _as(arrs["age_tab"], _dp), float(tables["d_half"]),
+                                        boxes.ctypes.data_as(C.POINTER(C.c_int32)), slots.ctypes.data_as(C.POINTER(C.c_int)),
+                                        _as(count, _dp), _as(sumsq, _dp), _as(w, _dp) if w.size else None)
+        if rc == SC_ERR_INVALID:
+            msg = self.lib.sc_last_error(self._h)
+            raise ValueError(msg.decode() if msg else "sc_crater_windows: bad argument")
+        self._check(rc, "sc_crater_windows")
+        if not return_windows:
+            return slots, count, sumsq
+        ends = np.cumsum(sizes)
+        shapes = np.repeat(np.stack([boxes[:, 1] - boxes[:, 0] + 1, boxes[:, 3] - boxes[:, 2] + 1], 1), n_a, axis=0)
+        wins = [w[e - n:e].reshape(sh) for e, n, sh in zip(ends, sizes, shapes)]
+        return slots, count, sumsq, wins
 
     # -- hot path -----------------------------------------------------------
     def reset_best(self):

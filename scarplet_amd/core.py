@@ -36,7 +36,7 @@ from scarplet_amd import _lib, _plan
 from scarplet_amd import WindowedTemplate as _WT
 from scarplet_amd.dem import DEMGrid
 
-__all__ = ["match", "match_scales", "match_template", "compare", "load",
+__all__ = ["match", "match_scales", "match_craters", "match_template", "compare", "load",
            "calculate_best_fit_parameters",
            "calculate_best_fit_parameters_serial", "Matcher"]
 
@@ -66,6 +66,14 @@ def _near_window(ctx, w):
 
 # what the passes of an exact search and the longer host routes need of its inputs (Matcher._search_exact)
 _Search = collections.namedtuple("_Search", "Template scale params angles kwargs bbox max_area group")
+
+
+def _refuse_crater(Template):
+    """Crater is not a (scale, age, angle) template: ``match`` & co. cannot construct it (nor can the reference's,
+    core.py:345 against WT.py:545)."""
+    if isinstance(Template, type) and issubclass(Template, _WT.Crater):
+        raise TypeError("Crater(r, kt, nx, ny, de) is not a (scale, age, angle) template and has no orientation to "
+                        "search: use scarplet_amd.match_craters(data, radii, ages) (docs/craters.md)")
 
 
 def _grid_of(data):
@@ -418,6 +426,7 @@ class Matcher(object):
         the float32 result stands, with a warning and exact_stats["skipped"].  ``exact=None``: on for the built-in
         template classes, off for plugins whose windows the host uploads.  Cost: 13 % on the row pass plus the
         pairs."""
+        _refuse_crater(Template)
         params = np.atleast_1d(np.asarray(params, dtype=float))
         angles = np.atleast_1d(np.asarray(angles, dtype=float))
         self._patches = []
@@ -433,6 +442,14 @@ class Matcher(object):
             self._id_par, self._id_ang = np.empty(0), np.empty(0)
         arr, bbox, max_area = self.describe(Template, scale, params, angles,
                                             id_base=len(self._id_par), **kwargs)
+        return self._search_described(arr, _Search(Template, scale, params, angles, kwargs, bbox, max_area, group),
+                                      method, reset, sync, exact)
+
+    def _search_described(self, arr, s, method, reset, sync, exact):
+        """The search of the descriptors ``arr`` of ``s`` (a _Search): plan, match, the exact mode's dispatch, the id
+        tables.  ``s.Template`` is None for descriptors no class can rebuild (search_craters: windows made on the
+        device); ``s.angles`` is then whatever plane 2 of the result holds."""
+        params, angles, bbox, max_area, group = s.params, s.angles, s.bbox, s.max_area, s.group
         self.plan, sp = self.plan_for(bbox, max_area, method, group,
                                       n_params=len(params))
         if reset:
@@ -449,7 +466,7 @@ class Matcher(object):
             if not (reset and sync):
                 raise ValueError("exact=True needs reset=True and sync=True")
             self.exact_stats = {"flagged_cells": 0, "patches": 0, "changed_cells": 0, "float64_cells": 0}
-            self._search_exact(arr, sp, method, _Search(Template, scale, params, angles, kwargs, bbox, max_area, group))
+            self._search_exact(arr, sp, method, s)
         else:
             self.ctx.match(arr, sp, sync=sync)
             self.method_used = "direct" if sp.method == _plan.METHOD_DIRECT else "fft"
@@ -576,7 +593,11 @@ class Matcher(object):
             warnings.warn("exact=True: the near-ties of this block were not settled (%s)" % self.exact_stats.get("settle", "host route off"))
             self.exact_stats["skipped"] = True
             return False
-        if route == "fft":
+        if route == "fft" and s.Template is None:
+            # (windows made on the device: no class to describe them again for the per-patch searches)
+            warnings.warn("exact=True: the near-ties of this search were not settled (%s)" % self.exact_stats.get("settle"))
+            self.exact_stats["skipped"] = True
+        elif route == "fft":
             self._rescore_near_ties(s.Template, s.scale, s.params, s.angles, s.kwargs)
         else:
             last = [tuple(c) for c in np.argwhere(self.ctx.near_ties())]
@@ -979,8 +1000,68 @@ class Matcher(object):
             out.append(np.array(self.result_array()))      # (a copy: large results are views of a recycled host block)
         return out
 
+    def search_craters(self, radii, ages, method="auto", exact=None, host_windows=None):
+        """Fold the Crater template of every (radius, age) into the running best (docs/craters.md).  The windows are
+        synthesised on the device straight into window slots (sc_crater_windows) and searched like any window
+        template, against ONE curvature plane, d2z_dx2 + d2z_dy2 - the Laplacian, not the reference's
+        ``_calculate_laplacian`` (d2z_dx2 alone): a ring has no preferred direction.  Radii stand where the
+        orientations of ``search`` stand: template (age ia, radius ib) has id ``ia * n_radii + ib`` and is folded
+        radius-major; plane 2 of the result is the radius.  ``radii`` are what ``Crater`` takes (r; the ring's radius
+        is r / de in coordinate units, the reference's own mix).  ``exact`` as in ``search`` (None: off, these are
+        window templates).  A radius whose support box leaves the grid is a ValueError.  Drops every window slot of
+        the context first (``clear_windows``) and leaves its own for the float64 scorers: clear them when done.
+        ``host_windows``: float64 windows over the support boxes, radius-major, uploaded instead of synthesised - the
+        route tools/time_craters.py measures the synthesis against."""
+        radii = np.atleast_1d(np.asarray(radii, dtype=float))
+        ages = np.atleast_1d(np.asarray(ages, dtype=float))
+        tables = _WT.crater_tables(radii, ages, self.nx, self.ny, self.de)
+        self._patches = []
+        self._cells64 = None
+        boxes = tables["boxes"]
+        lims = np.array([_WT.crater_limits(b, self.nx, self.ny) for b in boxes])
+        if getattr(self, "nan_dem", False):
+            # every cell a template leaves unmasked turns NaN (_nan_fold): the union of the rectangles
+            nan = np.zeros((self.ny, self.nx), dtype=bool)
+            for ilo, ihi, jlo, jhi in lims:
+                nan[ilo:ihi + 1, jlo:jhi + 1] = True
+            zero = np.zeros((self.ny, self.nx))
+            self._nan_result = np.stack([np.where(nan, np.nan, 0.0), zero, zero.copy(), np.where(nan, np.nan, 0.0)])
+            self.params, self.angles = ages, radii
+            return self
+        self._nan_result = None
+        self._id_par, self._id_ang = np.empty(0), np.empty(0)
+        self.ctx.clear_windows()
+        if host_windows is None:
+            slots, count, sumsq = self.ctx.crater_windows(tables)
+        else:
+            slots = [self.ctx.upload_window(w) for w in host_windows]
+            count = np.array([float(np.count_nonzero(w)) for w in host_windows])
+            sumsq = np.array([float(np.sum(w ** 2)) for w in host_windows])
+        n_r, n_a = len(radii), len(ages)
+        arr = (_lib.sc_template * (n_r * n_a))()
+        for ib in range(n_r):
+            for ia in range(n_a):
+                k = ib * n_a + ia
+                t = arr[k]
+                t.kind, t.flags = _WT.KIND_WINDOW, 0
+                t.cos_a, t.sin_a, t.c, t.d = 1.0, 0.0, 0.0, 0.0
+                t.p0, t.p1 = count[k], sumsq[k]
+                t.cc, t.sc2, t.ss = 1.0, 0.0, 1.0
+                t.ilo, t.ihi, t.jlo, t.jhi = (int(v) for v in lims[ib])
+                t.pmin, t.pmax, t.qmin, t.qmax = (int(v) for v in boxes[ib])
+                t.id = ia * n_r + ib
+                t.window = int(slots[k])
+        bbox = _plan.bbox_union([tuple(int(v) for v in b) for b in boxes])
+        # what the real-space kernel walks of a ring is every row from its first to its last non-zero: the disc, not
+        # the count(W != 0) of the rim - the planner weighs that against the FFT tiles
+        half = 0.5 * (boxes[:, 1] - boxes[:, 0] + 1).max()
+        max_area = int(max(count.max(), np.pi * half * half))
+        return self._search_described(arr, _Search(None, None, ages, radii, {}, bbox, max_area, None), method, True, True,
+                                      exact)
+
     def match_template(self, Template, scale, age, angle, method="auto",
                        **kwargs):
+        _refuse_crater(Template)
         if getattr(self, "nan_dem", False):
             return self._nan_maps(Template(scale, age, angle, self.nx, self.ny, self.de, **kwargs))
         arr, bbox, max_area = self.describe(Template, scale, [age], [angle],
@@ -1005,6 +1086,7 @@ def match_template(data, Template, scale, age, angle, **kwargs):
 
     Returns ``(amp, age, angle, snr)`` with ``age`` and ``angle`` the scalar
     inputs, like the reference."""
+    _refuse_crater(Template)
     opts = {k: kwargs.pop(k) for k in ("device", "method") if k in kwargs}
     m = Matcher(data, device=opts.get("device", 0))
     try:
@@ -1022,6 +1104,7 @@ def calculate_best_fit_parameters(dem, Template, scale, age,
     one-degree orientation grid (core.py:139-195).  Returns a (4, ny, nx)
     array: amp, age, angle, snr.  Like the reference, extra keyword arguments
     are accepted but not forwarded to the template (core.py:145, 182)."""
+    _refuse_crater(Template)
     device = kwargs.pop("device", 0)
     method = kwargs.pop("method", "auto")
     exact = kwargs.pop("exact", None)
@@ -1043,6 +1126,7 @@ def calculate_best_fit_parameters_serial(dem, Template, scale,
     cell the float64 reference's (age, orientation) for any template class,
     the Shifted classes and user plugins included (Matcher.search); the
     default (None) settles the built-in classes only."""
+    _refuse_crater(Template)
     device = kwargs.pop("device", 0)
     method = kwargs.pop("method", "auto")
     exact = kwargs.pop("exact", None)
@@ -1091,6 +1175,7 @@ def match(data, Template, **kwargs):
     the record (core.py:230-240) - on float32 maps, so where the float64
     reference saw no tie this may see one.  One device pass and two 8-byte-per-
     cell transfers per template: for small DEMs and for inspecting ties."""
+    _refuse_crater(Template)
     fold = kwargs.pop("fold", "fused")
     if fold not in ("fused", "reference"):
         raise ValueError("fold must be 'fused' or 'reference'")
@@ -1130,11 +1215,32 @@ def match(data, Template, **kwargs):
         m.ctx.clear_windows()
 
 
+def match_craters(data, radii, ages=None, method="auto", exact=None, device=0):
+    """Search a DEM for crater rims (docs/craters.md): the reference's ``Crater`` template (WindowedTemplate.py:
+    528-605) for every radius of ``radii`` (as ``Crater`` takes it) and every age of ``ages`` (default: the reference's
+    grid 10**arange(0, 3.5, 0.1)), synthesised on the device and matched against the Laplacian
+    d2z_dx2 + d2z_dy2 of the DEM.  Returns a (4, ny, nx) array: amplitude, age, RADIUS, SNR of the best template at
+    every cell.  A template is masked at the cells where its support box does not fit the grid; cells every template
+    masks are zero in all four planes.  ``method`` and ``exact`` as in ``match``
+    (``exact=None``: the float32 search as it is).  A radius too large for the grid is a ValueError; a DEM with NaN
+    cells is answered as ``match`` answers it."""
+    z, dx, _ = _grid_of(data)
+    ages = _plan.age_grid() if ages is None else ages
+    _WT.crater_tables(radii, ages, z.shape[1], z.shape[0], dx)       # (refused before a device is asked for)
+    m = Matcher(data, device=device)
+    try:
+        m.search_craters(radii, ages, method=method, exact=exact)
+        return np.array(m.result_array())
+    finally:
+        m.ctx.clear_windows()
+
+
 def match_scales(data, Template, scales, **kwargs):
     """``match`` for several scales of one template family on one DEM (the reference: one sl.match call per scale,
     channels.ipynb): the DEM goes to the device once, the orientations' curvature spectra are computed once.  Keyword
     arguments as ``match`` (``age=`` or the 35-age grid, ``ang_min`` / ``ang_max``, ``method``, ``exact``, ``device``).
     Returns a list with one (4, ny, nx) array per scale - the planes of ``match``: amp, age, angle, snr."""
+    _refuse_crater(Template)
     device = kwargs.pop("device", 0)
     method = kwargs.pop("method", "auto")
     exact = kwargs.pop("exact", None)

@@ -199,13 +199,17 @@ extern "C" int sc_clear_windows(sc_ctx* ctx) {
     if (!ctx) return SC_ERR_INVALID;
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& w : ctx->windows) {
-        if (w.w) (void)hipFree(w.w);
-        if (w.w64) (void)hipFree(w.w64);
-        if (w.m) (void)hipFree(w.m);
+        if (!w.pooled) {
+            if (w.w) (void)hipFree(w.w);
+            if (w.w64) (void)hipFree(w.w64);
+            if (w.m) (void)hipFree(w.m);
+        }
         if (w.mask_lim) (void)hipFree(w.mask_lim);
         if (w.mask_err) (void)hipFree(w.mask_err);
     }
     ctx->windows.clear();
+    for (void* p : ctx->window_pools) (void)hipFree(p);
+    ctx->window_pools.clear();
     return SC_OK;
 }
 

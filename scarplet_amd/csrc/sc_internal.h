@@ -58,6 +58,7 @@ struct WindowSlot {
     int h = 0, wd = 0;
     uint8_t* mask_lim = nullptr;
     uint8_t* mask_err = nullptr;
+    bool pooled = false;       // w, w64 and m lie in one of the context's window_pools (sc_crater_windows), not in allocations of their own
 };
 
 #include "sc_fft_route.h"         // SC_MAX_GROUP, SC_MAX_BATCH, SC_MAX_ORIENT; the FFT path's choice of kernels
@@ -109,6 +110,7 @@ struct sc_ctx {
     DevBuf cblk;
     int curv_rows = 0;         // planes of cblk that hold the current orientations' row spectra and are not in uc / uc2 (0: uc / uc2 hold them)
     std::vector<WindowSlot> windows;
+    std::vector<void*> window_pools;   // sc_crater_windows: one allocation per call behind all its slots; freed by sc_clear_windows
     // host copies of what a search uploads asynchronously (descriptors, sums, tile list): they must outlive
     // the copy, so they live here - no stream synchronisation between the upload and the launches
     std::vector<TemplDev> h_templ;
