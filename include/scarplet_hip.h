@@ -631,6 +631,58 @@ int sc_bootstrap_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, cons
                               int min_blocks, int R, double level, uint64_t seed, sc_segment_boot* out_rows,
                               int32_t* out_hist, int8_t* out_index, double* out_a);
 
+/*
+ * Joint scarp fits in windows along the strike (docs/strike.md): the offset 2 a and the age kt as functions of the
+ * position along a segment.  The cells of a segment arrive sorted along its strike; a window is a contiguous range
+ * [win_lo, win_hi) of them (cell indices into `cells`), cut on the host - the library never compares floats to cut a
+ * window.  Window g of segment s (seg_win_start[s] <= g < seg_win_start[s + 1]) is station g - seg_win_start[s].  The
+ * model is sc_fit_segments' on the window's usable profiles: a and kt shared, an intercept and a slope per profile.
+ *   stage one   the sampling and parking of sc_fit_segments (D = 0) or sc_fit_segments_shift (D > 0): See_ci, Sep_ci of
+ *               every usable profile and age, at d_ci with a shift - the shifts are stage one's, not re-fitted per window
+ *   Spp_c       per usable profile, the sum over its valid points in ascending order of the squared residuals about its
+ *               own line b = beta, c0 = pbar - beta sbar: the residual sum of sc_fit_profiles with a = 0
+ *   sums        SSee_i, SSep_i, SSpp and the integer n over the window's usable profiles in hand-over order: runs of 64
+ *               consecutive ones summed in sequence from the window's first, then the run sums in sequence from the first.
+ *               One profile is no addition at all
+ *   fit         n_profiles usable profiles, dof = n - 2 n_profiles - 1 - (D > 0 ? n_profiles : 0).  Not fitted (status 1,
+ *               indices -1, NaN floats, a NaN curve): n_profiles < min_profiles, dof < 1, SSee_i 0 or not finite at any
+ *               age, or no age with a number for Q.  Else Q_i = SSep_i^2 / SSee_i, kt_index = argmax_i Q_i (ties to the
+ *               smallest index; a NaN never wins), a = SSep / SSee there; sse_i = max(SSpp - Q_i, 0), sse that of
+ *               kt_index, rmse = sqrt(sse / dof); lo_index and hi_index: the run of ages around kt_index with
+ *               sse_i <= sse (1 + delta / dof).  Status 2 and 4 as sc_fit_profiles; 8: a usable profile of the window has
+ *               |d_ci| == D at the best age, D > 0
+ * SSpp - Q_i cancels where the scarp explains almost all of the profiles' energy: the error of sse_i is a few ulps of
+ * SSpp, not of sse_i (kt_index and a have no subtraction).  sc_fit_segments' explicit residuals remain the route for a
+ * single pooled fit.  An empty window (win_lo == win_hi) is allowed: n_cells 0, status 1.  out_rows: NW rows; out_sse:
+ * NW x A (sse_i) or NULL.  Refused before any device work: what sc_fit_segments_shift refuses, CSR arrays or ranges
+ * that do not fit together (seg_start[s] <= win_lo <= win_hi <= seg_start[s + 1]), NW > 2^31 - 1.  No float atomics,
+ * every sum in a fixed order: the same bytes on every run.  Timed as SC_K_PROFILE.
+ */
+typedef struct sc_strike_fit {
+    int32_t  label;
+    int32_t  station;         /* the window's number within its segment          */
+    int32_t  n_cells;         /* cells of the window                             */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n;               /* their valid points, pooled                      */
+    int32_t  dof;
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) + 8 (a shift at its limit) */
+    double   kt, kt_lo, kt_hi;
+    double   a;               /* the window's amplitude: its offset is 2 a       */
+    double   sse, rmse;       /* rmse = sqrt(sse / dof)                          */
+} sc_strike_fit;
+int sc_fit_strike(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                  const long long* seg_start, const int32_t* seg_label, long long S, const long long* seg_win_start,
+                  const long long* win_lo, const long long* win_hi, long long NW, const double* ages, int A, int h, int w,
+                  int D, double de, double delta, int min_samples, int min_profiles, sc_strike_fit* out_rows,
+                  double* out_sse);
+int sc_fit_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                      const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                      const long long* seg_win_start, const long long* win_lo, const long long* win_hi, long long NW,
+                      const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
+                      int min_profiles, sc_strike_fit* out_rows, double* out_sse);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -760,7 +812,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*: the table and every kernel of every chunk */
+#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

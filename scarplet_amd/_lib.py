@@ -163,6 +163,21 @@ SEGMENT_BOOT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_boot._fields_]
 BOOT_MAX_REPLICATES = 4096                                             # SC_BOOT_MAX_REPLICATES
 
 
+class sc_strike_fit(C.Structure):
+    """One row of sc_fit_strike / sc_fit_strike_dem (docs/strike.md)."""
+    _fields_ = [("label", C.c_int32), ("station", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32),
+                ("n", C.c_int32), ("dof", C.c_int32), ("kt_index", C.c_int32), ("lo_index", C.c_int32),
+                ("hi_index", C.c_int32), ("status", C.c_int32),
+                ("kt", C.c_double), ("kt_lo", C.c_double), ("kt_hi", C.c_double),
+                ("a", C.c_double), ("sse", C.c_double), ("rmse", C.c_double)]
+
+
+STRIKE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_strike_fit._fields_],
+                             "formats": [np.int32] * 10 + [np.float64] * 6,
+                             "offsets": [getattr(sc_strike_fit, f).offset for f, _ in sc_strike_fit._fields_],
+                             "itemsize": C.sizeof(sc_strike_fit)})
+
+
 class sc_xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("kind", C.c_int32),
                 ("sy0", C.c_int32), ("sx0", C.c_int32),
@@ -263,6 +278,14 @@ SIGNATURES = {
                                             C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_strike": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
+    "sc_fit_strike_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                    C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
+                                    C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -689,6 +712,33 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, hg, idx, amp
+
+    # -- joint fits in windows along the strike (docs/strike.md) -------------------------
+    def fit_strike(self, cells, sa, ca, seg_start, seg_label, seg_win_start, win_lo, win_hi, ages, h, w, D, de, delta,
+                   min_samples, min_profiles, curve=False, z=None):
+        """sc_fit_strike on the context's DEM, or sc_fit_strike_dem on ``z`` (float64, C-contiguous, 2-D): (rows, (NW, A)
+        float64 curves or None).  cells, seg_start, seg_win_start, win_lo and win_hi int64, seg_label int32, sa / ca /
+        ages float64, all 1-D and C-contiguous; the cells grouped by segment and sorted along its strike."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32), (seg_win_start, np.int64), (win_lo, np.int64), (win_hi, np.int64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S, NW = len(cells), len(ages), len(seg_label), len(win_lo)
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1 and len(seg_win_start) == S + 1 and len(win_hi) == NW
+        rows = np.zeros(NW, dtype=STRIKE_FIT_DTYPE)
+        sse = np.empty((NW, A), dtype=np.float64) if curve else None
+        llp = C.POINTER(C.c_longlong)
+        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, seg_win_start.ctypes.data_as(llp),
+                win_lo.ctypes.data_as(llp), win_hi.ctypes.data_as(llp), NW, _as(ages, _dp), A, int(h), int(w), int(D),
+                float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+                _as(sse, _dp) if curve else None]
+        name = "sc_fit_strike"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, sse
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

@@ -1,5 +1,5 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
-// included by sc_profile.hip and sc_segment.hip alone - and by sc_bootstrap.hip for the host side of stage one.  The
+// included by sc_profile.hip and sc_segment.hip alone - and by sc_bootstrap.hip and sc_strike.hip for stage one.  The
 // library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
 // in the order of its text wherever it is called: the four calls return the same bits in every field they share because
 // they call the same helpers.
@@ -26,7 +26,7 @@ int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx);
 // the launch of the erf table over j = -h..h (d_ages on the device; timed as SC_K_PROFILE)
 int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
 
-// ---- sc_segment.hip, shared with sc_bootstrap.hip ----------------------------------------------------------------------------
+// ---- sc_segment.hip, shared with sc_bootstrap.hip and sc_strike.hip ----------------------------------------------------------------------------
 // the argument checks of a segment call (D < 0: the call without a shift) and the cells of one segment its park holds
 int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
                 const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
@@ -51,6 +51,11 @@ int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, c
                         const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st);
 int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
                        const double* d_tab, const sg_stage& st, int& launches);
+
+// the degrees of freedom of a segment - or of a window of one, sc_strike.hip - of m usable profiles and n pooled points
+// (D = 0 in the call without a shift), and whether it is fitted
+__device__ __forceinline__ int sg_dof(int m, int n, int D) { return n - 2 * m - 1 - (D > 0 ? m : 0); }
+__device__ __forceinline__ bool sg_fitted(int m, int dof, int min_profiles) { return m >= min_profiles && dof >= 1; }
 
 // ---- the centre shift (docs/profiles.md, "The centre shift") --------------------------------------------------------------
 // candidates in the order 0, -1, +1, -2, +2, ...: rank r -> shift d
@@ -253,6 +258,19 @@ __device__ __forceinline__ double pf_sse(const double* prof, int np, int h, doub
 // sse_min (1 + delta / dof), and the interval walked from the best age while sse <= thr.  The same in every lane.
 struct pf_pick { int best, lo, hi; double sse_min; };
 
+// the walk alone, from a best age found elsewhere (sc_strike.hip: the argmax of Q_i) with sse_best its sse
+__device__ __forceinline__ pf_pick pf_walk(double sse, int lane, int A, int best, double sse_best, double delta, int dof) {
+    pf_pick k;
+    k.sse_min = sse_best;
+    k.best = best;
+    const double thr = sse_best * (1.0 + delta / (double)dof);
+    const unsigned long long ok = __ballot(lane < A && sse <= thr);
+    k.lo = k.hi = k.best;
+    while (k.lo > 0 && ((ok >> (k.lo - 1)) & 1ull)) --k.lo;
+    while (k.hi < A - 1 && ((ok >> (k.hi + 1)) & 1ull)) ++k.hi;
+    return k;
+}
+
 __device__ __forceinline__ pf_pick pf_choose(double sse, int lane, int A, double delta, int dof) {
     double m = lane < A ? sse : INFINITY;
     if (m != m) m = INFINITY;
@@ -263,15 +281,7 @@ __device__ __forceinline__ pf_pick pf_choose(double sse, int lane, int A, double
         const int oi = __shfl_xor(mi, o, 64);
         if (om < m || (om == m && oi < mi)) { m = om; mi = oi; }
     }
-    pf_pick k;
-    k.sse_min = m;
-    k.best = min(mi, A - 1);
-    const double thr = m * (1.0 + delta / (double)dof);
-    const unsigned long long ok = __ballot(lane < A && sse <= thr);
-    k.lo = k.hi = k.best;
-    while (k.lo > 0 && ((ok >> (k.lo - 1)) & 1ull)) --k.lo;
-    while (k.hi < A - 1 && ((ok >> (k.hi + 1)) & 1ull)) ++k.hi;
-    return k;
+    return pf_walk(sse, lane, A, min(mi, A - 1), m, delta, dof);
 }
 
 // status bits 2 and 4: the interval is open below, above

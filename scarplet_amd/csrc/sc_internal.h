@@ -193,6 +193,9 @@ struct sc_ctx {
     // segments over blocks, the block terms (See, Sep per block and age), every replicate's index and amplitude, the
     // histograms and the rows
     DevBuf bs_blk, bs_sblk, bs_terms, bs_index, bs_a, bs_hist, bs_rows;
+    // sc_fit_strike*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR array of
+    // segments over windows, Spp of every cell, the rows and the curves
+    DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);

@@ -218,11 +218,6 @@ __global__ __launch_bounds__(64) void k_sg_sum2(const double* __restrict__ part,
     }
 }
 
-// the degrees of freedom of a segment of m usable profiles and n pooled points (D = 0 in the call without a shift), and
-// whether it is fitted
-__device__ __forceinline__ int sg_dof(int m, int n, int D) { return n - 2 * m - 1 - (D > 0 ? m : 0); }
-__device__ __forceinline__ bool sg_fitted(int m, int dof, int min_profiles) { return m >= min_profiles && dof >= 1; }
-
 // the explicit residuals of every usable cell of a fitted segment, with the segment's a_i: sse_ci replaces See_ci.  The
 // table covers j = -(h + D)..(h + D) and the cell's column at age i is its row j - d_ci; shifts null: d_ci = 0
 template <bool TAB_LDS>

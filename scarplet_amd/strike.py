@@ -1,0 +1,131 @@
+"""Joint scarp fits in windows along the strike of a trace segment, on the device (docs/strike.md).
+
+``fit_segments`` gives a whole segment one age and one offset; ``fit_along_strike`` gives both as functions of the
+position along the trace: at stations spaced ``step`` apart along every segment's strike, the amplitude and the age are
+fitted jointly to the profiles of the cells within ``window / 2`` of the station, by the model of ``fit_segments``
+(sc_fit_strike, include/scarplet_hip.h).  The windows are cut here, in float64 numpy, and handed over as integer ranges.
+"""
+import numpy as np
+
+from scarplet_amd import _lib, bootstrap, profiles, segments
+
+FIT_FIELDS = [(f, _lib.STRIKE_FIT_DTYPE.fields[f][0]) for f in _lib.STRIKE_FIT_DTYPE.names] + \
+    [("height", np.float64), ("t", np.float64), ("row", np.float64), ("col", np.float64)]
+FIT_DTYPE = np.dtype(FIT_FIELDS)
+
+
+def windows_of(cells, nx, de, strike, seg_start, window, step):
+    """The hand-over order, the stations and the windows of ``cells`` grouped by segment (CSR ``seg_start``), ``strike``
+    one per segment.  The along-strike coordinate is ``t = de (row cos a_s + col sin a_s)`` (``bootstrap.blocks_of``'s);
+    the cells of a segment are sorted by (t, position), stable.  Per segment ``span = t_max - t_min``, ``ns =
+    floor(span / step) + 1`` stations centred on the segment, ``u_k = t_min + (span - (ns - 1) step) / 2 + k step``;
+    the window of a station is the range ``[searchsorted(t, u_k - window / 2, "left"), searchsorted(t, u_k + window / 2,
+    "right"))`` of the segment's sorted cells, as indices into the sorted cells.  All in float64.  Returns (by, t,
+    seg_win_start, win_lo, win_hi, centre): ``by`` the permutation that sorts the cells, ``t`` sorted, the others int64
+    and float64, one per window."""
+    cells = np.asarray(cells, dtype=np.int64)
+    seg_start = np.asarray(seg_start, dtype=np.int64)
+    n = np.diff(seg_start)
+    S = len(n)
+    a = np.repeat(np.asarray(strike, dtype=np.float64), n)
+    t = de * ((cells // nx).astype(np.float64) * np.cos(a) + (cells % nx).astype(np.float64) * np.sin(a))
+    seg = np.repeat(np.arange(S), n)
+    by = np.lexsort((t, seg))                                          # (stable: input order is kept among equal t)
+    t = t[by]
+    seg_win_start = np.zeros(S + 1, dtype=np.int64)
+    lo, hi, centre = [], [], []
+    half = window / 2
+    for s in range(S):
+        k0, k1 = int(seg_start[s]), int(seg_start[s + 1])
+        if k1 > k0:
+            ts = t[k0:k1]
+            tmin = ts[0]
+            span = ts[-1] - tmin
+            ns = int(np.floor(span / step)) + 1
+            u = tmin + (span - (ns - 1) * step) / 2 + np.arange(ns, dtype=np.float64) * step
+            lo.append(k0 + np.searchsorted(ts, u - half, "left"))
+            hi.append(k0 + np.searchsorted(ts, u + half, "right"))
+            centre.append(u)
+            seg_win_start[s + 1] = seg_win_start[s] + ns
+        else:
+            seg_win_start[s + 1] = seg_win_start[s]
+    cat = lambda v, dt: np.ascontiguousarray(np.concatenate(v), dtype=dt) if v else np.zeros(0, dtype=dt)
+    return by, t, seg_win_start, cat(lo, np.int64), cat(hi, np.int64), cat(centre, np.float64)
+
+
+def check_args(shape, de, cells, labels, angle, half_length, swath, window, step, ages, delta, min_samples, min_profiles,
+               max_shift):
+    """What the library takes, validated and normalised; ValueError otherwise.  The arguments shared with
+    ``fit_segments`` go through ``segments.check_args`` and ``profiles.check_shift``.  ``window`` is required, in data
+    units, finite and at least the cell size; ``step`` defaults to ``window / 2`` and must be finite with ``de <= step
+    <= window``, so that no cell falls between two windows.  The cells are then sorted by (label, t, input position)
+    and the windows cut (``windows_of``) along the axial mean of each segment's angles.  Returns (cells, sa, ca, seg_start,
+    seg_label, seg_win_start, win_lo, win_hi, ages, h, w, D, de, delta, min_samples, min_profiles) and (centre, row,
+    col): each window's ``u_k`` and the means of its cells' rows and columns (NaN for an empty window)."""
+    # (the park is checked as sc_fit_segments_shift counts it)
+    idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = segments.check_args(
+        shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=True)
+    D = profiles.check_shift(max_shift, False, de, h, ms)
+    D = 0 if D is None else D
+    if window is None:
+        raise ValueError("window is required: the length of a window along the strike, in data units")
+    win = profiles._number(window, "window")
+    if win < de:
+        raise ValueError("window must be at least the cell size %r, got %r" % (de, window))
+    stp = win / 2 if step is None else profiles._number(step, "step")
+    if not de <= stp <= win:
+        raise ValueError("step must lie between the cell size %r and the window %r, got %r%s"
+                         % (de, win, stp, " (window / 2: pass a step)" if step is None else ""))
+    ny, nx = (int(v) for v in shape)
+    pick = kept[order]
+    a = profiles._angles_of(angle, profiles._cells_of(cells, ny, nx), ny, nx)[pick]
+    strike = bootstrap.segment_strikes(a, seg_start)
+    by, _, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, win, stp)
+    idx, sa, ca = idx[by], sa[by], ca[by]
+    if len(centre) > 2 ** 31 - 1:
+        raise ValueError("%d windows: more than 2^31 - 1" % len(centre))
+    # the means of the rows and columns of a window's cells: integer sums, one float64 division
+    cr = np.concatenate([[0], np.cumsum(idx // nx)])
+    cc = np.concatenate([[0], np.cumsum(idx % nx)])
+    cnt = (win_hi - win_lo).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        row = np.where(cnt > 0, (cr[win_hi] - cr[win_lo]) / cnt, np.nan)
+        col = np.where(cnt > 0, (cc[win_hi] - cc[win_lo]) / cnt, np.nan)
+    return ((np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, seg_label,
+             seg_win_start, win_lo, win_hi, kt, h, w, D, de, d, ms, mp), (centre, row, col))
+
+
+def fit_along_strike(data, cells, labels, angle, half_length, swath=0, window=None, step=None, ages=None, delta=1.0,
+                     min_samples=4, min_profiles=1, max_shift=None, return_curve=False, device=0):
+    """The offset and the age of every segment as functions of the position along its strike (docs/strike.md).
+
+    ``data``, ``cells``, ``labels``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta``, ``min_samples``,
+    ``min_profiles`` and ``max_shift`` are those of ``sl.fit_segments``.  Along the strike of each segment (the axial
+    mean of its cells' angles; a cell lies at ``t = de (row cos a_s + col sin a_s)``) stations are placed ``step`` apart,
+    centred on the segment; at each the shared amplitude and age are fitted jointly to the profiles of the cells with
+    ``|t - u_k| <= window / 2``, every profile keeping an intercept and a slope of its own.  ``window`` is required, in
+    data units, at least the cell size; ``step`` defaults to ``window / 2`` and must lie between the cell size and the
+    window.  With ``max_shift`` every profile keeps the shifts it takes on its own: they are not re-fitted per window.
+    A window with fewer than ``min_profiles`` usable profiles or less than one degree of freedom is not fitted
+    (``status`` 1, indices -1, NaN floats).
+
+    Returns a structured array, one row per (label, station), sorted by both: ``label, station, n_cells, n_profiles, n,
+    dof, kt_index, lo_index, hi_index, status, kt, kt_lo, kt_hi, a, sse, rmse, height`` (= 2 a), ``t`` (the station's
+    along-strike coordinate ``u_k``), ``row, col`` (the float64 means of the rows and columns of the window's cells; NaN
+    for an empty window).  ``return_curve`` adds the (NW, A) sse curves.  The same bytes on every run."""
+    z, de = profiles._dem_of(data)
+    args, where = check_args(z.shape, de, cells, labels, angle, half_length, swath, window, step, ages, delta,
+                             min_samples, min_profiles, max_shift)
+    z = np.ascontiguousarray(z, dtype=np.float64)
+    from scarplet_amd.core import _context
+    return _run(_context(device), args, where, return_curve, z=z)
+
+
+def _run(ctx, args, where, return_curve, z=None):
+    rows, curve = ctx.fit_strike(*args, curve=bool(return_curve), z=z)
+    out = np.zeros(len(rows), dtype=FIT_DTYPE)
+    for f in rows.dtype.names:
+        out[f] = rows[f]
+    out["height"] = 2.0 * rows["a"]
+    out["t"], out["row"], out["col"] = where
+    return (out, curve) if return_curve else out
