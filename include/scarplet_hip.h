@@ -683,6 +683,35 @@ int sc_fit_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long l
                       const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
                       int min_profiles, sc_strike_fit* out_rows, double* out_sse);
 
+/*
+ * The search's float64 SNR surface at chosen cells (docs/surface.md, scarplet_amd/csrc/sc_surface.hip).
+ *   t        n_par * n_ang descriptors, orientation-major (template of parameter ia and orientation ib at ib * n_par + ia:
+ *            what Matcher.describe makes).  They become the context's template table as in sc_settle_pairs: nothing is
+ *            matched, the running-best record, its patches and the near-tie lists stay as they are; the float64 scorers'
+ *            "last search" (sc_score_cells_f64) afterwards is this table.
+ *   cells    K (row, col) pairs, global; repeats allowed; rows and cubes come back in this order
+ *   keep     1 - drop, in (0, 1]: the intervals and n_within hold the templates scoring >= snr * keep (one multiply)
+ *   rows     K rows (host)
+ *   snr, amp K * n_ang * n_par float64 each (host), the cell's scores in the order of t; either may be NULL
+ * S[k][t] and Amp[k][t] are match_template() (core.py:297-377) in float64 as the real-space closed form (sc_score_cells_f64's
+ * arithmetic; n and sum(W**2) summed in a fixed order).  A NaN score counts as -inf.  The first maximum of S[k] gives
+ * par_index, ang_index, snr, amp; par_lo .. par_hi is the run of parameters around par_index whose best score over the
+ * orientations stays >= snr * keep, ang_lo .. ang_hi likewise (it does not wrap); n_within counts the templates >= snr * keep.
+ * status: 1 no score > 0 (the cell lies outside every template's window limits: indices -1, n_within 0, snr and amp NaN);
+ * else the sum of 2 (par_lo == 0), 4 (par_hi == n_par - 1), 8 (ang_lo == 0), 16 (ang_hi == n_ang - 1).
+ * SC_ERR_INVALID / SC_ERR_UNSUPPORTED: an empty grid, more than 65535 templates, more than 2^31 - 1 cells, a cell outside
+ * the DEM, keep outside (0, 1], a DEM with NaN cells, a context that holds a block of a larger DEM, a table that is not
+ * orientation-major.  The cells go through in chunks whose two score cubes take at most 256 MiB of device memory.  Timed
+ * under SC_K_SETTLE.  The same bytes on every run.
+ */
+typedef struct sc_surface_row {
+    int32_t par_index, ang_index, par_lo, par_hi, ang_lo, ang_hi, n_within, status;
+    double snr, amp;
+} sc_surface_row;
+int sc_snr_surface(sc_ctx* ctx, const sc_template* t, int n_par, int n_ang, const int32_t* cells /* K (row, col) pairs */,
+                   long long K, double keep, sc_surface_row* rows, double* snr /* K * n_ang * n_par, or NULL */,
+                   double* amp /* or NULL */);
+
 /* Float32 resolution of the FFT path on THIS surface, measured by the searches since the last
  * sc_reset_best: *wins = cells a template of the FFT path won, *near_floor = those whose residual
  * T3 - T1 (what the SNR divides by, core.py:362-366) lies within 256 x the transforms' float32
@@ -809,7 +838,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_FWD_COLS    4
 #define SC_K_INV_COLS    5
 #define SC_K_INV_ROWS    6
-#define SC_K_SETTLE      7      /* sc_settle_exact: all its kernels as one bracket */
+#define SC_K_SETTLE      7      /* sc_settle_exact, sc_snr_surface: all their kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
 #define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk */

@@ -178,6 +178,21 @@ STRIKE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_strike_fit._fields_],
                              "itemsize": C.sizeof(sc_strike_fit)})
 
 
+class sc_surface_row(C.Structure):
+    """One row of sc_snr_surface (docs/surface.md)."""
+    _fields_ = [("par_index", C.c_int32), ("ang_index", C.c_int32), ("par_lo", C.c_int32), ("par_hi", C.c_int32),
+                ("ang_lo", C.c_int32), ("ang_hi", C.c_int32), ("n_within", C.c_int32), ("status", C.c_int32),
+                ("snr", C.c_double), ("amp", C.c_double)]
+
+
+SURFACE_ROW_DTYPE = np.dtype({"names": [f for f, _ in sc_surface_row._fields_],
+                              "formats": [np.int32] * 8 + [np.float64] * 2,
+                              "offsets": [getattr(sc_surface_row, f).offset for f, _ in sc_surface_row._fields_],
+                              "itemsize": C.sizeof(sc_surface_row)})
+SURFACE_MAX_TEMPLATES = 65535                                          # (sc_snr_surface refuses more)
+SURFACE_CELL_BATCH = 8                                                 # SF_CB of sc_surface.hip: cells per workgroup of k_sf_score
+
+
 class sc_xfer(C.Structure):
     _fields_ = [("peer", C.c_int32), ("kind", C.c_int32),
                 ("sy0", C.c_int32), ("sx0", C.c_int32),
@@ -286,6 +301,8 @@ SIGNATURES = {
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
+    "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
+                                 C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "sc_get_template_sums": (C.c_int, [_P, C.c_int, _dp, _dp]),
     "sc_profile": (C.c_int, [_P, C.c_int]),
@@ -739,6 +756,23 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, sse
+
+    # -- the SNR surface at chosen cells (docs/surface.md) ---------------------------------
+    def snr_surface(self, templates, n_par, n_ang, cells, keep, surface=False):
+        """sc_snr_surface on the context's DEM: (rows, snr, amp).  ``templates``: the n_par * n_ang descriptors of
+        Matcher.describe (orientation-major); ``cells``: (K, 2) int32 (row, col); ``keep`` = 1 - drop.  With ``surface`` the
+        two (K, n_ang, n_par) float64 cubes, else None.  The record stays; the scorers' last search is this table after."""
+        cells = np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 2)
+        K = len(cells)
+        assert len(templates) == int(n_par) * int(n_ang)
+        rows = np.zeros(K, dtype=SURFACE_ROW_DTYPE)
+        snr = np.empty((K, int(n_ang), int(n_par)), dtype=np.float64) if surface else None
+        amp = np.empty((K, int(n_ang), int(n_par)), dtype=np.float64) if surface else None
+        self._check(self.lib.sc_snr_surface(self._h, templates, int(n_par), int(n_ang), cells.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            K, float(keep), rows.ctypes.data_as(C.c_void_p),
+                                            _as(snr, _dp) if surface else None, _as(amp, _dp) if surface else None),
+                    "sc_snr_surface")
+        return rows, snr, amp
 
     # -- measurement ----------------------------------------------------------
     def profile(self, stride):

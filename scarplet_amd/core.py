@@ -922,6 +922,19 @@ class Matcher(object):
         D = profiles.check_shift(max_shift, return_shift, args[6], args[4], args[8])
         return profiles._run(self.ctx, args, self.nx, return_curve, label=label, shift=D, return_shift=return_shift)
 
+    def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
+        """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
+        every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within
+        ``drop`` of it.  Given the ``Traces`` of ``extract_traces`` it takes the cells of the segments (``labels > 0``,
+        row-major order) and adds a ``label`` column; else cells as ``sl.snr_surface`` takes them.  The record of this
+        matcher's search stays as it is (``result_array()`` returns the same bytes before and after); the float64
+        scorers' "last search" (``ctx.score_cells_f64``) afterwards is the surface's template table, with its own
+        ``n`` and ``sum(W**2)``.  A plugin's uploaded windows stay in the context's window slots, as after ``search``
+        (the scorers read them): ``ctx.clear_windows()`` releases them.  The bytes are those of ``sl.snr_surface`` on
+        the same data."""
+        from scarplet_amd import surface
+        return surface.run(self, Template, scale, params, angles, traces_or_cells, drop, return_surface, kwargs)
+
     def fit_segments(self, traces, half_length, swath=0, ages=None, delta=1.0, min_samples=4, min_profiles=1,
                      return_cells=False, return_curve=False, strike="cell", max_shift=None, return_shift=False):
         """``sl.fit_segments`` on the DEM this matcher holds on the device (docs/segments.md) - no upload: one age,

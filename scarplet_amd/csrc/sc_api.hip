@@ -52,7 +52,8 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,
-                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse};
+                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse,
+                     &c->sf_work, &c->sf_cells, &c->sf_cube, &c->sf_rows};
     size_t s = 0;
     for (DevBuf* b : arr) s += b->cap;
     for (auto& w : c->windows) s += (size_t)w.h * w.wd * 13;
@@ -236,7 +237,8 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,
-                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse};
+                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse,
+                     &c->sf_work, &c->sf_cells, &c->sf_cube, &c->sf_rows};
     for (DevBuf* b : arr) buf_free(*b);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp[k]);
     for (int k = 0; k < 4; ++k) buf_free(c->cmp_in[k]);

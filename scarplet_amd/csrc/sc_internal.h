@@ -196,6 +196,11 @@ struct sc_ctx {
     // sc_fit_strike*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR array of
     // segments over windows, Spp of every cell, the rows and the curves
     DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
+    // sc_window_runs: the host's copy of the run table's offsets (uploaded asynchronously)
+    std::vector<unsigned> h_soff;
+    // sc_snr_surface: the call's tables (sums, run offsets, union runs), and per chunk of cells the cell list, the two
+    // score cubes (and the reduction's P / Q where they do not fit LDS) and the rows
+    DevBuf sf_work, sf_cells, sf_cube, sf_rows;
 };
 
 int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...);
@@ -224,6 +229,10 @@ int sc_launch_result(sc_ctx* ctx, const float* amp, const float* snr, const uint
 // the descriptors of a search as the device's template table (TemplDev), without matching them: sc_settle_pairs
 int sc_load_templates(sc_ctx* ctx, const sc_template* t, int n);
 int sc_near_buffers(sc_ctx* ctx, unsigned long long** ev_count, uint32_t** ev, unsigned long long* ev_cap);
+// sc_settle.hip: n = count(W != 0) and sum(W**2) of the table's n templates in a fixed order (k_st_sums) and the runs of their
+// window rows (k_st_spans, into ctx->st_spans) from score_prepare_f64's windows; sums (2 n doubles), soff (n + 1 words:
+// first entry of a template's rows in the run table) and maxlen (n ints: its longest run) are the caller's device buffers
+int sc_window_runs(sc_ctx* ctx, int n, const unsigned long long* woff, const double* wbuf, double* sums, unsigned* soff, int* maxlen);
 // sc_settle.hip: the patches of sc_settle_exact over four converted float64 planes of nc cells each
 int sc_apply_patches(sc_ctx* ctx, const double* tab_par, const double* tab_ang, int n_ids, size_t nc, double* planes);
 int sc_result_planes(sc_ctx* ctx, const double* param_of_id, const double* angle_of_id, int n_ids,

@@ -21,7 +21,8 @@
 //   k_st_sum / k_st_scan1 / k_st_offsets        exclusive scan -> off[slot]
 //   k_st_init_lists, k_st_events<true>          pair lists: entry 0 the final holder, then the events' templates
 //   k_window_f64, k_curv_planes<double>         (score_prepare_f64); k_st_sums: n and sum(W**2) in a fixed order
-//   k_st_spans                                  the windows' row runs (their supports are a seventh of their boxes)
+//   k_st_spans                                  the windows' row runs (their supports are a seventh of their boxes);
+//                                               both behind sc_window_runs, which sc_snr_surface calls too
 //   k_st_score                                  one wave per pair; repeats of a template in a list and lists of one
 //                                               template are not scored
 //   k_st_resolve                                per slot the largest float64 SNR, ties to the earlier template; the audit:
@@ -563,6 +564,29 @@ inline size_t up64(size_t b) { return (b + 63) & ~(size_t)63; }
 
 }  // namespace
 
+// What the run-walking float64 scorers (k_st_score here, k_sf_score of sc_surface.hip) need of the windows score_prepare_f64
+// made: k_st_sums and k_st_spans over the n templates of the context's table.  sums (2 n doubles), soff (n + 1 words) and
+// maxlen (n ints) are device buffers of the caller; the run table lies in ctx->st_spans.
+int sc_window_runs(sc_ctx* ctx, int n, const unsigned long long* woff, const double* wbuf, double* sums, unsigned* soff, int* maxlen) {
+    // rows of every template's window before it: the offsets of the run table (the context's vector: the upload is asynchronous)
+    std::vector<unsigned>& h_soff = ctx->h_soff;
+    h_soff.assign((size_t)n + 1, 0u);
+    int wh_max = 1;
+    for (int k = 0; k < n; ++k) {
+        h_soff[k + 1] = h_soff[k] + (unsigned)ctx->h_templ[k].wh;
+        wh_max = std::max(wh_max, ctx->h_templ[k].wh);
+    }
+    int rc;
+    if ((rc = sc_ensure(ctx, ctx->st_spans, sizeof(int2) * (size_t)h_soff[n] + 64))) return rc;
+    SC_HIP(ctx, hipMemcpyAsync(soff, h_soff.data(), 4 * h_soff.size(), hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(maxlen, 0, 4 * (size_t)n, ctx->stream));
+    hipLaunchKernelGGL(k_st_sums, dim3(n), dim3(256), 0, ctx->stream, (const TemplDev*)ctx->templ.p, woff, wbuf, sums);
+    hipLaunchKernelGGL(k_st_spans, dim3((wh_max + 3) / 4, n), dim3(256), 0, ctx->stream, (const TemplDev*)ctx->templ.p, woff, wbuf,
+                       (const unsigned*)soff, (int2*)ctx->st_spans.p, maxlen);
+    SC_HIP(ctx, hipGetLastError());
+    return SC_OK;
+}
+
 // the patch buffer: cell_of (u32 x n), id (u32 x n), amp, snr (f64 x n)
 static void patch_views(sc_ctx* ctx, size_t n, uint32_t** cell_of, uint32_t** p_id, double** p_amp, double** p_snr) {
     char* p = (char*)ctx->st_patch.p;
@@ -645,20 +669,11 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
     double* sums64 = (double*)(wk + o_sums);
     unsigned* soff = (unsigned*)(wk + o_soff);
     int* maxlen = (int*)(wk + o_mlen);
-    // rows of every template's window before it: the offsets of the run table
-    std::vector<unsigned> h_soff((size_t)n + 1, 0u);
-    int wh_max = 1;
-    for (int k = 0; k < n; ++k) {
-        h_soff[k + 1] = h_soff[k] + (unsigned)ctx->h_templ[k].wh;
-        wh_max = std::max(wh_max, ctx->h_templ[k].wh);
-    }
     if ((rc = sc_ensure(ctx, ctx->st_patch, 2 * up64(8 * ns_max) + 2 * up64(4 * ns_max) + 64))) return rc;
     sc_prof_begin(ctx, SC_K_SETTLE);              // (one bracket over the whole call: every return below closes it)
     struct ProfEnd { sc_ctx* c; ~ProfEnd() { sc_prof_end(c); } } prof_end{ctx};
     SC_HIP(ctx, hipMemsetAsync(stats, 0, 8 * ST_STATS, ctx->stream));
     SC_HIP(ctx, hipMemcpyAsync(d_tab, idtab.data(), 4 * idtab.size(), hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(soff, h_soff.data(), 4 * h_soff.size(), hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemsetAsync(maxlen, 0, 4 * (size_t)n, ctx->stream));
     hipLaunchKernelGGL(k_st_flag_count, dim3(nblk), dim3(256), 0, ctx->stream, near, tm, blk);
     hipLaunchKernelGGL(k_st_scan1, dim3(1), dim3(1024), 0, ctx->stream, blk, nblk, stats);
     SC_HIP(ctx, hipGetLastError());
@@ -720,10 +735,7 @@ static int settle_impl(sc_ctx* ctx, int n_twin, double max_work, long long* stat
     const double *wbuf = nullptr, *pa = nullptr, *mix = nullptr;
     if ((rc = score_prepare_f64(ctx, n, &woff, &wbuf, &pa, &mix))) return rc;
     const size_t npl = (size_t)g.ly * g.lx;
-    hipLaunchKernelGGL(k_st_sums, dim3(n), dim3(256), 0, ctx->stream, (const TemplDev*)ctx->templ.p, woff, wbuf, sums64);
-    if ((rc = sc_ensure(ctx, ctx->st_spans, sizeof(int2) * (size_t)h_soff[n] + 64))) return rc;
-    hipLaunchKernelGGL(k_st_spans, dim3((wh_max + 3) / 4, n), dim3(256), 0, ctx->stream, (const TemplDev*)ctx->templ.p, woff, wbuf,
-                       (const unsigned*)soff, (int2*)ctx->st_spans.p, maxlen);
+    if ((rc = sc_window_runs(ctx, n, woff, wbuf, sums64, soff, maxlen))) return rc;
     // (a multiple of eight workgroups: the kernel deals the pair list out over the XCDs in eighths)
 #define ST_SCORE(WPPV, BLOCKS, THREADS)                                                                                       \
     hipLaunchKernelGGL(k_st_score<WPPV>, dim3((unsigned)(((BLOCKS) + 7) / 8 * 8)), dim3(THREADS), 0, ctx->stream, pa, pa + npl, \

@@ -396,6 +396,11 @@ class DistMatcher(object):
         """This rank's tile of (amp, age, angle, snr)."""
         return self.m.result()
 
+    def snr_surface(self, *args, **kwargs):
+        """Not on a DEM cut into blocks: ``sl.snr_surface`` scores against the whole periodic DEM of one device."""
+        raise ValueError("snr_surface needs the whole DEM on one device; a DistMatcher holds a block of it "
+                         "(use sl.snr_surface or a Matcher)")
+
     def gather(self, dst=0, out=None):
         """Assemble the full maps on rank ``dst`` (None elsewhere): over RCCL
         (sc_gather_result, device to root's host array) with the 'rccl' backend,
