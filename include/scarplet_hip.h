@@ -684,6 +684,60 @@ int sc_fit_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long l
                       int min_profiles, sc_strike_fit* out_rows, double* out_sse);
 
 /*
+ * Strike-slip offsets across a trace (docs/lateral.md, scarplet_amd/csrc/sc_lateral.hip): at each of K cells two
+ * fault-parallel profiles are cut, one on either side of the trace, and the lag along the strike at which they agree
+ * best comes back as one sc_lateral_fit.
+ *   cells   K linear indices r * nx + c;  sa, ca: sin and cos of the strike's angle at the cell, as sc_fit_profiles
+ *           takes them
+ *   samples along-strike index t, across index q: rr = r + (t ca - q sa), cc = c + (q ca + t sa) - the point of
+ *           sc_fit_profiles with k = t and j = q, inside, interpolated and valid exactly as there
+ *   profiles u_t, t = -h..h: the mean of the valid samples at q = -q0, -(q0 + 1), .., -q1, summed in that order;
+ *           v_t, t = -(h + D)..(h + D): the same at q = +q0, .., +q1.  NaN where no sample is valid
+ *   lag d   in -D..D, over the points t = -h..h with u_t and v_{t + d} both valid (n_d of them, s = t de), every sum
+ *           over ascending t: the plain sums of s, u, v give sbar, ubar, vbar; the centred Stt, Stu, Stv give
+ *           bu = Stu / Stt and bv = Stv / Stt; with ru = (u - ubar) - bu (s - sbar) and rv likewise, Suu = sum ru^2,
+ *           Svv = sum rv^2, Suv = sum ru rv, sse = sum (rv - ru)^2 (explicit residuals).  mse_d = sse / (n_d - 2),
+ *           rho_d = Suv / sqrt(Suu Svv), NaN unless Suu Svv > 0.  The lag is skipped - mse_d NaN - when
+ *           n_d < min_samples or Stt is not > 0
+ *   best    lag = argmin mse_d over the candidates in the order 0, -1, +1, -2, +2, ..: a NaN never wins, the first
+ *           smallest wins a tie.  No lag fitted: status 1, n = lag = lo = hi = 0, NaN in every float field
+ *   interval thr = mse (1 + delta / (n - 2)); lo walks down from lag while mse[lo - 1] <= thr, hi up likewise (a NaN
+ *           stops the walk)
+ *   offset  (lag + frac) de: frac = 0.5 (m- - m+) / ((m- - m0) + (m+ - m0)) of the mse at lag - 1, lag, lag + 1
+ *           where -D < lag < D, both neighbours are finite and the denominator is > 0; else frac = 0
+ *   status  1, or the sum of 2 (lo == -D), 4 (hi == D), 8 (|lag| == D, D > 0), 16 (some lag was skipped)
+ * out_rows: K rows in the order of the cells (repeats allowed); out_mse: K x (2 D + 1) float64, mse_d at column
+ * d + D, or NULL.  No atomics, every sum in a fixed order: the same bytes on every run and for every order of the
+ * cells.  SC_ERR_INVALID: a null argument, K < 0, a cell outside the grid, sa / ca not finite, h < 1, q0 < 1,
+ * q1 < q0, D < 0, min_samples < 3 or > 2 h + 1, delta < 0 or not finite, de not finite or <= 0, ny or nx < 2.
+ * SC_ERR_UNSUPPORTED: h > SC_PROFILE_MAX_HALF, q1 > SC_LATERAL_MAX_FAR, q1 - q0 + 1 > SC_LATERAL_MAX_BAND,
+ * D > SC_LATERAL_MAX_LAG, K > 2^31 - 1, a context that holds a block of a larger grid.  The buffers are those of
+ * sc_fit_profiles: the record, the result planes, the kept spectra, the trace and fill buffers are not touched.
+ * Timed as SC_K_PROFILE.
+ */
+#define SC_LATERAL_MAX_LAG   255     /* D                                              */
+#define SC_LATERAL_MAX_BAND  64      /* q1 - q0 + 1: the lines averaged on each side   */
+#define SC_LATERAL_MAX_FAR   1024    /* q1                                             */
+typedef struct sc_lateral_fit {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  n;               /* points of the best lag (0: not fitted)          */
+    int32_t  lag;             /* best lag, cells along the strike                */
+    int32_t  lo, hi;          /* the interval, as lags                           */
+    int32_t  status;          /* 1 (not fitted), or 2 (open below) + 4 (open above) + 8 (lag at its limit) + 16 (a lag skipped) */
+    double   offset, offset_lo, offset_hi;   /* (lag + frac) de, lo de, hi de    */
+    double   mse, rho;        /* of the best lag                                 */
+    double   dz, tilt;        /* vbar - ubar and bv - bu there                   */
+} sc_lateral_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_lateral_offsets(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K, int h,
+                       int q0, int q1, int D, double de, double delta, int min_samples, sc_lateral_fit* out_rows,
+                       double* out_mse);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_lateral_offsets_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                           const double* ca, long long K, int h, int q0, int q1, int D, double de, double delta,
+                           int min_samples, sc_lateral_fit* out_rows, double* out_mse);
+
+/*
  * The search's float64 SNR surface at chosen cells (docs/surface.md, scarplet_amd/csrc/sc_surface.hip).
  *   t        n_par * n_ang descriptors, orientation-major (template of parameter ia and orientation ib at ib * n_par + ia:
  *            what Matcher.describe makes).  They become the context's template table as in sc_settle_pairs: nothing is
@@ -841,7 +895,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact, sc_snr_surface: all their kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk */
+#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk; sc_lateral_offsets*: the kernel of every chunk */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

@@ -178,6 +178,21 @@ STRIKE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_strike_fit._fields_],
                              "itemsize": C.sizeof(sc_strike_fit)})
 
 
+class sc_lateral_fit(C.Structure):
+    """One row of sc_lateral_offsets / sc_lateral_offsets_dem (docs/lateral.md)."""
+    _fields_ = [("cell", C.c_int64), ("n", C.c_int32), ("lag", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32),
+                ("status", C.c_int32),
+                ("offset", C.c_double), ("offset_lo", C.c_double), ("offset_hi", C.c_double),
+                ("mse", C.c_double), ("rho", C.c_double), ("dz", C.c_double), ("tilt", C.c_double)]
+
+
+LATERAL_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_lateral_fit._fields_],
+                              "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 7,
+                              "offsets": [getattr(sc_lateral_fit, f).offset for f, _ in sc_lateral_fit._fields_],
+                              "itemsize": C.sizeof(sc_lateral_fit)})
+LATERAL_MAX_LAG, LATERAL_MAX_BAND, LATERAL_MAX_FAR = 255, 64, 1024     # SC_LATERAL_MAX_*
+
+
 class sc_surface_row(C.Structure):
     """One row of sc_snr_surface (docs/surface.md)."""
     _fields_ = [("par_index", C.c_int32), ("ang_index", C.c_int32), ("par_lo", C.c_int32), ("par_hi", C.c_int32),
@@ -301,6 +316,10 @@ SIGNATURES = {
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
                                     C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
+    "sc_lateral_offsets": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    "sc_lateral_offsets_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -756,6 +775,26 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, sse
+
+    # -- strike-slip offsets across a trace (docs/lateral.md) -------------------------------
+    def lateral_offsets(self, cells, sa, ca, h, q0, q1, D, de, delta, min_samples, curve=False, z=None):
+        """sc_lateral_offsets on the context's DEM, or sc_lateral_offsets_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, (K, 2 D + 1) float64 mse curves or None).  cells int64, sa / ca float64, all 1-D and C-contiguous."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K = len(cells)
+        assert len(sa) == K and len(ca) == K
+        rows = np.zeros(K, dtype=LATERAL_FIT_DTYPE)
+        mse = np.empty((K, 2 * int(D) + 1), dtype=np.float64) if curve else None
+        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, int(h), int(q0), int(q1), int(D),
+                float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(mse, _dp) if curve else None]
+        name = "sc_lateral_offsets"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, mse
 
     # -- the SNR surface at chosen cells (docs/surface.md) ---------------------------------
     def snr_surface(self, templates, n_par, n_ang, cells, keep, surface=False):

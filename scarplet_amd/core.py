@@ -1031,6 +1031,40 @@ class Matcher(object):
                                     delta, min_samples, min_profiles, max_shift)
         return st._run(self.ctx, args, where, return_curve)
 
+    def lateral_offsets(self, traces_or_cells, half_length, near, far, max_offset, delta=1.0, min_samples=8,
+                        return_curve=False, angle=None, strike="segment"):
+        """``sl.lateral_offsets`` on the DEM this matcher holds on the device (docs/lateral.md) - no upload: the
+        strike-slip offset across the trace at every station.  Given the ``Traces`` of ``extract_traces`` the stations
+        are the cells of the segments (``labels > 0``, row-major order) and the table gains a ``label`` column;
+        ``strike="segment"`` (the default here: the profiles must run parallel to the fault, and single-cell
+        orientations are noisy) gives every cell its segment's ``strike`` from the table, as in ``fit_segments``,
+        ``strike="cell"`` reads the angle plane of this matcher's result - which is also what cells (as
+        ``sl.lateral_offsets`` takes them) get unless ``angle`` says otherwise.  The bytes are those of
+        ``sl.lateral_offsets`` on the same data and angles."""
+        from scarplet_amd import lateral, traces as tr
+        if not getattr(self, "whole", False):
+            raise ValueError("lateral_offsets needs the whole DEM on the device, not a block of it")
+        if strike not in ("cell", "segment"):
+            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
+        label = None
+        cells = traces_or_cells
+        if isinstance(traces_or_cells, tr.Traces):
+            labels = np.asarray(traces_or_cells.labels)
+            if labels.shape != (self.ny, self.nx):
+                raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
+            cells = np.flatnonzero(labels.ravel() > 0)
+            label = labels.ravel()[cells]
+            if angle is None and strike == "segment":
+                seg = traces_or_cells.segments
+                if len(cells) and (len(seg) < label.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
+                    raise ValueError("the traces' table does not number the segments of its label plane")
+                angle = np.asarray(seg["strike"], dtype=np.float64)[label - 1]
+        if angle is None:
+            angle = self.result_array()[2]
+        args = lateral.check_args((self.ny, self.nx), self.de, cells, angle, half_length, near, far, max_offset, delta,
+                                  min_samples)
+        return lateral._run(self.ctx, args, self.nx, return_curve, label=label)
+
     def search_scales(self, Template, scales, params, angles, method="auto", exact=None, **kwargs):
         """A multi-scale job (BASELINE config C5: Channel at five scales x 181 orientations; the reference runs it as one
         sl.match per scale on the same data, docs/source/examples/channels.ipynb - its 4-plane result has no scale
