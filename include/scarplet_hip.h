@@ -738,6 +738,70 @@ int sc_lateral_offsets_dem(sc_ctx* ctx, const double* z, int ny, int nx, const l
                            int min_samples, sc_lateral_fit* out_rows, double* out_mse);
 
 /*
+ * Weights and robust fits (docs/profiles.md, "Weights and robust fits"; scarplet_amd/csrc/sc_robust.hip): the fit of
+ * sc_fit_profiles with a weight u_j on every point and, per age, T rounds of iteratively reweighted least squares under
+ * the Huber or the Tukey loss, on one scale per profile.
+ *   samples  as sc_fit_profiles.  With a weight plane (ny x nx float64 on the host, uploaded by the call) the same
+ *            bilinear formula is applied to it at the same position; a sample is valid when the elevation sample is
+ *            valid and the weight sample is finite and >= 0; p_j and u_j are the means of the two over the same valid k
+ *            in ascending k; a point whose u_j is not > 0 is a missing point, and n counts what is left.  weights NULL:
+ *            u_j = 1
+ *   fit(q)   the four passes of sc_fit_profiles with every sum weighted by q_j, in the same order: W = sum q,
+ *            sbar = sum q s / W (pbar, ebar likewise); Sss = sum q sc^2 (Sps, Ses likewise), beta = Sps / Sss,
+ *            gamma = Ses / Sss; e2 = (e - ebar) - gamma sc, p2 = (p - pbar) - beta sc, See = sum q e2^2,
+ *            Sep = sum q e2 p2; a = Sep / See, b = beta - a gamma, c0 = (pbar - a ebar) - b sbar; r_j the explicit
+ *            residuals
+ *   iterate 0  q = u for every age; ls_index = argmin of sum u r^2, ties to the smaller index.  loss SC_ROBUST_NONE
+ *            stops here: the loss curve is that sum, scale is NaN, n_down 0 and ls_index = kt_index
+ *   scale    sigma = `scale` where it is > 0; scale = 0: 1.4826 times the element of rank (n - 1) / 2 (0-based,
+ *            ascending; an exact order statistic, no averaging) of |r_j| at ls_index over the n points.  sigma not > 0:
+ *            the row of iterate 0 with loss = sse and status 16
+ *   iterates t = 1..iterations, per age from that age's previous iterate: q_j = u_j f(|r_j|), c = tuning sigma;
+ *            Huber f = 1 where |r| <= c, else c / |r|; Tukey f = (1 - (|r| / c)^2)^2 where |r| < c, else 0; then
+ *            fit(q).  An age with fewer than min_samples points with q > 0 on either side of j = 0 at some iterate, or
+ *            See not > 0, has loss NaN and never wins
+ *   loss     of the last iterate, sum u_j rho(r_j): Huber rho = r^2 where |r| <= c, else 2 c |r| - c^2; Tukey
+ *            rho = (c^2 / 3)(1 - (1 - (r / c)^2)^3) where |r| < c, else c^2 / 3
+ *   choice   kt_index, lo_index and hi_index as sc_fit_profiles, on the loss curve: thr = loss_min (1 + delta / (n - 3)).
+ *            sse = sum u r^2 of the last iterate at kt_index, rmse = sqrt(loss / (n - 3)), n_down = its points whose
+ *            f(|r_j|) < 1.  Status 1, 2 and 4 as sc_fit_profiles; 16 as above; 1 | 32: every age's loss is NaN
+ * weights NULL (or a plane of ones) with SC_ROBUST_NONE returns the bytes of sc_fit_profiles in every shared field.
+ * out_rows: K rows in the order of the cells; out_loss: K x A float64 or NULL.  No atomics, no float sum across lanes,
+ * the order statistic by integer counts: the same bytes on every run and for every order of the cells.
+ * SC_ERR_INVALID: what sc_fit_profiles refuses, a loss that is none of the three, and with a robust loss a tuning
+ * constant not finite or <= 0, iterations < 1, a scale not finite or < 0.  SC_ERR_UNSUPPORTED: what sc_fit_profiles
+ * refuses, iterations > SC_ROBUST_MAX_ITER.  The buffers are those of sc_fit_profiles and one for the weight plane.
+ * Timed as SC_K_PROFILE.
+ */
+#define SC_ROBUST_NONE     0
+#define SC_ROBUST_HUBER    1
+#define SC_ROBUST_TUKEY    2
+#define SC_ROBUST_MAX_ITER 64
+typedef struct sc_profile_robust_fit {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  n;               /* valid points of the profile (u_j > 0)           */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;   /* the interval, as indices of the age grid   */
+    int32_t  status;          /* 1, 2, 4 as sc_profile_fit; 16: no scale; 1 | 32: no age survived */
+    double   kt, kt_lo, kt_hi;
+    double   a, b, c0;        /* of the best age's last iterate                  */
+    double   sse, rmse;       /* sum u r^2 there; sqrt(loss / (n - 3))           */
+    double   loss, scale;     /* sum u rho(r) there; sigma                       */
+    int32_t  n_down;          /* points of that fit with f(|r|) < 1              */
+    int32_t  ls_index;        /* best age of iterate 0                           */
+} sc_profile_robust_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_profiles_robust(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                           const double* ages, int A, int h, int w, double de, double delta, int min_samples,
+                           const double* weights, int loss, double tuning, int iterations, double scale,
+                           sc_profile_robust_fit* out_rows, double* out_loss);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_profiles_robust_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                               const double* ca, long long K, const double* ages, int A, int h, int w, double de,
+                               double delta, int min_samples, const double* weights, int loss, double tuning,
+                               int iterations, double scale, sc_profile_robust_fit* out_rows, double* out_loss);
+
+/*
  * The search's float64 SNR surface at chosen cells (docs/surface.md, scarplet_amd/csrc/sc_surface.hip).
  *   t        n_par * n_ang descriptors, orientation-major (template of parameter ia and orientation ib at ib * n_par + ia:
  *            what Matcher.describe makes).  They become the context's template table as in sc_settle_pairs: nothing is
@@ -895,7 +959,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact, sc_snr_surface: all their kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles*, sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk; sc_lateral_offsets*: the kernel of every chunk */
+#define SC_K_PROFILE     10     /* sc_fit_profiles* (_robust too), sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk; sc_lateral_offsets*: the kernel of every chunk */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

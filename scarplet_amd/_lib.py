@@ -109,6 +109,19 @@ PROFILE_SHIFT_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_shift_fit._fi
                                 "itemsize": C.sizeof(sc_profile_shift_fit)})
 
 
+class sc_profile_robust_fit(C.Structure):
+    """One row of sc_fit_profiles_robust / sc_fit_profiles_robust_dem: sc_profile_fit, then the loss and the scale."""
+    _fields_ = sc_profile_fit._fields_ + [("loss", C.c_double), ("scale", C.c_double), ("n_down", C.c_int32),
+                                          ("ls_index", C.c_int32)]
+
+
+PROFILE_ROBUST_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_robust_fit._fields_],
+                                 "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 10 + [np.int32] * 2,
+                                 "offsets": [getattr(sc_profile_robust_fit, f).offset for f, _ in sc_profile_robust_fit._fields_],
+                                 "itemsize": C.sizeof(sc_profile_robust_fit)})
+ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2                      # SC_ROBUST_*
+ROBUST_MAX_ITER = 64                                                   # SC_ROBUST_MAX_ITER
+
 class sc_segment_fit(C.Structure):
     """One row of sc_fit_segments / sc_fit_segments_dem (docs/segments.md)."""
     _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n", C.c_int32),
@@ -280,6 +293,12 @@ SIGNATURES = {
                                   C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
     "sc_fit_profiles_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
                                       C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    "sc_fit_profiles_robust": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_double,
+                                         C.c_void_p, _dp]),
+    "sc_fit_profiles_robust_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
+                                             C.c_double, C.c_int, C.c_double, C.c_void_p, _dp]),
     "sc_fit_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
                                   C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
@@ -694,6 +713,31 @@ class Context(object):
         rest = [float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None]
         plane = self._fit_call("sc_fit_profiles", head, rest, shift, shift_plane, (K, A), z)
         return (rows, sse) if shift is None else (rows, sse, plane)
+
+    def fit_profiles_robust(self, cells, sa, ca, ages, h, w, de, delta, min_samples, weights=None, loss=ROBUST_NONE,
+                            tuning=0.0, iterations=1, scale=0.0, curve=False, z=None):
+        """sc_fit_profiles_robust on the context's DEM, or sc_fit_profiles_robust_dem on ``z`` (float64, C-contiguous,
+        2-D): (rows, (K, A) float64 loss curves or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous;
+        ``weights``: None or a float64, C-contiguous plane of the DEM's shape; ``scale`` 0: estimated per profile."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A = len(cells), len(ages)
+        assert len(sa) == K and len(ca) == K
+        if weights is not None:                              # (of the DEM's shape: the caller's check where z is the context's)
+            assert weights.dtype == np.float64 and weights.ndim == 2 and weights.flags.c_contiguous
+            assert z is None or weights.shape == z.shape
+        rows = np.zeros(K, dtype=PROFILE_ROBUST_DTYPE)
+        out = np.empty((K, A), dtype=np.float64) if curve else None
+        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
+                float(de), float(delta), int(min_samples), _as(weights, _dp) if weights is not None else None, int(loss),
+                float(tuning), int(iterations), float(scale), rows.ctypes.data_as(C.c_void_p), _as(out, _dp) if curve else None]
+        name = "sc_fit_profiles_robust"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, out
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
     def fit_segments(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,

@@ -1,5 +1,6 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
-// included by sc_profile.hip and sc_segment.hip alone - and by sc_bootstrap.hip and sc_strike.hip for stage one.  The
+// included by sc_profile.hip and sc_segment.hip alone - by sc_bootstrap.hip and sc_strike.hip for stage one, and by
+// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term.  The
 // library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
 // in the order of its text wherever it is called: the four calls return the same bits in every field they share because
 // they call the same helpers.
@@ -287,6 +288,38 @@ __device__ __forceinline__ pf_pick pf_choose(double sse, int lane, int A, double
 // status bits 2 and 4: the interval is open below, above
 __device__ __forceinline__ int pf_open(const pf_pick& k, int A) { return (k.lo == 0 ? 2 : 0) + (k.hi == A - 1 ? 4 : 0); }
 
+// ---- the rows ----------------------------------------------------------------------------------------------------------------
+// the fields sc_profile_fit, sc_profile_shift_fit and sc_profile_robust_fit share, of a cell that is not fitted and of one that is (the rows
+// were cleared: their padding is part of what the caller compares)
+template <class ROW>
+__device__ __forceinline__ void pf_row_unfit(ROW* out, long long cell, int n) {
+    const double nan = __builtin_nan("");
+    out->cell = cell;
+    out->n = n;
+    out->kt_index = -1;
+    out->lo_index = -1;
+    out->hi_index = -1;
+    out->status = 1;
+    out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
+    out->a = nan; out->b = nan; out->c0 = nan;
+    out->sse = nan; out->rmse = nan;
+}
+
+template <class ROW>
+__device__ __forceinline__ void pf_row_fit(ROW* out, long long cell, int n, const pf_pick& k, int status,
+                                           const double* __restrict__ ages, double a, double b, double c0, double sse,
+                                           int dof) {
+    out->cell = cell;
+    out->n = n;
+    out->kt_index = k.best;
+    out->lo_index = k.lo;
+    out->hi_index = k.hi;
+    out->status = status;
+    out->kt = ages[k.best]; out->kt_lo = ages[k.lo]; out->kt_hi = ages[k.hi];
+    out->a = a; out->b = b; out->c0 = c0;
+    out->sse = sse; out->rmse = sqrt(sse / (double)dof);
+}
+
 // ---- the shift search --------------------------------------------------------------------------------------------------------------
 // One wave, one profile: for every age i the shift d_i with the smallest sse among d = -D..D.  The LANES RUN OVER THE
 // (shift rank, age) PAIRS, age-minor, 64 pairs a round; each lane runs pf_column, pf_slope and pf_sse for its pair with
@@ -338,4 +371,155 @@ __device__ __forceinline__ void sh_search(const double* prof, const double* tab,
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+}
+
+// ---- the weighted fit (docs/profiles.md, "Weights and robust fits") ---------------------------------------------------------------
+// The sweeps above with every sum weighted, in the same order.  Point j's weight is q_j = u_j f(|r_j|): u_j the profile's
+// own weight (WT: from the wave's LDS beside the profile; else 1) and f the robust factor of the residual r_j of the
+// age's PREVIOUS iterate (c0, b, a), which the lane holds in registers - q is recomputed in every sweep and stored
+// nowhere.  LOSS 0: q = u (iterate 0, the weighted least squares fit); 1: Huber; 2: Tukey; c = k sigma.  A product by 1
+// is exact, so with u = 1 and f = 1 every sum here has the bits of its unweighted twin above.
+struct rb_prev { double c0, b, a, c; };
+
+template <int LOSS>
+__device__ __forceinline__ double rb_factor(double r, double c) {
+    const double x = fabs(r);
+    if (LOSS == 1) return x <= c ? 1.0 : c / x;
+    if (LOSS == 2) {
+        if (!(x < c)) return 0.0;
+        const double t = x / c, g = 1.0 - t * t;
+        return g * g;
+    }
+    return 1.0;
+}
+
+// rho(r): r^2 capped (Huber: linear beyond c; Tukey: constant c^2 / 3 beyond c)
+template <int LOSS>
+__device__ __forceinline__ double rb_rho(double r, double c) {
+    const double x = fabs(r);
+    if (LOSS == 1) return x <= c ? r * r : 2.0 * c * x - c * c;
+    if (LOSS == 2) {
+        if (!(x < c)) return c * c / 3.0;
+        const double t = r / c, g = 1.0 - t * t;
+        return (c * c / 3.0) * (1.0 - g * g * g);
+    }
+    return r * r;
+}
+
+__device__ __forceinline__ double rb_resid(double p, double s, double e, const rb_prev& v) {
+    return p - ((v.c0 + v.b * s) + v.a * e);
+}
+
+template <int LOSS, bool WT>
+__device__ __forceinline__ double rb_q(const double* u, int jj, double p, double s, double e, const rb_prev& v) {
+    if (!LOSS) return WT ? u[jj] : 1.0;
+    const double f = rb_factor<LOSS>(rb_resid(p, s, e, v), v.c);
+    return WT ? u[jj] * f : f;
+}
+
+// pass 0: n counts the profile's points, n_neg and n_pos those with q > 0 on either side
+struct rb_mom { int n, n_neg, n_pos; double W, Ss, Sp, Se; };
+
+template <int LOSS, bool WT>
+__device__ __forceinline__ rb_mom rb_moments(const double* prof, const double* u, int np, int h, double de, const double* col,
+                                             int A, const rb_prev& v) {
+    rb_mom m = {0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de, e = col[(size_t)jj * A];
+        const double q = rb_q<LOSS, WT>(u, jj, p, s, e, v);
+        ++m.n;
+        m.n_neg += (jj < h && q > 0.0) ? 1 : 0;
+        m.n_pos += (jj > h && q > 0.0) ? 1 : 0;
+        m.W += q;
+        m.Ss += q * s;
+        m.Sp += q * p;
+        m.Se += q * e;
+    }
+    return m;
+}
+
+// passes 1 and 2, then the coefficients: (c0, b, a) of the refit into `next`; false where See is not > 0
+template <int LOSS, bool WT>
+__device__ __forceinline__ bool rb_solve(const double* prof, const double* u, int np, int h, double de, const double* col,
+                                         int A, const rb_prev& v, const rb_mom& m, rb_prev& next) {
+    const double sbar = m.Ss / m.W, pbar = m.Sp / m.W, ebar = m.Se / m.W;
+    double Sss = 0.0, Sps = 0.0, Ses = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de, e = col[(size_t)jj * A];
+        const double q = rb_q<LOSS, WT>(u, jj, p, s, e, v);
+        const double sc = s - sbar;
+        Sss += q * (sc * sc);
+        Sps += q * (sc * (p - pbar));
+        Ses += q * (sc * (e - ebar));
+    }
+    const double beta = Sps / Sss, gamma = Ses / Sss;
+    double See = 0.0, Sep = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de, e = col[(size_t)jj * A];
+        const double q = rb_q<LOSS, WT>(u, jj, p, s, e, v);
+        const double sc = s - sbar;
+        const double e2 = (e - ebar) - gamma * sc;
+        const double p2 = (p - pbar) - beta * sc;
+        See += q * (e2 * e2);
+        Sep += q * (e2 * p2);
+    }
+    next.a = Sep / See;
+    next.c = v.c;
+    pf_slope(sbar, pbar, beta, ebar, gamma, next.a, next.b, next.c0);
+    return See > 0.0;
+}
+
+// the last pass over the residuals of (c0, b, a): sum u r^2, sum u rho(r) and the points whose factor is < 1
+template <int LOSS, bool WT>
+__device__ __forceinline__ void rb_loss(const double* prof, const double* u, int np, int h, double de, const double* col, int A,
+                                        const rb_prev& v, double& sse, double& loss, int& n_down) {
+    sse = 0.0;
+    loss = 0.0;
+    n_down = 0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de;
+        const double res = rb_resid(p, s, col[(size_t)jj * A], v);
+        const double uj = WT ? u[jj] : 1.0;
+        sse += uj * (res * res);
+        if (LOSS) {
+            loss += uj * rb_rho<LOSS>(res, v.c);
+            n_down += rb_factor<LOSS>(res, v.c) < 1.0 ? 1 : 0;
+        }
+    }
+    if (!LOSS) loss = sse;
+}
+
+// The element of rank `rank` (0-based, ascending) of |r_j| over the profile's points, r the residuals of (c0, b, a) at
+// column col: the lanes run over the points, and the answer is built bit by bit from the top on the bit patterns of the
+// non-negative doubles (which order as the values do) - cand is kept where at most `rank` values lie below it.  The
+// residuals are recomputed in every round; the counts are integers: exact, and the same in every lane.
+__device__ __forceinline__ double rb_select(const double* prof, int np, int h, double de, const double* col, int A,
+                                            const rb_prev& v, int lane, int rank) {
+    unsigned long long best = 0;
+    for (int bit = 62; bit >= 0; --bit) {
+        const unsigned long long cand = best | (1ull << bit);
+        int below = 0;
+        for (int j0 = 0; j0 < np; j0 += 64) {
+            const int jj = j0 + lane;
+            bool lt = false;
+            if (jj < np) {
+                const double p = prof[jj];
+                if (p == p) {
+                    const double x = fabs(rb_resid(p, (double)(jj - h) * de, col[(size_t)jj * A], v));
+                    lt = (unsigned long long)__double_as_longlong(x) < cand;
+                }
+            }
+            below += __popcll(__ballot(lt));
+        }
+        if (below <= rank) best = cand;
+    }
+    return __longlong_as_double((long long)best);
 }

@@ -37,37 +37,6 @@ __global__ __launch_bounds__(256) void k_pf_table(const double* __restrict__ age
     }
 }
 
-// the fields sc_profile_fit and sc_profile_shift_fit share, of a cell that is not fitted and of one that is (the rows
-// were cleared: their padding is part of what the caller compares)
-template <class ROW>
-__device__ __forceinline__ void pf_row_unfit(ROW* out, long long cell, int n) {
-    const double nan = __builtin_nan("");
-    out->cell = cell;
-    out->n = n;
-    out->kt_index = -1;
-    out->lo_index = -1;
-    out->hi_index = -1;
-    out->status = 1;
-    out->kt = nan; out->kt_lo = nan; out->kt_hi = nan;
-    out->a = nan; out->b = nan; out->c0 = nan;
-    out->sse = nan; out->rmse = nan;
-}
-
-template <class ROW>
-__device__ __forceinline__ void pf_row_fit(ROW* out, long long cell, int n, const pf_pick& k, int status,
-                                           const double* __restrict__ ages, double a, double b, double c0, double sse,
-                                           int dof) {
-    out->cell = cell;
-    out->n = n;
-    out->kt_index = k.best;
-    out->lo_index = k.lo;
-    out->hi_index = k.hi;
-    out->status = status;
-    out->kt = ages[k.best]; out->kt_lo = ages[k.lo]; out->kt_hi = ages[k.hi];
-    out->a = a; out->b = b; out->c0 = c0;
-    out->sse = sse; out->rmse = sqrt(sse / (double)dof);
-}
-
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict__ z, int ny, int nx,
                                                        const long long* __restrict__ cells,

@@ -23,6 +23,11 @@ FIT_DTYPE = np.dtype(FIT_FIELDS)
 # ... and with max_shift: the best age's shift, in cells and in data units
 SHIFT_FIT_FIELDS = FIT_FIELDS + [("shift_index", np.int32), ("shift", np.float64)]
 SHIFT_FIT_DTYPE = np.dtype(SHIFT_FIT_FIELDS)
+# ... and with weights or a robust loss: the loss and the scale of the best age, the points it down-weighted, and the best
+# age of the plain weighted fit
+ROBUST_FIT_FIELDS = FIT_FIELDS + [("loss", np.float64), ("scale", np.float64), ("n_down", np.int32), ("ls_index", np.int32)]
+ROBUST_FIT_DTYPE = np.dtype(ROBUST_FIT_FIELDS)
+ROBUST_LOSSES = {"huber": (_lib.ROBUST_HUBER, 1.345), "tukey": (_lib.ROBUST_TUKEY, 4.685)}
 
 
 def _number(x, name):
@@ -155,9 +160,56 @@ def check_shift(max_shift, return_shift, de, h, min_samples):
     return D
 
 
+def check_robust(shape, weights, robust, tuning, iterations, robust_scale, max_shift):
+    """None where neither ``weights`` nor ``robust`` is given, else (plane or None, loss, k, T, sigma or 0.0) for the
+    library; ValueError otherwise.  A NaN in the plane marks ground without a weight, as a NaN of the DEM does."""
+    if weights is None and robust is None:
+        if tuning is not None or robust_scale is not None:
+            raise ValueError("tuning and robust_scale need robust")
+        return None
+    if max_shift is not None:
+        raise ValueError("weights and robust are not built together with max_shift")
+    plane = None
+    if weights is not None:
+        try:
+            plane = np.asarray(weights, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("weights must be a plane of numbers")
+        if plane.shape != tuple(int(v) for v in shape):
+            raise ValueError("weights must have the grid's shape %r, got %r" % (tuple(shape), plane.shape))
+        if np.isinf(plane).any() or (plane < 0).any():
+            raise ValueError("weights must be finite and >= 0")
+        plane = np.ascontiguousarray(plane)
+    if robust is None:
+        if tuning is not None or robust_scale is not None:
+            raise ValueError("tuning and robust_scale need robust")
+        return plane, _lib.ROBUST_NONE, 0.0, 1, 0.0
+    if not isinstance(robust, str) or robust not in ROBUST_LOSSES:
+        raise ValueError("robust must be None, 'huber' or 'tukey', got %r" % (robust,))
+    loss, k = ROBUST_LOSSES[robust]
+    if tuning is not None:
+        k = _number(tuning, "tuning")
+        if k <= 0:
+            raise ValueError("tuning must be > 0, got %r" % (tuning,))
+    if isinstance(iterations, (bool, np.bool_)):
+        raise ValueError("iterations must be an integer")
+    try:
+        T = operator.index(iterations)
+    except TypeError:
+        raise ValueError("iterations must be an integer, got %r" % (iterations,))
+    if T < 1 or T > _lib.ROBUST_MAX_ITER:
+        raise ValueError("iterations must lie in 1..%d, got %r" % (_lib.ROBUST_MAX_ITER, iterations))
+    sigma = 0.0
+    if robust_scale is not None:
+        sigma = _number(robust_scale, "robust_scale")
+        if sigma <= 0:
+            raise ValueError("robust_scale must be > 0, got %r" % (robust_scale,))
+    return plane, loss, k, T, sigma
+
+
 def _table(rows, nx, label=None):
     """The library's rows -> the Python table (row, col, the row's fields, height = 2 a; ``label`` when given)."""
-    fields = SHIFT_FIT_FIELDS if "shift" in rows.dtype.names else FIT_FIELDS
+    fields = SHIFT_FIT_FIELDS if "shift" in rows.dtype.names else ROBUST_FIT_FIELDS if "loss" in rows.dtype.names else FIT_FIELDS
     dt = np.dtype(fields + ([] if label is None else [("label", np.int32)]))
     out = np.zeros(len(rows), dtype=dt)
     for f in rows.dtype.names:
@@ -184,7 +236,8 @@ def _dem_of(data):
 
 
 def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4, return_curve=False,
-                 device=0, max_shift=None, return_shift=False):
+                 device=0, max_shift=None, return_shift=False, weights=None, robust=None, tuning=None, iterations=8,
+                 robust_scale=None):
     """Fit the diffusion scarp to elevation profiles cut across the strike at ``cells`` (docs/profiles.md).
 
     ``data``: the DEMGrid.  ``cells``: linear indices ``r * nx + c``, a ``(rows, cols)`` tuple, or a bool plane (its
@@ -206,17 +259,34 @@ def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0,
     in the order 0, -1, +1, ...).  The table gains ``shift_index`` (d of the best age) and ``shift`` (d de), the
     curves are the minima over d, one degree of freedom goes to the shift (``n - 4`` for ``n - 3`` when the range is
     not 0), and ``status`` gains 8 where ``|shift_index|`` is the end of the range.  ``return_shift`` adds the
-    (K, A) int8 plane of every age's d, after the curves."""
+    (K, A) int8 plane of every age's d, after the curves.
+
+    ``weights`` (an (ny, nx) plane, finite and >= 0; NaN: ground without a weight) is sampled as the DEM is and weights
+    every point of every sum; ``robust`` ("huber" or "tukey") adds ``iterations`` rounds of iteratively reweighted least
+    squares per age with the constant ``tuning`` (default 1.345 / 4.685) on one scale per profile - ``robust_scale``, or
+    1.4826 times the median absolute residual of the plain weighted fit's best age (docs/profiles.md, "Weights and
+    robust fits").  The choice and the interval then run on the robust loss; the table gains ``loss``, ``scale``,
+    ``n_down`` (the points the best age down-weighted) and ``ls_index`` (the best age before the robust step), ``sse``
+    is the weighted sum of squared residuals of the final fit, ``rmse = sqrt(loss / (n - 3))``, the curves are the
+    losses, and ``status`` gains 16 where the scale is 0 (the row is the weighted least squares row) and is 33 where no
+    age kept enough points.  Neither is built together with ``max_shift``."""
     z, de = _dem_of(data)
     args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
     D = check_shift(max_shift, return_shift, args[6], args[4], args[8])
+    rb = check_robust(z.shape, weights, robust, tuning, iterations, robust_scale, max_shift)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift)
+    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift, robust=rb)
 
 
-def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False):
+def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False, robust=None):
     idx, sa, ca, kt, h, w, de, d, ms = args
+    if robust is not None:
+        plane, loss, k, T, sigma = robust
+        rows, curve = ctx.fit_profiles_robust(idx, sa, ca, kt, h, w, de, d, ms, weights=plane, loss=loss, tuning=k, iterations=T,
+                                              scale=sigma, curve=bool(return_curve), z=z)
+        out = _table(rows, nx, label)
+        return (out, curve) if return_curve else out
     if shift is None:
         rows, curve = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z)
         out = _table(rows, nx, label)
