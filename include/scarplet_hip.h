@@ -802,6 +802,62 @@ int sc_fit_profiles_robust_dem(sc_ctx* ctx, const double* z, int ny, int nx, con
                                int iterations, double scale, sc_profile_robust_fit* out_rows, double* out_loss);
 
 /*
+ * The initial slope (docs/profiles.md, "The initial slope"; scarplet_amd/csrc/sc_ramp.hip): the fit of sc_fit_profiles
+ * with the scarp started as a ramp of half-width L = m de, not as a vertical step (Hanks & Andrews 1989).  The initial
+ * profile b s + a clamp(s / L, -1, 1), diffused for kt, is
+ *   z(s) = c0 + b s + a g(s; kt, L),   g = (F(s + L) - F(s - L)) / (2 L),
+ *   F(x) = x erf(x / (2 sqrt(kt))) + 2 sqrt(kt / pi) exp(-x^2 / (4 kt)),   F' = erf(x / (2 sqrt(kt))),
+ * and g -> erf(s / (2 sqrt(kt))) as L -> 0.  m = 0..M is a whole number of cells.
+ *   samples  as sc_fit_profiles: the same points, validity rule, n, n_neg, n_pos and min_samples rule
+ *   tables   Ftab over x = -(h + M)..(h + M) and the A ages: with X = (double)x de, X erf(X / (2 sqrt(kt_i))) +
+ *            (2 sqrt(kt_i / pi)) exp(-(X X) / (4 kt_i)); the erf table of sc_fit_profiles serves m = 0
+ *   column   m = 0: e_ij is the erf table's entry; m >= 1: e_ij = (Ftab[j + m][i] - Ftab[j - m][i]) / (2 m de), the
+ *            divisor formed as (double)(2 m) de
+ *   fit      for each pair (age i, half-width m) the four passes of sc_fit_profiles with that column; n, sbar, pbar, Sss,
+ *            beta and p2 depend on neither and are formed once.  A pair whose See is not > 0, or whose sse is NaN, never
+ *            wins
+ *   per age  SC_RAMP_FREE: m_i = argmin_m sse_im over m = 0..M, the first smallest winning.  SC_RAMP_SLOPE: over
+ *            m = 1..M the key | |b_im + a_im / (m de)| - slope |, the first smallest winning; m = 0, an infinite slope,
+ *            is no candidate.  sse*_i = sse_{i, m_i} in both modes (NaN where no pair of the age can win)
+ *   choice   kt_index = argmin_i sse*_i, ties to the smaller index; dof = n - 3 - (M > 0) with SC_RAMP_FREE, n - 3 with
+ *            SC_RAMP_SLOPE (the constraint fixes the width); dof < 1 gives status 1.  rmse = sqrt(sse / dof), thr =
+ *            sse_min (1 + delta / dof), lo_index / hi_index walk along sse*.  Status 1, 2 and 4 as sc_fit_profiles; 8:
+ *            width_index == M with M > 0 - the range ended before the fit did
+ * M = 0 returns the bytes of sc_fit_profiles in every shared field.  out_rows: K rows in the order of the cells; out_sse:
+ * K x A float64 (sse*) or NULL; out_width: K x A int8 (m_i of every age, 0 in the rows of cells with status 1) or NULL.
+ * `slope` is read with SC_RAMP_SLOPE alone.  Refused before any device work: what sc_fit_profiles refuses, and M < 0,
+ * M > h - min_samples, a mode that is neither, SC_RAMP_SLOPE with M < 1 or a slope that is not finite and > 0
+ * (SC_ERR_INVALID); M > SC_PROFILE_MAX_WIDTH (SC_ERR_UNSUPPORTED).  No atomics, no float sum across lanes: the same bytes
+ * on every run and for every order of the cells.  The buffers are those of sc_fit_profiles_shift and one for Ftab.
+ * Timed as SC_K_PROFILE.
+ */
+#define SC_PROFILE_MAX_WIDTH 64
+#define SC_RAMP_FREE  0
+#define SC_RAMP_SLOPE 1
+typedef struct sc_profile_ramp_fit {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  n;               /* valid points of the profile                     */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;   /* the interval, as indices of the age grid   */
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) + 8 (width at its limit) */
+    double   kt, kt_lo, kt_hi;
+    double   a, b, c0;        /* of the best (age, half-width): the scarp's offset is 2 a */
+    double   sse, rmse;       /* rmse = sqrt(sse / dof)                          */
+    int32_t  width_index;     /* m of the best age, in cells (0 where not fitted) */
+    double   width;           /* m de, the half-width L (NaN where not fitted)   */
+    double   initial_slope;   /* b + a / (m de), signed; copysign(inf, a) at m = 0; NaN where not fitted */
+} sc_profile_ramp_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_profiles_ramp(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                         const double* ages, int A, int h, int w, int M, int mode, double slope, double de, double delta,
+                         int min_samples, sc_profile_ramp_fit* out_rows, double* out_sse, int8_t* out_width);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_profiles_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                             const double* ca, long long K, const double* ages, int A, int h, int w, int M, int mode,
+                             double slope, double de, double delta, int min_samples, sc_profile_ramp_fit* out_rows,
+                             double* out_sse, int8_t* out_width);
+
+/*
  * The search's float64 SNR surface at chosen cells (docs/surface.md, scarplet_amd/csrc/sc_surface.hip).
  *   t        n_par * n_ang descriptors, orientation-major (template of parameter ia and orientation ib at ib * n_par + ia:
  *            what Matcher.describe makes).  They become the context's template table as in sc_settle_pairs: nothing is

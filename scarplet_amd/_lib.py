@@ -122,6 +122,19 @@ PROFILE_ROBUST_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_robust_fit._
 ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2                      # SC_ROBUST_*
 ROBUST_MAX_ITER = 64                                                   # SC_ROBUST_MAX_ITER
 
+class sc_profile_ramp_fit(C.Structure):
+    """One row of sc_fit_profiles_ramp / sc_fit_profiles_ramp_dem: sc_profile_fit, then the half-width of the best age."""
+    _fields_ = sc_profile_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
+
+
+PROFILE_RAMP_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_ramp_fit._fields_],
+                               "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8 + [np.int32, np.float64, np.float64],
+                               "offsets": [getattr(sc_profile_ramp_fit, f).offset for f, _ in sc_profile_ramp_fit._fields_],
+                               "itemsize": C.sizeof(sc_profile_ramp_fit)})
+PROFILE_MAX_WIDTH = 64                                                 # SC_PROFILE_MAX_WIDTH
+RAMP_FREE, RAMP_SLOPE = 0, 1                                           # SC_RAMP_*
+
+
 class sc_segment_fit(C.Structure):
     """One row of sc_fit_segments / sc_fit_segments_dem (docs/segments.md)."""
     _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n", C.c_int32),
@@ -299,6 +312,12 @@ SIGNATURES = {
     "sc_fit_profiles_robust_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
                                              C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
                                              C.c_double, C.c_int, C.c_double, C.c_void_p, _dp]),
+    "sc_fit_profiles_ramp": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp,
+                                       C.c_void_p]),
+    "sc_fit_profiles_ramp_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                           C.c_int, C.c_void_p, _dp, C.c_void_p]),
     "sc_fit_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
                                   C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
@@ -738,6 +757,30 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, out
+
+    def fit_profiles_ramp(self, cells, sa, ca, ages, h, w, de, delta, min_samples, width, mode=RAMP_FREE, slope=0.0,
+                          curve=False, width_plane=False, z=None):
+        """sc_fit_profiles_ramp on the context's DEM, or sc_fit_profiles_ramp_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, curve or None, (K, A) int8 half-widths or None).  cells int64, sa / ca / ages float64, all 1-D and
+        C-contiguous; ``width``: M, the range of the half-width in cells; ``slope`` is read with RAMP_SLOPE alone."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A = len(cells), len(ages)
+        assert len(sa) == K and len(ca) == K
+        rows = np.zeros(K, dtype=PROFILE_RAMP_DTYPE)
+        sse = np.empty((K, A), dtype=np.float64) if curve else None
+        plane = np.zeros((K, A), dtype=np.int8) if width_plane else None
+        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
+                int(width), int(mode), float(slope), float(de), float(delta), int(min_samples),
+                rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None,
+                plane.ctypes.data_as(C.c_void_p) if width_plane else None]
+        name = "sc_fit_profiles_ramp"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, sse, plane
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
     def fit_segments(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,

@@ -48,7 +48,7 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,
@@ -233,7 +233,7 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,

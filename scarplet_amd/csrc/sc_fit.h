@@ -1,6 +1,6 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
 // included by sc_profile.hip and sc_segment.hip alone - by sc_bootstrap.hip and sc_strike.hip for stage one, and by
-// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term.  The
+// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, and by sc_ramp.hip.  The
 // library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
 // in the order of its text wherever it is called: the four calls return the same bits in every field they share because
 // they call the same helpers.
@@ -364,6 +364,139 @@ __device__ __forceinline__ void sh_search(const double* prof, const double* tab,
                 slot[3 * A + i] = t.ebar;
                 slot[4 * A + i] = t.gamma;
                 srank[i] = r;
+            }
+        }
+        // (one wave: the next round's winners, and the caller, read what these lanes wrote)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// ---- the initial slope (docs/profiles.md, "The initial slope") -----------------------------------------------------------------
+// The column of a diffused ramp of half-width m >= 1 cells is a difference of two rows of ONE table per age, F over
+// x = -(h + M)..(h + M): e_ij = (F[j + m][i] - F[j - m][i]) / (2 m de), formed in that order.  rp_col holds the two
+// rows' first entries of the lane's age (point jj reads hi[jj * A] and lo[jj * A]) and the divisor.  rp_column and
+// rp_sse are pf_column and pf_sse with that column: the operations of their text, in its order.
+struct rp_col {
+    const double *hi, *lo;
+    double den;
+    int A;
+    __device__ __forceinline__ double operator()(int jj) const { return (hi[(size_t)jj * A] - lo[(size_t)jj * A]) / den; }
+};
+
+__device__ __forceinline__ rp_col rp_col_of(const double* ftab, int A, int M, int m, int i, double de) {
+    rp_col c;
+    c.hi = ftab + (size_t)(M + m) * A + i;               // (row x = j + m sits at jj + M + m, jj = j + h)
+    c.lo = ftab + (size_t)(M - m) * A + i;
+    c.den = (double)(2 * m) * de;
+    c.A = A;
+    return c;
+}
+
+__device__ __forceinline__ pf_col rp_column(const double* prof, int np, int h, double de, const pf_lin& L, const rp_col& e) {
+    pf_col t;
+    double Se = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        Se += e(jj);
+    }
+    t.ebar = Se / L.dn;
+    double Ses = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double sc = (double)(jj - h) * de - L.sbar;
+        Ses += sc * (e(jj) - t.ebar);
+    }
+    t.gamma = Ses / L.Sss;
+    double See = 0.0, Sep = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double sc = (double)(jj - h) * de - L.sbar;
+        const double e2 = (e(jj) - t.ebar) - t.gamma * sc;
+        const double p2 = (p - L.pbar) - L.beta * sc;
+        See += e2 * e2;
+        Sep += e2 * p2;
+    }
+    t.See = See;
+    t.Sep = Sep;
+    return t;
+}
+
+__device__ __forceinline__ double rp_sse(const double* prof, int np, int h, double de, const rp_col& e, double a, double b,
+                                         double c0) {
+    double sse = 0.0;
+    for (int jj = 0; jj < np; ++jj) {
+        const double p = prof[jj];
+        if (p != p) continue;
+        const double s = (double)(jj - h) * de;
+        const double res = p - ((c0 + b * s) + a * e(jj));
+        sse += res * res;
+    }
+    return sse;
+}
+
+// the signed initial slope of a pair with m >= 1
+__device__ __forceinline__ double rp_slope_of(double a, double b, int m, double de) { return b + a / ((double)m * de); }
+
+// One wave, one profile: for every age i the half-width m_i among m = m0..M (m0 = 0 with the width free, 1 with the slope
+// given) with the smallest key - sse_im, or the distance | |b + a / (m de)| - slope |.  sh_search's shape: the LANES RUN
+// OVER THE (m, age) PAIRS, age-minor, 64 pairs a round; the lanes of a round that share an age sit A apart and the
+// shuffle argmin on (key, m) - a pair that cannot win counts as +inf, the smaller m wins a tie - leaves the round's
+// winner of every age known to its lowest lane; the winner merges into the wave's slot, where a later round (larger
+// m) wins only when strictly smaller.  The m = 0 pairs (all in the first round: A <= 64) read the erf table `etab`
+// (rows -h..h, in global memory) and run pf_column and pf_sse, the plain call's arithmetic; the others read `ftab`.
+// slot: SH_TERMS x A doubles (key, sse, a, b, c0 of the winner; sse NaN where no pair of the age can win), then A
+// ints (its m).  No atomics, no float sum across lanes.
+__device__ __forceinline__ void rp_search(const double* prof, const double* __restrict__ etab, const double* ftab, int np, int h,
+                                          int A, int M, bool given, double slope, double de, int lane, const pf_lin& L,
+                                          double* slot) {
+    int* sm = (int*)(slot + (size_t)SH_TERMS * A);
+    const int m0 = given ? 1 : 0;
+    const int P = A * (M + 1 - m0);
+    const int low = lane % A;                            // the lowest lane of this lane's age in a round
+    for (int q0 = 0; q0 < P; q0 += 64) {
+        const bool on = q0 + lane < P;
+        const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
+        const int r = q / A, i = q - r * A, m = m0 + r;
+        pf_col t;
+        double a, b, c0, sse;
+        if (m == 0) {
+            const double* col = etab + i;
+            t = pf_column(prof, np, h, de, L, col, A);
+            a = t.Sep / t.See;
+            pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
+            sse = pf_sse(prof, np, h, de, col, A, a, b, c0);
+        } else {
+            const rp_col e = rp_col_of(ftab, A, M, m, i, de);
+            t = rp_column(prof, np, h, de, L, e);
+            a = t.Sep / t.See;
+            pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
+            sse = rp_sse(prof, np, h, de, e, a, b, c0);
+        }
+        const bool alive = on && t.See > 0.0 && sse == sse;
+        double key = given ? fabs(fabs(rp_slope_of(a, b, m, de)) - slope) : sse;
+        if (!(alive && key == key)) key = INFINITY;
+        // the round's winner of every age: argmin over the lanes A apart (a lane past the end hands back its own value)
+        double km = key;
+        int mm = on ? m : INT_MAX;
+        for (int off = A; off < 64; off <<= 1) {
+            const double ok = __shfl_down(km, off, 64);
+            const int om = __shfl_down(mm, off, 64);
+            if (ok < km || (ok == km && om < mm)) { km = ok; mm = om; }
+        }
+        const int win = __shfl(mm, low, 64);
+        if (on && m == win) {                            // (one lane per age)
+            if (q0 == 0 || key < slot[i]) {              // (every age meets its first candidate in the first round)
+                slot[i] = key;
+                slot[A + i] = alive ? sse : __builtin_nan("");
+                slot[2 * A + i] = a;
+                slot[3 * A + i] = b;
+                slot[4 * A + i] = c0;
+                sm[i] = m;
             }
         }
         // (one wave: the next round's winners, and the caller, read what these lanes wrote)

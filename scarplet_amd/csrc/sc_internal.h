@@ -182,6 +182,7 @@ struct sc_ctx {
     DevBuf pf_z, pf_cells, pf_dir, pf_ages, pf_tab, pf_rows, pf_sse;
     DevBuf pf_shift;           // sc_fit_profiles_shift*: the chosen shift of every (cell, age) of a chunk, int8
     DevBuf pf_wt;              // sc_fit_profiles_robust*: the uploaded weight plane (the rest are the buffers above)
+    DevBuf pf_ftab;            // sc_fit_profiles_ramp*: the table of F over x = -(h + M)..(h + M)
     // (sc_lateral_offsets* borrows pf_z, pf_cells, pf_dir, pf_rows and pf_sse: its DEM, stations, rows and mse curves)
     // sc_fit_segments*: the call's own buffers - an uploaded DEM (the _dem call), ages and the erf table; per chunk of
     // whole segments the cells, (sa, ca), each cell's segment, the CSR arrays of cells and of 64-profile blocks, the

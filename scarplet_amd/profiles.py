@@ -27,6 +27,9 @@ SHIFT_FIT_DTYPE = np.dtype(SHIFT_FIT_FIELDS)
 # age of the plain weighted fit
 ROBUST_FIT_FIELDS = FIT_FIELDS + [("loss", np.float64), ("scale", np.float64), ("n_down", np.int32), ("ls_index", np.int32)]
 ROBUST_FIT_DTYPE = np.dtype(ROBUST_FIT_FIELDS)
+# ... and with max_width: the half-width of the best age's initial ramp, in cells and in data units, and its gradient
+RAMP_FIT_FIELDS = FIT_FIELDS + [("width_index", np.int32), ("width", np.float64), ("initial_slope", np.float64)]
+RAMP_FIT_DTYPE = np.dtype(RAMP_FIT_FIELDS)
 ROBUST_LOSSES = {"huber": (_lib.ROBUST_HUBER, 1.345), "tukey": (_lib.ROBUST_TUKEY, 4.685)}
 
 
@@ -207,9 +210,41 @@ def check_robust(shape, weights, robust, tuning, iterations, robust_scale, max_s
     return plane, loss, k, T, sigma
 
 
+def check_width(max_width, initial_slope, return_width, de, h, min_samples, max_shift=None, weights=None, robust=None):
+    """None for ``max_width=None``, else (M, mode, slope) for the library: M = floor(max_width / de), the range of the
+    initial ramp's half-width in cells; ValueError otherwise.  ``de``, ``h`` and ``min_samples`` as check_args returns
+    them."""
+    if max_width is None:
+        if initial_slope is not None:
+            raise ValueError("initial_slope needs max_width")
+        if return_width:
+            raise ValueError("return_width needs max_width")
+        return None
+    if max_shift is not None or weights is not None or robust is not None:
+        raise ValueError("max_width is not built together with max_shift, weights or robust")
+    mw = _number(max_width, "max_width")
+    if mw < 0:
+        raise ValueError("max_width must be >= 0, got %r" % (max_width,))
+    M = int(math.floor(mw / de))
+    top = min(_lib.PROFILE_MAX_WIDTH, h - min_samples)
+    if M > top:
+        raise ValueError("max_width %r is %d cells: more than %d (at most %d, and half_length less min_samples)"
+                         % (max_width, M, top, _lib.PROFILE_MAX_WIDTH))
+    if initial_slope is None:
+        return M, _lib.RAMP_FREE, 0.0
+    g = _number(initial_slope, "initial_slope")
+    if g <= 0:
+        raise ValueError("initial_slope is a magnitude and must be > 0, got %r" % (initial_slope,))
+    if M < 1:
+        raise ValueError("initial_slope needs a max_width of at least one cell, got %r at a cell size of %r" % (max_width, de))
+    return M, _lib.RAMP_SLOPE, g
+
+
 def _table(rows, nx, label=None):
     """The library's rows -> the Python table (row, col, the row's fields, height = 2 a; ``label`` when given)."""
-    fields = SHIFT_FIT_FIELDS if "shift" in rows.dtype.names else ROBUST_FIT_FIELDS if "loss" in rows.dtype.names else FIT_FIELDS
+    names = rows.dtype.names
+    fields = SHIFT_FIT_FIELDS if "shift" in names else ROBUST_FIT_FIELDS if "loss" in names else \
+        RAMP_FIT_FIELDS if "width" in names else FIT_FIELDS
     dt = np.dtype(fields + ([] if label is None else [("label", np.int32)]))
     out = np.zeros(len(rows), dtype=dt)
     for f in rows.dtype.names:
@@ -237,7 +272,7 @@ def _dem_of(data):
 
 def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4, return_curve=False,
                  device=0, max_shift=None, return_shift=False, weights=None, robust=None, tuning=None, iterations=8,
-                 robust_scale=None):
+                 robust_scale=None, max_width=None, initial_slope=None, return_width=False):
     """Fit the diffusion scarp to elevation profiles cut across the strike at ``cells`` (docs/profiles.md).
 
     ``data``: the DEMGrid.  ``cells``: linear indices ``r * nx + c``, a ``(rows, cols)`` tuple, or a bool plane (its
@@ -269,18 +304,38 @@ def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0,
     ``n_down`` (the points the best age down-weighted) and ``ls_index`` (the best age before the robust step), ``sse``
     is the weighted sum of squared residuals of the final fit, ``rmse = sqrt(loss / (n - 3))``, the curves are the
     losses, and ``status`` gains 16 where the scale is 0 (the row is the weighted least squares row) and is 33 where no
-    age kept enough points.  Neither is built together with ``max_shift``."""
+    age kept enough points.  Neither is built together with ``max_shift``.
+
+    ``max_width`` (data units; None: the scarp starts as a vertical step) fits the scarp that started as a ramp of
+    half-width ``L = m de``, ``m <= floor(max_width / de)`` cells (docs/profiles.md, "The initial slope"): ``a g(s; kt, L)``
+    with ``g = (F(s + L) - F(s - L)) / (2 L)``, ``F(x) = x erf(x / (2 sqrt(kt))) + 2 sqrt(kt / pi) exp(-x^2 / (4 kt))``,
+    for ``a erf(...)``.  With ``initial_slope=None`` the width is free: every age takes the ``m`` of its smallest sse, and one
+    degree of freedom goes to the width.  With ``initial_slope`` (a gradient magnitude, > 0: the angle of repose) every age
+    takes the ``m >= 1`` whose ``|b + a / (m de)|`` is nearest to it, at ``n - 3`` degrees of freedom.  The table gains
+    ``width_index`` (m of the best age), ``width`` (m de) and ``initial_slope`` (the signed ``b + a / (m de)``; +-inf at
+    ``m = 0``), the curves are the chosen pairs' sse, and ``status`` gains 8 where ``width_index`` is the end of the range.
+    ``return_width`` adds the (K, A) int8 plane of every age's m, after the curves.  Not built together with
+    ``max_shift``, ``weights`` or ``robust``."""
     z, de = _dem_of(data)
     args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
     D = check_shift(max_shift, return_shift, args[6], args[4], args[8])
     rb = check_robust(z.shape, weights, robust, tuning, iterations, robust_scale, max_shift)
+    rp = check_width(max_width, initial_slope, return_width, args[6], args[4], args[8], max_shift, weights, robust)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift, robust=rb)
+    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift, robust=rb, ramp=rp,
+                return_width=return_width)
 
 
-def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False, robust=None):
+def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False, robust=None, ramp=None,
+         return_width=False):
     idx, sa, ca, kt, h, w, de, d, ms = args
+    if ramp is not None:
+        M, mode, slope = ramp
+        rows, curve, plane = ctx.fit_profiles_ramp(idx, sa, ca, kt, h, w, de, d, ms, M, mode=mode, slope=slope,
+                                                   curve=bool(return_curve), width_plane=bool(return_width), z=z)
+        res = [_table(rows, nx, label)] + ([curve] if return_curve else []) + ([plane] if return_width else [])
+        return res[0] if len(res) == 1 else tuple(res)
     if robust is not None:
         plane, loss, k, T, sigma = robust
         rows, curve = ctx.fit_profiles_robust(idx, sa, ca, kt, h, w, de, d, ms, weights=plane, loss=loss, tuning=k, iterations=T,
