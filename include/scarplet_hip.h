@@ -858,6 +858,69 @@ int sc_fit_profiles_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const
                              double* out_sse, int8_t* out_width);
 
 /*
+ * The initial slope of the joint fit (docs/segments.md, "The initial slope"; scarplet_amd/csrc/sc_segment_ramp.hip): the
+ * fit of sc_fit_segments with the scarp of sc_fit_profiles_ramp,
+ *   z_c(s) = c0_c + b_c s + a g(s; kt, L),   L = m de,   m = 0..M a whole number of cells.
+ * The amplitude, the age AND the half-width are the segment's; every profile keeps its own intercept and far-field slope.
+ *   samples  the sampling and the usable-profile rule of sc_fit_segments; the erf table of sc_fit_profiles (by its launch)
+ *            serves m = 0, Ftab of sc_fit_profiles_ramp over x = -(h + M)..(h + M) serves m >= 1: e_cij = (Ftab[j + m][i] -
+ *            Ftab[j - m][i]) / ((double)(2 m) de), formed in that order
+ *   per profile c and pair (i, m): ebar, gamma, See_cim, Sep_cim as sc_fit_profiles (m = 0) and sc_fit_profiles_ramp (m >= 1)
+ *            form them, summed over ascending j in one lane; n, sbar, pbar, Sss, beta and p2 depend on neither i nor m and
+ *            are formed once
+ *   segment  a_im = (sum_c Sep_cim) / (sum_c See_cim); b_cim = beta_c - a_im gamma_cim; c0_cim = (pbar_c - a_im ebar_cim) -
+ *            b_cim sbar_c; sse_cim = sum_j of the squared explicit residuals; sse_im = sum_c sse_cim; bbar_im = (sum_c b_cim) /
+ *            (double)n_profiles.  Every sum over c is the blocked sum of sc_fit_segments (64 consecutive usable profiles
+ *            in input order in sequence, then the block sums in sequence; one profile: no addition).  A pair whose sum
+ *            See is not > 0, or whose sse is NaN, never wins
+ *   per age  SC_RAMP_FREE: m_i = argmin_m sse_im over m = 0..M, the first smallest winning.  SC_RAMP_SLOPE: over m = 1..M
+ *            the key | |bbar_im + a_im / ((double)m de)| - slope |, the first smallest winning: the constraint of
+ *            sc_fit_profiles_ramp with the segment's mean far-field slope for one profile's.  sse*_i = sse_{i, m_i}
+ *   choice   kt_index = argmin_i sse*_i, ties to the smaller index; dof = n - 2 n_profiles - 1 - (M > 0) with SC_RAMP_FREE
+ *            (the width is the segment's: one degree of freedom), n - 2 n_profiles - 1 with SC_RAMP_SLOPE; fitted when
+ *            n_profiles >= min_profiles and dof >= 1.  rmse, thr and the walks run along sse*, as in sc_fit_segments.
+ *            Status 1, 2 and 4 as sc_fit_segments; 8: width_index == M with M > 0
+ * M = 0 returns the bytes of sc_fit_segments in every shared field of rows, cell table and curve; a segment of one usable
+ * profile returns the kt_index, lo_index, hi_index, status, a, sse, rmse, width_index and initial_slope of
+ * sc_fit_profiles_ramp for that cell, and its b and c0 in the cell table, bit for bit.  out_rows: S rows; out_cells: K rows
+ * (b, c0 and sse of each profile at the best pair) or NULL; out_sse: S x A float64 (sse*) or NULL; out_width: S x A int8
+ * (m_i, 0 in the rows of status 1) or NULL.  Per cell the call parks the profile and four float64 terms per pair: 8 ((2h +
+ * 1) + 4 A (M + 1)) bytes, counted against SC_SEGMENT_MAX_PARK; chunks are whole segments and a single segment that needs
+ * more is SC_ERR_UNSUPPORTED (367 thousand cells at h = 100, 35 ages and M = 8).  Refused before any device work: what
+ * sc_fit_segments refuses, and what sc_fit_profiles_ramp refuses of M, mode and slope (SC_ERR_INVALID; M >
+ * SC_PROFILE_MAX_WIDTH: SC_ERR_UNSUPPORTED).  No atomics, no float sum across lanes: the same bytes on every run.  The
+ * buffers are those of sc_fit_segments and two of the call's own.  Timed as SC_K_PROFILE.
+ */
+typedef struct sc_segment_ramp_fit {
+    int32_t  label;
+    int32_t  n_cells;         /* cells of the segment                            */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n;               /* pooled valid points of the usable profiles      */
+    int32_t  dof;             /* n - 2 n_profiles - 1 - (M > 0 with the width free) */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) + 8 (width at its limit) */
+    double   kt, kt_lo, kt_hi;
+    double   a;               /* the segment's amplitude: its offset is 2 a      */
+    double   sse, rmse;       /* rmse = sqrt(sse / dof)                          */
+    int32_t  width_index;     /* m of the best age, in cells (0 where not fitted) */
+    double   width;           /* m de, the half-width L (NaN where not fitted)   */
+    double   initial_slope;   /* bbar + a / (m de), signed; copysign(inf, a) at m = 0; NaN where not fitted */
+} sc_segment_ramp_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_segments_ramp(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                         const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                         int h, int w, int M, int mode, double slope, double de, double delta, int min_samples,
+                         int min_profiles, sc_segment_ramp_fit* out_rows, sc_segment_cell* out_cells, double* out_sse,
+                         int8_t* out_width);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_segments_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                             const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                             long long S, const double* ages, int A, int h, int w, int M, int mode, double slope,
+                             double de, double delta, int min_samples, int min_profiles, sc_segment_ramp_fit* out_rows,
+                             sc_segment_cell* out_cells, double* out_sse, int8_t* out_width);
+
+/*
  * The search's float64 SNR surface at chosen cells (docs/surface.md, scarplet_amd/csrc/sc_surface.hip).
  *   t        n_par * n_ang descriptors, orientation-major (template of parameter ia and orientation ib at ib * n_par + ia:
  *            what Matcher.describe makes).  They become the context's template table as in sc_settle_pairs: nothing is

@@ -173,6 +173,17 @@ SEGMENT_SHIFT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_shift_ce
                                      "itemsize": C.sizeof(sc_segment_shift_cell)})
 
 
+class sc_segment_ramp_fit(C.Structure):
+    """One row of sc_fit_segments_ramp / sc_fit_segments_ramp_dem: sc_segment_fit, then the half-width of the best age."""
+    _fields_ = sc_segment_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
+
+
+SEGMENT_RAMP_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_ramp_fit._fields_],
+                                   "formats": [np.int32] * 9 + [np.float64] * 6 + [np.int32, np.float64, np.float64],
+                                   "offsets": [getattr(sc_segment_ramp_fit, f).offset for f, _ in sc_segment_ramp_fit._fields_],
+                                   "itemsize": C.sizeof(sc_segment_ramp_fit)})
+
+
 class sc_segment_boot(C.Structure):
     """One row of sc_bootstrap_segments / sc_bootstrap_segments_dem (docs/bootstrap.md)."""
     _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n_blocks", C.c_int32),
@@ -336,6 +347,14 @@ SIGNATURES = {
                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_segments_ramp": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                       C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp,
+                                       C.c_void_p]),
+    "sc_fit_segments_ramp_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                           C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
     "sc_bootstrap_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -804,6 +823,34 @@ class Context(object):
                 tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
         plane = self._fit_call("sc_fit_segments", head, rest, shift, shift_plane, (K, A), z)
         return (rows, tab, sse) if shift is None else (rows, tab, sse, plane)
+
+    def fit_segments_ramp(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles, width,
+                          mode=RAMP_FREE, slope=0.0, cell_table=False, curve=False, width_plane=False, z=None):
+        """sc_fit_segments_ramp on the context's DEM, or sc_fit_segments_ramp_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, cell table or None, curve or None, (S, A) int8 half-widths or None).  The arrays as fit_segments takes
+        them; ``width``: M, the range of the half-width in cells; ``slope`` is read with RAMP_SLOPE alone."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S = len(cells), len(ages), len(seg_label)
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
+        rows = np.zeros(S, dtype=SEGMENT_RAMP_FIT_DTYPE)
+        tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE) if cell_table else None
+        sse = np.empty((S, A), dtype=np.float64) if curve else None
+        plane = np.zeros((S, A), dtype=np.int8) if width_plane else None
+        llp = C.POINTER(C.c_longlong)
+        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), int(width), int(mode),
+                float(slope), float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None,
+                plane.ctypes.data_as(C.c_void_p) if width_plane else None]
+        name = "sc_fit_segments_ramp"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, tab, sse, plane
 
     # -- block-bootstrap intervals per segment (docs/bootstrap.md) -----------------------
     def bootstrap_segments(self, cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, ages, h, w, D, de,

@@ -1,6 +1,7 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
 // included by sc_profile.hip and sc_segment.hip alone - by sc_bootstrap.hip and sc_strike.hip for stage one, and by
-// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, and by sc_ramp.hip.  The
+// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, and by sc_ramp.hip and
+// sc_segment_ramp.hip, the initial slope of the two.  The
 // library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
 // in the order of its text wherever it is called: the four calls return the same bits in every field they share because
 // they call the same helpers.
@@ -27,6 +28,12 @@ int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx);
 // the launch of the erf table over j = -h..h (d_ages on the device; timed as SC_K_PROFILE)
 int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
 
+// ---- sc_ramp.hip, shared with sc_segment_ramp.hip ---------------------------------------------------------------------------
+// the rules of the width range M, the mode and the slope of sc_fit_profiles_ramp / sc_fit_segments_ramp
+int sc_rp_check(sc_ctx* ctx, const char* who, int h, int M, int mode, double slope, int min_samples);
+// the launch of the table of F over x = -ht..ht (d_ages on the device; timed as SC_K_PROFILE)
+int sc_rp_table(sc_ctx* ctx, const double* d_ages, int A, int ht, double de, double* d_ftab);
+
 // ---- sc_segment.hip, shared with sc_bootstrap.hip and sc_strike.hip ----------------------------------------------------------------------------
 // the argument checks of a segment call (D < 0: the call without a shift) and the cells of one segment its park holds
 int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
@@ -52,6 +59,8 @@ int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, c
                         const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st);
 int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
                        const double* d_tab, const sg_stage& st, int& launches);
+// k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
+void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
 
 // the degrees of freedom of a segment - or of a window of one, sc_strike.hip - of m usable profiles and n pooled points
 // (D = 0 in the call without a shift), and whether it is fitted

@@ -192,6 +192,8 @@ struct sc_ctx {
     DevBuf sg_z, sg_ages, sg_tab, sg_cells, sg_dir, sg_cseg, sg_start, sg_blk, sg_label, sg_prof, sg_int, sg_scal,
         sg_age, sg_list, sg_part, sg_tot, sg_tsse, sg_cnt, sg_rows, sg_out, sg_sse;
     DevBuf sg_shift;           // sc_fit_segments_shift*: d_ci parked beside the per-age terms, int8
+    // sc_fit_segments_ramp*: the sg_ buffers with A (M + 1) columns for A, the table of F and m_i of every (segment, age), int8
+    DevBuf sg_ftab, sg_width;
     // sc_bootstrap_segments*: stage one lives in the sg_ buffers; per chunk the CSR arrays of blocks over cells and of
     // segments over blocks, the block terms (See, Sep per block and age), every replicate's index and amplitude, the
     // histograms and the rows

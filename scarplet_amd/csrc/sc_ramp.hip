@@ -95,7 +95,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_ramp(const double* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static int rp_check(sc_ctx* ctx, const char* who, int h, int M, int mode, double slope, int min_samples) {
+int sc_rp_check(sc_ctx* ctx, const char* who, int h, int M, int mode, double slope, int min_samples) {
     if (M < 0) return sc_fail(ctx, SC_ERR_INVALID, "%s: the width range must be >= 0 cells", who);
     if (M > SC_PROFILE_MAX_WIDTH)
         return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a half-width of %d cells, more than %d", who, M, SC_PROFILE_MAX_WIDTH);
@@ -107,6 +107,14 @@ static int rp_check(sc_ctx* ctx, const char* who, int h, int M, int mode, double
         if (M < 1) return sc_fail(ctx, SC_ERR_INVALID, "%s: a given slope needs a width range of at least one cell", who);
         if (!(isfinite(slope) && slope > 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "%s: the slope must be finite and > 0", who);
     }
+    return SC_OK;
+}
+
+int sc_rp_table(sc_ctx* ctx, const double* d_ages, int A, int ht, double de, double* d_ftab) {
+    sc_prof_begin(ctx, SC_K_PROFILE);
+    k_rp_table<<<std::max(1, std::min(256, ((2 * ht + 1) * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, ht, de, d_ftab);
+    SC_HIP(ctx, hipGetLastError());
+    sc_prof_end(ctx, 1);
     return SC_OK;
 }
 
@@ -143,10 +151,7 @@ static int rp_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
     // (the erf table of the m = 0 pairs is the plain call's, by its launch: the same bits)
     if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_etab))) return rc;
-    sc_prof_begin(ctx, SC_K_PROFILE);
-    k_rp_table<<<std::max(1, std::min(256, (nt * A + 255) / 256)), 256, 0, ctx->stream>>>(d_ages, A, ht, de, d_ftab);
-    SC_HIP(ctx, hipGetLastError());
-    sc_prof_end(ctx, 1);
+    if ((rc = sc_rp_table(ctx, d_ages, A, ht, de, d_ftab))) return rc;
 
     std::vector<double> dir;
     for (long long k0 = 0; k0 < K; k0 += chunk) {
@@ -187,7 +192,7 @@ static int rp_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                    int8_t* out_width) {
     int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
-    if ((rc = rp_check(ctx, who, h, M, mode, slope, min_samples))) return rc;
+    if ((rc = sc_rp_check(ctx, who, h, M, mode, slope, min_samples))) return rc;
     if (K == 0) return SC_OK;
     const double* z_dev = ctx->z_dev;
     if (z) {

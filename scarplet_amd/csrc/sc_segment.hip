@@ -452,9 +452,13 @@ int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int 
         k_partial<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, de, min_samples, d_tab, st.prof,
                                                            st.cn, st.used, st.scal, st.planes);
     if (m) ++launches;
-    k_sg_rank<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.Sc, st.cn, st.used, st.list, st.cnt);
+    sc_sg_rank_launch(ctx, st);
     ++launches;
     return SC_OK;
+}
+
+void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st) {
+    k_sg_rank<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.Sc, st.cn, st.used, st.list, st.cnt);
 }
 
 // the dynamic-LDS limit of the parking kernel, raised before the first chunk

@@ -1,0 +1,480 @@
+// sc_fit_segments_ramp*: the initial slope of sl.fit_segments (docs/segments.md, "The initial slope").
+//
+// The joint fit of sc_fit_segments with the scarp of sc_fit_profiles_ramp: z_c(s) = c0_c + b_c s + a g(s; kt, L), L = m de.
+// The amplitude, the age AND the half-width are the segment's, so nothing is searched per profile: every (m, age) pair
+// is one column of the joint problem, C = A (M + 1) columns where sc_fit_segments has A.  The pieces are those of sc_fit.h.
+//   k_sr_partial  one wave per cell: pf_cut (the profile goes to LDS and is PARKED), pf_moments and pf_line without a
+//                 column, once; then the lanes run over the (m, age) pairs, age-minor, 64 a round: pf_column on the erf
+//                 table at m = 0 - the plain call's arithmetic -, rp_column on the table of F at m >= 1.  Parks ebar,
+//                 gamma, See, Sep of every pair, pair-minor: a round's 64 lanes write 64 neighbouring doubles
+//   (k_sg_rank, sc_segment.hip)
+//   k_sr_sum1     one wave per block of 64 consecutive usable profiles and 64 columns: the block's terms summed in
+//                 sequence from the first
+//   k_sr_sum2     one wave per segment and 64 columns: the block sums in sequence from the first.  k_sg_sum1 and
+//                 k_sg_sum2 with a column count: the same additions in the same order per column
+//   k_sr_resid    one wave per cell: the parked profile back into LDS, lanes over the pairs, pf_slope with the segment's
+//                 a_im, then pf_sse / rp_sse; sse_cim takes the place of See_cim and b_cim that of Sep_cim
+//   (k_sr_sum1 and k_sr_sum2 again, on sse_cim and b_cim)
+//   k_sr_choose   one wave per segment, lane i age i: the argmin over m on (key, m) in ascending m - the key is sse_im, or
+//                 the distance of the segment's mean initial slope from the given one -, then pf_choose along sse*, the
+//                 row, and lanes over the segment's cells for the cell table at the best pair
+// The table of F sits in LDS when it fits PF_TAB_LDS bytes, as in k_pf_ramp; the erf table of the m = 0 pairs stays in
+// global memory.  No atomics at all, no float sum across lanes.
+#include "sc_fit.h"
+#include <math.h>
+#include <algorithm>
+
+#define SR_BLOCK 64                      // usable profiles per block of the segmented sum (SG_BLOCK)
+#define SR_MAX_SEGS (1ll << 20)          // segments per chunk
+#define SR_MAX_TOTALS (1ll << 25)        // (blocks + segments) x columns per chunk: bounds the partials and totals
+
+// the degrees of freedom of a segment of m usable profiles and n pooled points: the free width is the segment's, one
+__device__ __forceinline__ int sr_dof(int m, int n, int M, bool given) { return n - 2 * m - 1 - (!given && M > 0 ? 1 : 0); }
+
+template <bool TAB_LDS>
+__global__ __launch_bounds__(PF_THREADS) void k_sr_partial(const double* __restrict__ z, int ny, int nx,
+                                                           const long long* __restrict__ cells,
+                                                           const double* __restrict__ dir, long long K, int A, int h,
+                                                           int w, int M, double de, int min_samples,
+                                                           const double* __restrict__ etab,
+                                                           const double* __restrict__ ftab_g, double* __restrict__ prof_g,
+                                                           int* __restrict__ cn, int* __restrict__ used,
+                                                           double* __restrict__ scal, double* __restrict__ planes) {
+    const int np = 2 * h + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const pf_lds L = pf_stage<TAB_LDS, false>(ftab_g, np, 2 * (h + M) + 1, A);
+    const int C = A * (M + 1);
+    const size_t stride = (size_t)K * C;                 // one per-cell-and-pair plane
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * PF_WAVES + wave;
+        const bool act = kc < K;
+        if (act) pf_cut(z, ny, nx, cells[kc], dir, kc, h, w, lane, L.prof, prof_g);
+        __syncthreads();
+        if (act) {
+            // what depends on neither the age nor the half-width, once
+            const pf_mom mo = pf_moments<false>(L.prof, np, h, de, nullptr, A);
+            const bool ok = mo.n_neg >= min_samples && mo.n_pos >= min_samples;
+            if (lane == 0) {
+                cn[kc] = mo.n;
+                used[kc] = ok ? 1 : 0;
+            }
+            if (ok) {
+                pf_col t;
+                const pf_lin f = pf_line<false>(L.prof, np, h, de, mo, nullptr, A, t);
+                if (lane == 0) {
+                    scal[3 * kc] = f.sbar;
+                    scal[3 * kc + 1] = f.pbar;
+                    scal[3 * kc + 2] = f.beta;
+                }
+                for (int q0 = 0; q0 < C; q0 += 64) {
+                    const bool on = q0 + lane < C;
+                    const int q = on ? q0 + lane : C - 1;    // lanes beyond the pairs repeat the last one and are ignored
+                    const int m = q / A, i = q - m * A;
+                    if (m == 0)
+                        t = pf_column(L.prof, np, h, de, f, etab + i, A);
+                    else
+                        t = rp_column(L.prof, np, h, de, f, rp_col_of(L.tab, A, M, m, i, de));
+                    if (on) {
+                        const size_t o = (size_t)kc * C + q;
+                        planes[o] = t.ebar;
+                        planes[stride + o] = t.gamma;
+                        planes[2 * stride + o] = t.See;
+                        planes[3 * stride + o] = t.Sep;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// block g of SR_BLOCK consecutive usable profiles of its segment, 64 of the C columns: P planes summed in sequence from
+// the first term.  Work item t = g NC + (the chunk of columns)
+template <int P>
+__global__ __launch_bounds__(64) void k_sr_sum1(const double* __restrict__ src, size_t stride, const int* __restrict__ list,
+                                                const int* __restrict__ seg_start, const int* __restrict__ blk_start,
+                                                const int* __restrict__ cnt, long long S, long long G, int C,
+                                                double* __restrict__ part) {
+    const int lane = threadIdx.x;
+    const long long NC = (C + 63) / 64;
+    for (long long t = blockIdx.x; t < G * NC; t += gridDim.x) {
+        const long long g = t / NC;
+        const int q = (int)(t - g * NC) * 64 + lane;
+        long long lo = 0, hi = S;                        // the segment with blk_start[s] <= g < blk_start[s + 1]
+        while (lo < hi) {
+            const long long mid = (lo + hi) >> 1;
+            if ((long long)blk_start[mid + 1] <= g) lo = mid + 1; else hi = mid;
+        }
+        const long long s = lo;
+        const int m = cnt[2 * s];
+        const int r0 = (int)(g - blk_start[s]) * SR_BLOCK;
+        if (r0 >= m || q >= C) continue;
+        const int r1 = min(m, r0 + SR_BLOCK);
+        const int* ls = list + seg_start[s];
+        double acc[P];
+        {
+            const size_t o = (size_t)ls[r0] * C + q;
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] = src[p * stride + o];
+        }
+        for (int r = r0 + 1; r < r1; ++r) {
+            const size_t o = (size_t)ls[r] * C + q;
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] += src[p * stride + o];
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) part[((size_t)g * P + p) * C + q] = acc[p];
+    }
+}
+
+// the block sums of each segment in sequence from the first.  Work item t = s NC + (the chunk of columns)
+template <int P>
+__global__ __launch_bounds__(64) void k_sr_sum2(const double* __restrict__ part, const int* __restrict__ blk_start,
+                                                const int* __restrict__ cnt, long long S, int C, double* __restrict__ tot) {
+    const int lane = threadIdx.x;
+    const long long NC = (C + 63) / 64;
+    for (long long t = blockIdx.x; t < S * NC; t += gridDim.x) {
+        const long long s = t / NC;
+        const int q = (int)(t - s * NC) * 64 + lane;
+        const int nb = (cnt[2 * s] + SR_BLOCK - 1) / SR_BLOCK;
+        if (nb == 0 || q >= C) continue;
+        const size_t g0 = (size_t)blk_start[s];
+        double acc[P];
+#pragma unroll
+        for (int p = 0; p < P; ++p) acc[p] = part[(g0 * P + p) * C + q];
+        for (int b = 1; b < nb; ++b) {
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] += part[((g0 + b) * P + p) * C + q];
+        }
+#pragma unroll
+        for (int p = 0; p < P; ++p) tot[((size_t)s * P + p) * C + q] = acc[p];
+    }
+}
+
+// the explicit residuals of every usable cell of a fitted segment at every pair, with the segment's a_im: sse_cim replaces
+// See_cim and b_cim replaces Sep_cim
+template <bool TAB_LDS>
+__global__ __launch_bounds__(PF_THREADS) void k_sr_resid(const double* __restrict__ prof_g, const int* __restrict__ cseg,
+                                                         const int* __restrict__ used, const int* __restrict__ cnt,
+                                                         const double* __restrict__ scal, double* __restrict__ planes,
+                                                         const double* __restrict__ tot, long long K, int A, int h, int M,
+                                                         int given, double de, int min_profiles,
+                                                         const double* __restrict__ etab,
+                                                         const double* __restrict__ ftab_g) {
+    const int np = 2 * h + 1;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const pf_lds L = pf_stage<TAB_LDS, false>(ftab_g, np, 2 * (h + M) + 1, A);
+    const int C = A * (M + 1);
+    const size_t stride = (size_t)K * C;
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * PF_WAVES + wave;
+        bool act = kc < K;
+        int s = 0;
+        if (act) {
+            s = cseg[kc];
+            const int m = cnt[2 * s];
+            act = used[kc] != 0 && sg_fitted(m, sr_dof(m, cnt[2 * s + 1], M, given != 0), min_profiles);
+        }
+        if (act)
+            for (int jj = lane; jj < np; jj += 64) L.prof[jj] = prof_g[(size_t)kc * np + jj];
+        __syncthreads();
+        if (act) {
+            const double sbar = scal[3 * kc], pbar = scal[3 * kc + 1], beta = scal[3 * kc + 2];
+            for (int q0 = 0; q0 < C; q0 += 64) {
+                const bool on = q0 + lane < C;
+                const int q = on ? q0 + lane : C - 1;        // lanes beyond the pairs repeat the last one and are ignored
+                const int m = q / A, i = q - m * A;
+                const size_t o = (size_t)kc * C + q;
+                const double See = tot[((size_t)s * 2) * C + q], Sep = tot[((size_t)s * 2 + 1) * C + q];
+                const double a = Sep / See;
+                double b, c0, sse;
+                pf_slope(sbar, pbar, beta, planes[o], planes[stride + o], a, b, c0);
+                if (m == 0)
+                    sse = pf_sse(L.prof, np, h, de, etab + i, A, a, b, c0);
+                else
+                    sse = rp_sse(L.prof, np, h, de, rp_col_of(L.tab, A, M, m, i, de), a, b, c0);
+                if (on) {
+                    planes[2 * stride + o] = sse;
+                    planes[3 * stride + o] = b;
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// the half-width of every age, the age of each segment, its interval and its row; the cell table at the best pair.
+// tot: See and Sep of every (segment, pair); tsum: sse and the sum of b_c
+__global__ __launch_bounds__(64) void k_sr_choose(const int* __restrict__ seg_start, const int* __restrict__ label,
+                                                  const int* __restrict__ cnt, long long S, long long K,
+                                                  const double* __restrict__ tot, const double* __restrict__ tsum,
+                                                  const double* __restrict__ ages, int A, int M, int given, double slope,
+                                                  double de, double delta, int min_profiles,
+                                                  const long long* __restrict__ cells, const int* __restrict__ cn,
+                                                  const int* __restrict__ used, const double* __restrict__ scal,
+                                                  const double* __restrict__ planes, sc_segment_ramp_fit* __restrict__ rows,
+                                                  sc_segment_cell* __restrict__ out_cells, double* __restrict__ curve,
+                                                  signed char* __restrict__ widths) {
+    const int lane = threadIdx.x;
+    const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
+    const double nan = __builtin_nan("");
+    const int C = A * (M + 1);
+    const size_t stride = (size_t)K * C;
+    const int m0 = given ? 1 : 0;
+    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+        const int start = seg_start[s], end = seg_start[s + 1];
+        const int m = cnt[2 * s], n = cnt[2 * s + 1];
+        const int dof = sr_dof(m, n, M, given != 0);
+        const bool fitted = sg_fitted(m, dof, min_profiles);
+        // (the rows were cleared: their padding is part of what the caller compares)
+        sc_segment_ramp_fit* out = rows + s;
+        int best = -1, mi = 0, m_best = 0;
+        double a_best = nan;
+        pf_pick k = {-1, -1, -1, nan};
+        int status = 1;
+        double a = nan, sse = nan, bbar = nan;
+        if (fitted) {
+            // the first smallest key over m in ascending order; a pair that cannot win counts as +inf
+            const double dm = (double)m;
+            double kbest = INFINITY;
+            for (int mm = m0; mm <= M; ++mm) {
+                const size_t q = (size_t)mm * A + ia;
+                const double See = tot[((size_t)s * 2) * C + q], Sep = tot[((size_t)s * 2 + 1) * C + q];
+                const double ssem = tsum[((size_t)s * 2) * C + q], bb = tsum[((size_t)s * 2 + 1) * C + q] / dm;
+                const double am = Sep / See;
+                const bool alive = See > 0.0 && ssem == ssem;
+                double key = given ? fabs(fabs(rp_slope_of(am, bb, mm, de)) - slope) : ssem;
+                if (!(alive && key == key)) key = INFINITY;
+                if (mm == m0 || key < kbest) {
+                    kbest = key;
+                    sse = alive ? ssem : nan;
+                    a = am;
+                    bbar = bb;
+                    mi = mm;
+                }
+            }
+            k = pf_choose(sse, lane, A, delta, dof);
+            best = k.best;
+            a_best = __shfl(a, best, 64);
+            m_best = __shfl(mi, best, 64);
+            status = pf_open(k, A) + (M > 0 && m_best == M ? 8 : 0);
+        }
+        if (curve && lane < A) curve[s * A + lane] = sse;
+        if (widths && lane < A) widths[s * A + lane] = (signed char)(fitted ? mi : 0);
+        if (lane == (fitted ? best : 0)) {
+            out->label = label[s];
+            out->n_cells = end - start;
+            out->n_profiles = m;
+            out->n = n;
+            out->dof = dof;
+            out->kt_index = k.best;
+            out->lo_index = k.lo;
+            out->hi_index = k.hi;
+            out->status = status;
+            out->kt = fitted ? ages[k.best] : nan;
+            out->kt_lo = fitted ? ages[k.lo] : nan;
+            out->kt_hi = fitted ? ages[k.hi] : nan;
+            out->a = a;
+            out->sse = sse;
+            out->rmse = fitted ? sqrt(sse / (double)dof) : nan;
+            out->width_index = fitted ? mi : 0;
+            out->width = fitted ? (double)mi * de : nan;
+            out->initial_slope = fitted ? (mi ? rp_slope_of(a, bbar, mi, de) : copysign(INFINITY, a)) : nan;
+        }
+        if (!out_cells) continue;
+        for (int c = start + lane; c < end; c += 64) {
+            sc_segment_cell* oc = out_cells + c;
+            const int u = used[c];
+            double b = nan, c0 = nan, csse = nan;
+            if (fitted && u) {
+                const size_t o = (size_t)c * C + (size_t)m_best * A + best;
+                pf_slope(scal[3 * c], scal[3 * c + 1], scal[3 * c + 2], planes[o], planes[stride + o], a_best, b, c0);
+                csse = planes[2 * stride + o];
+            }
+            oc->cell = cells[c];
+            oc->used = u;
+            oc->n = cn[c];
+            oc->b = b; oc->c0 = c0; oc->sse = csse;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+static unsigned sr_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
+static unsigned sr_grid_cells(long long m) {
+    return (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
+}
+
+static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
+                  const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
+                  int w, int M, int mode, double slope, double de, double delta, int min_samples, int min_profiles,
+                  sc_segment_ramp_fit* out_rows, sc_segment_cell* out_cells, double* out_sse, int8_t* out_width) {
+    if (S == 0) return SC_OK;
+    const int given = mode == SC_RAMP_SLOPE ? 1 : 0;
+    const int np = 2 * h + 1, ht = h + M, nt = 2 * ht + 1, C = A * (M + 1);
+    const size_t etab_bytes = sizeof(double) * (size_t)np * A, ftab_bytes = sizeof(double) * (size_t)nt * A;
+    const long long cap = sc_sg_cap_cells(C, h, -1);
+    const long long NC = (C + 63) / 64;
+    int rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_tab, etab_bytes))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_ftab, ftab_bytes))) return rc;
+    double* d_ages = (double*)ctx->sg_ages.p;
+    double* d_etab = (double*)ctx->sg_tab.p;
+    double* d_ftab = (double*)ctx->sg_ftab.p;
+
+    const bool tab_lds = ftab_bytes <= PF_TAB_LDS;
+    const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds);
+    const auto k_partial = tab_lds ? k_sr_partial<true> : k_sr_partial<false>;
+    const auto k_resid = tab_lds ? k_sr_resid<true> : k_sr_resid<false>;
+    if ((rc = sc_lds_attr(ctx, (const void*)k_partial, lds))) return rc;
+    if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
+
+    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
+    // (the erf table of the m = 0 pairs is the plain call's, by its launch: the same bits)
+    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_etab))) return rc;
+    if ((rc = sc_rp_table(ctx, d_ages, A, ht, de, d_ftab))) return rc;
+
+    sg_stage st;
+    std::vector<int> cseg, blk;
+    for (long long s0 = 0; s0 < S;) {
+        // a chunk of whole segments: as many as fit the parked bytes, and the totals
+        long long s1 = s0 + 1;
+        long long nblk = (seg_start[s1] - seg_start[s0] + SR_BLOCK - 1) / SR_BLOCK;
+        while (s1 < S && s1 - s0 < SR_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) {
+            const long long nb = (seg_start[s1 + 1] - seg_start[s1] + SR_BLOCK - 1) / SR_BLOCK;
+            if ((nblk + nb + (s1 + 1 - s0)) * C > SR_MAX_TOTALS) break;
+            nblk += nb;
+            ++s1;
+        }
+        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
+        blk.resize((size_t)Sc + 1);
+        cseg.resize((size_t)m);
+        blk[0] = 0;
+        for (long long s = 0; s < Sc; ++s) {
+            const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
+            blk[s + 1] = blk[s] + (int)((a1 - a0 + SR_BLOCK - 1) / SR_BLOCK);
+            for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
+        }
+        const long long G = blk[Sc];
+        const size_t mC = (size_t)m * C;
+        // (the stage of sc_fit_segments with C columns for A: the same buffers, four planes of m C doubles)
+        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, C, h, -1, st))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * C))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * C))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * 2 * (size_t)Sc * C))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_ramp_fit) * (size_t)Sc))) return rc;
+        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, sizeof(sc_segment_cell) * (size_t)m))) return rc;
+        if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
+        if (out_width && (rc = sc_ensure(ctx, ctx->sg_width, (size_t)Sc * A))) return rc;
+        int* d_cseg = (int*)ctx->sg_cseg.p;
+        int* d_blk = (int*)ctx->sg_blk.p;
+        double* d_part = (double*)ctx->sg_part.p;
+        double* d_tot = (double*)ctx->sg_tot.p;
+        double* d_tsum = (double*)ctx->sg_tsse.p;
+        sc_segment_ramp_fit* d_rows = (sc_segment_ramp_fit*)ctx->sg_rows.p;
+        sc_segment_cell* d_out = out_cells ? (sc_segment_cell*)ctx->sg_out.p : nullptr;
+        double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
+        signed char* d_width = out_width ? (signed char*)ctx->sg_width.p : nullptr;
+
+        if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
+        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_ramp_fit) * (size_t)Sc, ctx->stream));
+
+        const unsigned gcell = sr_grid_cells(m);
+        int launches = 0;
+        sc_prof_begin(ctx, SC_K_PROFILE);
+        if (m) {
+            k_partial<<<gcell, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, M, de, min_samples, d_etab,
+                                                              d_ftab, st.prof, st.cn, st.used, st.scal, st.planes);
+            ++launches;
+        }
+        sc_sg_rank_launch(ctx, st);
+        ++launches;
+        if (G) {
+            k_sr_sum1<2><<<sr_grid(G * NC), 64, 0, ctx->stream>>>(st.planes + 2 * mC, mC, st.list, st.seg, d_blk, st.cnt, Sc, G, C, d_part);
+            k_sr_sum2<2><<<sr_grid(Sc * NC), 64, 0, ctx->stream>>>(d_part, d_blk, st.cnt, Sc, C, d_tot);
+            k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_cseg, st.used, st.cnt, st.scal, st.planes, d_tot, m, A, h, M,
+                                                            given, de, min_profiles, d_etab, d_ftab);
+            k_sr_sum1<2><<<sr_grid(G * NC), 64, 0, ctx->stream>>>(st.planes + 2 * mC, mC, st.list, st.seg, d_blk, st.cnt, Sc, G, C, d_part);
+            k_sr_sum2<2><<<sr_grid(Sc * NC), 64, 0, ctx->stream>>>(d_part, d_blk, st.cnt, Sc, C, d_tsum);
+            launches += 5;
+        }
+        k_sr_choose<<<sr_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tsum, d_ages, A, M, given, slope, de,
+                                                        delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes, d_rows,
+                                                        d_out, d_sse, d_width);
+        ++launches;
+        SC_HIP(ctx, hipGetLastError());
+        sc_prof_end(ctx, launches);
+        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_ramp_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_cells && m)
+            SC_HIP(ctx, hipMemcpyAsync(out_cells + k0, d_out, sizeof(sc_segment_cell) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        if (out_sse)
+            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)s0 * A, d_sse, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
+                                       ctx->stream));
+        if (out_width)
+            SC_HIP(ctx, hipMemcpyAsync(out_width + (size_t)s0 * A, d_width, (size_t)Sc * A, hipMemcpyDeviceToHost, ctx->stream));
+        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s0 = s1;
+    }
+    return SC_OK;
+}
+
+// The two calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
+// host, uploaded - or on the context's DEM (z null)
+static int sr_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                   const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                   const double* ages, int A, int h, int w, int M, int mode, double slope, double de, double delta,
+                   int min_samples, int min_profiles, sc_segment_ramp_fit* out_rows, sc_segment_cell* out_cells,
+                   double* out_sse, int8_t* out_width) {
+    int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, -1, de, delta, min_samples,
+                         min_profiles, out_rows);
+    if (rc) return rc;
+    if ((rc = sc_rp_check(ctx, who, h, M, mode, slope, min_samples))) return rc;
+    const long long cap = sc_sg_cap_cells(A * (M + 1), h, -1);
+    for (long long s = 0; s < S; ++s)
+        if (seg_start[s + 1] - seg_start[s] > cap)
+            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h, A and M", who,
+                           seg_start[s + 1] - seg_start[s], cap);
+    const double* z_dev = ctx->z_dev;
+    if (z) {
+        if (S == 0) return SC_OK;
+        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
+        z_dev = (const double*)ctx->sg_z.p;
+    } else {
+        SC_HIP(ctx, hipSetDevice(ctx->device));
+    }
+    return sr_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, M, mode, slope, de, delta, min_samples,
+                  min_profiles, out_rows, out_cells, out_sse, out_width);
+}
+
+extern "C" int sc_fit_segments_ramp(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                                    const long long* seg_start, const int32_t* seg_label, long long S, const double* ages,
+                                    int A, int h, int w, int M, int mode, double slope, double de, double delta,
+                                    int min_samples, int min_profiles, sc_segment_ramp_fit* out_rows,
+                                    sc_segment_cell* out_cells, double* out_sse, int8_t* out_width) {
+    if (!ctx) return SC_ERR_INVALID;
+    int rc = sc_pf_whole_grid(ctx, "sc_fit_segments_ramp");
+    if (rc) return rc;
+    return sr_call(ctx, "sc_fit_segments_ramp", nullptr, ctx->g.ny, ctx->g.nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A,
+                   h, w, M, mode, slope, de, delta, min_samples, min_profiles, out_rows, out_cells, out_sse, out_width);
+}
+
+extern "C" int sc_fit_segments_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells,
+                                        const double* sa, const double* ca, long long K, const long long* seg_start,
+                                        const int32_t* seg_label, long long S, const double* ages, int A, int h, int w,
+                                        int M, int mode, double slope, double de, double delta, int min_samples,
+                                        int min_profiles, sc_segment_ramp_fit* out_rows, sc_segment_cell* out_cells,
+                                        double* out_sse, int8_t* out_width) {
+    if (!ctx || !z) return SC_ERR_INVALID;
+    return sr_call(ctx, "sc_fit_segments_ramp_dem", z, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, M, mode,
+                   slope, de, delta, min_samples, min_profiles, out_rows, out_cells, out_sse, out_width);
+}

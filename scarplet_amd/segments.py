@@ -21,6 +21,10 @@ CELL_DTYPE = np.dtype(CELL_FIELDS)
 # ... and with max_shift: each profile's shift at the segment's best age, in cells and in data units
 SHIFT_CELL_FIELDS = CELL_FIELDS[:-1] + [("shift_index", np.int32), ("shift", np.float64), ("label", np.int32)]
 SHIFT_CELL_DTYPE = np.dtype(SHIFT_CELL_FIELDS)
+# ... and with max_width: the half-width of the segment's initial ramp, in cells and in data units, and its gradient
+RAMP_FIT_FIELDS = FIT_FIELDS[:-1] + [("width_index", np.int32), ("width", np.float64), ("initial_slope", np.float64),
+                                     ("height", np.float64)]
+RAMP_FIT_DTYPE = np.dtype(RAMP_FIT_FIELDS)
 
 
 def _labels_of(labels, idx, ny, nx):
@@ -71,8 +75,20 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta,
             np.ascontiguousarray(seg_label, dtype=np.int32), kt, h, w, de, d, ms, mp, order, kept)
 
 
+def check_park(args, M):
+    """The park cap of a call with ``max_width``: 8 ((2h + 1) + 4 A (M + 1)) bytes per cell, a segment at a time
+    (sc_fit_segments_ramp).  ``args`` as check_args returns them; ValueError for a segment above the cap."""
+    seg_start, kt, h = args[3], args[5], args[6]
+    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt) * (M + 1)))
+    counts = np.diff(seg_start)
+    if len(counts) and counts.max() > cap:
+        raise ValueError("a segment of %d cells: more than %d at this half_length, number of ages and max_width"
+                         % (counts.max(), cap))
+
+
 def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
-                 min_profiles=1, return_cells=False, return_curve=False, device=0, max_shift=None, return_shift=False):
+                 min_profiles=1, return_cells=False, return_curve=False, device=0, max_shift=None, return_shift=False,
+                 max_width=None, initial_slope=None, return_width=False):
     """Fit ONE diffusion scarp per segment to the profiles cut across the strike at its cells (docs/segments.md).
 
     ``data``, ``cells``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta`` and ``min_samples`` are those of
@@ -94,27 +110,46 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     every age as ``sl.fit_profiles(..., max_shift=...)`` chooses it; the joint fit then has each profile's erf moved by
     its shift.  ``dof`` loses one more per profile when the range is not 0, ``status`` gains 8 where a usable profile's
     shift at the best age is the end of the range, the cell table gains ``shift_index`` and ``shift``, and
-    ``return_shift`` adds the (K, A) int8 plane of every cell's shift at every age, in input order, last."""
+    ``return_shift`` adds the (K, A) int8 plane of every cell's shift at every age, in input order, last.
+
+    ``max_width`` (data units; None: the scarp starts as a vertical step) fits the scarp that started as a ramp of
+    half-width ``L = m de``, ``m <= floor(max_width / de)`` cells, the model of ``sl.fit_profiles(..., max_width=...)``
+    with the half-width shared by the segment like the amplitude and the age (docs/segments.md, "The initial slope").
+    With ``initial_slope=None`` the width is free: every age takes the ``m`` of its smallest pooled sse, and one degree of
+    freedom goes to the width.  With ``initial_slope`` (a gradient magnitude, > 0) every age takes the ``m >= 1`` whose
+    ``|bbar + a / (m de)|`` is nearest to it, ``bbar`` the mean far-field slope of the segment's profiles.  The table
+    gains ``width_index``, ``width`` (m de) and ``initial_slope`` (signed; +-inf at ``m = 0``) ahead of ``height``, the
+    curves are the chosen pairs' sse, ``status`` gains 8 where ``width_index`` is the end of the range, and
+    ``return_width`` adds the (S, A) int8 plane of every age's m, last.  Not built together with ``max_shift``."""
     z, de = profiles._dem_of(data)
     args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles,
                       shift=max_shift is not None)
     D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
+    rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
+    if rp is not None:
+        check_park(args, rp[0])
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift)
+    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift,
+                ramp=rp, return_width=return_width)
 
 
-def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False):
+def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False, ramp=None, return_width=False):
     idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
     plane = None
-    if shift is None:
+    if ramp is not None:
+        M, mode, slope = ramp
+        rows, tab, curve, widths = ctx.fit_segments_ramp(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, M, mode=mode,
+                                                         slope=slope, cell_table=bool(return_cells), curve=bool(return_curve),
+                                                         width_plane=bool(return_width), z=z)
+    elif shift is None:
         rows, tab, curve = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
                                             cell_table=bool(return_cells), curve=bool(return_curve), z=z)
     else:
         rows, tab, curve, plane = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
                                                    cell_table=bool(return_cells), curve=bool(return_curve), z=z,
                                                    shift=shift, shift_plane=bool(return_shift))
-    out = np.zeros(len(rows), dtype=FIT_DTYPE)
+    out = np.zeros(len(rows), dtype=FIT_DTYPE if ramp is None else RAMP_FIT_DTYPE)
     for f in rows.dtype.names:
         out[f] = rows[f]
     out["height"] = 2.0 * rows["a"]
@@ -137,4 +172,6 @@ def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_s
         back = np.empty(len(order), dtype=np.int64)
         back[order] = np.arange(len(order))
         res.append(np.ascontiguousarray(plane[back]))
+    if return_width:
+        res.append(widths)
     return res[0] if len(res) == 1 else tuple(res)
