@@ -802,6 +802,87 @@ int sc_fit_profiles_robust_dem(sc_ctx* ctx, const double* z, int ny, int nx, con
                                int iterations, double scale, sc_profile_robust_fit* out_rows, double* out_loss);
 
 /*
+ * Weights and robust joint fits (docs/segments.md, "Weights and robust fits"; scarplet_amd/csrc/sc_segment_robust.hip): the
+ * fit of sc_fit_segments with the weights and the losses of sc_fit_profiles_robust, on ONE scale per segment.
+ *   samples  p_cj and u_cj as sc_fit_profiles_robust forms them (weights NULL: u = 1); a profile is usable with at least
+ *            min_samples valid points on either side; n is the pooled number of valid points of the usable profiles and
+ *            dof = n - 2 n_profiles - 1 (down-weighted points still count); fitted under the rule of sc_fit_segments
+ *   fit(q)   per active profile the weighted passes 0 to 2 of sc_fit_profiles_robust give sbar, pbar, beta, ebar, gamma,
+ *            See_ci, Sep_ci; a_i = (sum_c Sep_ci) / (sum_c See_ci); b_ci = beta_ci - a_i gamma_ci; c0_ci = (pbar_ci -
+ *            a_i ebar_ci) - b_ci sbar_ci; r_cj = p_cj - ((c0_ci + b_ci s_j) + a_i e_ij).  Sums over c: the blocked sum of
+ *            sc_fit_segments over the usable profiles in input order; a profile that adds nothing adds +0.0 in its
+ *            place, so the shape of the sum depends on n_profiles alone
+ *   iterate 0  q = u; ls_index = argmin_i sum_c sum_j u r^2, ties to the smaller index.  SC_ROBUST_NONE ends here, on that
+ *            curve, with scale NaN, n_down 0, n_dormant 0 and ls_index = kt_index
+ *   scale    `scale` where it is > 0, else ONE sigma per segment: 1.4826 times the element of rank (n - 1) / 2 (0-based,
+ *            ascending; an exact order statistic by integer counts) of the pooled |r_cj| at ls_index over all n points of
+ *            the usable profiles.  sigma not > 0: the row of iterate 0 with loss = sse and status 16
+ *   iterates t = 1..iterations, per age from that age's previous (c0_ci, b_ci, a_i): q_cj = u_cj f(|r_cj|), c = tuning
+ *            sigma, f and rho those of sc_fit_profiles_robust; then fit(q).  A profile with fewer than min_samples points
+ *            of q > 0 at j < 0, or at j > 0, is DORMANT at that iterate and age: it adds +0.0 to both sums (no say in
+ *            a_i), keeps the (c0, b) of the last iterate in which it was active, has its residuals re-formed with the new
+ *            a_i and may wake at a later iterate.  An age whose sum See is not > 0 at some iterate has loss NaN from then
+ *            on and never wins (the age at which every profile is dormant among them)
+ *   loss     of the last iterate, sum_c sum_j u rho(r), through the blocked sum
+ *   choice   kt_index, lo_index, hi_index as sc_fit_segments, on the loss curve: thr = loss_min (1 + delta / dof).  sse =
+ *            sum u r^2 there, rmse = sqrt(loss / dof), n_down = the points of that fit with f < 1 over the profiles,
+ *            n_dormant = the profiles dormant in it.  Status 1, 2, 4 as sc_fit_segments; 16 as above; 1 | 32: every
+ *            age's loss is NaN - indices -1, floats NaN, scale stays
+ * weights NULL (or a plane of ones) with SC_ROBUST_NONE returns the bytes of sc_fit_segments in every shared field of
+ * rows, cell table and curve; a segment of one usable profile returns kt_index, lo_index, hi_index, status, a, sse, rmse,
+ * loss, scale, n_down and ls_index of sc_fit_profiles_robust for that cell, and its b and c0 in the cell table, bit for
+ * bit.  out_rows: S rows; out_cells: K rows in the order of the cells, or NULL (b, c0, sse of the final fit at the best
+ * age, the profile's share of the loss, its down-weighted points, 1 where it was dormant); out_loss: S x A float64, or NULL.
+ * Integer atomics in the order statistic alone; no float atomics, every float sum in a fixed order: the same bytes on every
+ * run and for every order of the segments.
+ * The park: per cell the profile, its weights where there is a plane, and SC_SEGMENT_ROBUST_PLANES planes per age (sbar, pbar,
+ * beta, ebar, gamma, See, Sep, c0, b) - 8 ((2h + 1)(1 + plane) + 9 A) bytes.  Chunks are whole segments of at most
+ * SC_SEGMENT_MAX_PARK such bytes; a single segment that needs more is SC_ERR_UNSUPPORTED.  SC_ERR_INVALID and
+ * SC_ERR_UNSUPPORTED otherwise as sc_fit_segments and sc_fit_profiles_robust return them, before any launch.  The buffers
+ * are those of sc_fit_segments and four of the call's own.  Timed as SC_K_PROFILE.
+ */
+#define SC_SEGMENT_ROBUST_PLANES 9
+typedef struct sc_segment_robust_fit {
+    int32_t  label;
+    int32_t  n_cells;         /* cells of the segment                            */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n;               /* pooled valid points of the usable profiles      */
+    int32_t  dof;             /* n - 2 n_profiles - 1                            */
+    int32_t  kt_index;        /* best age (-1: not fitted)                       */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 1, 2, 4 as sc_segment_fit; 16: no scale; 1 | 32: no age survived */
+    double   kt, kt_lo, kt_hi;
+    double   a;               /* the segment's amplitude: its offset is 2 a      */
+    double   sse, rmse;       /* sum u r^2 at the best age; sqrt(loss / dof)     */
+    double   loss, scale;     /* sum u rho(r) there; the segment's sigma         */
+    int32_t  n_down;          /* points of that fit with f(|r|) < 1              */
+    int32_t  ls_index;        /* best age of iterate 0                           */
+    int32_t  n_dormant;       /* profiles dormant in that fit                    */
+} sc_segment_robust_fit;
+typedef struct sc_segment_robust_cell {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  used;            /* 1: a usable profile                             */
+    int32_t  n;               /* valid points of the profile                     */
+    double   b, c0, sse;      /* of the final fit at the segment's best age; NaN where not used or the segment is not fitted */
+    double   loss;            /* the profile's share of the segment's loss       */
+    int32_t  n_down;          /* its points with f(|r|) < 1                      */
+    int32_t  dormant;         /* 1: dormant in that fit                          */
+} sc_segment_robust_cell;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_segments_robust(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                           const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                           int h, int w, double de, double delta, int min_samples, int min_profiles,
+                           const double* weights, int loss, double tuning, int iterations, double scale,
+                           sc_segment_robust_fit* out_rows, sc_segment_robust_cell* out_cells, double* out_loss);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_segments_robust_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                               const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                               long long S, const double* ages, int A, int h, int w, double de, double delta,
+                               int min_samples, int min_profiles, const double* weights, int loss, double tuning,
+                               int iterations, double scale, sc_segment_robust_fit* out_rows,
+                               sc_segment_robust_cell* out_cells, double* out_loss);
+
+/*
  * The initial slope (docs/profiles.md, "The initial slope"; scarplet_amd/csrc/sc_ramp.hip): the fit of sc_fit_profiles
  * with the scarp started as a ramp of half-width L = m de, not as a vertical step (Hanks & Andrews 1989).  The initial
  * profile b s + a clamp(s / L, -1, 1), diffused for kt, is

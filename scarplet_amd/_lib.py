@@ -184,6 +184,34 @@ SEGMENT_RAMP_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_ramp_fit._
                                    "itemsize": C.sizeof(sc_segment_ramp_fit)})
 
 
+class sc_segment_robust_fit(C.Structure):
+    """One row of sc_fit_segments_robust / sc_fit_segments_robust_dem: sc_segment_fit, then the loss and the scale."""
+    _fields_ = sc_segment_fit._fields_ + [("loss", C.c_double), ("scale", C.c_double), ("n_down", C.c_int32),
+                                          ("ls_index", C.c_int32), ("n_dormant", C.c_int32)]
+
+
+class sc_segment_robust_cell(C.Structure):
+    """One cell of the cell table of sc_fit_segments_robust / sc_fit_segments_robust_dem."""
+    _fields_ = sc_segment_cell._fields_ + [("loss", C.c_double), ("n_down", C.c_int32), ("dormant", C.c_int32)]
+
+
+SEGMENT_ROBUST_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_robust_fit._fields_],
+                                     "formats": [np.int32] * 9 + [np.float64] * 8 + [np.int32] * 3,
+                                     "offsets": [getattr(sc_segment_robust_fit, f).offset for f, _ in sc_segment_robust_fit._fields_],
+                                     "itemsize": C.sizeof(sc_segment_robust_fit)})
+SEGMENT_ROBUST_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_robust_cell._fields_],
+                                      "formats": [np.int64, np.int32, np.int32] + [np.float64] * 4 + [np.int32] * 2,
+                                      "offsets": [getattr(sc_segment_robust_cell, f).offset
+                                                  for f, _ in sc_segment_robust_cell._fields_],
+                                      "itemsize": C.sizeof(sc_segment_robust_cell)})
+SEGMENT_ROBUST_PLANES = 9                                              # SC_SEGMENT_ROBUST_PLANES
+
+
+def segment_robust_cap(h, n_ages, plane):
+    """The cells of one segment the park of sc_fit_segments_robust holds: 8 ((2h + 1)(1 + plane) + 9 A) bytes a cell."""
+    return SEGMENT_MAX_PARK // (8 * ((2 * h + 1) * (2 if plane else 1) + SEGMENT_ROBUST_PLANES * n_ages))
+
+
 class sc_segment_boot(C.Structure):
     """One row of sc_bootstrap_segments / sc_bootstrap_segments_dem (docs/bootstrap.md)."""
     _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n_blocks", C.c_int32),
@@ -355,6 +383,14 @@ SIGNATURES = {
                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                            C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_segments_robust": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                         C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
+                                         C.c_double, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_double,
+                                         C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_segments_robust_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
+                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, C.c_int,
+                                             C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, _dp]),
     "sc_bootstrap_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -851,6 +887,37 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, tab, sse, plane
+
+    def fit_segments_robust(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
+                            weights=None, loss=ROBUST_NONE, tuning=0.0, iterations=1, scale=0.0, cell_table=False, curve=False,
+                            z=None):
+        """sc_fit_segments_robust on the context's DEM, or sc_fit_segments_robust_dem on ``z`` (float64, C-contiguous,
+        2-D): (rows, cell table or None, (S, A) float64 loss curves or None).  The arrays as fit_segments takes them;
+        ``weights``: None or a float64, C-contiguous plane of the DEM's shape; ``scale`` 0: estimated per segment."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S = len(cells), len(ages), len(seg_label)
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
+        if weights is not None:                              # (of the DEM's shape: the caller's check where z is the context's)
+            assert weights.dtype == np.float64 and weights.ndim == 2 and weights.flags.c_contiguous
+            assert z is None or weights.shape == z.shape
+        rows = np.zeros(S, dtype=SEGMENT_ROBUST_FIT_DTYPE)
+        tab = np.zeros(K, dtype=SEGMENT_ROBUST_CELL_DTYPE) if cell_table else None
+        out = np.empty((S, A), dtype=np.float64) if curve else None
+        llp = C.POINTER(C.c_longlong)
+        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), float(de), float(delta),
+                int(min_samples), int(min_profiles), _as(weights, _dp) if weights is not None else None, int(loss),
+                float(tuning), int(iterations), float(scale), rows.ctypes.data_as(C.c_void_p),
+                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(out, _dp) if curve else None]
+        name = "sc_fit_segments_robust"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, tab, out
 
     # -- block-bootstrap intervals per segment (docs/bootstrap.md) -----------------------
     def bootstrap_segments(self, cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, ages, h, w, D, de,

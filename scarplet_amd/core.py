@@ -943,7 +943,8 @@ class Matcher(object):
 
     def fit_segments(self, traces, half_length, swath=0, ages=None, delta=1.0, min_samples=4, min_profiles=1,
                      return_cells=False, return_curve=False, strike="cell", max_shift=None, return_shift=False,
-                     max_width=None, initial_slope=None, return_width=False):
+                     max_width=None, initial_slope=None, return_width=False, weights=None, robust=None, tuning=None,
+                     iterations=8, robust_scale=None):
         """``sl.fit_segments`` on the DEM this matcher holds on the device (docs/segments.md) - no upload: one age,
         one amplitude and one interval per segment of ``traces`` (the ``Traces`` of ``extract_traces``), fitted
         jointly to the profiles of all its cells.  One row per row of ``traces.segments``, in that order.
@@ -951,7 +952,8 @@ class Matcher(object):
         ``strike="segment"`` gives every cell of a segment that segment's ``strike`` from the table: parallel
         profiles, sturdier where single-cell orientations are noisy.  The bytes are those of ``sl.fit_segments`` on
         the same data, ``max_shift`` and ``return_shift`` included - and ``max_width``, ``initial_slope`` and
-        ``return_width``."""
+        ``return_width``, and ``weights``, ``robust``, ``tuning``, ``iterations`` and ``robust_scale`` (the weight plane
+        is uploaded by the call)."""
         from scarplet_amd import profiles, segments, traces as tr
         if not getattr(self, "whole", False):
             raise ValueError("fit_segments needs the whole DEM on the device, not a block of it")
@@ -974,11 +976,13 @@ class Matcher(object):
         args = segments.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, ages, delta,
                                    min_samples, min_profiles, shift=max_shift is not None)
         D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
+        rb = segments.check_robust((self.ny, self.nx), args, weights, robust, tuning, iterations, robust_scale, max_shift,
+                                   max_width)
         rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
         if rp is not None:
             segments.check_park(args, rp[0])
         return segments._run(self.ctx, args, self.nx, return_cells, return_curve, shift=D, return_shift=return_shift, ramp=rp,
-                             return_width=return_width)
+                             return_width=return_width, robust=rb)
 
     def bootstrap_segments(self, traces, half_length, block_length, swath=0, replicates=1000, level=0.95, seed=0, ages=None,
                            min_samples=4, min_profiles=1, min_blocks=5, max_shift=None, return_hist=False,

@@ -1,7 +1,7 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
 // included by sc_profile.hip and sc_segment.hip alone - by sc_bootstrap.hip and sc_strike.hip for stage one, and by
-// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, and by sc_ramp.hip and
-// sc_segment_ramp.hip, the initial slope of the two.  The
+// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, by sc_segment_robust.hip, the
+// joint fit on those sweeps, and by sc_ramp.hip and sc_segment_ramp.hip, the initial slope of the two.  The
 // library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
 // in the order of its text wherever it is called: the four calls return the same bits in every field they share because
 // they call the same helpers.
@@ -61,6 +61,16 @@ int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int 
                        const double* d_tab, const sg_stage& st, int& launches);
 // k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
+
+// k_sg_sum1<2> and k_sg_sum2<2> on two neighbouring per-cell-and-age planes (src, src + m A) of the stage's chunk: the blocked
+// sum of docs/segments.md into tot (Sc x 2 x A); blk: the CSR array of blocks over the chunk's segments, G its blocks
+// (sc_segment_robust.hip)
+void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int A, double* part,
+                      double* tot);
+
+// ---- sc_robust.hip, shared with sc_segment_robust.hip -----------------------------------------------------------------------
+// the rules of the loss, the tuning constant, the iterations and the scale of sc_fit_profiles_robust / sc_fit_segments_robust
+int sc_rb_check(sc_ctx* ctx, const char* who, int loss, double tuning, int iterations, double scale);
 
 // the degrees of freedom of a segment - or of a window of one, sc_strike.hip - of m usable profiles and n pooled points
 // (D = 0 in the call without a shift), and whether it is fitted
@@ -559,6 +569,51 @@ __device__ __forceinline__ double rb_q(const double* u, int jj, double p, double
     return WT ? u[jj] * f : f;
 }
 
+// one point of a profile and of the weight plane under it: the means over the samples valid in BOTH, in ascending k
+__device__ __forceinline__ void rb_point(const double* __restrict__ z, const double* __restrict__ wt, int ny, int nx, double r,
+                                         double c, double sa, double ca, int jj, int h, int w, double& p, double& u) {
+    const double j = (double)(jj - h);
+    const double jsa = j * sa, jca = j * ca;
+    double accp = 0.0, accu = 0.0;
+    int cnt = 0;
+    for (int kk = -w; kk <= w; ++kk) {
+        const double k = (double)kk;
+        const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
+        double v, g;
+        if (pf_sample(z, ny, nx, rr, cc, v) && pf_sample(wt, ny, nx, rr, cc, g) && g >= 0.0) {
+            accp += v;
+            accu += g;
+            ++cnt;
+        }
+    }
+    p = u = __builtin_nan("");
+    if (cnt) {
+        const double um = accu / (double)cnt;
+        if (um > 0.0) {
+            p = accp / (double)cnt;
+            u = um;
+        }
+    }
+}
+
+// the profile and its weights of input cell kc, lanes over the points: into the wave's LDS and, where park is given, global
+// memory (the profiles first, then the weights, K cells each)
+__device__ __forceinline__ void rb_cut(const double* __restrict__ z, const double* __restrict__ wt, int ny, int nx,
+                                       long long cell, const double* __restrict__ dir, long long kc, int h, int w, int lane,
+                                       double* prof, double* u, double* __restrict__ park_p = nullptr,
+                                       double* __restrict__ park_u = nullptr) {
+    const int np = 2 * h + 1;
+    const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
+    const double r = (double)(cell / nx), c = (double)(cell % nx);
+    for (int jj = lane; jj < np; jj += 64) {
+        rb_point(z, wt, ny, nx, r, c, sa, ca, jj, h, w, prof[jj], u[jj]);
+        if (park_p) {
+            park_p[(size_t)kc * np + jj] = prof[jj];
+            park_u[(size_t)kc * np + jj] = u[jj];
+        }
+    }
+}
+
 // pass 0: n counts the profile's points, n_neg and n_pos those with q > 0 on either side
 struct rb_mom { int n, n_neg, n_pos; double W, Ss, Sp, Se; };
 
@@ -582,10 +637,14 @@ __device__ __forceinline__ rb_mom rb_moments(const double* prof, const double* u
     return m;
 }
 
-// passes 1 and 2, then the coefficients: (c0, b, a) of the refit into `next`; false where See is not > 0
+// passes 1 and 2: the weighted terms of a profile at one age, without the division by its own See - what the joint fit
+// sums over a segment's profiles (sc_segment_robust.hip) and what rb_solve divides
+struct rb_par { double sbar, pbar, beta, ebar, gamma, See, Sep; };
+
 template <int LOSS, bool WT>
-__device__ __forceinline__ bool rb_solve(const double* prof, const double* u, int np, int h, double de, const double* col,
-                                         int A, const rb_prev& v, const rb_mom& m, rb_prev& next) {
+__device__ __forceinline__ rb_par rb_terms(const double* prof, const double* u, int np, int h, double de, const double* col,
+                                           int A, const rb_prev& v, const rb_mom& m) {
+    rb_par t;
     const double sbar = m.Ss / m.W, pbar = m.Sp / m.W, ebar = m.Se / m.W;
     double Sss = 0.0, Sps = 0.0, Ses = 0.0;
     for (int jj = 0; jj < np; ++jj) {
@@ -611,10 +670,20 @@ __device__ __forceinline__ bool rb_solve(const double* prof, const double* u, in
         See += q * (e2 * e2);
         Sep += q * (e2 * p2);
     }
-    next.a = Sep / See;
+    t.sbar = sbar; t.pbar = pbar; t.beta = beta; t.ebar = ebar; t.gamma = gamma;
+    t.See = See; t.Sep = Sep;
+    return t;
+}
+
+// ... then the coefficients: (c0, b, a) of the refit into `next`; false where See is not > 0
+template <int LOSS, bool WT>
+__device__ __forceinline__ bool rb_solve(const double* prof, const double* u, int np, int h, double de, const double* col,
+                                         int A, const rb_prev& v, const rb_mom& m, rb_prev& next) {
+    const rb_par t = rb_terms<LOSS, WT>(prof, u, np, h, de, col, A, v, m);
+    next.a = t.Sep / t.See;
     next.c = v.c;
-    pf_slope(sbar, pbar, beta, ebar, gamma, next.a, next.b, next.c0);
-    return See > 0.0;
+    pf_slope(t.sbar, t.pbar, t.beta, t.ebar, t.gamma, next.a, next.b, next.c0);
+    return t.See > 0.0;
 }
 
 // the last pass over the residuals of (c0, b, a): sum u r^2, sum u rho(r) and the points whose factor is < 1

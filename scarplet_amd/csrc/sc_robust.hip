@@ -25,42 +25,6 @@
 #define RB_LDS_BYTES (160 * 1024)        // the LDS of a CU
 #define RB_MAD 1.4826
 
-// one point of a profile and of the weight plane under it: the means over the samples valid in BOTH, in ascending k
-__device__ __forceinline__ void rb_point(const double* __restrict__ z, const double* __restrict__ wt, int ny, int nx, double r,
-                                         double c, double sa, double ca, int jj, int h, int w, double& p, double& u) {
-    const double j = (double)(jj - h);
-    const double jsa = j * sa, jca = j * ca;
-    double accp = 0.0, accu = 0.0;
-    int cnt = 0;
-    for (int kk = -w; kk <= w; ++kk) {
-        const double k = (double)kk;
-        const double rr = r + (k * ca - jsa), cc = c + (jca + k * sa);
-        double v, g;
-        if (pf_sample(z, ny, nx, rr, cc, v) && pf_sample(wt, ny, nx, rr, cc, g) && g >= 0.0) {
-            accp += v;
-            accu += g;
-            ++cnt;
-        }
-    }
-    p = u = __builtin_nan("");
-    if (cnt) {
-        const double um = accu / (double)cnt;
-        if (um > 0.0) {
-            p = accp / (double)cnt;
-            u = um;
-        }
-    }
-}
-
-__device__ __forceinline__ void rb_cut(const double* __restrict__ z, const double* __restrict__ wt, int ny, int nx,
-                                       long long cell, const double* __restrict__ dir, long long kc, int h, int w, int lane,
-                                       double* prof, double* u) {
-    const int np = 2 * h + 1;
-    const double sa = dir[2 * kc], ca = dir[2 * kc + 1];
-    const double r = (double)(cell / nx), c = (double)(cell % nx);
-    for (int jj = lane; jj < np; jj += 64) rb_point(z, wt, ny, nx, r, c, sa, ca, jj, h, w, prof[jj], u[jj]);
-}
-
 // a row without a fit: status 1, or 1 | 32 where every age died
 __device__ __forceinline__ void rb_row_unfit(sc_profile_robust_fit* out, long long cell, int n, int status, double scale) {
     pf_row_unfit(out, cell, n);
@@ -188,7 +152,7 @@ static rb_kernel rb_pick(bool tab_lds, bool wt, int loss) {
     return wt ? rb_pick_loss<false, true>(loss) : rb_pick_loss<false, false>(loss);
 }
 
-static int rb_check(sc_ctx* ctx, const char* who, int loss, double tuning, int iterations, double scale) {
+int sc_rb_check(sc_ctx* ctx, const char* who, int loss, double tuning, int iterations, double scale) {
     if (loss != SC_ROBUST_NONE && loss != SC_ROBUST_HUBER && loss != SC_ROBUST_TUKEY)
         return sc_fail(ctx, SC_ERR_INVALID, "%s: the loss must be SC_ROBUST_NONE, _HUBER or _TUKEY", who);
     if (loss == SC_ROBUST_NONE) return SC_OK;
@@ -269,7 +233,7 @@ static int rb_call(sc_ctx* ctx, const double* z, int ny, int nx, const long long
     const char* who = "sc_fit_profiles_robust";
     int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
-    if ((rc = rb_check(ctx, who, loss, tuning, iterations, scale))) return rc;
+    if ((rc = sc_rb_check(ctx, who, loss, tuning, iterations, scale))) return rc;
     if (K == 0) return SC_OK;
     const double* z_dev = ctx->z_dev;
     if (z) {

@@ -461,6 +461,13 @@ void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st) {
     k_sg_rank<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.Sc, st.cn, st.used, st.list, st.cnt);
 }
 
+void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int A, double* part,
+                      double* tot) {
+    const size_t mA = (size_t)st.m * A;
+    k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(src, mA, st.list, st.seg, blk, st.cnt, st.Sc, G, A, part);
+    k_sg_sum2<2><<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(part, blk, st.cnt, st.Sc, A, tot);
+}
+
 // the dynamic-LDS limit of the parking kernel, raised before the first chunk
 int sc_sg_stage_attr(sc_ctx* ctx, int A, int h, int D) {
     const bool shift = D >= 0;

@@ -25,6 +25,14 @@ SHIFT_CELL_DTYPE = np.dtype(SHIFT_CELL_FIELDS)
 RAMP_FIT_FIELDS = FIT_FIELDS[:-1] + [("width_index", np.int32), ("width", np.float64), ("initial_slope", np.float64),
                                      ("height", np.float64)]
 RAMP_FIT_DTYPE = np.dtype(RAMP_FIT_FIELDS)
+# ... and with weights or a robust loss: the loss and the scale of the best age, the points it down-weighted, the best age
+# before the robust step and the profiles the last iterate left dormant; per cell its share of the loss, its down-weighted
+# points and whether it was dormant
+ROBUST_FIT_FIELDS = FIT_FIELDS[:-1] + [("loss", np.float64), ("scale", np.float64), ("n_down", np.int32), ("ls_index", np.int32),
+                                       ("n_dormant", np.int32), ("height", np.float64)]
+ROBUST_FIT_DTYPE = np.dtype(ROBUST_FIT_FIELDS)
+ROBUST_CELL_FIELDS = CELL_FIELDS[:-1] + [("loss", np.float64), ("n_down", np.int32), ("dormant", np.int32), ("label", np.int32)]
+ROBUST_CELL_DTYPE = np.dtype(ROBUST_CELL_FIELDS)
 
 
 def _labels_of(labels, idx, ny, nx):
@@ -86,9 +94,33 @@ def check_park(args, M):
                          % (counts.max(), cap))
 
 
+def check_robust_park(args, plane):
+    """The park cap of a call with ``weights`` or ``robust``: 8 ((2h + 1)(1 + plane) + 9 A) bytes per cell, a segment at a
+    time (sc_fit_segments_robust; ``_lib.segment_robust_cap``).  ``args`` as check_args returns them; ValueError for a
+    segment above the cap."""
+    seg_start, kt, h = args[3], args[5], args[6]
+    cap = _lib.segment_robust_cap(h, len(kt), plane)
+    counts = np.diff(seg_start)
+    if len(counts) and counts.max() > cap:
+        raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages with weights or robust"
+                         % (counts.max(), cap))
+
+
+def check_robust(shape, args, weights, robust, tuning, iterations, robust_scale, max_shift, max_width):
+    """``profiles.check_robust`` for the joint fit: None, or (plane or None, loss, k, T, sigma or 0.0); neither option is
+    built together with ``max_shift`` or ``max_width``, and the park must hold every segment.  ValueError otherwise."""
+    if (weights is not None or robust is not None) and max_width is not None:
+        raise ValueError("weights and robust are not built together with max_width")
+    rb = profiles.check_robust(shape, weights, robust, tuning, iterations, robust_scale, max_shift)
+    if rb is not None:
+        check_robust_park(args, rb[0] is not None)
+    return rb
+
+
 def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
                  min_profiles=1, return_cells=False, return_curve=False, device=0, max_shift=None, return_shift=False,
-                 max_width=None, initial_slope=None, return_width=False):
+                 max_width=None, initial_slope=None, return_width=False, weights=None, robust=None, tuning=None,
+                 iterations=8, robust_scale=None):
     """Fit ONE diffusion scarp per segment to the profiles cut across the strike at its cells (docs/segments.md).
 
     ``data``, ``cells``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta`` and ``min_samples`` are those of
@@ -120,24 +152,41 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     ``|bbar + a / (m de)|`` is nearest to it, ``bbar`` the mean far-field slope of the segment's profiles.  The table
     gains ``width_index``, ``width`` (m de) and ``initial_slope`` (signed; +-inf at ``m = 0``) ahead of ``height``, the
     curves are the chosen pairs' sse, ``status`` gains 8 where ``width_index`` is the end of the range, and
-    ``return_width`` adds the (S, A) int8 plane of every age's m, last.  Not built together with ``max_shift``."""
+    ``return_width`` adds the (S, A) int8 plane of every age's m, last.  Not built together with ``max_shift``.
+
+    ``weights``, ``robust``, ``tuning``, ``iterations`` and ``robust_scale`` are those of ``sl.fit_profiles``: a weight on
+    every point of every sum, and ``iterations`` rounds of iteratively reweighted least squares per age under the Huber or
+    the Tukey loss, on ONE scale per segment - ``robust_scale``, or 1.4826 times the median of the pooled absolute
+    residuals of the least-squares fit at its best age (docs/segments.md, "Weights and robust fits").  A profile that the
+    Tukey loss leaves with fewer than ``min_samples`` weighted points on a side is dormant: it has no say in the shared
+    amplitude until it wakes.  The choice and the interval run on the robust loss; the table gains ``loss``, ``scale``,
+    ``n_down``, ``ls_index`` and ``n_dormant`` ahead of ``height``, the cell table ``loss``, ``n_down`` and ``dormant``,
+    ``status`` 16 marks a segment without a scale (the least-squares row) and ``1 | 32`` one none of whose ages survived, and
+    ``return_curve`` returns the loss curves.  Not built together with ``max_shift`` or ``max_width``."""
     z, de = profiles._dem_of(data)
     args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles,
                       shift=max_shift is not None)
     D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
+    rb = check_robust(z.shape, args, weights, robust, tuning, iterations, robust_scale, max_shift, max_width)
     rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
     if rp is not None:
         check_park(args, rp[0])
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
     return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift,
-                ramp=rp, return_width=return_width)
+                ramp=rp, return_width=return_width, robust=rb)
 
 
-def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False, ramp=None, return_width=False):
+def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False, ramp=None, return_width=False,
+         robust=None):
     idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
     plane = None
-    if ramp is not None:
+    if robust is not None:
+        wt, loss, k, T, sigma = robust
+        rows, tab, curve = ctx.fit_segments_robust(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, weights=wt,
+                                                   loss=loss, tuning=k, iterations=T, scale=sigma,
+                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+    elif ramp is not None:
         M, mode, slope = ramp
         rows, tab, curve, widths = ctx.fit_segments_ramp(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, M, mode=mode,
                                                          slope=slope, cell_table=bool(return_cells), curve=bool(return_curve),
@@ -149,13 +198,13 @@ def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_s
         rows, tab, curve, plane = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
                                                    cell_table=bool(return_cells), curve=bool(return_curve), z=z,
                                                    shift=shift, shift_plane=bool(return_shift))
-    out = np.zeros(len(rows), dtype=FIT_DTYPE if ramp is None else RAMP_FIT_DTYPE)
+    out = np.zeros(len(rows), dtype=ROBUST_FIT_DTYPE if robust is not None else FIT_DTYPE if ramp is None else RAMP_FIT_DTYPE)
     for f in rows.dtype.names:
         out[f] = rows[f]
     out["height"] = 2.0 * rows["a"]
     res = [out]
     if return_cells:
-        ct = np.zeros(len(tab), dtype=CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE)
+        ct = np.zeros(len(tab), dtype=ROBUST_CELL_DTYPE if robust is not None else CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE)
         back = np.empty(len(order), dtype=np.int64)                    # sorted position of each kept cell
         back[order] = np.arange(len(order))
         for f in tab.dtype.names:
