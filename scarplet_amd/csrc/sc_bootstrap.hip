@@ -385,14 +385,9 @@ static int bs_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                          min_profiles, out_rows);
     if (rc) return rc;
     if ((rc = bs_check(ctx, who, K, seg_start, S, seg_blk_start, blk_start, NB, min_blocks, R, level))) return rc;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (S == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->sg_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && S == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;
     return bs_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, seg_blk_start, blk_start, ages, A, h, w, D, de,
                   min_samples, min_profiles, min_blocks, R, level, seed, out_rows, out_hist, out_index, out_a);
 }

@@ -1,18 +1,30 @@
 // The fit of sc_fit_profiles* and sc_fit_segments* (docs/profiles.md, docs/segments.md), each piece of it written once:
-// included by sc_profile.hip and sc_segment.hip alone - by sc_bootstrap.hip and sc_strike.hip for stage one, and by
-// sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every term, by sc_segment_robust.hip, the
-// joint fit on those sweeps, and by sc_ramp.hip and sc_segment_ramp.hip, the initial slope of the two.  The
-// library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its text
-// in the order of its text wherever it is called: the four calls return the same bits in every field they share because
+// the arithmetic AND the frame around it.  Included by sc_profile.hip and sc_segment.hip - by sc_bootstrap.hip and
+// sc_strike.hip for stage one -, by sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every
+// term, by sc_segment_robust.hip, the joint fit on those sweeps, by sc_ramp.hip and sc_segment_ramp.hip, the initial slope
+// of the two, and by sc_lateral.hip for the sampler and the host frame.  Who owns what:
+//   host    sc_profile.hip defines the frame of every per-cell call: the DEM's source (sc_pf_dem), the erf table
+//           (sc_pf_table) and the chunked driver (sc_pf_chunks), to which a call hands its one launch line.
+//           sc_segment.hip defines stage one of the segment calls and the segmented sum (sc_sg_sum_launch)
+//   device  pf_stage and pf_each_cell are the frame of a kernel with one wave per cell; pf_column, pf_rest and pf_sse take
+//           their column through an accessor (pf_at: a table's column, rp_col: the ramp's); pf_candidate, pair_winner
+//           and wave_sync are what sh_search and rp_search share
+// The library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its
+// text in the order of its text wherever it is called: the calls return the same bits in every field they share because
 // they call the same helpers.
 #pragma once
 #include "sc_internal.h"
+#include <functional>
 #include <vector>
 
 #define PF_WAVES 4                       // cells in flight per workgroup: one wave per cell
 #define PF_THREADS (64 * PF_WAVES)
 #define PF_TAB_LDS 65536                 // the erf table goes to LDS up to this many bytes
 #define PF_MAX_GRID 2048
+#ifndef PF_CHUNK
+#define PF_CHUNK (1ll << 19)             // cells per launch of a per-cell call: bounds its buffers (rows, 8 A B a curve)
+#endif
+#define SG_BLOCK 64                      // usable profiles per block of the segmented sum
 
 // ---- sc_profile.hip, shared with sc_segment.hip (`who` names the call in the messages) ----------------------------------
 // the argument checks of a profile call
@@ -25,8 +37,26 @@ int sc_pf_check_shift(sc_ctx* ctx, const char* who, int h, int D, int min_sample
 int sc_pf_whole_grid(sc_ctx* ctx, const char* who);
 // the _dem calls: z (ny x nx float64 on the host) into the call's own buffer
 int sc_pf_upload(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx);
+// the DEM a call works on: z uploaded into buf, or - z null - the context's own (the device is set either way)
+int sc_pf_dem(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx, const double** z_dev);
 // the launch of the erf table over j = -h..h (d_ages on the device; timed as SC_K_PROFILE)
 int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, double* d_tab);
+// The chunked driver of the per-cell calls (K >= 1 cells, at most `chunk` a launch, in the pf_ buffers of the context).  Per
+// chunk: cells and (sa, ca) go up, the rows are cleared, `launch` issues the call's ONE kernel launch on the chunk's m
+// cells inside the SC_K_PROFILE bracket, the rows and the planes that were asked for come back, and the stream is
+// synchronised.  A plane is an optional per-cell output: the float64 curve or the int8 shifts / widths (host null: none,
+// and its device pointer is null)
+struct pf_plane { void* host; DevBuf* buf; size_t cell_bytes; };
+struct pf_chunk { long long* cells; double* dir; void* rows; void* plane[2]; };
+typedef std::function<void(const pf_chunk&, long long m)> pf_launch;
+int sc_pf_chunks(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K, long long chunk,
+                 size_t row_bytes, void* out_rows, const pf_plane& p0, const pf_plane& p1, const pf_launch& launch);
+// the grids of a kernel with one wave per cell over m cells, and of one with a workgroup per item (segment, block) over n
+static inline unsigned pf_grid(long long m) {
+    const long long g = (m + PF_WAVES - 1) / PF_WAVES;
+    return (unsigned)(g < 1 ? 1 : g > PF_MAX_GRID ? PF_MAX_GRID : g);
+}
+static inline unsigned sg_grid(long long n) { return (unsigned)(n < 1 ? 1 : n > 65536 ? 65536 : n); }
 
 // ---- sc_ramp.hip, shared with sc_segment_ramp.hip ---------------------------------------------------------------------------
 // the rules of the width range M, the mode and the slope of sc_fit_profiles_ramp / sc_fit_segments_ramp
@@ -62,11 +92,11 @@ int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int 
 // k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
 
-// k_sg_sum1<2> and k_sg_sum2<2> on two neighbouring per-cell-and-age planes (src, src + m A) of the stage's chunk: the blocked
-// sum of docs/segments.md into tot (Sc x 2 x A); blk: the CSR array of blocks over the chunk's segments, G its blocks
-// (sc_segment_robust.hip)
-void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int A, double* part,
-                      double* tot);
+// k_sg_sum1<P> and k_sg_sum2<P> on P (1 or 2) neighbouring per-cell-and-column planes (src, src + m C) of the stage's chunk:
+// the blocked sum of docs/segments.md into tot (Sc x P x C); blk: the CSR array of blocks over the chunk's segments, G its
+// blocks.  C = A columns, or the A (M + 1) pairs of sc_segment_ramp.hip
+void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int C, int P,
+                      double* part, double* tot);
 
 // ---- sc_robust.hip, shared with sc_segment_robust.hip -----------------------------------------------------------------------
 // the rules of the loss, the tuning constant, the iterations and the scale of sc_fit_profiles_robust / sc_fit_segments_robust
@@ -116,6 +146,42 @@ __device__ __forceinline__ pf_lds pf_stage(const double* __restrict__ tab_g, int
     }
     __syncthreads();
     return L;
+}
+
+// The loop of such a kernel, written once: workgroups stride over rounds of PF_WAVES cells, so that the cells in flight are
+// neighbours of the input order.  Wave w of round g takes input cell kc = g PF_WAVES + w: cut(kc, cell) puts its profile
+// into the wave's LDS, fit(kc, cell) does the rest.  The loop's bound is uniform per workgroup, so every wave meets both
+// barriers of every round - a wave past the end with nothing to do
+template <class CUT, class FIT>
+__device__ __forceinline__ void pf_each_cell(const long long* __restrict__ cells, long long K, CUT cut, FIT fit) {
+    const int wave = threadIdx.x >> 6;
+    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
+    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
+        const long long kc = g * PF_WAVES + wave;
+        const bool act = kc < K;
+        long long cell = 0;
+        if (act) {
+            cell = cells[kc];
+            cut(kc, cell);
+        }
+        __syncthreads();
+        if (act) fit(kc, cell);
+        __syncthreads();
+    }
+}
+
+// what a cell without a fit leaves in the optional planes: NaN in its curve, 0 in its shifts / widths
+__device__ __forceinline__ void pf_unfit_planes(long long kc, int lane, int A, double* __restrict__ curve,
+                                                signed char* __restrict__ plane) {
+    if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
+    if (plane && lane < A) plane[kc * A + lane] = 0;
+}
+
+// (one wave: the lanes read what the others wrote, and what they read is overwritten afterwards)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // ---- sampling (docs/profiles.md, "Samples") ----------------------------------------------------------------------------------
@@ -212,15 +278,24 @@ __device__ __forceinline__ pf_lin pf_line(const double* prof, int np, int h, dou
     return L;
 }
 
+// From here on a sweep takes its column through an accessor E: e(jj) is the column's entry at point jj.  pf_at is a
+// column of a table - the entry of one age in A doubles a row, col[jj * A] -, rp_col (below) the diffused ramp's.
+struct pf_tab_col {
+    const double* col;
+    int A;
+    __device__ __forceinline__ double operator()(int jj) const { return col[(size_t)jj * A]; }
+};
+__device__ __forceinline__ pf_tab_col pf_at(const double* col, int A) { return pf_tab_col{col, A}; }
+
 // pass 2: what is left of e after 1 and s, against what is left of p (t.ebar and t.gamma in, t.See and t.Sep out)
-__device__ __forceinline__ void pf_rest(const double* prof, int np, int h, double de, const pf_lin& L, const double* col,
-                                        int A, pf_col& t) {
+template <class E>
+__device__ __forceinline__ void pf_rest(const double* prof, int np, int h, double de, const pf_lin& L, const E& e, pf_col& t) {
     double See = 0.0, Sep = 0.0;
     for (int jj = 0; jj < np; ++jj) {
         const double p = prof[jj];
         if (p != p) continue;
         const double sc = (double)(jj - h) * de - L.sbar;
-        const double e2 = (col[(size_t)jj * A] - t.ebar) - t.gamma * sc;
+        const double e2 = (e(jj) - t.ebar) - t.gamma * sc;
         const double p2 = (p - L.pbar) - L.beta * sc;
         See += e2 * e2;
         Sep += e2 * p2;
@@ -230,14 +305,14 @@ __device__ __forceinline__ void pf_rest(const double* prof, int np, int h, doubl
 }
 
 // passes 0 to 2 of a column alone, the profile's own terms given
-__device__ __forceinline__ pf_col pf_column(const double* prof, int np, int h, double de, const pf_lin& L, const double* col,
-                                            int A) {
+template <class E>
+__device__ __forceinline__ pf_col pf_column(const double* prof, int np, int h, double de, const pf_lin& L, const E& e) {
     pf_col t;
     double Se = 0.0;
     for (int jj = 0; jj < np; ++jj) {
         const double p = prof[jj];
         if (p != p) continue;
-        Se += col[(size_t)jj * A];
+        Se += e(jj);
     }
     t.ebar = Se / L.dn;
     double Ses = 0.0;
@@ -245,10 +320,10 @@ __device__ __forceinline__ pf_col pf_column(const double* prof, int np, int h, d
         const double p = prof[jj];
         if (p != p) continue;
         const double sc = (double)(jj - h) * de - L.sbar;
-        Ses += sc * (col[(size_t)jj * A] - t.ebar);
+        Ses += sc * (e(jj) - t.ebar);
     }
     t.gamma = Ses / L.Sss;
-    pf_rest(prof, np, h, de, L, col, A, t);
+    pf_rest(prof, np, h, de, L, e, t);
     return t;
 }
 
@@ -260,17 +335,29 @@ __device__ __forceinline__ void pf_slope(double sbar, double pbar, double beta, 
 }
 
 // pass 3: the explicit residuals
-__device__ __forceinline__ double pf_sse(const double* prof, int np, int h, double de, const double* col, int A, double a,
-                                         double b, double c0) {
+template <class E>
+__device__ __forceinline__ double pf_sse(const double* prof, int np, int h, double de, const E& e, double a, double b,
+                                         double c0) {
     double sse = 0.0;
     for (int jj = 0; jj < np; ++jj) {
         const double p = prof[jj];
         if (p != p) continue;
         const double s = (double)(jj - h) * de;
-        const double res = p - ((c0 + b * s) + a * col[(size_t)jj * A]);
+        const double res = p - ((c0 + b * s) + a * e(jj));
         sse += res * res;
     }
     return sse;
+}
+
+// passes 0 to 3 of one candidate column, the profile's own terms given: its terms t, its own a = Sep / See with (b, c0),
+// and the sse of that fit
+template <class E>
+__device__ __forceinline__ double pf_candidate(const double* prof, int np, int h, double de, const pf_lin& L, const E& e,
+                                               pf_col& t, double& a, double& b, double& c0) {
+    t = pf_column(prof, np, h, de, L, e);
+    a = t.Sep / t.See;
+    pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
+    return pf_sse(prof, np, h, de, e, a, b, c0);
 }
 
 // ---- the choice over the ages ---------------------------------------------------------------------------------------------------
@@ -339,41 +426,45 @@ __device__ __forceinline__ void pf_row_fit(ROW* out, long long cell, int n, cons
     out->sse = sse; out->rmse = sqrt(sse / (double)dof);
 }
 
-// ---- the shift search --------------------------------------------------------------------------------------------------------------
-// One wave, one profile: for every age i the shift d_i with the smallest sse among d = -D..D.  The LANES RUN OVER THE
-// (shift rank, age) PAIRS, age-minor, 64 pairs a round; each lane runs pf_column, pf_slope and pf_sse for its pair with
-// e_ij taken from row j - d of the table (rows -(h + D)..(h + D), A doubles each).  The lanes of a round that share an
-// age sit A lanes apart: an argmin over them by shuffles (offsets A, 2 A, 4 A, ...) on the key (sse, rank) - a NaN
-// counts as +inf, the smaller rank wins a tie, so the order of the combination does not matter - leaves the round's
-// winner of every age known to its lowest lane; the winning lane merges its terms into the wave's slot, where a later
-// round wins only when strictly smaller (ranks ascend from round to round).  The first smallest in the order 0, -1,
-// +1, ... wins, whatever the round it fell into.  slot: SH_TERMS x A doubles (sse, See, Sep, ebar, gamma of the
-// winner), then A ints (its rank).  No atomics, no float sum across lanes.
+// ---- the search over (candidate, age) pairs ----------------------------------------------------------------------------------------
+// One wave, one profile, and for every age i the best of a list of candidates - the shifts of sh_search, the half-widths
+// of rp_search.  The LANES RUN OVER THE (candidate rank, age) PAIRS, age-minor, 64 pairs a round; each lane runs
+// pf_candidate for its pair.  The lanes of a round that share an age sit A lanes apart: an argmin over them by shuffles
+// (offsets A, 2 A, 4 A, ...) on the key (key, rank) - a pair that cannot win counts as +inf, the smaller rank wins a tie,
+// so the order of the combination does not matter - leaves the round's winner of every age known to its lowest lane;
+// the winning lane merges its terms into the wave's slot, where a later round wins only when strictly smaller (ranks
+// ascend from round to round).  The first smallest in the order of the ranks wins, whatever the round it fell into.
+// slot: SH_TERMS x A doubles of the winner, then A ints (its rank, or its m).  No atomics, no float sum across lanes.
+// the rank that wins this lane's age in the round: argmin over the lanes A apart (a lane past the end hands back its own
+// value; a lane that is not `on` enters with rank INT_MAX), read from the age's lowest lane.  (By reference: by value
+// k_pf_ramp takes four more VGPRs than with the loop written out, and crosses 96)
+__device__ __forceinline__ int pair_winner(const double& key, const int& rank, int A, int lane) {
+    double m = key;
+    int mr = rank;
+    for (int off = A; off < 64; off <<= 1) {
+        const double om = __shfl_down(m, off, 64);
+        const int orr = __shfl_down(mr, off, 64);
+        if (om < m || (om == m && orr < mr)) { m = om; mr = orr; }
+    }
+    return __shfl(mr, lane % A, 64);
+}
+
+// the shift d_i with the smallest sse among d = -D..D, in the order 0, -1, +1, ...: e_ij is taken from row j - d of the
+// table (rows -(h + D)..(h + D), A doubles each); a NaN sse counts as +inf.  slot: sse, See, Sep, ebar, gamma; the rank
 __device__ __forceinline__ void sh_search(const double* prof, const double* tab, int np, int h, int A, int D, double de,
                                           int lane, const pf_lin& L, double* slot) {
     int* srank = (int*)(slot + (size_t)SH_TERMS * A);
     const int P = A * (2 * D + 1);
-    const int low = lane % A;                            // the lowest lane of this lane's age in a round
     for (int q0 = 0; q0 < P; q0 += 64) {
         const bool on = q0 + lane < P;
         const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
         const int r = q / A, i = q - r * A;
-        const double* col = tab + (size_t)(D - sh_shift_of(r)) * A + i;
-        const pf_col t = pf_column(prof, np, h, de, L, col, A);
-        const double a = t.Sep / t.See;
-        double b, c0;
-        pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
-        const double sse = pf_sse(prof, np, h, de, col, A, a, b, c0);
+        pf_col t;
+        double a, b, c0;
+        const double sse = pf_candidate(prof, np, h, de, L, pf_at(tab + (size_t)(D - sh_shift_of(r)) * A + i, A), t, a, b, c0);
         // the round's winner of every age: argmin over the lanes A apart (a lane past the end hands back its own value)
         const double key = (on && sse == sse) ? sse : INFINITY;
-        double m = key;
-        int mr = on ? r : INT_MAX;
-        for (int off = A; off < 64; off <<= 1) {
-            const double om = __shfl_down(m, off, 64);
-            const int orr = __shfl_down(mr, off, 64);
-            if (om < m || (om == m && orr < mr)) { m = om; mr = orr; }
-        }
-        const int win = __shfl(mr, low, 64);
+        const int win = pair_winner(key, on ? r : INT_MAX, A, lane);
         if (on && r == win) {                            // (one lane per age)
             const double cur = slot[i];
             if (q0 == 0 || key < ((cur == cur) ? cur : INFINITY)) {       // (every age meets its rank 0 in the first round)
@@ -385,18 +476,15 @@ __device__ __forceinline__ void sh_search(const double* prof, const double* tab,
                 srank[i] = r;
             }
         }
-        // (one wave: the next round's winners, and the caller, read what these lanes wrote)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();                                     // (the next round's winners, and the caller, read the slot)
     }
 }
 
 // ---- the initial slope (docs/profiles.md, "The initial slope") -----------------------------------------------------------------
 // The column of a diffused ramp of half-width m >= 1 cells is a difference of two rows of ONE table per age, F over
 // x = -(h + M)..(h + M): e_ij = (F[j + m][i] - F[j - m][i]) / (2 m de), formed in that order.  rp_col holds the two
-// rows' first entries of the lane's age (point jj reads hi[jj * A] and lo[jj * A]) and the divisor.  rp_column and
-// rp_sse are pf_column and pf_sse with that column: the operations of their text, in its order.
+// rows' first entries of the lane's age (point jj reads hi[jj * A] and lo[jj * A]) and the divisor: the accessor with
+// which pf_column and pf_sse fit a ramp.
 struct rp_col {
     const double *hi, *lo;
     double den;
@@ -413,101 +501,34 @@ __device__ __forceinline__ rp_col rp_col_of(const double* ftab, int A, int M, in
     return c;
 }
 
-__device__ __forceinline__ pf_col rp_column(const double* prof, int np, int h, double de, const pf_lin& L, const rp_col& e) {
-    pf_col t;
-    double Se = 0.0;
-    for (int jj = 0; jj < np; ++jj) {
-        const double p = prof[jj];
-        if (p != p) continue;
-        Se += e(jj);
-    }
-    t.ebar = Se / L.dn;
-    double Ses = 0.0;
-    for (int jj = 0; jj < np; ++jj) {
-        const double p = prof[jj];
-        if (p != p) continue;
-        const double sc = (double)(jj - h) * de - L.sbar;
-        Ses += sc * (e(jj) - t.ebar);
-    }
-    t.gamma = Ses / L.Sss;
-    double See = 0.0, Sep = 0.0;
-    for (int jj = 0; jj < np; ++jj) {
-        const double p = prof[jj];
-        if (p != p) continue;
-        const double sc = (double)(jj - h) * de - L.sbar;
-        const double e2 = (e(jj) - t.ebar) - t.gamma * sc;
-        const double p2 = (p - L.pbar) - L.beta * sc;
-        See += e2 * e2;
-        Sep += e2 * p2;
-    }
-    t.See = See;
-    t.Sep = Sep;
-    return t;
-}
-
-__device__ __forceinline__ double rp_sse(const double* prof, int np, int h, double de, const rp_col& e, double a, double b,
-                                         double c0) {
-    double sse = 0.0;
-    for (int jj = 0; jj < np; ++jj) {
-        const double p = prof[jj];
-        if (p != p) continue;
-        const double s = (double)(jj - h) * de;
-        const double res = p - ((c0 + b * s) + a * e(jj));
-        sse += res * res;
-    }
-    return sse;
-}
-
 // the signed initial slope of a pair with m >= 1
 __device__ __forceinline__ double rp_slope_of(double a, double b, int m, double de) { return b + a / ((double)m * de); }
 
-// One wave, one profile: for every age i the half-width m_i among m = m0..M (m0 = 0 with the width free, 1 with the slope
-// given) with the smallest key - sse_im, or the distance | |b + a / (m de)| - slope |.  sh_search's shape: the LANES RUN
-// OVER THE (m, age) PAIRS, age-minor, 64 pairs a round; the lanes of a round that share an age sit A apart and the
-// shuffle argmin on (key, m) - a pair that cannot win counts as +inf, the smaller m wins a tie - leaves the round's
-// winner of every age known to its lowest lane; the winner merges into the wave's slot, where a later round (larger
-// m) wins only when strictly smaller.  The m = 0 pairs (all in the first round: A <= 64) read the erf table `etab`
-// (rows -h..h, in global memory) and run pf_column and pf_sse, the plain call's arithmetic; the others read `ftab`.
-// slot: SH_TERMS x A doubles (key, sse, a, b, c0 of the winner; sse NaN where no pair of the age can win), then A
-// ints (its m).  No atomics, no float sum across lanes.
+// the half-width m_i among m = m0..M (m0 = 0 with the width free, 1 with the slope given) with the smallest key - sse_im,
+// or the distance | |b + a / (m de)| - slope |; the smaller m wins a tie.  The m = 0 pairs (all in the first round:
+// A <= 64) read the erf table `etab` (rows -h..h, in global memory), the plain call's arithmetic; the others read `ftab`.
+// slot: key, sse, a, b, c0 (sse NaN where no pair of the age can win); m
 __device__ __forceinline__ void rp_search(const double* prof, const double* __restrict__ etab, const double* ftab, int np, int h,
                                           int A, int M, bool given, double slope, double de, int lane, const pf_lin& L,
                                           double* slot) {
     int* sm = (int*)(slot + (size_t)SH_TERMS * A);
     const int m0 = given ? 1 : 0;
     const int P = A * (M + 1 - m0);
-    const int low = lane % A;                            // the lowest lane of this lane's age in a round
     for (int q0 = 0; q0 < P; q0 += 64) {
         const bool on = q0 + lane < P;
         const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
         const int r = q / A, i = q - r * A, m = m0 + r;
         pf_col t;
         double a, b, c0, sse;
-        if (m == 0) {
-            const double* col = etab + i;
-            t = pf_column(prof, np, h, de, L, col, A);
-            a = t.Sep / t.See;
-            pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
-            sse = pf_sse(prof, np, h, de, col, A, a, b, c0);
-        } else {
-            const rp_col e = rp_col_of(ftab, A, M, m, i, de);
-            t = rp_column(prof, np, h, de, L, e);
-            a = t.Sep / t.See;
-            pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
-            sse = rp_sse(prof, np, h, de, e, a, b, c0);
-        }
+        if (m == 0)
+            sse = pf_candidate(prof, np, h, de, L, pf_at(etab + i, A), t, a, b, c0);
+        else
+            sse = pf_candidate(prof, np, h, de, L, rp_col_of(ftab, A, M, m, i, de), t, a, b, c0);
         const bool alive = on && t.See > 0.0 && sse == sse;
         double key = given ? fabs(fabs(rp_slope_of(a, b, m, de)) - slope) : sse;
         if (!(alive && key == key)) key = INFINITY;
         // the round's winner of every age: argmin over the lanes A apart (a lane past the end hands back its own value)
-        double km = key;
-        int mm = on ? m : INT_MAX;
-        for (int off = A; off < 64; off <<= 1) {
-            const double ok = __shfl_down(km, off, 64);
-            const int om = __shfl_down(mm, off, 64);
-            if (ok < km || (ok == km && om < mm)) { km = ok; mm = om; }
-        }
-        const int win = __shfl(mm, low, 64);
+        const int win = pair_winner(key, on ? m : INT_MAX, A, lane);
         if (on && m == win) {                            // (one lane per age)
             if (q0 == 0 || key < slot[i]) {              // (every age meets its first candidate in the first round)
                 slot[i] = key;
@@ -518,10 +539,7 @@ __device__ __forceinline__ void rp_search(const double* prof, const double* __re
                 sm[i] = m;
             }
         }
-        // (one wave: the next round's winners, and the caller, read what these lanes wrote)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();                                     // (the next round's winners, and the caller, read the slot)
     }
 }
 

@@ -15,6 +15,8 @@
 //                  smaller rank wins a tie - then the winner's lane hands over what it kept; the walk of the interval
 //                  and the parabola read the LDS curve, the same in every lane
 // No atomics, no float sum across lanes: the same bytes on every run and for every order of the stations.
+// The host side is the LDS sizing and one call of sc_pf_chunks (sc_profile.hip), to which it hands its own grid and
+// workgroup shape and its own cap on the chunk.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -22,19 +24,11 @@
 #define LT_MAX_WAVES 4                   // stations in flight per workgroup, where their LDS fits
 #define LT_LDS_BYTES (160 * 1024)        // the LDS of a CU
 #define LT_MAX_GRID 4096
-#define LT_CHUNK (1ll << 19)             // stations per launch: bounds the call's buffers (88 B a row)
-#define LT_CURVE_DOUBLES (1ll << 25)     // ... and 256 MiB of curves where they are asked for
+#define LT_CURVE_DOUBLES (1ll << 25)     // stations per launch: PF_CHUNK, and 256 MiB of curves where they are asked for
 
 // doubles of a wave's LDS: u, v and the mse curve
 __host__ __device__ __forceinline__ size_t lt_wave_doubles(int h, int D) {
     return (size_t)(2 * h + 1) + (size_t)(2 * (h + D) + 1) + (size_t)(2 * D + 1);
-}
-
-// (one wave: the lanes read what the others wrote, and what they read is overwritten afterwards)
-__device__ __forceinline__ void lt_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // one point of a fault-parallel profile: the mean of the valid samples at q = sgn q0, sgn (q0 + 1), .., sgn q1 in that
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(64 * LT_MAX_WAVES) void k_lt_fit(const double* __re
         // stage 1
         for (int jj = lane; jj < np; jj += 64) u[jj] = lt_point(z, ny, nx, r, c, sa, ca, jj - h, q0, q1, -1);
         for (int jj = lane; jj < nv; jj += 64) v[jj] = lt_point(z, ny, nx, r, c, sa, ca, jj - (h + D), q0, q1, +1);
-        lt_wave_sync();
+        wave_sync();
         // stage 2
         double bm = INFINITY, brho = nan, bdz = nan, btilt = nan;
         int br = INT_MAX, bn = 0;
@@ -172,7 +166,7 @@ __global__ __launch_bounds__(64 * LT_MAX_WAVES) void k_lt_fit(const double* __re
             if (om < m || (om == m && orr < mr)) { m = om; mr = orr; }
         }
         const bool any_skipped = __ballot(skipped) != 0ull;
-        lt_wave_sync();                                  // (the curve is whole)
+        wave_sync();                                     // (the curve is whole)
         sc_lateral_fit* out = rows + kc;                 // (the rows were cleared: their padding is compared too)
         if (mr == INT_MAX) {
             if (lane == 0) {
@@ -208,7 +202,7 @@ __global__ __launch_bounds__(64 * LT_MAX_WAVES) void k_lt_fit(const double* __re
                 out->mse = m; out->rho = rho; out->dz = dz; out->tilt = tilt;
             }
         }
-        lt_wave_sync();                                  // (the next station overwrites what these lanes read)
+        wave_sync();                                     // (the next station overwrites what these lanes read)
     }
 }
 
@@ -244,51 +238,24 @@ static int lt_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
                   sc_lateral_fit* out_rows, double* out_mse) {
     if (K == 0) return SC_OK;
     const int nl = 2 * D + 1;
-    long long chunk = std::min<long long>(K, LT_CHUNK);
+    long long chunk = PF_CHUNK;
     if (out_mse) chunk = std::min<long long>(chunk, std::max<long long>(1, LT_CURVE_DOUBLES / nl));
-    int rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, sizeof(sc_lateral_fit) * (size_t)chunk))) return rc;
-    if (out_mse && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)nl * (size_t)chunk))) return rc;
-    long long* d_cells = (long long*)ctx->pf_cells.p;
-    double* d_dir = (double*)ctx->pf_dir.p;
-    sc_lateral_fit* d_rows = (sc_lateral_fit*)ctx->pf_rows.p;
-    double* d_mse = out_mse ? (double*)ctx->pf_sse.p : nullptr;
 
     // as many waves a workgroup as their LDS allows (the limits of lt_check leave room for LT_MAX_WAVES)
     const size_t wave_bytes = sizeof(double) * lt_wave_doubles(h, D);
     const int waves = (int)std::max<size_t>(1, std::min<size_t>(LT_MAX_WAVES, LT_LDS_BYTES / wave_bytes));
     const size_t lds = wave_bytes * (size_t)waves;
     if (lds > LT_LDS_BYTES) return sc_fail(ctx, SC_ERR_UNSUPPORTED, "sc_lateral_offsets: %zu bytes of LDS a station", wave_bytes);
+    int rc;
     if ((rc = sc_lds_attr(ctx, (const void*)k_lt_fit, lds))) return rc;
 
-    std::vector<double> dir;
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const long long m = std::min(chunk, K - k0);
-        dir.resize(2 * (size_t)m);
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_lateral_fit) * (size_t)m, ctx->stream));
+    const pf_plane curve = {out_mse, &ctx->pf_sse, sizeof(double) * (size_t)nl}, none = {nullptr, nullptr, 0};
+    return sc_pf_chunks(ctx, cells, sa, ca, K, chunk, sizeof(sc_lateral_fit), out_rows, curve, none,
+                        [&](const pf_chunk& d, long long m) {
         const unsigned grid = (unsigned)std::min<long long>((m + waves - 1) / waves, LT_MAX_GRID);
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        k_lt_fit<<<grid, 64 * waves, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, h, q0, q1, D, de, delta, min_samples,
-                                                        d_rows, d_mse);
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + k0, d_rows, sizeof(sc_lateral_fit) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_mse)
-            SC_HIP(ctx, hipMemcpyAsync(out_mse + (size_t)k0 * nl, d_mse, sizeof(double) * (size_t)nl * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        // (dir is reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return SC_OK;
+        k_lt_fit<<<grid, 64 * waves, lds, ctx->stream>>>(z, ny, nx, d.cells, d.dir, m, h, q0, q1, D, de, delta, min_samples,
+                                                        (sc_lateral_fit*)d.rows, (double*)d.plane[0]);
+    });
 }
 
 // the two calls after their null checks: the argument checks, then the search on z - ny x nx on the host, uploaded - or
@@ -298,14 +265,9 @@ static int lt_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                    sc_lateral_fit* out_rows, double* out_mse) {
     int rc = lt_check(ctx, who, ny, nx, cells, sa, ca, K, h, q0, q1, D, de, delta, min_samples, out_rows);
     if (rc) return rc;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (K == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->pf_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->pf_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && K == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->pf_z, z, ny, nx, &z_dev))) return rc;
     return lt_run(ctx, z_dev, ny, nx, cells, sa, ca, K, h, q0, q1, D, de, delta, min_samples, out_rows, out_mse);
 }
 

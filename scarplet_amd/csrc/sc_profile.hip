@@ -20,12 +20,13 @@
 //                (shift, age) pairs (sh_search), whose winners per age come back in the wave's slot of LDS, and
 //                pf_choose runs on sse*.
 // The table sits in LDS when it fits PF_TAB_LDS bytes (35 ages at h = 100: 56 KB) and in global memory otherwise
-// (pf_stage).  No atomics at all.
+// (pf_stage).  No atomics at all.  Both kernels run in sc_fit.h's loop (pf_each_cell).
+// The host side owns the frame of EVERY per-cell call - these, sc_ramp.hip, sc_robust.hip and sc_lateral.hip: sc_pf_dem
+// (the DEM on the host, or the context's), sc_pf_table and sc_pf_chunks, the chunked driver, which a call hands its
+// launch line as a lambda.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
-
-#define PF_CHUNK (1ll << 19)             // cells per launch: bounds the call's buffers (96 B a row, 8 A B a curve)
 
 __global__ __launch_bounds__(256) void k_pf_table(const double* __restrict__ ages, int A, int h, double de,
                                                   double* __restrict__ tab) {
@@ -45,42 +46,32 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_fit(const double* __restrict_
                                                        double delta, int min_samples, const double* __restrict__ tab_g,
                                                        sc_profile_fit* __restrict__ rows, double* __restrict__ curve) {
     const int np = 2 * h + 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const pf_lds L = pf_stage<TAB_LDS, false>(tab_g, np, np, A);
     const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
     const double* col = L.tab + ia;
-    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
-    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * PF_WAVES + wave;
-        const bool act = kc < K;
-        long long cell = 0;
-        if (act) {
-            cell = cells[kc];
-            pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr);
-        }
-        __syncthreads();
-        if (act) {
+    pf_each_cell(
+        cells, K, [&](long long kc, long long cell) { pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr); },
+        [&](long long kc, long long cell) {
             const pf_mom mo = pf_moments<true>(L.prof, np, h, de, col, A);
             sc_profile_fit* out = rows + kc;
             if (mo.n_neg < min_samples || mo.n_pos < min_samples) {
                 if (lane == 0) pf_row_unfit(out, cell, mo.n);
-                if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
+                pf_unfit_planes(kc, lane, A, curve, nullptr);
             } else {
                 pf_col t;
                 const pf_lin f = pf_line<true>(L.prof, np, h, de, mo, col, A, t);
-                pf_rest(L.prof, np, h, de, f, col, A, t);
+                pf_rest(L.prof, np, h, de, f, pf_at(col, A), t);
                 const double a = t.Sep / t.See;
                 double b, c0;
                 pf_slope(f.sbar, f.pbar, f.beta, t.ebar, t.gamma, a, b, c0);
-                const double sse = pf_sse(L.prof, np, h, de, col, A, a, b, c0);
+                const double sse = pf_sse(L.prof, np, h, de, pf_at(col, A), a, b, c0);
                 if (curve && lane < A) curve[kc * A + lane] = sse;
                 const int dof = mo.n - 3;
                 const pf_pick k = pf_choose(sse, lane, A, delta, dof);
                 if (lane == k.best) pf_row_fit(out, cell, mo.n, k, pf_open(k, A), ages, a, b, c0, sse, dof);
             }
-        }
-        __syncthreads();
-    }
+        });
 }
 
 template <bool TAB_LDS>
@@ -93,22 +84,14 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restric
                                                          sc_profile_shift_fit* __restrict__ rows,
                                                          double* __restrict__ curve, signed char* __restrict__ shifts) {
     const int np = 2 * h + 1;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const pf_lds L = pf_stage<TAB_LDS, true>(tab_g, np, 2 * (h + D) + 1, A);
     const double* slot = L.slot;
     const int* srank = (const int*)(slot + (size_t)SH_TERMS * A);
     const int ia = min(lane, A - 1);                     // lanes beyond the ages repeat the last one and are ignored
-    const long long rounds = (K + PF_WAVES - 1) / PF_WAVES;
-    for (long long g = blockIdx.x; g < rounds; g += gridDim.x) {      // (uniform per workgroup: the barriers below)
-        const long long kc = g * PF_WAVES + wave;
-        const bool act = kc < K;
-        long long cell = 0;
-        if (act) {
-            cell = cells[kc];
-            pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr);
-        }
-        __syncthreads();
-        if (act) {
+    pf_each_cell(
+        cells, K, [&](long long kc, long long cell) { pf_cut(z, ny, nx, cell, dir, kc, h, w, lane, L.prof, nullptr); },
+        [&](long long kc, long long cell) {
             // what depends on neither the age nor the shift, once
             const pf_mom mo = pf_moments<false>(L.prof, np, h, de, nullptr, A);
             const int dof = mo.n - 3 - (D > 0 ? 1 : 0);
@@ -119,8 +102,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restric
                     out->shift_index = 0;
                     out->shift = __builtin_nan("");
                 }
-                if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
-                if (shifts && lane < A) shifts[kc * A + lane] = 0;
+                pf_unfit_planes(kc, lane, A, curve, shifts);
             } else {
                 pf_col t;
                 const pf_lin f = pf_line<false>(L.prof, np, h, de, mo, nullptr, A, t);
@@ -141,9 +123,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_shift(const double* __restric
                     out->shift = (double)d * de;
                 }
             }
-        }
-        __syncthreads();
-    }
+        });
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -212,6 +192,59 @@ int sc_pf_table(sc_ctx* ctx, const double* d_ages, int A, int h, double de, doub
     return SC_OK;
 }
 
+int sc_pf_dem(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx, const double** z_dev) {
+    if (!z) {
+        SC_HIP(ctx, hipSetDevice(ctx->device));
+        *z_dev = ctx->z_dev;
+        return SC_OK;
+    }
+    int rc = sc_pf_upload(ctx, buf, z, ny, nx);
+    *z_dev = (const double*)buf.p;
+    return rc;
+}
+
+int sc_pf_chunks(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K, long long chunk,
+                 size_t row_bytes, void* out_rows, const pf_plane& p0, const pf_plane& p1, const pf_launch& launch) {
+    const pf_plane planes[2] = {p0, p1};
+    chunk = std::min(K, chunk);
+    int rc;
+    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->pf_rows, row_bytes * (size_t)chunk))) return rc;
+    pf_chunk d = {(long long*)ctx->pf_cells.p, (double*)ctx->pf_dir.p, ctx->pf_rows.p, {nullptr, nullptr}};
+    for (int p = 0; p < 2; ++p) {
+        if (!planes[p].host) continue;
+        if ((rc = sc_ensure(ctx, *planes[p].buf, planes[p].cell_bytes * (size_t)chunk))) return rc;
+        d.plane[p] = planes[p].buf->p;
+    }
+    std::vector<double> dir;
+    for (long long k0 = 0; k0 < K; k0 += chunk) {
+        const long long m = std::min(chunk, K - k0);
+        dir.resize(2 * (size_t)m);
+        for (long long k = 0; k < m; ++k) {
+            dir[2 * k] = sa[k0 + k];
+            dir[2 * k + 1] = ca[k0 + k];
+        }
+        SC_HIP(ctx, hipMemcpyAsync(d.cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(d.dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
+        SC_HIP(ctx, hipMemsetAsync(d.rows, 0, row_bytes * (size_t)m, ctx->stream));
+        sc_prof_begin(ctx, SC_K_PROFILE);
+        launch(d, m);
+        SC_HIP(ctx, hipGetLastError());
+        sc_prof_end(ctx, 1);
+        SC_HIP(ctx, hipMemcpyAsync((char*)out_rows + row_bytes * (size_t)k0, d.rows, row_bytes * (size_t)m, hipMemcpyDeviceToHost,
+                                   ctx->stream));
+        for (int p = 0; p < 2; ++p)
+            if (planes[p].host)
+                SC_HIP(ctx, hipMemcpyAsync((char*)planes[p].host + planes[p].cell_bytes * (size_t)k0, d.plane[p],
+                                           planes[p].cell_bytes * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        // (dir is reused by the next chunk, and the caller owns the outputs on return)
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return SC_OK;
+}
+
 // D < 0: the call without a shift, its kernel and its rows (sc_profile_fit; sc_profile_shift_fit otherwise)
 static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   long long K, const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
@@ -219,24 +252,12 @@ static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if (K == 0) return SC_OK;
     const bool shift = D >= 0;
     const int np = 2 * h + 1, ht = h + (shift ? D : 0), nt = 2 * ht + 1;
-    const size_t row_bytes = shift ? sizeof(sc_profile_shift_fit) : sizeof(sc_profile_fit);
     const size_t tab_bytes = sizeof(double) * (size_t)nt * A;
-    const long long chunk = std::min<long long>(K, PF_CHUNK);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->pf_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_tab, tab_bytes))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, row_bytes * (size_t)chunk))) return rc;
-    if (out_sse && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)A * (size_t)chunk))) return rc;
-    if (out_shift && (rc = sc_ensure(ctx, ctx->pf_shift, (size_t)A * (size_t)chunk))) return rc;
     double* d_ages = (double*)ctx->pf_ages.p;
     double* d_tab = (double*)ctx->pf_tab.p;
-    long long* d_cells = (long long*)ctx->pf_cells.p;
-    double* d_dir = (double*)ctx->pf_dir.p;
-    void* d_rows = ctx->pf_rows.p;
-    double* d_sse = out_sse ? (double*)ctx->pf_sse.p : nullptr;
-    signed char* d_shift = out_shift ? (signed char*)ctx->pf_shift.p : nullptr;
 
     const bool tab_lds = tab_bytes <= PF_TAB_LDS;
     const size_t lds = pf_lds_bytes(np, nt, A, shift, tab_lds);
@@ -248,40 +269,17 @@ static int pf_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
     if ((rc = sc_pf_table(ctx, d_ages, A, ht, de, d_tab))) return rc;
 
-    std::vector<double> dir;
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const long long m = std::min(chunk, K - k0);
-        dir.resize(2 * (size_t)m);
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, row_bytes * (size_t)m, ctx->stream));
-        const unsigned grid = (unsigned)std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID);
-        sc_prof_begin(ctx, SC_K_PROFILE);
+    const pf_plane curve = {out_sse, &ctx->pf_sse, sizeof(double) * (size_t)A}, shifts = {out_shift, &ctx->pf_shift, (size_t)A};
+    return sc_pf_chunks(ctx, cells, sa, ca, K, PF_CHUNK, shift ? sizeof(sc_profile_shift_fit) : sizeof(sc_profile_fit), out_rows,
+                        curve, shifts, [&](const pf_chunk& d, long long m) {
         if (shift)
-            k_shift<<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, D, de, delta, min_samples,
-                                                           d_tab, (sc_profile_shift_fit*)d_rows, d_sse, d_shift);
+            k_shift<<<pf_grid(m), PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d.cells, d.dir, m, d_ages, A, h, w, D, de, delta,
+                                                                 min_samples, d_tab, (sc_profile_shift_fit*)d.rows,
+                                                                 (double*)d.plane[0], (signed char*)d.plane[1]);
         else
-            k_fit<<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, de, delta, min_samples,
-                                                         d_tab, (sc_profile_fit*)d_rows, d_sse);
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync((char*)out_rows + row_bytes * (size_t)k0, d_rows, row_bytes * (size_t)m, hipMemcpyDeviceToHost,
-                                   ctx->stream));
-        if (out_sse)
-            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)k0 * A, d_sse, sizeof(double) * (size_t)A * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        if (out_shift)
-            SC_HIP(ctx, hipMemcpyAsync(out_shift + (size_t)k0 * A, d_shift, (size_t)A * (size_t)m, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        // (dir is reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return SC_OK;
+            k_fit<<<pf_grid(m), PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d.cells, d.dir, m, d_ages, A, h, w, de, delta, min_samples,
+                                                               d_tab, (sc_profile_fit*)d.rows, (double*)d.plane[0]);
+    });
 }
 
 // The four calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
@@ -292,14 +290,9 @@ static int pf_call(sc_ctx* ctx, const char* who, bool shift, const double* z, in
     int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, ages, A, h, w, de, delta, min_samples, out_rows);
     if (rc) return rc;
     if (shift && (rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (K == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->pf_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->pf_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && K == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->pf_z, z, ny, nx, &z_dev))) return rc;
     return pf_run(ctx, z_dev, ny, nx, cells, sa, ca, K, ages, A, h, w, shift ? D : -1, de, delta, min_samples, out_rows, out_sse,
                   out_shift);
 }

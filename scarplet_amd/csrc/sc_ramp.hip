@@ -12,11 +12,11 @@
 // otherwise (pf_stage).  The erf table of the m = 0 pairs - the plain call's, by the plain call's launch - stays in
 // global memory: a second LDS table does not fit beside F at the default shape, the m = 0 pairs are A of the
 // A (M + 1) and every wave of the device reads the same 56 KB, which the L2 holds.  No atomics at all.
+// The host side is the table set-up, the kernel choice and one call of sc_pf_chunks (sc_profile.hip).  k_pf_ramp keeps
+// its own loop head: in pf_each_cell the given-slope search measured 1 % slower (profiles/fit_frame_refactor.txt).
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
-
-#define RP_CHUNK (1ll << 19)             // cells per launch, as the plain call
 
 __global__ __launch_bounds__(256) void k_rp_table(const double* __restrict__ ages, int A, int ht, double de,
                                                   double* __restrict__ tab) {
@@ -67,8 +67,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pf_ramp(const double* __restrict
                     out->width = __builtin_nan("");
                     out->initial_slope = __builtin_nan("");
                 }
-                if (curve && lane < A) curve[kc * A + lane] = __builtin_nan("");
-                if (widths && lane < A) widths[kc * A + lane] = 0;
+                pf_unfit_planes(kc, lane, A, curve, widths);
             } else {
                 pf_col t;
                 const pf_lin f = pf_line<false>(L.prof, np, h, de, mo, nullptr, A, t);
@@ -122,26 +121,14 @@ static int rp_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
                   long long K, const double* ages, int A, int h, int w, int M, int mode, double slope, double de, double delta,
                   int min_samples, sc_profile_ramp_fit* out_rows, double* out_sse, int8_t* out_width) {
     const int np = 2 * h + 1, ht = h + M, nt = 2 * ht + 1;
-    const size_t row_bytes = sizeof(sc_profile_ramp_fit);
     const size_t etab_bytes = sizeof(double) * (size_t)np * A, ftab_bytes = sizeof(double) * (size_t)nt * A;
-    const long long chunk = std::min<long long>(K, RP_CHUNK);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->pf_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_tab, etab_bytes))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_ftab, ftab_bytes))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, row_bytes * (size_t)chunk))) return rc;
-    if (out_sse && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)A * (size_t)chunk))) return rc;
-    if (out_width && (rc = sc_ensure(ctx, ctx->pf_shift, (size_t)A * (size_t)chunk))) return rc;
     double* d_ages = (double*)ctx->pf_ages.p;
     double* d_etab = (double*)ctx->pf_tab.p;
     double* d_ftab = (double*)ctx->pf_ftab.p;
-    long long* d_cells = (long long*)ctx->pf_cells.p;
-    double* d_dir = (double*)ctx->pf_dir.p;
-    sc_profile_ramp_fit* d_rows = (sc_profile_ramp_fit*)ctx->pf_rows.p;
-    double* d_sse = out_sse ? (double*)ctx->pf_sse.p : nullptr;
-    signed char* d_width = out_width ? (signed char*)ctx->pf_shift.p : nullptr;
 
     const bool tab_lds = ftab_bytes <= PF_TAB_LDS;
     const size_t lds = pf_lds_bytes(np, nt, A, true, tab_lds);
@@ -153,35 +140,13 @@ static int rp_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_etab))) return rc;
     if ((rc = sc_rp_table(ctx, d_ages, A, ht, de, d_ftab))) return rc;
 
-    std::vector<double> dir;
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const long long m = std::min(chunk, K - k0);
-        dir.resize(2 * (size_t)m);
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, row_bytes * (size_t)m, ctx->stream));
-        const unsigned grid = (unsigned)std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID);
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        kern<<<grid, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, M, mode, slope, de, delta,
-                                                    min_samples, d_etab, d_ftab, d_rows, d_sse, d_width);
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + k0, d_rows, row_bytes * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sse)
-            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)k0 * A, d_sse, sizeof(double) * (size_t)A * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        if (out_width)
-            SC_HIP(ctx, hipMemcpyAsync(out_width + (size_t)k0 * A, d_width, (size_t)A * (size_t)m, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        // (dir is reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return SC_OK;
+    const pf_plane curve = {out_sse, &ctx->pf_sse, sizeof(double) * (size_t)A}, widths = {out_width, &ctx->pf_shift, (size_t)A};
+    return sc_pf_chunks(ctx, cells, sa, ca, K, PF_CHUNK, sizeof(sc_profile_ramp_fit), out_rows, curve, widths,
+                        [&](const pf_chunk& d, long long m) {
+        kern<<<pf_grid(m), PF_THREADS, lds, ctx->stream>>>(z, ny, nx, d.cells, d.dir, m, d_ages, A, h, w, M, mode, slope, de, delta,
+                                                          min_samples, d_etab, d_ftab, (sc_profile_ramp_fit*)d.rows,
+                                                          (double*)d.plane[0], (signed char*)d.plane[1]);
+    });
 }
 
 // The two calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
@@ -194,13 +159,8 @@ static int rp_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     if (rc) return rc;
     if ((rc = sc_rp_check(ctx, who, h, M, mode, slope, min_samples))) return rc;
     if (K == 0) return SC_OK;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if ((rc = sc_pf_upload(ctx, ctx->pf_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->pf_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->pf_z, z, ny, nx, &z_dev))) return rc;
     return rp_run(ctx, z_dev, ny, nx, cells, sa, ca, K, ages, A, h, w, M, mode, slope, de, delta, min_samples, out_rows, out_sse,
                   out_width);
 }

@@ -17,11 +17,12 @@
 //                with f < 1; pf_choose on the loss curve
 // Every sum is a plain loop over ascending j in one lane, the order statistic is integer work: no atomics, no float sum
 // across lanes, the same bytes on every run and for every order of the cells.  Plain C++ throughout.
+// The host side is the table set-up, the kernel choice and one call of sc_pf_chunks (sc_profile.hip).  k_rb_fit keeps
+// its own loop head: in pf_each_cell the Tukey fit measured 1.4 % slower (profiles/fit_frame_refactor.txt).
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
 
-#define RB_CHUNK (1ll << 19)             // cells per launch: bounds the call's buffers (120 B a row, 8 A B a curve)
 #define RB_LDS_BYTES (160 * 1024)        // the LDS of a CU
 #define RB_MAD 1.4826
 
@@ -71,7 +72,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_rb_fit(const double* __restrict_
             bool done = false;
             if (mo.n_neg < min_samples || mo.n_pos < min_samples) {
                 if (lane == 0) rb_row_unfit(out, cell, mo.n, 1, nan);
-                if (curve && lane < A) curve[kc * A + lane] = nan;
+                pf_unfit_planes(kc, lane, A, curve, nullptr);
                 done = true;
             }
             rb_prev v = none;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_rb_fit(const double* __restrict_
                 rb_loss<0, WT>(prof, u, np, h, de, col, A, v, sse, loss, n_down);
                 if (__ballot(lane < A && sse == sse) == 0ull) {
                     if (lane == 0) rb_row_unfit(out, cell, mo.n, 1 | 32, nan);
-                    if (curve && lane < A) curve[kc * A + lane] = nan;
+                    pf_unfit_planes(kc, lane, A, curve, nullptr);
                     done = true;
                 }
             }
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_rb_fit(const double* __restrict_
                     if (dead) loss = nan;
                     if (__ballot(lane < A && loss == loss) == 0ull) {
                         if (lane == 0) rb_row_unfit(out, cell, mo.n, 1 | 32, sigma);
-                        if (curve && lane < A) curve[kc * A + lane] = nan;
+                        pf_unfit_planes(kc, lane, A, curve, nullptr);
                         done = true;
                     }
                 }
@@ -169,22 +170,12 @@ static int rb_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
                   int min_samples, int loss, double tuning, int iterations, double scale, sc_profile_robust_fit* out_rows,
                   double* out_loss) {
     const int np = 2 * h + 1;
-    const size_t row_bytes = sizeof(sc_profile_robust_fit);
     const size_t tab_bytes = sizeof(double) * (size_t)np * A;
-    const long long chunk = std::min<long long>(K, RB_CHUNK);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->pf_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_tab, tab_bytes))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->pf_rows, row_bytes * (size_t)chunk))) return rc;
-    if (out_loss && (rc = sc_ensure(ctx, ctx->pf_sse, sizeof(double) * (size_t)A * (size_t)chunk))) return rc;
     double* d_ages = (double*)ctx->pf_ages.p;
     double* d_tab = (double*)ctx->pf_tab.p;
-    long long* d_cells = (long long*)ctx->pf_cells.p;
-    double* d_dir = (double*)ctx->pf_dir.p;
-    sc_profile_robust_fit* d_rows = (sc_profile_robust_fit*)ctx->pf_rows.p;
-    double* d_loss = out_loss ? (double*)ctx->pf_sse.p : nullptr;
 
     // (the profiles and their weights come first: the table goes to LDS only where the CU still holds it beside them)
     const int np2 = wt ? 2 * np : np;
@@ -196,32 +187,13 @@ static int rb_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
     SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
 
-    std::vector<double> dir;
-    for (long long k0 = 0; k0 < K; k0 += chunk) {
-        const long long m = std::min(chunk, K - k0);
-        dir.resize(2 * (size_t)m);
-        for (long long k = 0; k < m; ++k) {
-            dir[2 * k] = sa[k0 + k];
-            dir[2 * k + 1] = ca[k0 + k];
-        }
-        SC_HIP(ctx, hipMemcpyAsync(d_cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_dir, dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, row_bytes * (size_t)m, ctx->stream));
-        const unsigned grid = (unsigned)std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID);
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        kern<<<grid, PF_THREADS, lds, ctx->stream>>>(z, wt, ny, nx, d_cells, d_dir, m, d_ages, A, h, w, de, delta, min_samples, tuning,
-                                                    iterations, scale, d_tab, d_rows, d_loss);
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, 1);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + k0, d_rows, row_bytes * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_loss)
-            SC_HIP(ctx, hipMemcpyAsync(out_loss + (size_t)k0 * A, d_loss, sizeof(double) * (size_t)A * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        // (dir is reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return SC_OK;
+    const pf_plane curve = {out_loss, &ctx->pf_sse, sizeof(double) * (size_t)A}, none = {nullptr, nullptr, 0};
+    return sc_pf_chunks(ctx, cells, sa, ca, K, PF_CHUNK, sizeof(sc_profile_robust_fit), out_rows, curve, none,
+                        [&](const pf_chunk& d, long long m) {
+        kern<<<pf_grid(m), PF_THREADS, lds, ctx->stream>>>(z, wt, ny, nx, d.cells, d.dir, m, d_ages, A, h, w, de, delta, min_samples,
+                                                          tuning, iterations, scale, d_tab, (sc_profile_robust_fit*)d.rows,
+                                                          (double*)d.plane[0]);
+    });
 }
 
 // The two calls after their null checks: the argument checks, then the fit on z - ny x nx on the host, uploaded - or on
@@ -235,13 +207,8 @@ static int rb_call(sc_ctx* ctx, const double* z, int ny, int nx, const long long
     if (rc) return rc;
     if ((rc = sc_rb_check(ctx, who, loss, tuning, iterations, scale))) return rc;
     if (K == 0) return SC_OK;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if ((rc = sc_pf_upload(ctx, ctx->pf_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->pf_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->pf_z, z, ny, nx, &z_dev))) return rc;
     const double* w_dev = nullptr;
     if (weights) {
         if ((rc = sc_pf_upload(ctx, ctx->pf_wt, weights, ny, nx))) return rc;

@@ -11,10 +11,11 @@
 //                 lanes run over the (shift, age) pairs (sh_search); parks the same terms AT d_ci, and d_ci itself
 //   k_sg_rank     one wave per segment: the usable cells of the segment in input order (ballot and popcount), their
 //                 number and the pooled number of valid points
-//   k_sg_sum1     one wave per block of 64 consecutive usable profiles, lanes over the ages: the block's terms summed
-//                 in sequence from the first
-//   k_sg_sum2     one wave per segment: the block sums in sequence from the first.  The shape of the sum depends on
-//                 n_profiles alone; one profile is no addition at all
+//   k_sg_sum1     one wave per block of 64 consecutive usable profiles and 64 of the C columns, lanes over the columns
+//                 (C = A ages here: one wave a block; sc_segment_ramp.hip sums its A (M + 1) pairs): the block's terms
+//                 summed in sequence from the first
+//   k_sg_sum2     one wave per segment and 64 columns: the block sums in sequence from the first.  The shape of the sum
+//                 depends on n_profiles alone; one profile is no addition at all
 //   k_sg_resid    one wave per cell: the parked profile back into LDS, lanes over the ages, pf_slope and pf_sse with
 //                 the segment's a_i and the column at d_ci (the unshifted call: no d_ci, D = 0); the cell's sse_ci
 //                 takes the place of See_ci
@@ -27,7 +28,6 @@
 #include <algorithm>
 #include <type_traits>
 
-#define SG_BLOCK 64                      // usable profiles per block of the segmented sum
 #define SG_MAX_SEGS (1ll << 20)          // segments per chunk: bounds the rows and totals of a call with empty segments
 
 // what k_sg_partial and k_sg_shift park of a cell apart from the per-age terms
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_sg_partial(const double* __restr
             if (ok) {
                 pf_col t;
                 const pf_lin f = pf_line<true>(L.prof, np, h, de, mo, col, A, t);
-                pf_rest(L.prof, np, h, de, f, col, A, t);
+                pf_rest(L.prof, np, h, de, f, pf_at(col, A), t);
                 sg_park_line(kc, lane, f, scal);
                 if (lane < A) {
                     const size_t o = (size_t)kc * A + lane;
@@ -162,14 +162,18 @@ __global__ __launch_bounds__(64) void k_sg_rank(const int* __restrict__ seg_star
     }
 }
 
-// block g of SG_BLOCK consecutive usable profiles of its segment: P planes summed in sequence from the first term
+// block g of SG_BLOCK consecutive usable profiles of its segment, 64 of the C columns: P planes summed in sequence from
+// the first term.  Work item t = g NC + (the chunk of columns); C <= 64 columns are one chunk, NC = 1 and t = g
 template <int P>
 __global__ __launch_bounds__(64) void k_sg_sum1(const double* __restrict__ src, size_t stride, const int* __restrict__ list,
                                                 const int* __restrict__ seg_start, const int* __restrict__ blk_start,
-                                                const int* __restrict__ cnt, long long S, long long G, int A,
+                                                const int* __restrict__ cnt, long long S, long long G, int C,
                                                 double* __restrict__ part) {
     const int lane = threadIdx.x;
-    for (long long g = blockIdx.x; g < G; g += gridDim.x) {
+    const long long NC = (C + 63) / 64;
+    for (long long t = blockIdx.x; t < G * NC; t += gridDim.x) {
+        const long long g = t / NC;
+        const int q = (int)(t - g * NC) * 64 + lane;
         long long lo = 0, hi = S;                        // the segment with blk_start[s] <= g < blk_start[s + 1]
         while (lo < hi) {
             const long long mid = (lo + hi) >> 1;
@@ -178,43 +182,46 @@ __global__ __launch_bounds__(64) void k_sg_sum1(const double* __restrict__ src, 
         const long long s = lo;
         const int m = cnt[2 * s];
         const int r0 = (int)(g - blk_start[s]) * SG_BLOCK;
-        if (r0 >= m || lane >= A) continue;
+        if (r0 >= m || q >= C) continue;
         const int r1 = min(m, r0 + SG_BLOCK);
         const int* ls = list + seg_start[s];
         double acc[P];
         {
-            const size_t o = (size_t)ls[r0] * A + lane;
+            const size_t o = (size_t)ls[r0] * C + q;
 #pragma unroll
             for (int p = 0; p < P; ++p) acc[p] = src[p * stride + o];
         }
         for (int r = r0 + 1; r < r1; ++r) {
-            const size_t o = (size_t)ls[r] * A + lane;
+            const size_t o = (size_t)ls[r] * C + q;
 #pragma unroll
             for (int p = 0; p < P; ++p) acc[p] += src[p * stride + o];
         }
 #pragma unroll
-        for (int p = 0; p < P; ++p) part[((size_t)g * P + p) * A + lane] = acc[p];
+        for (int p = 0; p < P; ++p) part[((size_t)g * P + p) * C + q] = acc[p];
     }
 }
 
-// the block sums of each segment in sequence from the first
+// the block sums of each segment in sequence from the first.  Work item t = s NC + (the chunk of columns)
 template <int P>
 __global__ __launch_bounds__(64) void k_sg_sum2(const double* __restrict__ part, const int* __restrict__ blk_start,
-                                                const int* __restrict__ cnt, long long S, int A, double* __restrict__ tot) {
+                                                const int* __restrict__ cnt, long long S, int C, double* __restrict__ tot) {
     const int lane = threadIdx.x;
-    for (long long s = blockIdx.x; s < S; s += gridDim.x) {
+    const long long NC = (C + 63) / 64;
+    for (long long t = blockIdx.x; t < S * NC; t += gridDim.x) {
+        const long long s = t / NC;
+        const int q = (int)(t - s * NC) * 64 + lane;
         const int nb = (cnt[2 * s] + SG_BLOCK - 1) / SG_BLOCK;
-        if (nb == 0 || lane >= A) continue;
+        if (nb == 0 || q >= C) continue;
         const size_t g0 = (size_t)blk_start[s];
         double acc[P];
 #pragma unroll
-        for (int p = 0; p < P; ++p) acc[p] = part[(g0 * P + p) * A + lane];
-        for (int q = 1; q < nb; ++q) {
+        for (int p = 0; p < P; ++p) acc[p] = part[(g0 * P + p) * C + q];
+        for (int b = 1; b < nb; ++b) {
 #pragma unroll
-            for (int p = 0; p < P; ++p) acc[p] += part[((g0 + q) * P + p) * A + lane];
+            for (int p = 0; p < P; ++p) acc[p] += part[((g0 + b) * P + p) * C + q];
         }
 #pragma unroll
-        for (int p = 0; p < P; ++p) tot[((size_t)s * P + p) * A + lane] = acc[p];
+        for (int p = 0; p < P; ++p) tot[((size_t)s * P + p) * C + q] = acc[p];
     }
 }
 
@@ -252,7 +259,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_sg_resid(const double* __restric
             const double a = Sep / See;
             double b, c0;
             pf_slope(scal[3 * kc], scal[3 * kc + 1], scal[3 * kc + 2], planes[o], planes[stride + o], a, b, c0);
-            const double sse = pf_sse(L.prof, np, h, de, col, A, a, b, c0);
+            const double sse = pf_sse(L.prof, np, h, de, pf_at(col, A), a, b, c0);
             if (lane < A) planes[2 * stride + o] = sse;
         }
         __syncthreads();
@@ -378,10 +385,6 @@ int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const 
     return SC_OK;
 }
 
-static unsigned sg_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
-static unsigned sg_grid_cells(long long m) {
-    return (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
-}
 
 // Stage one of a chunk of whole segments s0..s1 (shared with sc_bootstrap.hip): the chunk's cells, (sa, ca), CSR array and
 // labels go up, and the buffers of what k_sg_partial / k_sg_shift park and k_sg_rank lists are sized.  No launch
@@ -444,7 +447,7 @@ int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int 
     const auto k_partial = tab_lds ? k_sg_partial<true> : k_sg_partial<false>;
     const auto k_shift = tab_lds ? k_sg_shift<true> : k_sg_shift<false>;
     const long long m = st.m;
-    const unsigned gcell = sg_grid_cells(m);
+    const unsigned gcell = pf_grid(m);
     if (m && shift)
         k_shift<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, D, de, min_samples, d_tab, st.prof,
                                                          st.cn, st.used, st.scal, st.planes, st.shift);
@@ -461,11 +464,14 @@ void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st) {
     k_sg_rank<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.Sc, st.cn, st.used, st.list, st.cnt);
 }
 
-void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int A, double* part,
-                      double* tot) {
-    const size_t mA = (size_t)st.m * A;
-    k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(src, mA, st.list, st.seg, blk, st.cnt, st.Sc, G, A, part);
-    k_sg_sum2<2><<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(part, blk, st.cnt, st.Sc, A, tot);
+void sc_sg_sum_launch(sc_ctx* ctx, const double* src, const sg_stage& st, const int* blk, long long G, int C, int P,
+                      double* part, double* tot) {
+    const size_t mC = (size_t)st.m * C;
+    const long long NC = (C + 63) / 64;
+    const auto sum1 = P == 2 ? k_sg_sum1<2> : k_sg_sum1<1>;
+    const auto sum2 = P == 2 ? k_sg_sum2<2> : k_sg_sum2<1>;
+    sum1<<<sg_grid(G * NC), 64, 0, ctx->stream>>>(src, mC, st.list, st.seg, blk, st.cnt, st.Sc, G, C, part);
+    sum2<<<sg_grid(st.Sc * NC), 64, 0, ctx->stream>>>(part, blk, st.cnt, st.Sc, C, tot);
 }
 
 // the dynamic-LDS limit of the parking kernel, raised before the first chunk
@@ -542,7 +548,6 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         int* d_used = st.used;
         double* d_scal = st.scal;
         double* d_planes = st.planes;
-        int* d_list = st.list;
         double* d_part = (double*)ctx->sg_part.p;
         double* d_tot = (double*)ctx->sg_tot.p;
         double* d_tsse = (double*)ctx->sg_tsse.p;
@@ -559,17 +564,15 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         // (so is the padding at the end of the shifted call's cell table)
         if (shift && d_out && m) SC_HIP(ctx, hipMemsetAsync(d_out, 0, cell_bytes * (size_t)m, ctx->stream));
 
-        const unsigned gcell = sg_grid_cells(m);
+        const unsigned gcell = pf_grid(m);
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
         if ((rc = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, d_tab, st, launches))) return rc;
         if (G) {
-            k_sg_sum1<2><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
-            k_sg_sum2<2><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tot);
+            sc_sg_sum_launch(ctx, d_planes + 2 * mA, st, d_blk, G, A, 2, d_part, d_tot);
             k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift, d_tot, m, A, h,
                                                             Dk, de, min_profiles, d_tab);
-            k_sg_sum1<1><<<sg_grid(G), 64, 0, ctx->stream>>>(d_planes + 2 * mA, mA, d_list, d_start, d_blk, d_cnt, Sc, G, A, d_part);
-            k_sg_sum2<1><<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_part, d_blk, d_cnt, Sc, A, d_tsse);
+            sc_sg_sum_launch(ctx, d_planes + 2 * mA, st, d_blk, G, A, 1, d_part, d_tsse);
             launches += 5;
         }
         if (shift)
@@ -608,14 +611,9 @@ static int sg_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
                       min_profiles, out_rows);
     if (rc) return rc;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (S == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->sg_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && S == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;
     return sg_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
                   min_profiles, out_rows, out_cells, out_sse, out_shift);
 }

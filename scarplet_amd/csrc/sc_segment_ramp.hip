@@ -5,16 +5,14 @@
 // is one column of the joint problem, C = A (M + 1) columns where sc_fit_segments has A.  The pieces are those of sc_fit.h.
 //   k_sr_partial  one wave per cell: pf_cut (the profile goes to LDS and is PARKED), pf_moments and pf_line without a
 //                 column, once; then the lanes run over the (m, age) pairs, age-minor, 64 a round: pf_column on the erf
-//                 table at m = 0 - the plain call's arithmetic -, rp_column on the table of F at m >= 1.  Parks ebar,
+//                 table at m = 0 - the plain call's arithmetic -, on the ramp's column (rp_col) of the table of F at m >= 1.  Parks ebar,
 //                 gamma, See, Sep of every pair, pair-minor: a round's 64 lanes write 64 neighbouring doubles
 //   (k_sg_rank, sc_segment.hip)
-//   k_sr_sum1     one wave per block of 64 consecutive usable profiles and 64 columns: the block's terms summed in
-//                 sequence from the first
-//   k_sr_sum2     one wave per segment and 64 columns: the block sums in sequence from the first.  k_sg_sum1 and
-//                 k_sg_sum2 with a column count: the same additions in the same order per column
+//   (k_sg_sum1 and k_sg_sum2, sc_segment.hip, over C columns: one wave per block of 64 consecutive usable profiles - per
+//   segment - and 64 columns, the terms summed in sequence from the first)
 //   k_sr_resid    one wave per cell: the parked profile back into LDS, lanes over the pairs, pf_slope with the segment's
-//                 a_im, then pf_sse / rp_sse; sse_cim takes the place of See_cim and b_cim that of Sep_cim
-//   (k_sr_sum1 and k_sr_sum2 again, on sse_cim and b_cim)
+//                 a_im, then pf_sse on the same columns; sse_cim takes the place of See_cim and b_cim that of Sep_cim
+//   (k_sg_sum1 and k_sg_sum2 again, on sse_cim and b_cim)
 //   k_sr_choose   one wave per segment, lane i age i: the argmin over m on (key, m) in ascending m - the key is sse_im, or
 //                 the distance of the segment's mean initial slope from the given one -, then pf_choose along sse*, the
 //                 row, and lanes over the segment's cells for the cell table at the best pair
@@ -24,7 +22,6 @@
 #include <math.h>
 #include <algorithm>
 
-#define SR_BLOCK 64                      // usable profiles per block of the segmented sum (SG_BLOCK)
 #define SR_MAX_SEGS (1ll << 20)          // segments per chunk
 #define SR_MAX_TOTALS (1ll << 25)        // (blocks + segments) x columns per chunk: bounds the partials and totals
 
@@ -72,9 +69,9 @@ __global__ __launch_bounds__(PF_THREADS) void k_sr_partial(const double* __restr
                     const int q = on ? q0 + lane : C - 1;    // lanes beyond the pairs repeat the last one and are ignored
                     const int m = q / A, i = q - m * A;
                     if (m == 0)
-                        t = pf_column(L.prof, np, h, de, f, etab + i, A);
+                        t = pf_column(L.prof, np, h, de, f, pf_at(etab + i, A));
                     else
-                        t = rp_column(L.prof, np, h, de, f, rp_col_of(L.tab, A, M, m, i, de));
+                        t = pf_column(L.prof, np, h, de, f, rp_col_of(L.tab, A, M, m, i, de));
                     if (on) {
                         const size_t o = (size_t)kc * C + q;
                         planes[o] = t.ebar;
@@ -86,69 +83,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_sr_partial(const double* __restr
             }
         }
         __syncthreads();
-    }
-}
-
-// block g of SR_BLOCK consecutive usable profiles of its segment, 64 of the C columns: P planes summed in sequence from
-// the first term.  Work item t = g NC + (the chunk of columns)
-template <int P>
-__global__ __launch_bounds__(64) void k_sr_sum1(const double* __restrict__ src, size_t stride, const int* __restrict__ list,
-                                                const int* __restrict__ seg_start, const int* __restrict__ blk_start,
-                                                const int* __restrict__ cnt, long long S, long long G, int C,
-                                                double* __restrict__ part) {
-    const int lane = threadIdx.x;
-    const long long NC = (C + 63) / 64;
-    for (long long t = blockIdx.x; t < G * NC; t += gridDim.x) {
-        const long long g = t / NC;
-        const int q = (int)(t - g * NC) * 64 + lane;
-        long long lo = 0, hi = S;                        // the segment with blk_start[s] <= g < blk_start[s + 1]
-        while (lo < hi) {
-            const long long mid = (lo + hi) >> 1;
-            if ((long long)blk_start[mid + 1] <= g) lo = mid + 1; else hi = mid;
-        }
-        const long long s = lo;
-        const int m = cnt[2 * s];
-        const int r0 = (int)(g - blk_start[s]) * SR_BLOCK;
-        if (r0 >= m || q >= C) continue;
-        const int r1 = min(m, r0 + SR_BLOCK);
-        const int* ls = list + seg_start[s];
-        double acc[P];
-        {
-            const size_t o = (size_t)ls[r0] * C + q;
-#pragma unroll
-            for (int p = 0; p < P; ++p) acc[p] = src[p * stride + o];
-        }
-        for (int r = r0 + 1; r < r1; ++r) {
-            const size_t o = (size_t)ls[r] * C + q;
-#pragma unroll
-            for (int p = 0; p < P; ++p) acc[p] += src[p * stride + o];
-        }
-#pragma unroll
-        for (int p = 0; p < P; ++p) part[((size_t)g * P + p) * C + q] = acc[p];
-    }
-}
-
-// the block sums of each segment in sequence from the first.  Work item t = s NC + (the chunk of columns)
-template <int P>
-__global__ __launch_bounds__(64) void k_sr_sum2(const double* __restrict__ part, const int* __restrict__ blk_start,
-                                                const int* __restrict__ cnt, long long S, int C, double* __restrict__ tot) {
-    const int lane = threadIdx.x;
-    const long long NC = (C + 63) / 64;
-    for (long long t = blockIdx.x; t < S * NC; t += gridDim.x) {
-        const long long s = t / NC;
-        const int q = (int)(t - s * NC) * 64 + lane;
-        const int nb = (cnt[2 * s] + SR_BLOCK - 1) / SR_BLOCK;
-        if (nb == 0 || q >= C) continue;
-        const size_t g0 = (size_t)blk_start[s];
-        double acc[P];
-#pragma unroll
-        for (int p = 0; p < P; ++p) acc[p] = part[(g0 * P + p) * C + q];
-        for (int b = 1; b < nb; ++b) {
-#pragma unroll
-            for (int p = 0; p < P; ++p) acc[p] += part[((g0 + b) * P + p) * C + q];
-        }
-#pragma unroll
-        for (int p = 0; p < P; ++p) tot[((size_t)s * P + p) * C + q] = acc[p];
     }
 }
 
@@ -192,9 +126,9 @@ __global__ __launch_bounds__(PF_THREADS) void k_sr_resid(const double* __restric
                 double b, c0, sse;
                 pf_slope(sbar, pbar, beta, planes[o], planes[stride + o], a, b, c0);
                 if (m == 0)
-                    sse = pf_sse(L.prof, np, h, de, etab + i, A, a, b, c0);
+                    sse = pf_sse(L.prof, np, h, de, pf_at(etab + i, A), a, b, c0);
                 else
-                    sse = rp_sse(L.prof, np, h, de, rp_col_of(L.tab, A, M, m, i, de), a, b, c0);
+                    sse = pf_sse(L.prof, np, h, de, rp_col_of(L.tab, A, M, m, i, de), a, b, c0);
                 if (on) {
                     planes[2 * stride + o] = sse;
                     planes[3 * stride + o] = b;
@@ -304,10 +238,6 @@ __global__ __launch_bounds__(64) void k_sr_choose(const int* __restrict__ seg_st
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static unsigned sr_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
-static unsigned sr_grid_cells(long long m) {
-    return (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
-}
 
 static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
@@ -318,7 +248,6 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     const int np = 2 * h + 1, ht = h + M, nt = 2 * ht + 1, C = A * (M + 1);
     const size_t etab_bytes = sizeof(double) * (size_t)np * A, ftab_bytes = sizeof(double) * (size_t)nt * A;
     const long long cap = sc_sg_cap_cells(C, h, -1);
-    const long long NC = (C + 63) / 64;
     int rc;
     if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_tab, etab_bytes))) return rc;
@@ -344,9 +273,9 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes, and the totals
         long long s1 = s0 + 1;
-        long long nblk = (seg_start[s1] - seg_start[s0] + SR_BLOCK - 1) / SR_BLOCK;
+        long long nblk = (seg_start[s1] - seg_start[s0] + SG_BLOCK - 1) / SG_BLOCK;
         while (s1 < S && s1 - s0 < SR_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) {
-            const long long nb = (seg_start[s1 + 1] - seg_start[s1] + SR_BLOCK - 1) / SR_BLOCK;
+            const long long nb = (seg_start[s1 + 1] - seg_start[s1] + SG_BLOCK - 1) / SG_BLOCK;
             if ((nblk + nb + (s1 + 1 - s0)) * C > SR_MAX_TOTALS) break;
             nblk += nb;
             ++s1;
@@ -357,7 +286,7 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         blk[0] = 0;
         for (long long s = 0; s < Sc; ++s) {
             const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            blk[s + 1] = blk[s] + (int)((a1 - a0 + SR_BLOCK - 1) / SR_BLOCK);
+            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
             for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
         }
         const long long G = blk[Sc];
@@ -388,7 +317,7 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
         SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_ramp_fit) * (size_t)Sc, ctx->stream));
 
-        const unsigned gcell = sr_grid_cells(m);
+        const unsigned gcell = pf_grid(m);
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
         if (m) {
@@ -399,15 +328,13 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         sc_sg_rank_launch(ctx, st);
         ++launches;
         if (G) {
-            k_sr_sum1<2><<<sr_grid(G * NC), 64, 0, ctx->stream>>>(st.planes + 2 * mC, mC, st.list, st.seg, d_blk, st.cnt, Sc, G, C, d_part);
-            k_sr_sum2<2><<<sr_grid(Sc * NC), 64, 0, ctx->stream>>>(d_part, d_blk, st.cnt, Sc, C, d_tot);
+            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, d_blk, G, C, 2, d_part, d_tot);
             k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_cseg, st.used, st.cnt, st.scal, st.planes, d_tot, m, A, h, M,
                                                             given, de, min_profiles, d_etab, d_ftab);
-            k_sr_sum1<2><<<sr_grid(G * NC), 64, 0, ctx->stream>>>(st.planes + 2 * mC, mC, st.list, st.seg, d_blk, st.cnt, Sc, G, C, d_part);
-            k_sr_sum2<2><<<sr_grid(Sc * NC), 64, 0, ctx->stream>>>(d_part, d_blk, st.cnt, Sc, C, d_tsum);
+            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, d_blk, G, C, 2, d_part, d_tsum);
             launches += 5;
         }
-        k_sr_choose<<<sr_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tsum, d_ages, A, M, given, slope, de,
+        k_sr_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tsum, d_ages, A, M, given, slope, de,
                                                         delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes, d_rows,
                                                         d_out, d_sse, d_width);
         ++launches;
@@ -444,14 +371,9 @@ static int sr_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
         if (seg_start[s + 1] - seg_start[s] > cap)
             return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h, A and M", who,
                            seg_start[s + 1] - seg_start[s], cap);
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (S == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->sg_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && S == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;
     return sr_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, ages, A, h, w, M, mode, slope, de, delta, min_samples,
                   min_profiles, out_rows, out_cells, out_sse, out_width);
 }

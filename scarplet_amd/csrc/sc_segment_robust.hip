@@ -28,7 +28,6 @@
 #include <math.h>
 #include <algorithm>
 
-#define SQ_BLOCK 64                      // usable profiles per block of the segmented sum (SG_BLOCK of sc_segment.hip)
 #define SQ_MAX_SEGS (1ll << 16)          // segments per chunk: bounds the histograms (1 KB a segment)
 #define SQ_LDS_BYTES (160 * 1024)        // the LDS of a CU
 #define SQ_MAD 1.4826
@@ -496,10 +495,6 @@ static long long sq_cap_cells(int A, int h, bool plane) {
     return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) * (plane ? 2 : 1) + (long long)SQ_PLANES * A));
 }
 
-static unsigned sq_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, 65536)); }
-static unsigned sq_grid_cells(long long m) {
-    return (unsigned)std::max<long long>(1, std::min<long long>((m + PF_WAVES - 1) / PF_WAVES, PF_MAX_GRID));
-}
 
 typedef void (*sq_partial_kernel)(const double*, const double*, int, int, const long long*, const double*, long long, int, int, int,
                                   double, int, const double*, double*, double*, int*, int*, double*);
@@ -564,7 +559,7 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
         blk[0] = 0;
         for (long long s = 0; s < Sc; ++s) {
             const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            blk[s + 1] = blk[s] + (int)((a1 - a0 + SQ_BLOCK - 1) / SQ_BLOCK);
+            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
             for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
         }
         const long long G = blk[Sc];
@@ -615,7 +610,7 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
         // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
         SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_robust_fit) * (size_t)Sc, ctx->stream));
 
-        const unsigned gcell = sq_grid_cells(m);
+        const unsigned gcell = pf_grid(m);
         int launches = 0;
         sc_prof_begin(ctx, SC_K_PROFILE);
         if (m) {
@@ -626,20 +621,20 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
         sc_sg_rank_launch(ctx, st);
         ++launches;
         if (G) {
-            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, d_part, d_tot);
+            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tot);
             k_loss0<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
                                                             min_profiles, 0.0, d_tab);
-            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, d_part, d_tl);
+            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tl);
             launches += 5;
         }
         if (robust) {
-            k_sq_begin<<<sq_grid(Sc), 64, 0, ctx->stream>>>(st.cnt, Sc, d_tot, d_tl, A, delta, min_profiles, scale, Q, d_hist, d_a0);
+            k_sq_begin<<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.cnt, Sc, d_tot, d_tl, A, delta, min_profiles, scale, Q, d_hist, d_a0);
             ++launches;
             if (G && !(scale > 0.0)) {
                 for (int r = 0; r < 8; ++r) {
                     k_sq_hist<<<gcell, PF_THREADS, 0, ctx->stream>>>(d_prof, d_cseg, st.used, Q, d_a0, st.planes, m, A, h, de, r, d_tab,
                                                                     d_hist);
-                    k_sq_pick<<<sq_grid(Sc), 64, 0, ctx->stream>>>(Sc, Q, r, d_hist);
+                    k_sq_pick<<<sg_grid(Sc), 64, 0, ctx->stream>>>(Sc, Q, r, d_hist);
                 }
                 launches += 16;
             }
@@ -647,18 +642,18 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
                 for (int t = 0; t < iterations; ++t) {
                     k_step<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, Q, d_tot, st.planes, m, A, h, de,
                                                                    min_samples, tuning, t > 0 ? 1 : 0, d_tab);
-                    sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, d_part, d_tot);
+                    sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tot);
                 }
                 k_lossT<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
                                                                 min_profiles, tuning, d_tab);
-                sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, d_part, d_tl);
+                sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tl);
                 launches += 3 * iterations + 3;
             }
-            k_sq_choose<true><<<sq_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
+            k_sq_choose<true><<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
                                                                   min_profiles, st.cells, st.cn, st.used, st.planes, d_rows, d_out,
                                                                   d_curve);
         } else {
-            k_sq_choose<false><<<sq_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
+            k_sq_choose<false><<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
                                                                    min_profiles, st.cells, st.cn, st.used, st.planes, d_rows, d_out,
                                                                    d_curve);
         }
@@ -696,14 +691,9 @@ static int sq_call(sc_ctx* ctx, const double* z, int ny, int nx, const long long
         if (seg_start[s + 1] - seg_start[s] > cap)
             return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h and A", who,
                            seg_start[s + 1] - seg_start[s], cap);
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (S == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->sg_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && S == 0) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;
     const double* w_dev = nullptr;
     if (weights && S > 0) {
         if ((rc = sc_pf_upload(ctx, ctx->sq_wt, weights, ny, nx))) return rc;

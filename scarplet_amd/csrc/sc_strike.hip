@@ -286,14 +286,9 @@ static int st_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                          min_profiles, out_rows);
     if (rc) return rc;
     if ((rc = st_check(ctx, who, seg_start, S, seg_win_start, win_lo, win_hi, NW, out_rows))) return rc;
-    const double* z_dev = ctx->z_dev;
-    if (z) {
-        if (S == 0 || NW == 0) return SC_OK;
-        if ((rc = sc_pf_upload(ctx, ctx->sg_z, z, ny, nx))) return rc;
-        z_dev = (const double*)ctx->sg_z.p;
-    } else {
-        SC_HIP(ctx, hipSetDevice(ctx->device));
-    }
+    if (z && (S == 0 || NW == 0)) return SC_OK;
+    const double* z_dev;
+    if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;
     if (NW == 0) return SC_OK;
     return st_run(ctx, z_dev, ny, nx, cells, sa, ca, seg_start, seg_label, S, seg_win_start, win_lo, win_hi, ages, A, h, w, D,
                   de, delta, min_samples, min_profiles, out_rows, out_sse);

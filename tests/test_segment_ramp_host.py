@@ -174,8 +174,10 @@ def test_the_makefile_lists_the_source():
 def test_segment_ramp_kernels_have_no_scratch():
     from test_isa_budget import kernel_table
     t = kernel_table("sc_segment_ramp.hip")
+    # (the segmented sum over the A (M + 1) columns is sc_segment.hip's k_sg_sum1<2> / k_sg_sum2<2>)
+    t.update({k: v for k, v in kernel_table("sc_segment.hip").items() if k.startswith("k_sg_sum")})
     for k in ("k_sr_partial<true>", "k_sr_partial<false>", "k_sr_resid<true>", "k_sr_resid<false>", "k_sr_choose",
-              "k_sr_sum1<2>", "k_sr_sum2<2>"):
+              "k_sg_sum1<2>", "k_sg_sum2<2>"):
         assert k in t, sorted(t)
         assert t[k]["scratch"] == 0, (k, t[k])
         assert t[k]["vgpr"] + t[k]["agpr"] <= 128, (k, t[k])               # four waves per SIMD
