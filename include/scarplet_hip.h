@@ -253,6 +253,15 @@ int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const d
  *              are the same bits either way, so are the results.  Setting the option (to any
  *              value) and loading a DEM drop what was kept.  Default 0 in the library; the
  *              Python host sets 8192.
+ *   "fit_chunk"  n > 0: every fit call (sc_fit_profiles*, sc_lateral_offsets*, sc_fit_segments*,
+ *              sc_bootstrap_segments*, sc_fit_strike*, sc_snr_surface) closes a chunk of its work at n cells
+ *              where its built-in bound (2^19 cells, the parked bytes of SC_SEGMENT_MAX_PARK, 256 MiB of
+ *              cubes) lies higher; it never raises one.  The per-cell calls launch on at most n cells; the
+ *              segment calls take whole segments while their cells stay within n, a longer segment alone
+ *              (a segment above SC_SEGMENT_MAX_PARK is refused as before); sc_snr_surface rounds n up to
+ *              whole batches of eight cells.  An integer >= 0, finite; 0 (default): the built-in bounds
+ *              alone.  Every output byte is the same for every value: the option exists so that the
+ *              tests run the chunks' hand-over on small inputs (tests/test_gpu_fit_chunks.py).
  */
 int sc_set_option(sc_ctx* ctx, const char* name, double value);
 

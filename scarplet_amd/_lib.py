@@ -516,7 +516,7 @@ class Context(object):
 
     def set_option(self, name, value):
         """Engine options (include/scarplet_hip.h sc_set_option): 'kappa',
-        'variant', 'y_gb', 'spectra_mb', 'fuse_fwd'."""
+        'variant', 'y_gb', 'spectra_mb', 'fuse_fwd', 'fit_chunk'."""
         self._check(self.lib.sc_set_option(self._h, name.encode(), float(value)),
                     "sc_set_option(%s)" % name)
         if name == "spectra_mb":

@@ -191,6 +191,9 @@ extern "C" int sc_set_option(sc_ctx* ctx, const char* name, double value) {
     } else if (!strcmp(name, "y_gb")) {
         if (!(value >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "y_gb must be >= 0");
         ctx->y_gb = value;
+    } else if (!strcmp(name, "fit_chunk")) {
+        if (!(value >= 0.0 && std::isfinite(value))) return sc_fail(ctx, SC_ERR_INVALID, "fit_chunk must be >= 0 and finite");
+        ctx->fit_chunk = value >= 0x1p62 ? (1ll << 62) : (long long)value;       // (it only ever lowers a built-in bound)
     } else {
         return sc_fail(ctx, SC_ERR_INVALID, "unknown option '%s'", name);
     }

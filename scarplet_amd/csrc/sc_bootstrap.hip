@@ -304,10 +304,9 @@ static int bs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     const int lds_fit = (int)(BS_LDS_MAX / (sizeof(double2) * (size_t)A));      // blocks of a segment that LDS holds
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes and the replicates' outputs
-        long long s1 = s0 + 1;
-        while (s1 < S && s1 - s0 < BS_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap &&
-               (s1 - s0 + 1) * (long long)R1 <= BS_MAX_OUT)
-            ++s1;
+        // (Sc R1 <= BS_MAX_OUT is a bound on the segments: Sc <= BS_MAX_OUT / R1, rounded down)
+        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, std::min<long long>(BS_MAX_SEGS, BS_MAX_OUT / (long long)R1),
+                                              sc_fit_chunk_bound(cap, ctx->fit_chunk));
         const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
         const long long b0 = seg_blk_start[s0], NBc = seg_blk_start[s1] - b0;
         blk.resize((size_t)NBc + 1);

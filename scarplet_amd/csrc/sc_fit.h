@@ -13,6 +13,7 @@
 // text in the order of its text wherever it is called: the calls return the same bits in every field they share because
 // they call the same helpers.
 #pragma once
+#include "sc_fit_chunk.h"
 #include "sc_internal.h"
 #include <functional>
 #include <vector>

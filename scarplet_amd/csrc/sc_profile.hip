@@ -206,7 +206,7 @@ int sc_pf_dem(sc_ctx* ctx, DevBuf& buf, const double* z, int ny, int nx, const d
 int sc_pf_chunks(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K, long long chunk,
                  size_t row_bytes, void* out_rows, const pf_plane& p0, const pf_plane& p1, const pf_launch& launch) {
     const pf_plane planes[2] = {p0, p1};
-    chunk = std::min(K, chunk);
+    chunk = std::min(K, sc_fit_chunk_bound(chunk, ctx->fit_chunk));
     int rc;
     if ((rc = sc_ensure(ctx, ctx->pf_cells, sizeof(long long) * (size_t)chunk))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_dir, sizeof(double) * 2 * (size_t)chunk))) return rc;

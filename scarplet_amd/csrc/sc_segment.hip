@@ -516,8 +516,7 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     std::vector<int> cseg, blk;
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes
-        long long s1 = s0 + 1;
-        while (s1 < S && s1 - s0 < SG_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) ++s1;
+        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, SG_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk));
         const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
         blk.resize((size_t)Sc + 1);
         cseg.resize((size_t)m);

@@ -270,16 +270,14 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
 
     sg_stage st;
     std::vector<int> cseg, blk;
+    // (the totals of a chunk as a CSR array over the segments: a segment's blocks and one more, C columns each)
+    std::vector<long long> tot_start((size_t)S + 1, 0);
+    for (long long s = 0; s < S; ++s)
+        tot_start[s + 1] = tot_start[s] + (seg_start[s + 1] - seg_start[s] + SG_BLOCK - 1) / SG_BLOCK + 1;
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes, and the totals
-        long long s1 = s0 + 1;
-        long long nblk = (seg_start[s1] - seg_start[s0] + SG_BLOCK - 1) / SG_BLOCK;
-        while (s1 < S && s1 - s0 < SR_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap) {
-            const long long nb = (seg_start[s1 + 1] - seg_start[s1] + SG_BLOCK - 1) / SG_BLOCK;
-            if ((nblk + nb + (s1 + 1 - s0)) * C > SR_MAX_TOTALS) break;
-            nblk += nb;
-            ++s1;
-        }
+        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, SR_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk),
+                                              tot_start.data(), SR_MAX_TOTALS / C);
         const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
         blk.resize((size_t)Sc + 1);
         cseg.resize((size_t)m);

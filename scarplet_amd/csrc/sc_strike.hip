@@ -212,10 +212,8 @@ static int st_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     std::vector<int> win, wstart;
     for (long long s0 = 0; s0 < S;) {
         // a chunk of whole segments: as many as fit the parked bytes and the windows' outputs
-        long long s1 = s0 + 1;
-        while (s1 < S && s1 - s0 < ST_MAX_SEGS && seg_start[s1 + 1] - seg_start[s0] <= cap &&
-               seg_win_start[s1 + 1] - seg_win_start[s0] <= ST_MAX_WIN)
-            ++s1;
+        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, ST_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk),
+                                              seg_win_start, ST_MAX_WIN);
         const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
         const long long g0 = seg_win_start[s0], NWc = seg_win_start[s1] - g0;
         win.resize(3 * (size_t)NWc);

@@ -16,6 +16,7 @@
 //                                       then walks the age's runs over the stage and keeps its two sums in registers
 //   k_sf_reduce                         a wave per cell: first maximum, the two walks, n_within, the row
 // No atomics on floating-point values and no order that depends on scheduling: the same bytes on every run.
+#include "sc_fit_chunk.h"
 #include "sc_internal.h"
 #include <algorithm>
 #include <math.h>
@@ -352,6 +353,8 @@ extern "C" int sc_snr_surface(sc_ctx* ctx, const sc_template* t, int n_par, int 
     long long KC = (long long)(SF_CUBE_BYTES / per_cell) / SF_CB * SF_CB;
     KC = std::max<long long>(KC, SF_CB);
     KC = std::min<long long>(KC, (K + SF_CB - 1) / SF_CB * SF_CB);
+    // (option "fit_chunk" lowers it, to whole batches of cells)
+    KC = sc_fit_chunk_bound(KC, (ctx->fit_chunk + SF_CB - 1) / SF_CB * SF_CB);
     const bool pq_lds = (size_t)(n_par + n_ang) <= 2048;                   // four cells' P and Q in 64 KB of LDS
     const size_t pq_bytes = pq_lds ? 0 : up64(8 * (size_t)(n_par + n_ang) * (size_t)((KC + 3) / 4 * 4));
     if ((rc = sc_ensure(ctx, ctx->sf_cube, 2 * up64(8 * (size_t)n * (size_t)KC) + pq_bytes))) return rc;
