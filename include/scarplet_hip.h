@@ -948,6 +948,63 @@ int sc_fit_profiles_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const
                              double* out_sse, int8_t* out_width);
 
 /*
+ * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and
+ * after it R levels of 64 candidate ages of the cell's OWN bracket - for the minimum and for either end of the interval.
+ * The samples, the validity rule, the min_samples rule, the orthogonalised fit and the explicit-residual sse are those of
+ * sc_fit_profiles; every field of sc_profile_fit, and out_sse, are its bytes.
+ *   column     of a candidate age x (a double): e_j = erf((double)j de / (2.0 sqrt(x))), the expression of the erf table -
+ *              at a grid age the table's bits
+ *   candidates of a bracket [p, q]: x_l = p + (q - p) ((double)l / 63.0) for l = 0..62 and x_63 = q; each is fitted by the
+ *              four passes of sc_fit_profiles with its column.  A NaN sse counts as +inf
+ *   status 1   every *_fine float is NaN, status_fine = 1
+ *   minimum    i = kt_index.  The first bracket is [ages[max(i - 1, 0)], ages[min(i + 1, A - 1)]].  R times: fit the 64
+ *              candidates, l* = argmin of their sse (ties to the smaller l), the next bracket is [x_max(l* - 1, 0),
+ *              x_min(l* + 1, 63)].  kt_fine = x_l* of the last level with its a, b, c0, sse - unless that sse is not <=
+ *              the grid's sse[i], or R = 0: then ages[i] with the grid's a, b, c0, sse.  So sse_fine <= sse.
+ *              rmse_fine = sqrt(sse_fine / (n - 3)), height_fine = 2 a_fine
+ *   interval   thr = sse_fine (1 + delta / (n - 3)).
+ *              lower end: g = the largest grid index with ages[g] <= kt_fine; j = g, g - 1, ... while j >= 0 and the
+ *              grid's sse[j] <= thr.  Off the grid: kt_lo_fine = ages[0] and status_fine gains 2.  Else outer = ages[j],
+ *              inner = ages[j + 1] if j + 1 <= g, else kt_fine; R times over [outer, inner]: fit the candidates, take the
+ *              smallest l >= 1 with sse <= thr (l = 63 always qualifies), the next bracket is [x_(l - 1), x_l].
+ *              kt_lo_fine = the last inner.
+ *              upper end, the mirror image: g = the smallest grid index with ages[g] >= kt_fine, walking up; off the
+ *              grid: kt_hi_fine = ages[A - 1] and status_fine gains 4; brackets [inner, outer], the largest l <= 62 with
+ *              sse <= thr (l = 0 always qualifies), next [x_l, x_(l + 1)].
+ *              R = 0 gives the grid's kt_lo and kt_hi, and status_fine = status
+ *   A = 1, or p == q: all candidates are equal, and the rules above give the grid age
+ * One lane owns one candidate and sums over ascending j; the argmin and the "first l within thr" are shuffles and ballots
+ * on (sse, l): no atomics, no float sum across lanes - the same bytes on every run, for every order of the cells and for
+ * every chunk size.  Refused before any device work: what sc_fit_profiles refuses; R < 0 (SC_ERR_INVALID); R >
+ * SC_PROFILE_MAX_REFINE (SC_ERR_UNSUPPORTED: a third level would decide on differences no second implementation
+ * reproduces).  The buffers are those of sc_fit_profiles.  Timed as SC_K_PROFILE.
+ */
+#define SC_PROFILE_MAX_REFINE 2
+typedef struct sc_profile_fine_fit {
+    int64_t  cell;            /* the fields of sc_profile_fit, in its layout     */
+    int32_t  n;
+    int32_t  kt_index;
+    int32_t  lo_index, hi_index;
+    int32_t  status;
+    double   kt, kt_lo, kt_hi;
+    double   a, b, c0;
+    double   sse, rmse;
+    double   kt_fine, kt_lo_fine, kt_hi_fine;   /* the minimum and the interval, off the grid */
+    double   a_fine, b_fine, c0_fine;           /* of kt_fine                                 */
+    double   sse_fine, rmse_fine;               /* sse_fine <= sse                            */
+    double   height_fine;                       /* 2 a_fine                                   */
+    int32_t  status_fine;     /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) */
+} sc_profile_fine_fit;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_profiles_refine(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                           const double* ages, int A, int h, int w, int R, double de, double delta, int min_samples,
+                           sc_profile_fine_fit* out_rows, double* out_sse);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_profiles_refine_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                               const double* ca, long long K, const double* ages, int A, int h, int w, int R, double de,
+                               double delta, int min_samples, sc_profile_fine_fit* out_rows, double* out_sse);
+
+/*
  * The initial slope of the joint fit (docs/segments.md, "The initial slope"; scarplet_amd/csrc/sc_segment_ramp.hip): the
  * fit of sc_fit_segments with the scarp of sc_fit_profiles_ramp,
  *   z_c(s) = c0_c + b_c s + a g(s; kt, L),   L = m de,   m = 0..M a whole number of cells.

@@ -135,6 +135,22 @@ PROFILE_MAX_WIDTH = 64                                                 # SC_PROF
 RAMP_FREE, RAMP_SLOPE = 0, 1                                           # SC_RAMP_*
 
 
+FINE_FLOATS = ("kt_fine", "kt_lo_fine", "kt_hi_fine", "a_fine", "b_fine", "c0_fine", "sse_fine", "rmse_fine", "height_fine")
+
+
+class sc_profile_fine_fit(C.Structure):
+    """One row of sc_fit_profiles_refine / sc_fit_profiles_refine_dem: sc_profile_fit, then the minimum and the interval off
+    the grid (docs/profiles.md, "Continuous ages")."""
+    _fields_ = sc_profile_fit._fields_ + [(f, C.c_double) for f in FINE_FLOATS] + [("status_fine", C.c_int32)]
+
+
+PROFILE_FINE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fine_fit._fields_],
+                               "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 17 + [np.int32],
+                               "offsets": [getattr(sc_profile_fine_fit, f).offset for f, _ in sc_profile_fine_fit._fields_],
+                               "itemsize": C.sizeof(sc_profile_fine_fit)})
+PROFILE_MAX_REFINE = 2                                                 # SC_PROFILE_MAX_REFINE
+
+
 class sc_segment_fit(C.Structure):
     """One row of sc_fit_segments / sc_fit_segments_dem (docs/segments.md)."""
     _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n", C.c_int32),
@@ -357,6 +373,11 @@ SIGNATURES = {
     "sc_fit_profiles_ramp_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                            C.c_int, C.c_void_p, _dp, C.c_void_p]),
+    "sc_fit_profiles_refine": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    "sc_fit_profiles_refine_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
+                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                             _dp]),
     "sc_fit_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                   C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
                                   C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
@@ -836,6 +857,27 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, sse, plane
+
+    def fit_profiles_refine(self, cells, sa, ca, ages, h, w, de, delta, min_samples, refine, curve=False, z=None):
+        """sc_fit_profiles_refine on the context's DEM, or sc_fit_profiles_refine_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous; ``refine``: R, the levels of
+        64 candidate ages below the grid."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A = len(cells), len(ages)
+        assert len(sa) == K and len(ca) == K
+        rows = np.zeros(K, dtype=PROFILE_FINE_DTYPE)
+        sse = np.empty((K, A), dtype=np.float64) if curve else None
+        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
+                int(refine), float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p),
+                _as(sse, _dp) if curve else None]
+        name = "sc_fit_profiles_refine"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, sse
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
     def fit_segments(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,

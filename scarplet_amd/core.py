@@ -899,14 +899,15 @@ class Matcher(object):
 
     def fit_profiles(self, traces_or_cells, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
                      return_curve=False, angle=None, max_shift=None, return_shift=False, weights=None, robust=None,
-                     tuning=None, iterations=8, robust_scale=None, max_width=None, initial_slope=None, return_width=False):
+                     tuning=None, iterations=8, robust_scale=None, max_width=None, initial_slope=None, return_width=False,
+                     refine=None):
         """``sl.fit_profiles`` on the DEM this matcher holds on the device (docs/profiles.md) - no upload.  Given
         the ``Traces`` of ``extract_traces`` it fits the cells of the segments (``labels > 0``, row-major order) with
         the angle plane of this matcher's result and adds a ``label`` column; given cells (as ``sl.fit_profiles``
         takes them) it reads that plane at the cells unless ``angle`` says otherwise.  The bytes are those of
         ``sl.fit_profiles`` on the same data, ``max_shift`` and ``return_shift`` included - and ``weights``, ``robust``,
         ``tuning``, ``iterations`` and ``robust_scale`` (the weight plane is uploaded; the DEM is not) - and ``max_width``,
-        ``initial_slope`` and ``return_width``."""
+        ``initial_slope`` and ``return_width`` - and ``refine``."""
         from scarplet_amd import profiles, traces
         if not getattr(self, "whole", False):
             raise ValueError("fit_profiles needs the whole DEM on the device, not a block of it")
@@ -925,8 +926,9 @@ class Matcher(object):
         D = profiles.check_shift(max_shift, return_shift, args[6], args[4], args[8])
         rb = profiles.check_robust((self.ny, self.nx), weights, robust, tuning, iterations, robust_scale, max_shift)
         rp = profiles.check_width(max_width, initial_slope, return_width, args[6], args[4], args[8], max_shift, weights, robust)
+        R = profiles.check_refine(refine, max_shift, weights, robust, max_width)
         return profiles._run(self.ctx, args, self.nx, return_curve, label=label, shift=D, return_shift=return_shift, robust=rb,
-                             ramp=rp, return_width=return_width)
+                             ramp=rp, return_width=return_width, refine=R)
 
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of

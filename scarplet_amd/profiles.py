@@ -30,6 +30,9 @@ ROBUST_FIT_DTYPE = np.dtype(ROBUST_FIT_FIELDS)
 # ... and with max_width: the half-width of the best age's initial ramp, in cells and in data units, and its gradient
 RAMP_FIT_FIELDS = FIT_FIELDS + [("width_index", np.int32), ("width", np.float64), ("initial_slope", np.float64)]
 RAMP_FIT_DTYPE = np.dtype(RAMP_FIT_FIELDS)
+# ... and with refine: the minimum and the interval off the grid, after ``height``
+FINE_FIT_FIELDS = FIT_FIELDS + [(f, np.float64) for f in _lib.FINE_FLOATS] + [("status_fine", np.int32)]
+FINE_FIT_DTYPE = np.dtype(FINE_FIT_FIELDS)
 ROBUST_LOSSES = {"huber": (_lib.ROBUST_HUBER, 1.345), "tukey": (_lib.ROBUST_TUKEY, 4.685)}
 
 
@@ -240,11 +243,31 @@ def check_width(max_width, initial_slope, return_width, de, h, min_samples, max_
     return M, _lib.RAMP_SLOPE, g
 
 
+def check_refine(refine, max_shift=None, weights=None, robust=None, max_width=None):
+    """None for ``refine=None``, else R, the levels of 64 candidate ages below the grid (0, 1 or 2); ValueError otherwise."""
+    if refine is None:
+        return None
+    if isinstance(refine, (bool, np.bool_)):
+        raise ValueError("refine must be None, 0, 1 or 2, got %r" % (refine,))
+    try:
+        R = operator.index(refine)
+    except TypeError:
+        v = float(refine) if isinstance(refine, (float, np.floating)) else math.nan
+        if not (math.isfinite(v) and v == math.floor(v)):
+            raise ValueError("refine must be None, 0, 1 or 2, got %r" % (refine,))
+        R = int(v)
+    if R < 0 or R > _lib.PROFILE_MAX_REFINE:
+        raise ValueError("refine must be None, 0, 1 or 2, got %r" % (refine,))
+    if max_shift is not None or weights is not None or robust is not None or max_width is not None:
+        raise ValueError("refine is not built together with max_shift, weights, robust or max_width")
+    return R
+
+
 def _table(rows, nx, label=None):
     """The library's rows -> the Python table (row, col, the row's fields, height = 2 a; ``label`` when given)."""
     names = rows.dtype.names
     fields = SHIFT_FIT_FIELDS if "shift" in names else ROBUST_FIT_FIELDS if "loss" in names else \
-        RAMP_FIT_FIELDS if "width" in names else FIT_FIELDS
+        RAMP_FIT_FIELDS if "width" in names else FINE_FIT_FIELDS if "kt_fine" in names else FIT_FIELDS
     dt = np.dtype(fields + ([] if label is None else [("label", np.int32)]))
     out = np.zeros(len(rows), dtype=dt)
     for f in rows.dtype.names:
@@ -272,7 +295,7 @@ def _dem_of(data):
 
 def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4, return_curve=False,
                  device=0, max_shift=None, return_shift=False, weights=None, robust=None, tuning=None, iterations=8,
-                 robust_scale=None, max_width=None, initial_slope=None, return_width=False):
+                 robust_scale=None, max_width=None, initial_slope=None, return_width=False, refine=None):
     """Fit the diffusion scarp to elevation profiles cut across the strike at ``cells`` (docs/profiles.md).
 
     ``data``: the DEMGrid.  ``cells``: linear indices ``r * nx + c``, a ``(rows, cols)`` tuple, or a bool plane (its
@@ -315,21 +338,32 @@ def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0,
     ``width_index`` (m of the best age), ``width`` (m de) and ``initial_slope`` (the signed ``b + a / (m de)``; +-inf at
     ``m = 0``), the curves are the chosen pairs' sse, and ``status`` gains 8 where ``width_index`` is the end of the range.
     ``return_width`` adds the (K, A) int8 plane of every age's m, after the curves.  Not built together with
-    ``max_shift``, ``weights`` or ``robust``."""
+    ``max_shift``, ``weights`` or ``robust``.
+
+    ``refine`` (None: the answer is an age of the grid; 0, 1 or 2) adds that many levels of 64 candidate ages of the cell's
+    own bracket below the grid - for the minimum and for either end of the interval (docs/profiles.md, "Continuous ages").
+    Every field of the plain table keeps the plain call's bytes; the table gains ``kt_fine, kt_lo_fine, kt_hi_fine, a_fine,
+    b_fine, c0_fine, sse_fine`` (<= ``sse``), ``rmse_fine, height_fine, status_fine``, and the curves stay the grid's.  Not
+    built together with ``max_shift``, ``weights``, ``robust`` or ``max_width``."""
     z, de = _dem_of(data)
     args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
     D = check_shift(max_shift, return_shift, args[6], args[4], args[8])
     rb = check_robust(z.shape, weights, robust, tuning, iterations, robust_scale, max_shift)
     rp = check_width(max_width, initial_slope, return_width, args[6], args[4], args[8], max_shift, weights, robust)
+    R = check_refine(refine, max_shift, weights, robust, max_width)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
     return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift, robust=rb, ramp=rp,
-                return_width=return_width)
+                return_width=return_width, refine=R)
 
 
 def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False, robust=None, ramp=None,
-         return_width=False):
+         return_width=False, refine=None):
     idx, sa, ca, kt, h, w, de, d, ms = args
+    if refine is not None:
+        rows, curve = ctx.fit_profiles_refine(idx, sa, ca, kt, h, w, de, d, ms, refine, curve=bool(return_curve), z=z)
+        out = _table(rows, nx, label)
+        return (out, curve) if return_curve else out
     if ramp is not None:
         M, mode, slope = ramp
         rows, curve, plane = ctx.fit_profiles_ramp(idx, sa, ca, kt, h, w, de, d, ms, M, mode=mode, slope=slope,
