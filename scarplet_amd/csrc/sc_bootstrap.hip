@@ -14,6 +14,8 @@
 //   k_bs_summary  one workgroup per segment: an integer histogram of the indices in LDS, the ranks walked along it, a_mean
 //                 and a_sd summed in replicate order by one thread, a bitonic sort of the a in LDS for a_lo and a_hi
 // No float atomics, no float sum across lanes: the same bytes on every run.
+// The host side is the caller's blocks of one chunk, cut to the chunk's cells, and the launches after stage one, handed to
+// sc_sg_chunks (sc_segment.hip); a replicate output of R + 1 values per segment is a segment output of that item size.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -288,88 +290,69 @@ static int bs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if (S == 0) return SC_OK;
     const int Ds = D > 0 ? D : -1;                       // D = 0 is the call without a shift: its kernel, its park
     const int ht = h + (D > 0 ? D : 0);
-    const long long cap = sc_sg_cap_cells(A, h, Ds);
     const size_t R1 = (size_t)R + 1;
     int rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_tab, sizeof(double) * (size_t)(2 * ht + 1) * A))) return rc;
-    double* d_ages = (double*)ctx->sg_ages.p;
-    double* d_tab = (double*)ctx->sg_tab.p;
     if ((rc = sc_sg_stage_attr(ctx, A, h, Ds))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sc_pf_table(ctx, d_ages, A, ht, de, d_tab))) return rc;
 
-    sg_stage st;
+    // a chunk holds as many whole segments as fit the parked bytes and the replicates' outputs
+    // (Sc R1 <= BS_MAX_OUT is a bound on the segments: Sc <= BS_MAX_OUT / R1, rounded down)
+    sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, Ds >= 0),
+                 std::min<long long>(BS_MAX_SEGS, BS_MAX_OUT / (long long)R1), nullptr, 0, 0};
+    // (the kernels write the histogram, the indices and the amplitudes whether or not they are asked for)
+    c.out = {{out_rows, &ctx->bs_rows, sizeof(sc_segment_boot), SG_SEGS, true},
+             {out_hist, &ctx->bs_hist, sizeof(int) * A, SG_SEGS, false, true},
+             {out_index, &ctx->bs_index, R1, SG_SEGS, false, true},
+             {out_a, &ctx->bs_a, sizeof(double) * R1, SG_SEGS, false, true}};
     std::vector<int> blk, sblk;
     const int lds_fit = (int)(BS_LDS_MAX / (sizeof(double2) * (size_t)A));      // blocks of a segment that LDS holds
-    for (long long s0 = 0; s0 < S;) {
-        // a chunk of whole segments: as many as fit the parked bytes and the replicates' outputs
-        // (Sc R1 <= BS_MAX_OUT is a bound on the segments: Sc <= BS_MAX_OUT / R1, rounded down)
-        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, std::min<long long>(BS_MAX_SEGS, BS_MAX_OUT / (long long)R1),
-                                              sc_fit_chunk_bound(cap, ctx->fit_chunk));
-        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        const long long b0 = seg_blk_start[s0], NBc = seg_blk_start[s1] - b0;
+    int *d_blk, *d_sblk, lds_blocks;
+    double2* d_terms;
+    long long NBc;
+    size_t lds;
+    c.prepare = [&](const sg_chunk& k) {
+        const long long Sc = k.st.Sc, b0 = seg_blk_start[k.s0];
+        NBc = seg_blk_start[k.s1] - b0;
         blk.resize((size_t)NBc + 1);
         sblk.resize((size_t)Sc + 1);
-        int lds_blocks = 0;
-        for (long long b = 0; b <= NBc; ++b) blk[b] = (int)(blk_start[b0 + b] - k0);
-        for (long long s = 0; s <= Sc; ++s) sblk[s] = (int)(seg_blk_start[s0 + s] - b0);
+        lds_blocks = 0;
+        for (long long b = 0; b <= NBc; ++b) blk[b] = (int)(blk_start[b0 + b] - k.k0);
+        for (long long s = 0; s <= Sc; ++s) sblk[s] = (int)(seg_blk_start[k.s0 + s] - b0);
         for (long long s = 0; s < Sc; ++s) {
             const int nb = sblk[s + 1] - sblk[s];
             if (nb <= lds_fit) lds_blocks = std::max(lds_blocks, nb);
         }
-        const size_t lds = sizeof(double2) * (size_t)lds_blocks * A;
-        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, A, h, Ds, st))) return rc;
+        lds = sizeof(double2) * (size_t)lds_blocks * A;
         if ((rc = sc_ensure(ctx, ctx->bs_blk, sizeof(int) * ((size_t)NBc + 1)))) return rc;
         if ((rc = sc_ensure(ctx, ctx->bs_sblk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
         if ((rc = sc_ensure(ctx, ctx->bs_terms, sizeof(double2) * (size_t)NBc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->bs_index, (size_t)Sc * R1))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->bs_a, sizeof(double) * (size_t)Sc * R1))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->bs_hist, sizeof(int) * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->bs_rows, sizeof(sc_segment_boot) * (size_t)Sc))) return rc;
         if ((rc = sc_lds_attr(ctx, (const void*)k_bs_reps, lds))) return rc;
-        int* d_blk = (int*)ctx->bs_blk.p;
-        int* d_sblk = (int*)ctx->bs_sblk.p;
-        double2* d_terms = (double2*)ctx->bs_terms.p;
-        signed char* d_index = (signed char*)ctx->bs_index.p;
-        double* d_a = (double*)ctx->bs_a.p;
-        int* d_hist = (int*)ctx->bs_hist.p;
-        sc_segment_boot* d_rows = (sc_segment_boot*)ctx->bs_rows.p;
+        d_blk = (int*)ctx->bs_blk.p;
+        d_sblk = (int*)ctx->bs_sblk.p;
+        d_terms = (double2*)ctx->bs_terms.p;
         SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)NBc + 1), hipMemcpyHostToDevice, ctx->stream));
         SC_HIP(ctx, hipMemcpyAsync(d_sblk, sblk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_boot) * (size_t)Sc, ctx->stream));
-
-        const size_t mA = (size_t)m * A;
+        return SC_OK;
+    };
+    c.launch = [&](const sg_chunk& k) {
+        const sg_stage& st = k.st;
+        const size_t mA = (size_t)st.m * A;
         const int tiles = (R + 1 + BS_WAVES * BS_TILE - 1) / (BS_WAVES * BS_TILE);
-        int launches = 0;
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        if ((rc = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, d_tab, st, launches))) return rc;
+        signed char* d_index = (signed char*)k.out[2];
+        double* d_a = (double*)k.out[3];
+        int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, k.tab, st);
         if (NBc) {
             k_bs_terms<<<(unsigned)std::max<long long>(1, std::min<long long>(NBc, 65536)), 64, 0, ctx->stream>>>(
                 st.used, st.planes + 2 * mA, st.planes + 3 * mA, d_blk, NBc, A, d_terms);
             ++launches;
         }
-        k_bs_reps<<<bs_grid(Sc * tiles), BS_THREADS, lds, ctx->stream>>>(d_sblk, st.label, st.cnt, d_terms, Sc, A, R, seed,
-                                                                        min_blocks, min_profiles, lds_blocks, d_index, d_a);
-        k_bs_summary<<<bs_grid(Sc), BS_THREADS, 0, ctx->stream>>>(st.seg, d_sblk, st.label, st.cnt, d_ages, Sc, A, R, level,
-                                                                 min_blocks, min_profiles, d_index, d_a, d_hist, d_rows);
-        launches += 2;
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, launches);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_boot) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_hist)
-            SC_HIP(ctx, hipMemcpyAsync(out_hist + (size_t)s0 * A, d_hist, sizeof(int) * (size_t)Sc * A, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (out_index)
-            SC_HIP(ctx, hipMemcpyAsync(out_index + (size_t)s0 * R1, d_index, (size_t)Sc * R1, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_a)
-            SC_HIP(ctx, hipMemcpyAsync(out_a + (size_t)s0 * R1, d_a, sizeof(double) * (size_t)Sc * R1, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        s0 = s1;
-    }
-    return SC_OK;
+        k_bs_reps<<<bs_grid(st.Sc * tiles), BS_THREADS, lds, ctx->stream>>>(d_sblk, st.label, st.cnt, d_terms, st.Sc, A, R, seed,
+                                                                           min_blocks, min_profiles, lds_blocks, d_index, d_a);
+        k_bs_summary<<<bs_grid(st.Sc), BS_THREADS, 0, ctx->stream>>>(st.seg, d_sblk, st.label, st.cnt, k.ages, st.Sc, A, R, level,
+                                                                    min_blocks, min_profiles, d_index, d_a, (int*)k.out[1],
+                                                                    (sc_segment_boot*)k.out[0]);
+        return launches + 2;
+    };
+    return sc_sg_chunks(ctx, c);
 }
 
 // the two calls after their null checks: every refusal, then the bootstrap on the context's DEM (z null) or on z, uploaded

@@ -5,8 +5,12 @@
 // of the two, and by sc_lateral.hip for the sampler and the host frame.  Who owns what:
 //   host    sc_profile.hip defines the frame of every per-cell call: the DEM's source (sc_pf_dem), the erf table
 //           (sc_pf_table) and the chunked driver (sc_pf_chunks), to which a call hands its one launch line.
-//           sc_segment.hip defines stage one of the segment calls and the segmented sum (sc_sg_sum_launch)
-//   device  pf_stage and pf_each_cell are the frame of a kernel with one wave per cell; pf_column, pf_rest and pf_sse take
+//           sc_segment.hip defines the frame of every segment call: the argument checks with the one cap refusal
+//           (sc_sg_check, sc_sg_check_cap), the chunked driver (sc_sg_chunks), to which a call hands the shape of its
+//           park, its outputs and its launches, stage one and the segmented sum (sc_sg_sum_launch).  What the host
+//           computes of a chunk - where it ends, its CSR arrays, the cap - is sc_fit_chunk.h's
+//   device  pf_stage and pf_each_cell are the frame of a kernel with one wave per cell, pf_fetch brings a parked profile
+//           back (k_sg_resid, k_sq_step, k_sq_loss); pf_column, pf_rest and pf_sse take
 //           their column through an accessor (pf_at: a table's column, rp_col: the ramp's); pf_candidate, pair_winner
 //           and wave_sync are what sh_search and rp_search share
 // The library is built with -ffp-contract=off and every helper here is inlined, so a helper does the operations of its
@@ -25,7 +29,6 @@
 #ifndef PF_CHUNK
 #define PF_CHUNK (1ll << 19)             // cells per launch of a per-cell call: bounds its buffers (rows, 8 A B a curve)
 #endif
-#define SG_BLOCK 64                      // usable profiles per block of the segmented sum
 
 // ---- sc_profile.hip, shared with sc_segment.hip (`who` names the call in the messages) ----------------------------------
 // the argument checks of a profile call
@@ -65,17 +68,25 @@ int sc_rp_check(sc_ctx* ctx, const char* who, int h, int M, int mode, double slo
 // the launch of the table of F over x = -ht..ht (d_ages on the device; timed as SC_K_PROFILE)
 int sc_rp_table(sc_ctx* ctx, const double* d_ages, int A, int ht, double de, double* d_ftab);
 
-// ---- sc_segment.hip, shared with sc_bootstrap.hip and sc_strike.hip ----------------------------------------------------------------------------
-// the argument checks of a segment call (D < 0: the call without a shift) and the cells of one segment its park holds
+// ---- sc_segment.hip, shared with every segment call ---------------------------------------------------------------------------
+// The park of a cell: `prof` doubles of the profile (2h + 1; twice that with a weight plane behind the profiles), `planes`
+// per-cell-and-column planes (4; SC_SEGMENT_ROBUST_PLANES) of C columns (A ages; the A (M + 1) pairs of the initial slope),
+// and - shift - d_ci, one byte a column.  The cells of one segment that it holds: sc_fit_park_cap of SC_SEGMENT_MAX_PARK
+struct sg_park { int prof, planes, C; bool shift; };
+static inline sg_park sg_park_plain(int A, int h, bool shift) { return {2 * h + 1, 4, A, shift}; }
+long long sc_sg_cap_cells(const sg_park& park);
+// the argument checks of a segment call (D < 0: the call without a shift), the last of them sc_sg_check_cap on the plain
+// park ("... at this h and A")
 int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
                 const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
                 const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples, int min_profiles,
                 const void* out_rows);
-long long sc_sg_cap_cells(int A, int h, int D);
+// SC_ERR_UNSUPPORTED for the first segment of more than `cap` cells: "<who>: a segment of N cells, more than <cap> <tail>"
+int sc_sg_check_cap(sc_ctx* ctx, const char* who, const long long* seg_start, long long S, long long cap, const char* tail);
 // Stage one of a chunk of whole segments: the host arrays that go up (kept until the stream is synchronised) and, on the
-// device, the chunk's cells, (sa, ca), CSR array over cells and labels, what k_sg_partial / k_sg_shift park (profiles, n
-// and used, sbar / pbar / beta, the four per-age planes ebar, gamma, See, Sep - at d_ci with a shift - and d_ci) and what
-// k_sg_rank leaves (the usable cells of each segment in order; n_profiles and the pooled n per segment)
+// device, the chunk's cells, (sa, ca), CSR array over cells and labels, what the parking kernel leaves (profiles, n
+// and used, sbar / pbar / beta, the park's planes - k_sg_partial / k_sg_shift: ebar, gamma, See, Sep, at d_ci with a shift -
+// and d_ci) and what k_sg_rank leaves (the usable cells of each segment in order; n_profiles and the pooled n per segment)
 struct sg_stage {
     std::vector<double> dir;
     std::vector<int> start;
@@ -85,11 +96,43 @@ struct sg_stage {
     int *seg = nullptr, *label = nullptr, *cn = nullptr, *used = nullptr, *list = nullptr, *cnt = nullptr;
     signed char* shift = nullptr;
 };
+// the dynamic-LDS limit of k_sg_partial / k_sg_shift, and their launch and k_sg_rank's inside the chunk's timing bracket:
+// returns the number of launches (the parking kernel - none for a chunk without cells - and k_sg_rank)
 int sc_sg_stage_attr(sc_ctx* ctx, int A, int h, int D);
-int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, const long long* seg_start,
-                        const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st);
 int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
-                       const double* d_tab, const sg_stage& st, int& launches);
+                       const double* d_tab, const sg_stage& st);
+
+// The chunked driver of the segment calls (S >= 1 segments, in the sg_ buffers of the context).  Once: the ages and the erf
+// table over j = -ht..ht go up and `tables` (if any) adds the call's further tables.  Per chunk of whole segments s0..s1 -
+// sc_fit_chunk_end under max_segs, the park's cap lowered by option "fit_chunk", and the second CSR array `aux` under max_aux -
+// stage one is sized by the park and its host arrays go up; a call that sums in blocks (`sums` > 0) gets cseg and blk on the
+// device and the buffers of sc_sg_sum_launch (part; tot, two planes of C columns a segment; tsum, `sums` planes: what
+// the second sum of the call leaves); the outputs are sized and those marked are cleared; `prepare` (if any) sizes and uploads what is private to the call; `launch` issues the call's
+// launches inside the SC_K_PROFILE bracket and returns their number, or an error; the outputs that were asked for come
+// back to their place, and the stream is synchronised.
+// An output: `item` bytes for each of the chunk's segments, cells or items of `aux`.  Its device copy is null where the
+// host pointer is - unless the kernels need it whether or not it is asked for (always)
+enum sg_axis { SG_SEGS, SG_CELLS, SG_AUX };
+struct sg_out { void* host; DevBuf* buf; size_t item; sg_axis axis; bool clear = false, always = false; };
+struct sg_chunk {
+    const sg_stage& st;                  // st.Sc segments, st.m cells
+    long long s0, s1, k0, G;             // the first and the end segment, the first cell; the blocks (0 without `sums`)
+    const int *cseg, *blk;               // the segment of every cell and the CSR array of blocks over segments, or null
+    double *part, *tot, *tsum;           // the partial sums of the blocks and the two totals of the segments, or null
+    const std::vector<void*>& out;       // the device copies of the outputs, in the order of the call's list
+    const double *ages, *tab;
+};
+struct sg_call {
+    const long long* cells; const double *sa, *ca; const long long* seg_start; const int32_t* seg_label; long long S;
+    const double* ages; int A, ht; double de;
+    sg_park park;
+    long long max_segs; const long long* aux; long long max_aux;
+    int sums;
+    std::vector<sg_out> out;
+    std::function<int(const double* d_ages)> tables;
+    std::function<int(const sg_chunk&)> prepare, launch;
+};
+int sc_sg_chunks(sc_ctx* ctx, const sg_call& call);
 // k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
 
@@ -365,6 +408,16 @@ __device__ __forceinline__ double pf_candidate(const double* prof, int np, int h
 // One wave, lane i holding sse_i (lanes >= A are ignored): argmin with ties to the smaller index (a NaN never wins), thr =
 // sse_min (1 + delta / dof), and the interval walked from the best age while sse <= thr.  The same in every lane.
 struct pf_pick { int best, lo, hi; double sse_min; };
+
+// the parked profile of cell kc - and, WT, its weights - back into the wave's LDS, lanes over the points
+template <bool WT>
+__device__ __forceinline__ void pf_fetch(const double* __restrict__ prof_g, const double* __restrict__ u_g, long long kc, int np,
+                                         int lane, double* prof, double* u) {
+    for (int jj = lane; jj < np; jj += 64) {
+        prof[jj] = prof_g[(size_t)kc * np + jj];
+        if (WT) u[jj] = u_g[(size_t)kc * np + jj];
+    }
+}
 
 // the walk alone, from a best age found elsewhere (sc_strike.hip: the argmax of Q_i) with sse_best its sse
 __device__ __forceinline__ pf_pick pf_walk(double sse, int lane, int A, int best, double sse_best, double delta, int dof) {

@@ -23,6 +23,9 @@
 //   k_sg_choose   one wave per segment: pf_choose, the row; then lanes over the segment's cells for the cell table at
 //                 the best age (sc_segment_cell, or sc_segment_shift_cell with d_ci at that age)
 // No atomics at all.  The erf table is k_pf_table's: the same bits as sc_fit_profiles*.
+// The host side holds the frame of every segment call (sc_fit.h): the argument checks, stage one, the segmented sum and
+// sc_sg_chunks, the chunked driver.  A call - sg_run here; sr_run, sq_run, bs_run, st_run in their files - is the shape of
+// its park, its bounds, its list of outputs and the launches of one chunk.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -249,8 +252,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_sg_resid(const double* __restric
             const int m = cnt[2 * s];
             act = used[kc] != 0 && sg_fitted(m, sg_dof(m, cnt[2 * s + 1], D), min_profiles);
         }
-        if (act)
-            for (int jj = lane; jj < np; jj += 64) L.prof[jj] = prof_g[(size_t)kc * np + jj];
+        if (act) pf_fetch<false>(prof_g, nullptr, kc, np, lane, L.prof, nullptr);
         __syncthreads();
         if (act) {
             const size_t o = (size_t)kc * A + ia;
@@ -355,8 +357,16 @@ __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_st
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 // (D < 0 throughout the host side: the call without a shift, its kernels and its bytes)
-long long sc_sg_cap_cells(int A, int h, int D) {
-    return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) + 4ll * A) + (D >= 0 ? A : 0));
+long long sc_sg_cap_cells(const sg_park& park) {
+    return sc_fit_park_cap(SC_SEGMENT_MAX_PARK, park.prof, park.planes, park.C, park.shift);
+}
+
+int sc_sg_check_cap(sc_ctx* ctx, const char* who, const long long* seg_start, long long S, long long cap, const char* tail) {
+    for (long long s = 0; s < S; ++s)
+        if (seg_start[s + 1] - seg_start[s] > cap)
+            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld %s", who,
+                           seg_start[s + 1] - seg_start[s], cap, tail);
+    return SC_OK;
 }
 
 int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa, const double* ca,
@@ -371,50 +381,37 @@ int sc_sg_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const 
     if (min_profiles < 1) return sc_fail(ctx, SC_ERR_INVALID, "%s: min_profiles must be >= 1", who);
     if (seg_start[0] != 0 || seg_start[S] != K)
         return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start must run from 0 to K", who);
-    const long long cap = sc_sg_cap_cells(A, h, D);
     for (long long s = 0; s < S; ++s) {
         if (seg_start[s + 1] < seg_start[s])
             return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_start decreases at segment %lld", who, s);
         if (seg_label[s] <= 0 || (s > 0 && seg_label[s] <= seg_label[s - 1]))
             return sc_fail(ctx, SC_ERR_INVALID, "%s: labels must be positive and strictly increasing", who);
     }
-    for (long long s = 0; s < S; ++s)
-        if (seg_start[s + 1] - seg_start[s] > cap)
-            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h and A", who,
-                           seg_start[s + 1] - seg_start[s], cap);
-    return SC_OK;
+    return sc_sg_check_cap(ctx, who, seg_start, S, sc_sg_cap_cells(sg_park_plain(A, h, D >= 0)), "at this h and A");
 }
 
 
-// Stage one of a chunk of whole segments s0..s1 (shared with sc_bootstrap.hip): the chunk's cells, (sa, ca), CSR array and
-// labels go up, and the buffers of what k_sg_partial / k_sg_shift park and k_sg_rank lists are sized.  No launch
-int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, const long long* seg_start,
-                        const int32_t* seg_label, long long s0, long long s1, int A, int h, int D, sg_stage& st) {
-    const bool shift = D >= 0;
-    const int np = 2 * h + 1;
-    const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
+// Stage one of the chunk of whole segments s0..s1: the chunk's cells, (sa, ca), CSR array and labels go up, and the buffers
+// of what the parking kernel parks - in the shape of `park` - and k_sg_rank lists are sized.  No launch
+static int sg_stage_prepare(sc_ctx* ctx, const sg_call& c, long long s0, long long s1, sg_stage& st) {
+    const long long Sc = s1 - s0, k0 = c.seg_start[s0], m = c.seg_start[s1] - k0;
+    const size_t mC = (size_t)m * c.park.C;
     int rc;
     st.Sc = Sc;
     st.m = m;
-    st.start.resize((size_t)Sc + 1);
-    st.dir.resize(2 * (size_t)m);
-    for (long long s = 0; s <= Sc; ++s) st.start[s] = (int)(seg_start[s0 + s] - k0);
-    for (long long k = 0; k < m; ++k) {
-        st.dir[2 * k] = sa[k0 + k];
-        st.dir[2 * k + 1] = ca[k0 + k];
-    }
-    const size_t mA = (size_t)m * A;
+    sc_fit_chunk_start(c.seg_start, s0, s1, st.start);
+    sc_fit_chunk_dir(c.sa, c.ca, k0, m, st.dir);
     if ((rc = sc_ensure(ctx, ctx->sg_cells, sizeof(long long) * (size_t)m))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_dir, sizeof(double) * 2 * (size_t)m))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_start, sizeof(int) * ((size_t)Sc + 1)))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_label, sizeof(int) * (size_t)Sc))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * np))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * c.park.prof))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_int, sizeof(int) * 2 * (size_t)m))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_scal, sizeof(double) * 3 * (size_t)m))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * 4 * mA))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * c.park.planes * mC))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_list, sizeof(int) * (size_t)m))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sg_cnt, sizeof(int) * 2 * (size_t)Sc))) return rc;
-    if (shift && (rc = sc_ensure(ctx, ctx->sg_shift, mA))) return rc;
+    if (c.park.shift && (rc = sc_ensure(ctx, ctx->sg_shift, mC))) return rc;
     st.cells = (long long*)ctx->sg_cells.p;
     st.dirs = (double*)ctx->sg_dir.p;
     st.seg = (int*)ctx->sg_start.p;
@@ -426,20 +423,20 @@ int sc_sg_stage_prepare(sc_ctx* ctx, const long long* cells, const double* sa, c
     st.planes = (double*)ctx->sg_age.p;
     st.list = (int*)ctx->sg_list.p;
     st.cnt = (int*)ctx->sg_cnt.p;
-    st.shift = shift ? (signed char*)ctx->sg_shift.p : nullptr;
+    st.shift = c.park.shift ? (signed char*)ctx->sg_shift.p : nullptr;
     if (m) {
-        SC_HIP(ctx, hipMemcpyAsync(st.cells, cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        SC_HIP(ctx, hipMemcpyAsync(st.cells, c.cells + k0, sizeof(long long) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
         SC_HIP(ctx, hipMemcpyAsync(st.dirs, st.dir.data(), sizeof(double) * 2 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
     }
     SC_HIP(ctx, hipMemcpyAsync(st.seg, st.start.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-    SC_HIP(ctx, hipMemcpyAsync(st.label, seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(st.label, c.seg_label + s0, sizeof(int) * (size_t)Sc, hipMemcpyHostToDevice, ctx->stream));
     return SC_OK;
 }
 
-// ... and its two launches, inside the caller's timing bracket: the parking kernel (none for a chunk without cells) and
-// k_sg_rank.  d_tab: the erf table over h + D (h without a shift).  Adds the number of launches to `launches`
+// ... and its two launches, inside the chunk's timing bracket: the parking kernel (none for a chunk without cells) and
+// k_sg_rank.  d_tab: the erf table over h + D (h without a shift).  Returns the number of launches
 int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int h, int w, int D, double de, int min_samples,
-                       const double* d_tab, const sg_stage& st, int& launches) {
+                       const double* d_tab, const sg_stage& st) {
     const bool shift = D >= 0;
     const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
     const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
@@ -454,10 +451,8 @@ int sc_sg_stage_launch(sc_ctx* ctx, const double* z, int ny, int nx, int A, int 
     else if (m)
         k_partial<<<gcell, PF_THREADS, lds1, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, de, min_samples, d_tab, st.prof,
                                                            st.cn, st.used, st.scal, st.planes);
-    if (m) ++launches;
     sc_sg_rank_launch(ctx, st);
-    ++launches;
-    return SC_OK;
+    return m ? 2 : 1;
 }
 
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st) {
@@ -484,6 +479,81 @@ int sc_sg_stage_attr(sc_ctx* ctx, int A, int h, int D) {
     return sc_lds_attr(ctx, shift ? (const void*)k_shift : (const void*)k_partial, pf_lds_bytes(np, nt, A, shift, tab_lds));
 }
 
+int sc_sg_chunks(sc_ctx* ctx, const sg_call& c) {
+    const long long S = c.S;
+    const long long* seg_start = c.seg_start;
+    const size_t nout = c.out.size();
+    int rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * c.A))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->sg_tab, sizeof(double) * (size_t)(2 * c.ht + 1) * c.A))) return rc;
+    double* d_ages = (double*)ctx->sg_ages.p;
+    double* d_tab = (double*)ctx->sg_tab.p;
+    SC_HIP(ctx, hipMemcpyAsync(d_ages, c.ages, sizeof(double) * c.A, hipMemcpyHostToDevice, ctx->stream));
+    // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
+    if ((rc = sc_pf_table(ctx, d_ages, c.A, c.ht, c.de, d_tab))) return rc;
+    if (c.tables && (rc = c.tables(d_ages))) return rc;
+
+    const long long max_cells = sc_fit_chunk_bound(sc_sg_cap_cells(c.park), ctx->fit_chunk);
+    sg_stage st;
+    std::vector<int> cseg, blk;
+    std::vector<void*> d_out(nout);
+    for (long long s0 = 0; s0 < S;) {
+        // a chunk of whole segments: as many as fit the parked bytes (and the bound on the second CSR array)
+        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, c.max_segs, max_cells, c.aux, c.max_aux);
+        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
+        // where an output of the chunk begins along its axis, and its items
+        const auto first = [&](const sg_out& o) { return o.axis == SG_SEGS ? s0 : o.axis == SG_CELLS ? k0 : c.aux[s0]; };
+        const auto count = [&](const sg_out& o) { return o.axis == SG_SEGS ? Sc : o.axis == SG_CELLS ? m : c.aux[s1] - c.aux[s0]; };
+        if ((rc = sg_stage_prepare(ctx, c, s0, s1, st))) return rc;
+        long long G = 0;
+        int *d_cseg = nullptr, *d_blk = nullptr;
+        double *d_part = nullptr, *d_tot = nullptr, *d_tsum = nullptr;
+        if (c.sums) {
+            const size_t C = (size_t)c.park.C;
+            G = sc_fit_chunk_blocks(seg_start, s0, s1, cseg, blk);
+            if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
+            if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+            if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * C))) return rc;
+            if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * C))) return rc;
+            if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * c.sums * (size_t)Sc * C))) return rc;
+            d_cseg = (int*)ctx->sg_cseg.p;
+            d_blk = (int*)ctx->sg_blk.p;
+            d_part = (double*)ctx->sg_part.p;
+            d_tot = (double*)ctx->sg_tot.p;
+            d_tsum = (double*)ctx->sg_tsse.p;
+            if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+            SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+        }
+        for (size_t i = 0; i < nout; ++i) {
+            const sg_out& o = c.out[i];
+            d_out[i] = nullptr;
+            if (!o.host && !o.always) continue;
+            if ((rc = sc_ensure(ctx, *o.buf, o.item * (size_t)count(o)))) return rc;
+            d_out[i] = o.buf->p;
+            // (the padding of a row or of a cell of the shifted table is part of what the caller compares: cleared, the
+            // kernel writes the fields)
+            if (o.clear && count(o)) SC_HIP(ctx, hipMemsetAsync(d_out[i], 0, o.item * (size_t)count(o), ctx->stream));
+        }
+        const sg_chunk chunk = {st, s0, s1, k0, G, d_cseg, d_blk, d_part, d_tot, d_tsum, d_out, d_ages, d_tab};
+        if (c.prepare && (rc = c.prepare(chunk))) return rc;
+
+        sc_prof_begin(ctx, SC_K_PROFILE);
+        const int launches = c.launch(chunk);
+        if (launches < 0) return launches;
+        SC_HIP(ctx, hipGetLastError());
+        sc_prof_end(ctx, launches);
+        for (size_t i = 0; i < nout; ++i) {
+            const sg_out& o = c.out[i];
+            if (o.host && count(o))
+                SC_HIP(ctx, hipMemcpyAsync((char*)o.host + o.item * (size_t)first(o), d_out[i], o.item * (size_t)count(o),
+                                           hipMemcpyDeviceToHost, ctx->stream));
+        }
+        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
+        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s0 = s1;
+    }
+    return SC_OK;
+}
 
 static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
@@ -491,114 +561,46 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
                   void* out_cells, double* out_sse, int8_t* out_shift) {
     if (S == 0) return SC_OK;
     const bool shift = D >= 0;
-    const int np = 2 * h + 1, nt = 2 * (h + (shift ? D : 0)) + 1;
+    const int np = 2 * h + 1, ht = h + (shift ? D : 0), nt = 2 * ht + 1;
     const size_t cell_bytes = shift ? sizeof(sc_segment_shift_cell) : sizeof(sc_segment_cell);
-    const size_t tab_bytes = sizeof(double) * (size_t)nt * A;
-    const long long cap = sc_sg_cap_cells(A, h, D);
-    int rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_tab, tab_bytes))) return rc;
-    double* d_ages = (double*)ctx->sg_ages.p;
-    double* d_tab = (double*)ctx->sg_tab.p;
-
-    const bool tab_lds = tab_bytes <= PF_TAB_LDS;
+    const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
     const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds);
     const auto k_resid = tab_lds ? k_sg_resid<true> : k_sg_resid<false>;
     const int Dk = shift ? D : 0;                        // what k_sg_resid and k_sg_choose take: no shift is a range of 0
+    int rc;
     if ((rc = sc_sg_stage_attr(ctx, A, h, D))) return rc;
     if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
 
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    // (rows -h..h of the table over h + D are the bits of the table over h: s = (double)j * de either way)
-    if ((rc = sc_pf_table(ctx, d_ages, A, h + (shift ? D : 0), de, d_tab))) return rc;
-
-    sg_stage st;
-    std::vector<int> cseg, blk;
-    for (long long s0 = 0; s0 < S;) {
-        // a chunk of whole segments: as many as fit the parked bytes
-        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, SG_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk));
-        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        blk.resize((size_t)Sc + 1);
-        cseg.resize((size_t)m);
-        blk[0] = 0;
-        for (long long s = 0; s < Sc; ++s) {
-            const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
-            for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
-        }
-        const long long G = blk[Sc];
-        const size_t mA = (size_t)m * A;
-        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, A, h, D, st))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_fit) * (size_t)Sc))) return rc;
-        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, cell_bytes * (size_t)m))) return rc;
-        if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
-        long long* d_cells = st.cells;
-        int* d_cseg = (int*)ctx->sg_cseg.p;
-        int* d_start = st.seg;
-        int* d_blk = (int*)ctx->sg_blk.p;
-        int* d_label = st.label;
-        double* d_prof = st.prof;
-        int* d_cn = st.cn;
-        int* d_used = st.used;
-        double* d_scal = st.scal;
-        double* d_planes = st.planes;
-        double* d_part = (double*)ctx->sg_part.p;
-        double* d_tot = (double*)ctx->sg_tot.p;
-        double* d_tsse = (double*)ctx->sg_tsse.p;
-        int* d_cnt = st.cnt;
-        sc_segment_fit* d_rows = (sc_segment_fit*)ctx->sg_rows.p;
-        void* d_out = out_cells ? ctx->sg_out.p : nullptr;
-        signed char* d_shift = st.shift;
-        double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
-
-        if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_fit) * (size_t)Sc, ctx->stream));
-        // (so is the padding at the end of the shifted call's cell table)
-        if (shift && d_out && m) SC_HIP(ctx, hipMemsetAsync(d_out, 0, cell_bytes * (size_t)m, ctx->stream));
-
-        const unsigned gcell = pf_grid(m);
-        int launches = 0;
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        if ((rc = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, d_tab, st, launches))) return rc;
-        if (G) {
-            sc_sg_sum_launch(ctx, d_planes + 2 * mA, st, d_blk, G, A, 2, d_part, d_tot);
-            k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_cseg, d_used, d_cnt, d_scal, d_planes, d_shift, d_tot, m, A, h,
-                                                            Dk, de, min_profiles, d_tab);
-            sc_sg_sum_launch(ctx, d_planes + 2 * mA, st, d_blk, G, A, 1, d_part, d_tsse);
+    sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, shift), SG_MAX_SEGS, nullptr, 0, 1};
+    // (the shifted call's cells end in padding; d_ci comes back from where it is parked)
+    c.out = {{out_rows, &ctx->sg_rows, sizeof(sc_segment_fit), SG_SEGS, true},
+             {out_cells, &ctx->sg_out, cell_bytes, SG_CELLS, shift},
+             {out_sse, &ctx->sg_sse, sizeof(double) * A, SG_SEGS},
+             {out_shift, &ctx->sg_shift, (size_t)A, SG_CELLS}};
+    c.launch = [&](const sg_chunk& k) {
+        const sg_stage& st = k.st;
+        const size_t mA = (size_t)st.m * A;
+        int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, k.tab, st);
+        if (k.G) {
+            sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 2, k.part, k.tot);
+            k_resid<<<pf_grid(st.m), PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, st.shift,
+                                                                    k.tot, st.m, A, h, Dk, de, min_profiles, k.tab);
+            sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 1, k.part, k.tsum);
             launches += 5;
         }
         if (shift)
-            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, Dk, delta,
-                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift, d_rows,
-                                                            (sc_segment_shift_cell*)d_out, d_sse);
+            k_sg_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, st.m, k.tot, k.tsum, k.ages, A, Dk,
+                                                               delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes,
+                                                               st.shift, (sc_segment_fit*)k.out[0],
+                                                               (sc_segment_shift_cell*)k.out[1], (double*)k.out[2]);
         else
-            k_sg_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(d_start, d_label, d_cnt, Sc, m, d_tot, d_tsse, d_ages, A, Dk, delta,
-                                                            min_profiles, d_cells, d_cn, d_used, d_scal, d_planes, d_shift, d_rows,
-                                                            (sc_segment_cell*)d_out, d_sse);
-        ++launches;
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, launches);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_cells && m)
-            SC_HIP(ctx, hipMemcpyAsync((char*)out_cells + cell_bytes * (size_t)k0, d_out, cell_bytes * (size_t)m,
-                                       hipMemcpyDeviceToHost, ctx->stream));
-        if (out_shift && m)
-            SC_HIP(ctx, hipMemcpyAsync(out_shift + (size_t)k0 * A, d_shift, mA, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sse)
-            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)s0 * A, d_sse, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        s0 = s1;
-    }
-    return SC_OK;
+            k_sg_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, st.m, k.tot, k.tsum, k.ages, A, Dk,
+                                                               delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes,
+                                                               st.shift, (sc_segment_fit*)k.out[0], (sc_segment_cell*)k.out[1],
+                                                               (double*)k.out[2]);
+        return launches + 1;
+    };
+    return sc_sg_chunks(ctx, c);
 }
 
 // The four calls after their null checks and the early check of D: the argument checks under the name `who`, then the

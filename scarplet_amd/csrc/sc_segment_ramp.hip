@@ -18,6 +18,10 @@
 //                 row, and lanes over the segment's cells for the cell table at the best pair
 // The table of F sits in LDS when it fits PF_TAB_LDS bytes, as in k_pf_ramp; the erf table of the m = 0 pairs stays in
 // global memory.  No atomics at all, no float sum across lanes.
+// The host side is the park's shape (C columns for A), the second table, and the launches of one chunk handed to
+// sc_sg_chunks (sc_segment.hip); the chunks are bounded by the totals as well, a second CSR array.  k_sr_resid keeps its
+// own lines for the parked profile: with pf_fetch the call measured 0.9 ms of 389 slower in two sessions, at unchanged
+// registers (profiles/segment_frame_refactor.txt).
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -239,6 +243,8 @@ __global__ __launch_bounds__(64) void k_sr_choose(const int* __restrict__ seg_st
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 
+static sg_park sr_park(int A, int h, int M) { return sg_park_plain(A * (M + 1), h, false); }
+
 static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
                   int w, int M, int mode, double slope, double de, double delta, int min_samples, int min_profiles,
@@ -246,111 +252,59 @@ static int sr_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if (S == 0) return SC_OK;
     const int given = mode == SC_RAMP_SLOPE ? 1 : 0;
     const int np = 2 * h + 1, ht = h + M, nt = 2 * ht + 1, C = A * (M + 1);
-    const size_t etab_bytes = sizeof(double) * (size_t)np * A, ftab_bytes = sizeof(double) * (size_t)nt * A;
-    const long long cap = sc_sg_cap_cells(C, h, -1);
-    int rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_tab, etab_bytes))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ftab, ftab_bytes))) return rc;
-    double* d_ages = (double*)ctx->sg_ages.p;
-    double* d_etab = (double*)ctx->sg_tab.p;
-    double* d_ftab = (double*)ctx->sg_ftab.p;
-
+    const size_t ftab_bytes = sizeof(double) * (size_t)nt * A;
     const bool tab_lds = ftab_bytes <= PF_TAB_LDS;
     const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds);
     const auto k_partial = tab_lds ? k_sr_partial<true> : k_sr_partial<false>;
     const auto k_resid = tab_lds ? k_sr_resid<true> : k_sr_resid<false>;
+    int rc;
     if ((rc = sc_lds_attr(ctx, (const void*)k_partial, lds))) return rc;
     if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
 
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    // (the erf table of the m = 0 pairs is the plain call's, by its launch: the same bits)
-    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_etab))) return rc;
-    if ((rc = sc_rp_table(ctx, d_ages, A, ht, de, d_ftab))) return rc;
-
-    sg_stage st;
-    std::vector<int> cseg, blk;
     // (the totals of a chunk as a CSR array over the segments: a segment's blocks and one more, C columns each)
-    std::vector<long long> tot_start((size_t)S + 1, 0);
-    for (long long s = 0; s < S; ++s)
-        tot_start[s + 1] = tot_start[s] + (seg_start[s + 1] - seg_start[s] + SG_BLOCK - 1) / SG_BLOCK + 1;
-    for (long long s0 = 0; s0 < S;) {
-        // a chunk of whole segments: as many as fit the parked bytes, and the totals
-        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, SR_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk),
-                                              tot_start.data(), SR_MAX_TOTALS / C);
-        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        blk.resize((size_t)Sc + 1);
-        cseg.resize((size_t)m);
-        blk[0] = 0;
-        for (long long s = 0; s < Sc; ++s) {
-            const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
-            for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
-        }
-        const long long G = blk[Sc];
+    std::vector<long long> tot_start;
+    sc_fit_block_totals(seg_start, S, tot_start);
+    // (the erf table of the m = 0 pairs is the plain call's, by its launch: the same bits; the park is the plain call's
+    // with C columns for A: four planes of m C doubles)
+    sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, h, de, sr_park(A, h, M), SR_MAX_SEGS, tot_start.data(),
+                 SR_MAX_TOTALS / C, 2};
+    c.out = {{out_rows, &ctx->sg_rows, sizeof(sc_segment_ramp_fit), SG_SEGS, true},
+             {out_cells, &ctx->sg_out, sizeof(sc_segment_cell), SG_CELLS},
+             {out_sse, &ctx->sg_sse, sizeof(double) * A, SG_SEGS},
+             {out_width, &ctx->sg_width, (size_t)A, SG_SEGS}};
+    double* d_ftab;
+    c.tables = [&](const double* d_ages) {
+        if ((rc = sc_ensure(ctx, ctx->sg_ftab, ftab_bytes))) return rc;
+        d_ftab = (double*)ctx->sg_ftab.p;
+        return sc_rp_table(ctx, d_ages, A, ht, de, d_ftab);
+    };
+    c.launch = [&](const sg_chunk& k) {
+        const sg_stage& st = k.st;
+        const long long m = st.m;
         const size_t mC = (size_t)m * C;
-        // (the stage of sc_fit_segments with C columns for A: the same buffers, four planes of m C doubles)
-        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, C, h, -1, st))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * C))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * C))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * 2 * (size_t)Sc * C))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_ramp_fit) * (size_t)Sc))) return rc;
-        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, sizeof(sc_segment_cell) * (size_t)m))) return rc;
-        if (out_sse && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
-        if (out_width && (rc = sc_ensure(ctx, ctx->sg_width, (size_t)Sc * A))) return rc;
-        int* d_cseg = (int*)ctx->sg_cseg.p;
-        int* d_blk = (int*)ctx->sg_blk.p;
-        double* d_part = (double*)ctx->sg_part.p;
-        double* d_tot = (double*)ctx->sg_tot.p;
-        double* d_tsum = (double*)ctx->sg_tsse.p;
-        sc_segment_ramp_fit* d_rows = (sc_segment_ramp_fit*)ctx->sg_rows.p;
-        sc_segment_cell* d_out = out_cells ? (sc_segment_cell*)ctx->sg_out.p : nullptr;
-        double* d_sse = out_sse ? (double*)ctx->sg_sse.p : nullptr;
-        signed char* d_width = out_width ? (signed char*)ctx->sg_width.p : nullptr;
-
-        if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_ramp_fit) * (size_t)Sc, ctx->stream));
-
         const unsigned gcell = pf_grid(m);
         int launches = 0;
-        sc_prof_begin(ctx, SC_K_PROFILE);
         if (m) {
-            k_partial<<<gcell, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, M, de, min_samples, d_etab,
+            k_partial<<<gcell, PF_THREADS, lds, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, A, h, w, M, de, min_samples, k.tab,
                                                               d_ftab, st.prof, st.cn, st.used, st.scal, st.planes);
             ++launches;
         }
         sc_sg_rank_launch(ctx, st);
         ++launches;
-        if (G) {
-            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, d_blk, G, C, 2, d_part, d_tot);
-            k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_cseg, st.used, st.cnt, st.scal, st.planes, d_tot, m, A, h, M,
-                                                            given, de, min_profiles, d_etab, d_ftab);
-            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, d_blk, G, C, 2, d_part, d_tsum);
+        if (k.G) {
+            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, k.blk, k.G, C, 2, k.part, k.tot);
+            k_resid<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, k.tot, m, A, h, M,
+                                                            given, de, min_profiles, k.tab, d_ftab);
+            sc_sg_sum_launch(ctx, st.planes + 2 * mC, st, k.blk, k.G, C, 2, k.part, k.tsum);
             launches += 5;
         }
-        k_sr_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tsum, d_ages, A, M, given, slope, de,
-                                                        delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes, d_rows,
-                                                        d_out, d_sse, d_width);
-        ++launches;
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, launches);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_ramp_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_cells && m)
-            SC_HIP(ctx, hipMemcpyAsync(out_cells + k0, d_out, sizeof(sc_segment_cell) * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_sse)
-            SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)s0 * A, d_sse, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (out_width)
-            SC_HIP(ctx, hipMemcpyAsync(out_width + (size_t)s0 * A, d_width, (size_t)Sc * A, hipMemcpyDeviceToHost, ctx->stream));
-        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        s0 = s1;
-    }
-    return SC_OK;
+        k_sr_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, m, k.tot, k.tsum, k.ages, A, M, given,
+                                                           slope, de, delta, min_profiles, st.cells, st.cn, st.used, st.scal,
+                                                           st.planes, (sc_segment_ramp_fit*)k.out[0], (sc_segment_cell*)k.out[1],
+                                                           (double*)k.out[2], (signed char*)k.out[3]);
+        return launches + 1;
+    };
+    return sc_sg_chunks(ctx, c);
 }
 
 // The two calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
@@ -364,11 +318,7 @@ static int sr_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                          min_profiles, out_rows);
     if (rc) return rc;
     if ((rc = sc_rp_check(ctx, who, h, M, mode, slope, min_samples))) return rc;
-    const long long cap = sc_sg_cap_cells(A * (M + 1), h, -1);
-    for (long long s = 0; s < S; ++s)
-        if (seg_start[s + 1] - seg_start[s] > cap)
-            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h, A and M", who,
-                           seg_start[s + 1] - seg_start[s], cap);
+    if ((rc = sc_sg_check_cap(ctx, who, seg_start, S, sc_sg_cap_cells(sr_park(A, h, M)), "at this h, A and M"))) return rc;
     if (z && S == 0) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;

@@ -24,6 +24,8 @@
 //   k_sq_choose   one wave per segment: pf_choose on the loss curve, the row, integer sums of n_down and of the dormant
 //                 profiles over the segment's cells, the cell table
 // No float atomics and no float sum across lanes: the same bytes on every run and for every order of the segments.
+// The host side is the park's shape, the kernel choice, and the launches of one chunk handed to sc_sg_chunks
+// (sc_segment.hip), with the select's state and histograms as the call's private buffers.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -77,16 +79,6 @@ __device__ __forceinline__ void sq_line(double* __restrict__ planes, size_t stri
     } else {
         c0 = planes[SQ_C0 * stride + o];
         b = planes[SQ_B * stride + o];
-    }
-}
-
-// the parked profile (and weights) of cell kc back into the wave's LDS
-template <bool WT>
-__device__ __forceinline__ void sq_fetch(const double* __restrict__ prof_g, const double* __restrict__ u_g, long long kc, int np,
-                                         int lane, double* prof, double* u) {
-    for (int jj = lane; jj < np; jj += 64) {
-        prof[jj] = prof_g[(size_t)kc * np + jj];
-        if (WT) u[jj] = u_g[(size_t)kc * np + jj];
     }
 }
 
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_sq_step(const double* __restrict
             s = cseg[kc];
             act = used[kc] != 0 && S.st[s] == 0;
         }
-        if (act) sq_fetch<WT>(prof_g, u_g, kc, np, lane, prof, u);
+        if (act) pf_fetch<WT>(prof_g, u_g, kc, np, lane, prof, u);
         __syncthreads();
         if (act) {
             const size_t o = (size_t)kc * A + ia;
@@ -220,7 +212,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_sq_loss(const double* __restrict
             const int m = cnt[2 * s];
             act = used[kc] != 0 && (LOSS ? S.st[s] == 0 : sg_fitted(m, sg_dof(m, cnt[2 * s + 1], 0), min_profiles));
         }
-        if (act) sq_fetch<WT>(prof_g, u_g, kc, np, lane, prof, u);
+        if (act) pf_fetch<WT>(prof_g, u_g, kc, np, lane, prof, u);
         __syncthreads();
         if (act) {
             const size_t o = (size_t)kc * A + ia;
@@ -490,11 +482,9 @@ __global__ __launch_bounds__(64) void k_sq_choose(const int* __restrict__ seg_st
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-// the cells of one segment the park holds: 8 ((2h + 1)(1 + plane) + 9 A) bytes a cell
-static long long sq_cap_cells(int A, int h, bool plane) {
-    return SC_SEGMENT_MAX_PARK / (8ll * ((2ll * h + 1) * (plane ? 2 : 1) + (long long)SQ_PLANES * A));
-}
-
+// the park: the weights behind the profiles where there is a plane, nine planes for sc_fit_segments' four -
+// 8 ((2h + 1)(1 + plane) + 9 A) bytes a cell
+static sg_park sq_park(int A, int h, bool plane) { return {(2 * h + 1) * (plane ? 2 : 1), SQ_PLANES, A, false}; }
 
 typedef void (*sq_partial_kernel)(const double*, const double*, int, int, const long long*, const double*, long long, int, int, int,
                                   double, int, const double*, double*, double*, int*, int*, double*);
@@ -521,13 +511,7 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
     const bool robust = loss != SC_ROBUST_NONE, plane = wt != nullptr;
     const int np = 2 * h + 1, np2 = plane ? 2 * np : np;
     const size_t tab_bytes = sizeof(double) * (size_t)np * A;
-    const long long cap = sq_cap_cells(A, h, plane);
     int rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_tab, tab_bytes))) return rc;
-    double* d_ages = (double*)ctx->sg_ages.p;
-    double* d_tab = (double*)ctx->sg_tab.p;
-
     // (the profiles and their weights come first: the table goes to LDS only where the CU still holds it beside them)
     const bool tab_lds = tab_bytes <= PF_TAB_LDS && pf_lds_bytes(np2, np, A, false, true) <= SQ_LDS_BYTES;
     const size_t lds = pf_lds_bytes(np2, np, A, false, tab_lds);
@@ -543,87 +527,49 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
     if ((rc = sc_lds_attr(ctx, (const void*)k_loss0, lds))) return rc;
     if (robust && (rc = sc_lds_attr(ctx, (const void*)k_lossT, lds))) return rc;
     if (robust && (rc = sc_lds_attr(ctx, (const void*)k_step, lds))) return rc;
+    const auto k_choose = robust ? k_sq_choose<true> : k_sq_choose<false>;
 
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sc_pf_table(ctx, d_ages, A, h, de, d_tab))) return rc;
-
-    sg_stage st;
-    std::vector<int> cseg, blk;
-    for (long long s0 = 0; s0 < S;) {
-        // a chunk of whole segments: as many as fit the parked bytes
-        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, SQ_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk));
-        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        blk.resize((size_t)Sc + 1);
-        cseg.resize((size_t)m);
-        blk[0] = 0;
-        for (long long s = 0; s < Sc; ++s) {
-            const long long a0 = seg_start[s0 + s] - k0, a1 = seg_start[s0 + s + 1] - k0;
-            blk[s + 1] = blk[s] + (int)((a1 - a0 + SG_BLOCK - 1) / SG_BLOCK);
-            for (long long k = a0; k < a1; ++k) cseg[k] = (int)s;
-        }
-        const long long G = blk[Sc];
+    sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, h, de, sq_park(A, h, plane), SQ_MAX_SEGS, nullptr, 0, 2};
+    c.out = {{out_rows, &ctx->sg_rows, sizeof(sc_segment_robust_fit), SG_SEGS, true},
+             {out_cells, &ctx->sg_out, sizeof(sc_segment_robust_cell), SG_CELLS},
+             {out_loss, &ctx->sg_sse, sizeof(double) * A, SG_SEGS}};
+    double* d_a0 = nullptr;
+    int* d_hist = nullptr;
+    sq_state Q = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (robust) c.prepare = [&](const sg_chunk& k) {
+        const long long Sc = k.st.Sc;
+        if ((rc = sc_ensure(ctx, ctx->sq_state, (size_t)Sc * (2 * sizeof(double) + 3 * sizeof(int))))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sq_hist, sizeof(int) * 256 * (size_t)Sc))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->sq_a, sizeof(double) * (size_t)Sc * A))) return rc;
+        Q.sigma = (double*)ctx->sq_state.p;
+        Q.prefix = (unsigned long long*)(Q.sigma + Sc);
+        Q.st = (int*)(Q.prefix + Sc);
+        Q.ls = Q.st + Sc;
+        Q.rank = Q.ls + Sc;
+        d_hist = (int*)ctx->sq_hist.p;
+        d_a0 = (double*)ctx->sq_a.p;
+        return SC_OK;
+    };
+    c.launch = [&](const sg_chunk& k) {
+        const sg_stage& st = k.st;
+        const long long Sc = st.Sc, m = st.m, G = k.G;
         const size_t mA = (size_t)m * A;
-        // (the stage of sc_fit_segments in the same buffers: nine planes for its four, the weights behind the profiles -
-        // sized first, so that the stage's own smaller requests leave them alone)
-        if ((rc = sc_ensure(ctx, ctx->sg_prof, sizeof(double) * (size_t)m * np2))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_age, sizeof(double) * SQ_PLANES * mA))) return rc;
-        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, A, h, -1, st))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_cseg, sizeof(int) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_blk, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_part, sizeof(double) * 2 * (size_t)G * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tot, sizeof(double) * 2 * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_tsse, sizeof(double) * 2 * (size_t)Sc * A))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sg_rows, sizeof(sc_segment_robust_fit) * (size_t)Sc))) return rc;
-        if (out_cells && (rc = sc_ensure(ctx, ctx->sg_out, sizeof(sc_segment_robust_cell) * (size_t)m))) return rc;
-        if (out_loss && (rc = sc_ensure(ctx, ctx->sg_sse, sizeof(double) * (size_t)Sc * A))) return rc;
-        if (robust) {
-            if ((rc = sc_ensure(ctx, ctx->sq_state, (size_t)Sc * (2 * sizeof(double) + 3 * sizeof(int))))) return rc;
-            if ((rc = sc_ensure(ctx, ctx->sq_hist, sizeof(int) * 256 * (size_t)Sc))) return rc;
-            if ((rc = sc_ensure(ctx, ctx->sq_a, sizeof(double) * (size_t)Sc * A))) return rc;
-        }
-        double* d_prof = st.prof;
         double* d_u = plane ? st.prof + (size_t)m * np : nullptr;
-        int* d_cseg = (int*)ctx->sg_cseg.p;
-        int* d_blk = (int*)ctx->sg_blk.p;
-        double* d_part = (double*)ctx->sg_part.p;
-        double* d_tot = (double*)ctx->sg_tot.p;
-        double* d_tl = (double*)ctx->sg_tsse.p;
-        sc_segment_robust_fit* d_rows = (sc_segment_robust_fit*)ctx->sg_rows.p;
-        sc_segment_robust_cell* d_out = out_cells ? (sc_segment_robust_cell*)ctx->sg_out.p : nullptr;
-        double* d_curve = out_loss ? (double*)ctx->sg_sse.p : nullptr;
-        sq_state Q = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        int* d_hist = nullptr;
-        double* d_a0 = nullptr;
-        if (robust) {
-            Q.sigma = (double*)ctx->sq_state.p;
-            Q.prefix = (unsigned long long*)(Q.sigma + Sc);
-            Q.st = (int*)(Q.prefix + Sc);
-            Q.ls = Q.st + Sc;
-            Q.rank = Q.ls + Sc;
-            d_hist = (int*)ctx->sq_hist.p;
-            d_a0 = (double*)ctx->sq_a.p;
-        }
-
-        if (m) SC_HIP(ctx, hipMemcpyAsync(d_cseg, cseg.data(), sizeof(int) * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_blk, blk.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        // (the rows' padding is part of what the caller compares: cleared, the kernel writes the fields)
-        SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_segment_robust_fit) * (size_t)Sc, ctx->stream));
-
+        double *d_part = k.part, *d_tot = k.tot, *d_tl = k.tsum;        // (tl: the loss and sum u r^2 of the last sweep)
         const unsigned gcell = pf_grid(m);
         int launches = 0;
-        sc_prof_begin(ctx, SC_K_PROFILE);
         if (m) {
-            k_partial<<<gcell, PF_THREADS, lds, ctx->stream>>>(z, wt, ny, nx, st.cells, st.dirs, m, A, h, w, de, min_samples, d_tab, d_prof,
+            k_partial<<<gcell, PF_THREADS, lds, ctx->stream>>>(z, wt, ny, nx, st.cells, st.dirs, m, A, h, w, de, min_samples, k.tab, st.prof,
                                                               d_u, st.cn, st.used, st.planes);
             ++launches;
         }
         sc_sg_rank_launch(ctx, st);
         ++launches;
         if (G) {
-            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tot);
-            k_loss0<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
-                                                            min_profiles, 0.0, d_tab);
-            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tl);
+            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, k.blk, G, A, 2, d_part, d_tot);
+            k_loss0<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_u, k.cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
+                                                            min_profiles, 0.0, k.tab);
+            sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, k.blk, G, A, 2, d_part, d_tl);
             launches += 5;
         }
         if (robust) {
@@ -631,7 +577,7 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
             ++launches;
             if (G && !(scale > 0.0)) {
                 for (int r = 0; r < 8; ++r) {
-                    k_sq_hist<<<gcell, PF_THREADS, 0, ctx->stream>>>(d_prof, d_cseg, st.used, Q, d_a0, st.planes, m, A, h, de, r, d_tab,
+                    k_sq_hist<<<gcell, PF_THREADS, 0, ctx->stream>>>(st.prof, k.cseg, st.used, Q, d_a0, st.planes, m, A, h, de, r, k.tab,
                                                                     d_hist);
                     k_sq_pick<<<sg_grid(Sc), 64, 0, ctx->stream>>>(Sc, Q, r, d_hist);
                 }
@@ -639,38 +585,22 @@ static int sq_run(sc_ctx* ctx, const double* z, const double* wt, int ny, int nx
             }
             if (G) {
                 for (int t = 0; t < iterations; ++t) {
-                    k_step<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, Q, d_tot, st.planes, m, A, h, de,
-                                                                   min_samples, tuning, t > 0 ? 1 : 0, d_tab);
-                    sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tot);
+                    k_step<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_u, k.cseg, st.used, Q, d_tot, st.planes, m, A, h, de,
+                                                                   min_samples, tuning, t > 0 ? 1 : 0, k.tab);
+                    sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, k.blk, G, A, 2, d_part, d_tot);
                 }
-                k_lossT<<<gcell, PF_THREADS, lds, ctx->stream>>>(d_prof, d_u, d_cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
-                                                                min_profiles, tuning, d_tab);
-                sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, d_blk, G, A, 2, d_part, d_tl);
+                k_lossT<<<gcell, PF_THREADS, lds, ctx->stream>>>(st.prof, d_u, k.cseg, st.used, st.cnt, Q, d_tot, st.planes, m, A, h, de,
+                                                                min_profiles, tuning, k.tab);
+                sc_sg_sum_launch(ctx, st.planes + SQ_SEE * mA, st, k.blk, G, A, 2, d_part, d_tl);
                 launches += 3 * iterations + 3;
             }
-            k_sq_choose<true><<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
-                                                                  min_profiles, st.cells, st.cn, st.used, st.planes, d_rows, d_out,
-                                                                  d_curve);
-        } else {
-            k_sq_choose<false><<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, d_ages, A, delta,
-                                                                   min_profiles, st.cells, st.cn, st.used, st.planes, d_rows, d_out,
-                                                                   d_curve);
         }
-        ++launches;
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, launches);
-        SC_HIP(ctx, hipMemcpyAsync(out_rows + s0, d_rows, sizeof(sc_segment_robust_fit) * (size_t)Sc, hipMemcpyDeviceToHost, ctx->stream));
-        if (out_cells && m)
-            SC_HIP(ctx, hipMemcpyAsync(out_cells + k0, d_out, sizeof(sc_segment_robust_cell) * (size_t)m, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        if (out_loss)
-            SC_HIP(ctx, hipMemcpyAsync(out_loss + (size_t)s0 * A, d_curve, sizeof(double) * (size_t)Sc * A, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        s0 = s1;
-    }
-    return SC_OK;
+        k_choose<<<sg_grid(Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, Sc, m, d_tot, d_tl, d_a0, Q, k.ages, A, delta, min_profiles,
+                                                     st.cells, st.cn, st.used, st.planes, (sc_segment_robust_fit*)k.out[0],
+                                                     (sc_segment_robust_cell*)k.out[1], (double*)k.out[2]);
+        return launches + 1;
+    };
+    return sc_sg_chunks(ctx, c);
 }
 
 // The two calls after their null checks: the argument checks, then the fit on z - ny x nx on the host, uploaded - or on
@@ -685,11 +615,8 @@ static int sq_call(sc_ctx* ctx, const double* z, int ny, int nx, const long long
                          min_profiles, out_rows);
     if (rc) return rc;
     if ((rc = sc_rb_check(ctx, who, loss, tuning, iterations, scale))) return rc;
-    const long long cap = sq_cap_cells(A, h, weights != nullptr);
-    for (long long s = 0; s < S; ++s)
-        if (seg_start[s + 1] - seg_start[s] > cap)
-            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: a segment of %lld cells, more than %lld at this h and A", who,
-                           seg_start[s + 1] - seg_start[s], cap);
+    if ((rc = sc_sg_check_cap(ctx, who, seg_start, S, sc_sg_cap_cells(sq_park(A, h, weights != nullptr)), "at this h and A")))
+        return rc;
     if (z && S == 0) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;

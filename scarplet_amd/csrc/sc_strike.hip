@@ -15,6 +15,8 @@
 //              Q_i = SSep_i^2 / SSee_i, a butterfly argmax with the smallest index winning a tie (a NaN never wins),
 //              a = SSep / SSee there; sse_i = max(SSpp - Q_i, 0); pf_walk from that age; the row and the optional curve
 // No float atomics, no float sum across lanes: the same bytes on every run.
+// The host side is the windows of one chunk, cut to the chunk's cells and segments, and the launches after stage one,
+// handed to sc_sg_chunks (sc_segment.hip): the rows and the curves run over the windows, the call's second CSR array.
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
@@ -198,78 +200,57 @@ static int st_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if (S == 0) return SC_OK;
     const int Ds = D > 0 ? D : -1;                       // D = 0 is the call without a shift: its kernel, its park
     const int ht = h + (D > 0 ? D : 0);
-    const long long cap = sc_sg_cap_cells(A, h, Ds);
     int rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_ages, sizeof(double) * A))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->sg_tab, sizeof(double) * (size_t)(2 * ht + 1) * A))) return rc;
-    double* d_ages = (double*)ctx->sg_ages.p;
-    double* d_tab = (double*)ctx->sg_tab.p;
     if ((rc = sc_sg_stage_attr(ctx, A, h, Ds))) return rc;
-    SC_HIP(ctx, hipMemcpyAsync(d_ages, ages, sizeof(double) * A, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = sc_pf_table(ctx, d_ages, A, ht, de, d_tab))) return rc;
 
-    sg_stage st;
+    // (a chunk holds as many whole segments as fit the parked bytes and the windows' outputs)
+    sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, Ds >= 0), ST_MAX_SEGS, seg_win_start,
+                 ST_MAX_WIN, 0};
+    c.out = {{out_rows, &ctx->st_rows, sizeof(sc_strike_fit), SG_AUX, true}, {out_sse, &ctx->st_sse, sizeof(double) * A, SG_AUX}};
     std::vector<int> win, wstart;
-    for (long long s0 = 0; s0 < S;) {
-        // a chunk of whole segments: as many as fit the parked bytes and the windows' outputs
-        const long long s1 = sc_fit_chunk_end(seg_start, s0, S, ST_MAX_SEGS, sc_fit_chunk_bound(cap, ctx->fit_chunk),
-                                              seg_win_start, ST_MAX_WIN);
-        const long long Sc = s1 - s0, k0 = seg_start[s0], m = seg_start[s1] - k0;
-        const long long g0 = seg_win_start[s0], NWc = seg_win_start[s1] - g0;
+    int *d_win, *d_wstart;
+    double* d_spp;
+    long long NWc;
+    c.prepare = [&](const sg_chunk& k) {
+        const long long Sc = k.st.Sc, g0 = seg_win_start[k.s0];
+        NWc = seg_win_start[k.s1] - g0;
         win.resize(3 * (size_t)NWc);
         wstart.resize((size_t)Sc + 1);
-        for (long long s = 0; s <= Sc; ++s) wstart[s] = (int)(seg_win_start[s0 + s] - g0);
+        for (long long s = 0; s <= Sc; ++s) wstart[s] = (int)(seg_win_start[k.s0 + s] - g0);
         for (long long s = 0; s < Sc; ++s)
             for (long long g = wstart[s]; g < wstart[s + 1]; ++g) {
-                win[3 * g] = (int)(win_lo[g0 + g] - k0);
-                win[3 * g + 1] = (int)(win_hi[g0 + g] - k0);
+                win[3 * g] = (int)(win_lo[g0 + g] - k.k0);
+                win[3 * g + 1] = (int)(win_hi[g0 + g] - k.k0);
                 win[3 * g + 2] = (int)s;
             }
-        if ((rc = sc_sg_stage_prepare(ctx, cells, sa, ca, seg_start, seg_label, s0, s1, A, h, Ds, st))) return rc;
         if ((rc = sc_ensure(ctx, ctx->st_win, sizeof(int) * 3 * (size_t)NWc))) return rc;
         if ((rc = sc_ensure(ctx, ctx->st_wstart, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->st_spp, sizeof(double) * (size_t)m))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->st_rows, sizeof(sc_strike_fit) * (size_t)NWc))) return rc;
-        if (out_sse && (rc = sc_ensure(ctx, ctx->st_sse, sizeof(double) * (size_t)NWc * A))) return rc;
-        int* d_win = (int*)ctx->st_win.p;
-        int* d_wstart = (int*)ctx->st_wstart.p;
-        double* d_spp = (double*)ctx->st_spp.p;
-        sc_strike_fit* d_rows = (sc_strike_fit*)ctx->st_rows.p;
-        double* d_sse = out_sse ? (double*)ctx->st_sse.p : nullptr;
-        if (NWc) {
-            SC_HIP(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(int) * 3 * (size_t)NWc, hipMemcpyHostToDevice, ctx->stream));
-            SC_HIP(ctx, hipMemsetAsync(d_rows, 0, sizeof(sc_strike_fit) * (size_t)NWc, ctx->stream));
-        }
+        if ((rc = sc_ensure(ctx, ctx->st_spp, sizeof(double) * (size_t)k.st.m))) return rc;
+        d_win = (int*)ctx->st_win.p;
+        d_wstart = (int*)ctx->st_wstart.p;
+        d_spp = (double*)ctx->st_spp.p;
+        if (NWc) SC_HIP(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(int) * 3 * (size_t)NWc, hipMemcpyHostToDevice, ctx->stream));
         SC_HIP(ctx, hipMemcpyAsync(d_wstart, wstart.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-
-        const size_t mA = (size_t)m * A;
-        int launches = 0;
-        sc_prof_begin(ctx, SC_K_PROFILE);
-        if ((rc = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, d_tab, st, launches))) return rc;
-        if (m && NWc) {
-            k_st_spp<<<st_grid(m), ST_THREADS, 0, ctx->stream>>>(st.prof, st.used, st.scal, m, h, de, d_spp);
+        return SC_OK;
+    };
+    c.launch = [&](const sg_chunk& k) {
+        const sg_stage& st = k.st;
+        const size_t mA = (size_t)st.m * A;
+        int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, k.tab, st);
+        if (st.m && NWc) {
+            k_st_spp<<<st_grid(st.m), ST_THREADS, 0, ctx->stream>>>(st.prof, st.used, st.scal, st.m, h, de, d_spp);
             ++launches;
         }
         if (NWc) {
             k_st_fit<<<st_grid(NWc), ST_THREADS, 0, ctx->stream>>>(d_win, d_wstart, st.label, NWc, st.cn, st.used,
                                                                   st.planes + 2 * mA, st.planes + 3 * mA, d_spp, st.shift,
-                                                                  d_ages, A, D, delta, min_profiles, d_rows, d_sse);
+                                                                  k.ages, A, D, delta, min_profiles, (sc_strike_fit*)k.out[0],
+                                                                  (double*)k.out[1]);
             ++launches;
         }
-        SC_HIP(ctx, hipGetLastError());
-        sc_prof_end(ctx, launches);
-        if (NWc) {
-            SC_HIP(ctx, hipMemcpyAsync(out_rows + g0, d_rows, sizeof(sc_strike_fit) * (size_t)NWc, hipMemcpyDeviceToHost,
-                                       ctx->stream));
-            if (out_sse)
-                SC_HIP(ctx, hipMemcpyAsync(out_sse + (size_t)g0 * A, d_sse, sizeof(double) * (size_t)NWc * A,
-                                           hipMemcpyDeviceToHost, ctx->stream));
-        }
-        // (the host arrays are reused by the next chunk, and the caller owns the outputs on return)
-        SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        s0 = s1;
-    }
-    return SC_OK;
+        return launches;
+    };
+    return sc_sg_chunks(ctx, c);
 }
 
 // the two calls after their null checks: every refusal, then the fit on the context's DEM (z null) or on z, uploaded

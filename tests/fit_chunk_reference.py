@@ -25,3 +25,29 @@ def per_cell_chunks(K, chunk, n):
     """Launches of a per-cell call over K cells."""
     c = min(K, bound(chunk, n))
     return 0 if K == 0 else -(-K // c)
+
+
+BLOCK = 64            # SG_BLOCK: usable profiles per block of the segmented sum
+
+
+def chunk_arrays(seg_start, s0, s1):
+    """What the host sends up of the chunk of segments s0..s1, its cells counted from its first: (start, blk, cseg, G) - the
+    CSR array of the cells over the chunk's segments, that of the blocks of 64 cells, the segment of every cell, and the
+    number of blocks."""
+    import numpy as np
+    start = np.asarray(seg_start[s0:s1 + 1], dtype=np.int64) - seg_start[s0]
+    size = np.diff(start)
+    blk = np.concatenate([[0], np.cumsum(-(-size // BLOCK))])
+    return start, blk, np.repeat(np.arange(s1 - s0), size), int(blk[-1])
+
+
+def block_totals(seg_start):
+    """The CSR array of the block totals of the call with max_width over all segments: a segment's blocks and one more."""
+    import numpy as np
+    return np.concatenate([[0], np.cumsum(-(-np.diff(np.asarray(seg_start, dtype=np.int64)) // BLOCK) + 1)])
+
+
+def park_cap(max_park, prof, planes, columns, shift):
+    """The cells of one segment that a park of max_park bytes holds: 8 (prof + planes columns) bytes a cell, and one byte a
+    column for the shifts."""
+    return max_park // (8 * (prof + planes * columns) + (columns if shift else 0))

@@ -20,6 +20,9 @@ second trip through its loop.  Here:
   last workgroup - against the family's restatement.  The segments of 2100 cells are left to (a): their restatement is a
   least-squares problem with 4201 columns per age, and alone in a sub-call such a segment is the shape
   tests/test_gpu_segments.py already holds against it.
+* ONE CONTEXT.  The six segment calls share the sg_ buffers of a context and one driver (sc_sg_chunks) that sizes them
+  from each call's description of its park: on one context, in both orders and at two sizes of the park, each call returns
+  the bytes it returns on a fresh context.
 
 Out of scope: the cap of k_st_spp / k_st_fit (65536 workgroups, 262 144 windows) and the 65536-block cap of k_bs_terms.
 """
@@ -413,6 +416,54 @@ def test_segment_calls_in_many_chunks(ctx, name, holes):
     again, n1 = both_routes(ctx, call, c["z"], de)
     same_bytes(again, base)
     assert n1 == n0
+
+
+# ---- the six segment calls share the sg_ buffers of one context ----------------------------------------------------------------
+def shared_case(h, A):
+    """96 x 80, a step along column 40 under a rough surface; segments of 1, 2, 64, 65 and 130 cells (below, at and above
+    one block of the segmented sum, two blocks and a rest), shuffled.  Every family's keys, at de = 1."""
+    rng = np.random.default_rng(20261022)
+    z = np.cumsum(rng.standard_normal((96, 80)), 1) * 0.05 + rng.standard_normal((96, 80)) * 0.03
+    z[:, 40:] += 2.0
+    rows, cols = np.meshgrid(np.arange(16, 80), np.arange(30, 50), indexing="ij")
+    cells = rng.choice((rows * 80 + cols).ravel(), 262, replace=False).astype(np.int64)
+    wt = rng.uniform(0.5, 2.0, z.shape)
+    wt[rng.random(z.shape) < 0.02] = 0.0                                 # (a weight of 0 leaves the sample out)
+    return dict(z=z, de=1.0, cells=cells, labels=rng.permutation(np.repeat([1, 2, 3, 4, 5], [1, 2, 64, 65, 130])),
+                angle=0.1 + 0.05 * rng.standard_normal(262), h=h, w=1, ages=10 ** np.linspace(0.0, 1.5, A), delta=1.0,
+                min_samples=3, min_profiles=1, D=2, M=2, slope=0.6, weights=wt, robust=dict(robust="huber", iterations=3),
+                block_length=4.0, R=20, seed=7, min_blocks=2, window=12.0, step=6.0)
+
+
+SHARED_CALLS = [("plain", segs_plain), ("shift", segs_shift), ("ramp", lambda c: segs_ramp(c, _lib.RAMP_FREE)),
+                ("robust", segs_robust), ("bootstrap", lambda c: segs_bootstrap(c, c["h"], c["w"])), ("strike", segs_strike)]
+
+
+def test_segment_calls_share_one_context(ctx):
+    """The plain, shifted, ramp, robust (with a weight plane), bootstrap and strike calls on ONE context, in that order and
+    in the reverse order, each at (h, A) = (5, 5) and (15, 64) in turn, so that every call meets buffers that a smaller and
+    a larger park sized - 4 planes of A columns, of A (M + 1), 9 planes and the weights, d_ci or not: each call's bytes
+    are those of the same call on a fresh context.  With empty segments first, in the middle and last."""
+    cases = {p: shared_case(*p) for p in ((5, 5), (15, 64))}
+    calls, fresh = {}, {}
+    for p, c in cases.items():
+        for name, build in SHARED_CALLS:
+            g, bind = build(c)
+            S = len(g.seg_start) - 1
+            assert sorted(np.diff(g.seg_start)) == [1, 2, 64, 65, 130]
+            calls[name, p] = bind(g.with_empty_segments([0, S // 2, S]))
+            own = _lib.Context(0)
+            try:
+                fresh[name, p] = calls[name, p](own, c["z"])
+            finally:
+                own.close()
+            assert all(v is not None for v in fresh[name, p])
+    small, large = list(cases)
+    # (the parameters alternate along the calls, and then the other way round)
+    order = [(name, (small, large)[(i + flip) % 2]) for flip in (0, 1) for i, (name, _) in enumerate(SHARED_CALLS)]
+    for seq in (order, order[::-1]):
+        for name, p in seq:
+            same_bytes(calls[name, p](ctx, cases[p]["z"]), fresh[name, p])
 
 
 # ---- sc_snr_surface: chunks of whole batches of cells, on the context's DEM --------------------------------------------------

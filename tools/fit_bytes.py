@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
-"""Developer check: the bytes of sl.fit_profiles and sl.fit_segments, with and without max_shift, as SHA-256 lines.
+"""Developer check: the bytes of sl.fit_profiles and of every segment call - sl.fit_segments with and without max_shift, with
+max_width in both modes, with weights and a robust loss, sl.bootstrap_segments and sl.fit_along_strike - as SHA-256 lines.
 
 Every case of the GPU tests (profile_reference.gpu_cases(), the profile and segment lists of shift_reference,
 segment_reference.gpu_cases()) goes through every call it has the inputs for, with every optional output requested:
 the unshifted call, the shifted call at the case's D (--shift cells where the case names none, cut to h - min_samples)
-and the shifted call at D = 0.  One line per (case, call, output).  Two libraries that compute the same thing print the
-same lines: run it once per library (SCARPLET_HIP_LIB selects one) and diff.  The hashes depend on the device's erf and
-are not fixtures."""
+and the shifted call at D = 0.  The other segment calls take the case lists of their own reference modules
+(segment_ramp_reference, segment_robust_reference for Huber and Tukey, bootstrap_reference, strike_reference).  One line
+per (case, call, output), the output hashed raw, and a last line with the totals and the launches counted.  --fit-chunk N sets option "fit_chunk"
+on the context the calls share, so that most cases run in several chunks (64 does that for these lists).  Two libraries
+that compute the same thing print the same lines: run it once per library (SCARPLET_HIP_LIB selects one) and diff.  The
+hashes depend on the device's erf and are not fixtures."""
 import argparse
 import hashlib
 import os
@@ -20,20 +24,34 @@ import numpy as np  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--shift", type=int, default=2)
 ap.add_argument("--small", action="store_true", help="without h1024 and the million cells of profile_reference")
+ap.add_argument("--fit-chunk", type=int, default=0, help='option "fit_chunk": the cells at which a driver closes a chunk')
+ap.add_argument("--segments-only", action="store_true", help="the segment calls alone: no fit_profiles")
 a = ap.parse_args()
 
 
 def main():
+    import bootstrap_reference as br
     import profile_reference as pr
+    import segment_ramp_reference as sx
     import segment_reference as sr
+    import segment_robust_reference as qr
     import shift_reference as sh
+    import strike_reference as stk
     import scarplet_amd as sl
-    from scarplet_amd import _lib
-    print("# build id %s" % _lib.load().sc_build_id().decode(), flush=True)
+    from scarplet_amd import _lib, core
+    # (to stderr: the build id is what differs between two libraries that print the same lines)
+    print("# build id %s, fit_chunk %d" % (_lib.load().sc_build_id().decode(), a.fit_chunk), file=sys.stderr, flush=True)
+    ctx = core._context(0)
+    ctx.set_option("fit_chunk", a.fit_chunk)
+    ctx.profile(0)                                       # (the launch counters from zero)
+    total = dict(calls=0, buffers=0, bytes=0)
 
     def emit(listname, case, call, names, arrays):
+        total["calls"] += 1
         for name, arr in zip(names, arrays if isinstance(arrays, tuple) else (arrays,)):
             arr = np.ascontiguousarray(arr)
+            total["buffers"] += 1
+            total["bytes"] += arr.nbytes
             print("%s | %s | %s | %s %s %s" % (listname, case["name"], call, name, arr.shape,
                                                hashlib.sha256(arr.tobytes()).hexdigest()), flush=True)
 
@@ -49,13 +67,42 @@ def main():
             for tag, d in ranges:
                 shifted = d is not None
                 skw = dict(max_shift=d * de, return_shift=True) if shifted else {}
-                out = sl.fit_profiles(g, case["cells"], case["angle"], h * de, w * de, return_curve=True, **kw, **skw)
-                emit(listname, case, "fit_profiles" + tag, ("table", "curve", "shift"), out)
+                if not a.segments_only:
+                    out = sl.fit_profiles(g, case["cells"], case["angle"], h * de, w * de, return_curve=True, **kw, **skw)
+                    emit(listname, case, "fit_profiles" + tag, ("table", "curve", "shift"), out)
                 if "labels" in case:
                     out = sl.fit_segments(g, case["cells"], case["labels"], case["angle"], h * de, w * de,
                                           min_profiles=case.get("min_profiles", 1), return_cells=True, return_curve=True,
                                           **kw, **skw)
                     emit(listname, case, "fit_segments" + tag, ("table", "cells", "curve", "shift"), out)
+
+    def segments(c, **kw):
+        return sl.fit_segments(sl.DEMGrid.from_array(c["z"], float(c["de"])), c["cells"], c["labels"], c["angle"], c["h"] * c["de"],
+                               c["w"] * c["de"], ages=c["ages"], delta=c["delta"], min_samples=c["min_samples"],
+                               min_profiles=c.get("min_profiles", 1), return_cells=True, return_curve=True, **kw)
+
+    for c in sx.gpu_cases():
+        for tag, slope in (("free", None), ("slope", c["slope"])):
+            out = segments(c, max_width=c["M"] * c["de"], initial_slope=slope, return_width=True)
+            emit("segment_ramp_reference", c, "fit_segments max_width " + tag, ("table", "cells", "curve", "width"), out)
+    for loss in ("huber", "tukey"):
+        for name, c in qr.gpu_cases(loss).items():
+            out = segments(c, weights=c["weights"], **c["robust"])
+            emit("segment_robust_reference " + loss, dict(name=name), "fit_segments robust", ("table", "cells", "curve"), out)
+    for c in br.gpu_cases():
+        out = sl.bootstrap_segments(sl.DEMGrid.from_array(c["z"], 1.0), c["cells"], c["labels"], c["angle"], float(br.H), float(br.W),
+                                    block_length=c["block_length"], replicates=c["R"], seed=c["seed"], ages=c["ages"],
+                                    min_samples=c["min_samples"], min_blocks=c["min_blocks"],
+                                    max_shift=float(c["D"]) if c["D"] else None, return_hist=True, return_replicates=True)
+        emit("bootstrap_reference", c, "bootstrap_segments", ("table", "hist", "index", "amplitude"), out)
+    for c in stk.gpu_cases():
+        out = sl.fit_along_strike(sl.DEMGrid.from_array(c["z"], 1.0), c["cells"], c["labels"], c["angle"], float(c["h"]), float(c["w"]),
+                                  window=c["window"], step=c["step"], ages=c["ages"], delta=c["delta"], min_samples=c["min_samples"],
+                                  min_profiles=c["min_profiles"], max_shift=float(c["D"]) if c["D"] else None, return_curve=True)
+        emit("strike_reference", c, "fit_along_strike", ("table", "curve"), out)
+    # (the launches show that the chunks ran: the same for two libraries, more with --fit-chunk)
+    print("# %d calls, %d buffers, %d bytes, %d launches under k_profile"
+          % (total["calls"], total["buffers"], total["bytes"], ctx.profile_get()["k_profile"][0]), flush=True)
 
 
 if __name__ == "__main__":

@@ -57,8 +57,8 @@ def main():
             ctx.profile(0)
         dev_ms[name] = float(np.median(dev))
         first = out[0] if isinstance(out, tuple) else out
-        print("%-36s k_profile device time %.2f ms (median of %d, warm; min %.2f, max %.2f); wall %.1f ms; %d of %d rows fitted"
-              % (name, dev_ms[name], a.reps, min(dev), max(dev), 1e3 * float(np.median(wall)), int((first["status"] != 1).sum()),
+        print("%-36s k_profile device time %.2f ms (median of %d, warm; min %.2f, max %.2f); wall %.2f ms (min %.2f, max %.2f); %d of %d rows fitted"
+              % (name, dev_ms[name], a.reps, min(dev), max(dev), 1e3 * float(np.median(wall)), 1e3 * min(wall), 1e3 * max(wall), int((first["status"] != 1).sum()),
                  len(first)))
     h, A, K = a.half, len(ages), a.cells
     print("%d cells of %d x %d in %d segments of %d, h %d, w %d, %d ages" % (K, a.n, a.n, lab[-1], a.segment, h, a.swath, A))

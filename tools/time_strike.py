@@ -79,8 +79,8 @@ def main():
             dev.append(ctx.profile_get()["k_profile"][1] - ms0)
             ctx.profile(0)
         dev_ms[name] = float(np.median(dev))
-        print("%-42s k_profile device time %.2f ms (median of %d, warm; min %.2f, max %.2f); wall %.1f ms; %d of %d rows done"
-              % (name, dev_ms[name], a.reps, min(dev), max(dev), 1e3 * float(np.median(wall)), int((out["status"] != 1).sum()),
+        print("%-42s k_profile device time %.2f ms (median of %d, warm; min %.2f, max %.2f); wall %.2f ms (min %.2f, max %.2f); %d of %d rows done"
+              % (name, dev_ms[name], a.reps, min(dev), max(dev), 1e3 * float(np.median(wall)), 1e3 * min(wall), 1e3 * max(wall), int((out["status"] != 1).sum()),
                  len(out)))
     print("%d cells of %d x %d in %d segments of %d, h %d, w %d, %d ages"
           % (a.cells, a.n, a.n, lab[-1], a.segment, a.half, a.swath, len(ages)))
