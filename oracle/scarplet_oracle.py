@@ -740,8 +740,16 @@ def snr_stack_windows_direct(z, dx, dy, kind, scale, ages, angles, wins, margin,
 #         The Ricker / Channel family keeps a wider one, 1e-3 (snr_ricker): its support is the float64 underflow of its
 #         exponential - FFT tiles with far more energy than the window's core - and single cells of the int16 Grand Canyon
 #         DEM sit above 5e-4 on the float32 FFT path (one of 262 144 in the five-width search of tests/test_gpu_configs.py).
+#         The real-space window is per support size as well (tests/test_gpu_direct_classes.py, profiles/direct_classes.txt):
+#         1e-4 was measured on supports of up to a few thousand taps.  A Scarp window of scale 60 and age 1000 at an oblique
+#         angle has 17 650 taps; on a 1030 x 1031 DEM with a noise floor its SNR is off by 7.7e-5 in a cell next to the
+#         window-limit border whose SNR is 0.013 (0.5 in the interior): the xcorr sum nearly cancels there, and it is ONE
+#         float32 chain over the taps - a plain float32 chain over the same taps in numpy is off by more at that cell, the
+#         T3 chain contributes nothing visible; the same in every kernel class (the classes' records are the same bits).
+#         Supports above 10 000 taps -> window 1.6e-4 (tie_rtol_direct_large).
 PARITY = dict(amp=(2e-4, 4e-6), snr=(5e-4, 2e-6), snr_ricker=(1e-3, 2e-6), tie_rtol=7e-4, tie_rtol_direct=1e-4,
-              tie_rtol_fft_scarp=1e-4)
+              tie_rtol_fft_scarp=1e-4, tie_rtol_direct_large=1.6e-4)
+DIRECT_LARGE_TAPS = 10000
 
 
 def snr_tolerance(kind=None):
@@ -752,11 +760,13 @@ def snr_tolerance(kind=None):
     return PARITY["snr_ricker"]
 
 
-def tie_window(method, kind=None):
+def tie_window(method, kind=None, taps=None):
     """The tie window of the device path ``method`` ('fft' / 'direct'; anything else - 'auto',
-    a mixed search - gets the FFT one) for templates of ``kind`` (None: not known, the widest)."""
+    a mixed search - gets the FFT one) for templates of ``kind`` (None: not known, the widest);
+    ``taps``: the largest support of the search, where the caller knows it (real space: supports
+    above DIRECT_LARGE_TAPS have a window of their own)."""
     if method == "direct":
-        return PARITY["tie_rtol_direct"]
+        return PARITY["tie_rtol_direct_large"] if taps is not None and taps > DIRECT_LARGE_TAPS else PARITY["tie_rtol_direct"]
     if kind is not None and str(kind) != RICKER and str(kind) in (SCARP, "right_upper_break", "left_upper_break"):
         return PARITY["tie_rtol_fft_scarp"]
     return PARITY["tie_rtol"]

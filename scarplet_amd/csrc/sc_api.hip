@@ -761,16 +761,12 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
                     d.mask_lim != nullptr || d.mask_err != nullptr;
             ++j;
         }
-        // real-space path: does some template of the run have window rows of 16 taps or more along x (SC_DR_SHARE_MIN)
-        // (about min(2c / |cos a|, 2d / |sin a|) cells for the built-in rectangles; a window uploaded
-        // by the host: unknown, taken as long)?  Decides the kernel form of the run's launch
+        // real-space path: does some template of the run have window rows of SC_DR_SHARE_MIN taps or more along x
+        // (direct_long_runs, sc_direct_route.h)?  Decides the kernel form of the run's launch
         // (launch_direct) - per RUN, so that a template's sums do not depend on what it is batched with
         bool long_runs = false;
-        for (int k = i; k < j && !long_runs; ++k) {
-            if (t[k].kind == SC_KIND_WINDOW) { long_runs = true; break; }
-            const double ca = fabs(t[k].cos_a) + 1e-9, sa = fabs(t[k].sin_a) + 1e-9;
-            long_runs = std::min(2.0 * t[k].c / ca, 2.0 * t[k].d / sa) / fabs(ctx->dx) >= 16.0;
-        }
+        for (int k = i; k < j && !long_runs; ++k)
+            long_runs = direct_long_runs(t[k].kind == SC_KIND_WINDOW, t[k].c, t[k].d, t[k].cos_a, t[k].sin_a, ctx->dx);
         runs.push_back({i, j - i, parity < 0 ? 0 : parity, full, long_runs});
         i = j;
     }
@@ -786,9 +782,8 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
             // (real space: small DEMs fold up to 32 orientations per launch, in order, inside the
             //  workgroup that owns a patch - a 512 x 512 search is 905 launches of a few microseconds
             //  otherwise; DEMs of a thousand workgroups per orientation gain nothing)
-            const long long wg1 = (long long)((g.cx1 - g.cx0 + 255) / 256) * ((g.cy1 - g.cy0 + 7) / 8);
             const int want = plan->method == SC_METHOD_FFT ? fft_batch_orientations(ctx, fg, runs[r].n, group)
-                                                           : (wg1 <= 1024 ? 32 : 1);
+                                                           : direct_batch_want(g.cy1 - g.cy0, g.cx1 - g.cx0);
             // compatible runs ahead, up to what one launch can hold (64 templates, 64 curvature planes)
             // (round 5: SC_MAX_BATCH templates per launch sequence - the row pass takes them in slices of whole
             //  orientations, at most SC_MAX_GROUP templates each: fft_inverse_fold)

@@ -62,6 +62,7 @@ struct WindowSlot {
 };
 
 #include "sc_fft_route.h"         // SC_MAX_GROUP, SC_MAX_BATCH, SC_MAX_ORIENT; the FFT path's choice of kernels
+#include "sc_direct_route.h"      // the real-space path's choice of kernel, slab and batch
 
 struct sc_ctx {
     int device = 0;

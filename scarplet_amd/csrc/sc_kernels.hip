@@ -581,14 +581,9 @@ k_direct(const float* __restrict__ curv, Geom g,
 //  * of the running best only the SNR lives in registers; the amplitude and the id of a cell are
 //    stored when a template wins it (round 4: no scratch in any form of the kernel).
 // ---------------------------------------------------------------------------
-#define DR2_LDS_FLOATS (39 * 1024 + 512)        // 158 KB
+// (DR2_LDS_FLOATS, DR2_WAVES, SC_DR_SHARE_MIN: sc_direct_route.h)
 #ifndef SC_DR_VMEMW
 #define SC_DR_VMEMW 1      // the real-space kernel's weights through vector loads (0: scalar loads, rounds 3 - 4a)
-#endif
-#define DR2_WAVES 8
-#ifndef SC_DR_SHARE_MIN
-#define SC_DR_SHARE_MIN 16    // shortest hole-free run (taps) whose T3 takes the shared form (8, the least the end-cell pieces allow, is slower:
-                              // 0.26 against 0.19 ms at 46 taps, 0.56 against 0.50 at 294 - profiles/r06_crossover.txt)
 #endif
 
 // grid = (ceil(wh_max / 4), n_templates), block = 256: one wave per window row.
@@ -1415,12 +1410,10 @@ int launch_direct(sc_ctx* ctx, int first, int n, bool to_maps, int nb, int wh_ma
         int rc = sc_near_buffers(ctx, &ev_count, &ev, &ev_cap);
         if (rc) return rc;
     }
-    // patch: 512 x 16 cells where that still gives every CU a workgroup, else 256 x 16, else 256 x 8
-    // The slab: all of the LDS (one workgroup per CU) unless the patch selection below gives the launch a smaller one.  Its
-    // size decides only how many template rows are staged at a time, not the order of any sum.
-    size_t lds = (size_t)DR2_LDS_FLOATS * sizeof(float);
+    // the patch, the slab and the form of T3: direct_route (sc_direct_route.h)
+    const DirectRoute route = direct_route(ch, cw, wh_max, ww_max, long_runs, ctx->variant);
+    const size_t lds = (size_t)route.lds_floats * sizeof(float);
     const size_t plane = (size_t)g.ly * g.lx;
-    auto wgs = [&](int txw, int ty) { return (long long)((cw + txw - 1) / txw) * ((ch + ty - 1) / ty); };
 #define DR2_LAUNCH(NBV, RWV, SHV, ...)                                                                     \
     {                                                                                              \
         int rc = sc_lds_attr(ctx, (const void*)k_direct2<NBV, RWV, SHV __VA_OPT__(,) __VA_ARGS__>, lds);                   \
@@ -1439,23 +1432,10 @@ int launch_direct(sc_ctx* ctx, int first, int n, bool to_maps, int nb, int wh_ma
                            (int)(lds / sizeof(float)));                                            \
         sc_prof_end(ctx);                                                                          \
     }
-    // (variant 11: T3 in the weighted form on every row; long_runs: some template of the launch has
-    //  rows of 16 taps or more - the shared form's kernel carries more registers, thin windows are
-    //  10 % faster on the plain one)
-    const bool share = ctx->variant != 11 && long_runs;
-    // (the 512-wide patch needs a slab of 512 + the padded window width cells x 16 rows)
-    const bool fits512 = (long long)(512 + ((ww_max + 3) & ~3)) * 16 <= DR2_LDS_FLOATS;
-    // (round 6) windows whose 256 x 16 slab fits half the LDS in one piece - up to about a thousand taps - take that patch
-    // with a slab of their own size: 128 registers and half the LDS are two workgroups per CU, four waves per SIMD, and the
-    // kernel is bound by instruction issue there (-4 .. -25 % against the 512 x 16 patch at two waves per SIMD,
-    // profiles/r06_crossover.txt; option "variant" 19: the whole LDS as before)
-    const long long need256 = (long long)(256 + ((ww_max + 3) & ~3)) * (16 + wh_max - 1);
-    const bool two_wg = need256 <= DR2_LDS_FLOATS / 2 - 256 && wgs(256, 16) >= 256 && ctx->variant != 19;
-    if (two_wg) {
-        lds = (size_t)need256 * sizeof(float);
-        if (share) DR2_LAUNCH(1, 2, true, true) else DR2_LAUNCH(1, 2, false, true)
-    } else if (fits512 && wgs(512, 16) >= 512 && ctx->variant != 16) { if (share) DR2_LAUNCH(2, 2, true) else DR2_LAUNCH(2, 2, false) }
-    else if (wgs(256, 16) >= 256) { if (share) DR2_LAUNCH(1, 2, true) else DR2_LAUNCH(1, 2, false) }
+    const bool share = route.share;
+    if (route.w4) { if (share) DR2_LAUNCH(1, 2, true, true) else DR2_LAUNCH(1, 2, false, true) }
+    else if (route.NB == 2) { if (share) DR2_LAUNCH(2, 2, true) else DR2_LAUNCH(2, 2, false) }
+    else if (route.RW == 2) { if (share) DR2_LAUNCH(1, 2, true) else DR2_LAUNCH(1, 2, false) }
     else { if (share) DR2_LAUNCH(1, 1, true) else DR2_LAUNCH(1, 1, false) }
 #undef DR2_LAUNCH
     SC_HIP(ctx, hipGetLastError());

@@ -649,10 +649,15 @@ def test_real_space_kernel_forms_agree(gpu_ctx):
 def test_direct_path_widest_window_on_a_large_dem(gpu_ctx):
     """A window close to the widest the real-space kernel stages (2 100 cells: the 512-cell patch
     would overflow its LDS slab, the 256-cell patch holds it) on a DEM large enough to be offered
-    the 512-cell patch: the result equals the FFT path's."""
+    the 512-cell patch - 400 x 10300: 21 x 25 = 525 patches of 512 x 16, direct_route wants 512 of them
+    and refuses the patch because (512 + 2100) x 16 floats do not fit; the 256 x 16 patch's slab holds
+    two of the window's three rows at a time (tests/test_direct_route_host.py: the same on the CPU): the result equals the FFT path's, and the float64 oracle's in the
+    corners, astride a patch seam, in the partial last patch and in the interior."""
     rng = np.random.default_rng(8)
-    z = (rng.standard_normal((400, 4600)) * 0.1).astype(np.float32)
+    ny, nx = 400, 10300
+    z = (rng.standard_normal((ny, nx)) * 0.1).astype(np.float32)
     m = sl.Matcher(grid(z, 1.0), ctx=gpu_ctx)
+    row = np.sin(np.arange(2100) * 0.01) + 0.5
 
     class Wide(WT.Scarp):
         def _device_descriptor(self):
@@ -660,8 +665,7 @@ def test_direct_path_widest_window_on_a_large_dem(gpu_ctx):
 
         def template(self):
             W = np.zeros((self.ny, self.nx))
-            W[self.ny // 2 - 1:self.ny // 2 + 2, self.nx // 2 - 1050:self.nx // 2 + 1050] = \
-                np.sin(np.arange(2100) * 0.01)[np.newaxis, :] + 0.5
+            W[self.ny // 2 - 1:self.ny // 2 + 2, self.nx // 2 - 1050:self.nx // 2 + 1050] = row[np.newaxis, :]
             return W
     try:
         a_d, s_d = m.match_template(Wide, 10, 1.0, 0.0, method="direct")
@@ -672,6 +676,32 @@ def test_direct_path_widest_window_on_a_large_dem(gpu_ctx):
         assert s_f.max() > 0 and np.isfinite(a_d).all()
     finally:
         m.ctx.clear_windows()
+    # the oracle at a few cells, as the real-space closed form of core.py:350-363 (oracle.xcorr_direct's sum, at those
+    # cells only): window row k, column l of the centred template reads curvature cell (i - ny//2 - k, j - nx//2 - l)
+    curv = orc.directional_curvature(z.astype(float), 1.0, 1.0, 0.0)
+    ks = np.repeat(np.arange(ny // 2 - 1, ny // 2 + 2), 2100)
+    ls = np.tile(np.arange(nx // 2 - 1050, nx // 2 + 1050), 3)
+    w = np.tile(row, 3)
+    ts, n = np.sum(w ** 2), len(w) + orc.EPS
+    lim = np.asarray(Wide(10, 1.0, 0.0, nx, ny, 1.0).get_window_limits(), dtype=bool)
+    # (rows below 10 / above 389 and columns below 6 / above 10293 lie outside this Scarp(10, 1.0, 0) class's window limits:
+    #  a few masked probes, the rest at the patch seams in y - 16 k, 16 k + 8 - and in x - 256 k - and in the last patches)
+    cells = [(i, j) for i in (0, 10, 15, 16, 23, 24, 200, 383, 384, 389, ny - 1)
+             for j in (0, 6, 255, 256, 511, 512, 5000, 10239, 10240, nx - 7, nx - 1)]
+    o = np.empty((len(cells), 2))
+    for q, (i, j) in enumerate(cells):
+        v = curv[(i - ny // 2 - ks) % ny, (j - nx // 2 - ls) % nx]
+        xcorr, T3 = np.sum(w * v), np.sum(v ** 2)
+        amp = xcorr / ts
+        T1 = ts * amp ** 2
+        o[q] = (0.0, 0.0) if lim[i, j] else (amp, abs(T1 / ((1 / n) * (T1 - 2 * amp * xcorr + T3) + orc.EPS)))
+    assert (o[:, 1] > 0).sum() >= len(cells) // 2                  # (the probes are not all masked)
+    ii, jj = np.array(cells).T
+    d_a, d_s = np.abs(a_d[ii, jj] - o[:, 0]), np.abs(s_d[ii, jj] - o[:, 1])
+    print("widest window, 256 x 16 class: max |d amp| %.2e of %.2e, max |d snr| %.2e of %.2e at %d cells"
+          % (d_a.max(), np.abs(o[:, 0]).max(), d_s.max(), o[:, 1].max(), len(cells)))
+    assert (d_a <= AMP_RTOL * np.abs(o[:, 0]) + AMP_ATOL * np.abs(o[:, 0]).max()).all()
+    assert (d_s <= SNR_RTOL * o[:, 1] + SNR_ATOL * o[:, 1].max()).all()
 
 
 def test_nan_dem_gives_the_reference_nan_maps(gpu_ctx):
