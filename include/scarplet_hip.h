@@ -1005,6 +1005,68 @@ int sc_fit_profiles_refine_dem(sc_ctx* ctx, const double* z, int ny, int nx, con
                                double delta, int min_samples, sc_profile_fine_fit* out_rows, double* out_sse);
 
 /*
+ * Continuous ages of the joint fit (docs/segments.md, "Continuous ages"; scarplet_amd/csrc/sc_segment_refine.hip): the fit
+ * of sc_fit_segments, and after it the refinement of sc_fit_profiles_refine on the segment's POOLED criterion.
+ *   shared     the samples, the usable-profile rule, n, n_profiles, dof, the grid fit and its curve are sc_fit_segments':
+ *              every field of sc_segment_fit and of sc_segment_cell, and out_sse, are its bytes (its launches)
+ *   column     of a candidate age x, and the candidates of a bracket [p, q]: those of sc_fit_profiles_refine
+ *   joint fit  at x: per usable profile c, ebar_c, gamma_c, See_c, Sep_c by passes 0 to 2 with the candidate's column;
+ *              a(x) = (sum_c Sep_c) / (sum_c See_c); b_c, c0_c and the explicit residuals sse_c with that a; sse(x) =
+ *              sum_c sse_c.  The sums over c are the blocked sums of sc_fit_segments - no addition for one profile.  A
+ *              NaN sse counts as +inf
+ *   minimum, interval, status_fine: the rules of sc_fit_profiles_refine, on the segment's grid curve and with the
+ *              segment's dof for n - 3.  rmse_fine = sqrt(sse_fine / dof)
+ *   status 1   every *_fine float is NaN, status_fine = 1
+ *   cells      b_fine, c0_fine, sse_fine: each usable profile's slope, intercept and share of the sse at kt_fine; NaN where
+ *              b is NaN; the grid's b, c0, sse where the grid age was kept
+ * R = 0 returns the grid's values in every fine field.  A segment of one usable profile returns the kt_fine, kt_lo_fine,
+ * kt_hi_fine, a_fine, sse_fine, rmse_fine and status_fine - and b_fine, c0_fine - of sc_fit_profiles_refine for that cell,
+ * bit for bit.  The refinement runs in 2 R rounds per chunk (R for the minimum, R for both ends side by side); a round's
+ * candidate terms are parked beside the per-age terms, 8 ((2h + 1) + 4 (A + 128)) bytes per cell with R > 0, counted
+ * against SC_SEGMENT_MAX_PARK; chunks are whole segments and a single segment that needs more is SC_ERR_UNSUPPORTED.  No
+ * copy to the host between the rounds, no atomics, every sum in a fixed order: the same bytes on every run and for every
+ * chunk size.  Refused before any device work: what sc_fit_segments refuses; R < 0 (SC_ERR_INVALID); R >
+ * SC_PROFILE_MAX_REFINE (SC_ERR_UNSUPPORTED).  The buffers are those of sc_fit_segments and one of the call's own.  Timed
+ * as SC_K_PROFILE.
+ */
+#define SC_SEGMENT_REFINE_COLUMNS 128   /* candidate columns parked per cell with R > 0: both ends of the interval in a round */
+typedef struct sc_segment_fine_fit {
+    int32_t  label;           /* the fields of sc_segment_fit, in its layout     */
+    int32_t  n_cells;
+    int32_t  n_profiles;
+    int32_t  n;
+    int32_t  dof;
+    int32_t  kt_index;
+    int32_t  lo_index, hi_index;
+    int32_t  status;
+    double   kt, kt_lo, kt_hi;
+    double   a;
+    double   sse, rmse;
+    double   kt_fine, kt_lo_fine, kt_hi_fine;   /* the minimum and the interval, off the grid */
+    double   a_fine;                            /* of kt_fine: the offset is 2 a_fine         */
+    double   sse_fine, rmse_fine;               /* sse_fine <= sse                            */
+    int32_t  status_fine;     /* 0, or 1 (not fitted), or 2 (open below) + 4 (open above) */
+} sc_segment_fine_fit;
+typedef struct sc_segment_fine_cell {
+    int64_t  cell;            /* the fields of sc_segment_cell, in its layout    */
+    int32_t  used;
+    int32_t  n;
+    double   b, c0, sse;
+    double   b_fine, c0_fine, sse_fine;         /* at kt_fine; NaN where b is NaN */
+} sc_segment_fine_cell;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_fit_segments_refine(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                           const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A,
+                           int h, int w, int R, double de, double delta, int min_samples, int min_profiles,
+                           sc_segment_fine_fit* out_rows, sc_segment_fine_cell* out_cells, double* out_sse);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_fit_segments_refine_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                               const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                               long long S, const double* ages, int A, int h, int w, int R, double de, double delta,
+                               int min_samples, int min_profiles, sc_segment_fine_fit* out_rows,
+                               sc_segment_fine_cell* out_cells, double* out_sse);
+
+/*
  * The initial slope of the joint fit (docs/segments.md, "The initial slope"; scarplet_amd/csrc/sc_segment_ramp.hip): the
  * fit of sc_fit_segments with the scarp of sc_fit_profiles_ramp,
  *   z_c(s) = c0_c + b_c s + a g(s; kt, L),   L = m de,   m = 0..M a whole number of cells.

@@ -223,6 +223,38 @@ SEGMENT_ROBUST_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_robust_
 SEGMENT_ROBUST_PLANES = 9                                              # SC_SEGMENT_ROBUST_PLANES
 
 
+SEGMENT_FINE_FLOATS = ("kt_fine", "kt_lo_fine", "kt_hi_fine", "a_fine", "sse_fine", "rmse_fine")
+SEGMENT_FINE_CELL_FLOATS = ("b_fine", "c0_fine", "sse_fine")
+
+
+class sc_segment_fine_fit(C.Structure):
+    """One row of sc_fit_segments_refine / sc_fit_segments_refine_dem: sc_segment_fit, then the minimum and the interval off
+    the grid (docs/segments.md, "Continuous ages")."""
+    _fields_ = sc_segment_fit._fields_ + [(f, C.c_double) for f in SEGMENT_FINE_FLOATS] + [("status_fine", C.c_int32)]
+
+
+class sc_segment_fine_cell(C.Structure):
+    """One cell of the cell table of sc_fit_segments_refine / sc_fit_segments_refine_dem."""
+    _fields_ = sc_segment_cell._fields_ + [(f, C.c_double) for f in SEGMENT_FINE_CELL_FLOATS]
+
+
+SEGMENT_FINE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fine_fit._fields_],
+                                   "formats": [np.int32] * 9 + [np.float64] * 12 + [np.int32],
+                                   "offsets": [getattr(sc_segment_fine_fit, f).offset for f, _ in sc_segment_fine_fit._fields_],
+                                   "itemsize": C.sizeof(sc_segment_fine_fit)})
+SEGMENT_FINE_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fine_cell._fields_],
+                                    "formats": [np.int64, np.int32, np.int32] + [np.float64] * 6,
+                                    "offsets": [getattr(sc_segment_fine_cell, f).offset for f, _ in sc_segment_fine_cell._fields_],
+                                    "itemsize": C.sizeof(sc_segment_fine_cell)})
+SEGMENT_REFINE_COLUMNS = 128                                           # SC_SEGMENT_REFINE_COLUMNS
+
+
+def segment_refine_cap(h, n_ages, refine):
+    """The cells of one segment the park of sc_fit_segments_refine holds: 8 ((2h + 1) + 4 (A + Cc)) bytes a cell, Cc the 128
+    candidate columns of a round (none with ``refine`` 0)."""
+    return SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * (n_ages + (SEGMENT_REFINE_COLUMNS if refine > 0 else 0))))
+
+
 def segment_robust_cap(h, n_ages, plane):
     """The cells of one segment the park of sc_fit_segments_robust holds: 8 ((2h + 1)(1 + plane) + 9 A) bytes a cell."""
     return SEGMENT_MAX_PARK // (8 * ((2 * h + 1) * (2 if plane else 1) + SEGMENT_ROBUST_PLANES * n_ages))
@@ -412,6 +444,13 @@ SIGNATURES = {
                                              C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
                                              C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, C.c_int,
                                              C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_segments_refine": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
+                                         C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
+    "sc_fit_segments_refine_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
+                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, _dp]),
     "sc_bootstrap_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -960,6 +999,32 @@ class Context(object):
             args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
         self._check(getattr(self.lib, name)(self._h, *args), name)
         return rows, tab, out
+
+    def fit_segments_refine(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
+                            refine, cell_table=False, curve=False, z=None):
+        """sc_fit_segments_refine on the context's DEM, or sc_fit_segments_refine_dem on ``z`` (float64, C-contiguous,
+        2-D): (rows, cell table or None, curve or None).  The arrays as fit_segments takes them; ``refine``: R, the
+        levels of 64 candidate ages below the grid."""
+        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
+                     (seg_label, np.int32)):
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        K, A, S = len(cells), len(ages), len(seg_label)
+        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
+        rows = np.zeros(S, dtype=SEGMENT_FINE_FIT_DTYPE)
+        tab = np.zeros(K, dtype=SEGMENT_FINE_CELL_DTYPE) if cell_table else None
+        sse = np.empty((S, A), dtype=np.float64) if curve else None
+        llp = C.POINTER(C.c_longlong)
+        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
+                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), int(refine), float(de),
+                float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
+                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
+        name = "sc_fit_segments_refine"
+        if z is not None:
+            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
+            name += "_dem"
+            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
+        self._check(getattr(self.lib, name)(self._h, *args), name)
+        return rows, tab, sse
 
     # -- block-bootstrap intervals per segment (docs/bootstrap.md) -----------------------
     def bootstrap_segments(self, cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, ages, h, w, D, de,

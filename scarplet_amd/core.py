@@ -946,7 +946,7 @@ class Matcher(object):
     def fit_segments(self, traces, half_length, swath=0, ages=None, delta=1.0, min_samples=4, min_profiles=1,
                      return_cells=False, return_curve=False, strike="cell", max_shift=None, return_shift=False,
                      max_width=None, initial_slope=None, return_width=False, weights=None, robust=None, tuning=None,
-                     iterations=8, robust_scale=None):
+                     iterations=8, robust_scale=None, refine=None):
         """``sl.fit_segments`` on the DEM this matcher holds on the device (docs/segments.md) - no upload: one age,
         one amplitude and one interval per segment of ``traces`` (the ``Traces`` of ``extract_traces``), fitted
         jointly to the profiles of all its cells.  One row per row of ``traces.segments``, in that order.
@@ -955,7 +955,7 @@ class Matcher(object):
         profiles, sturdier where single-cell orientations are noisy.  The bytes are those of ``sl.fit_segments`` on
         the same data, ``max_shift`` and ``return_shift`` included - and ``max_width``, ``initial_slope`` and
         ``return_width``, and ``weights``, ``robust``, ``tuning``, ``iterations`` and ``robust_scale`` (the weight plane
-        is uploaded by the call)."""
+        is uploaded by the call), and ``refine``."""
         from scarplet_amd import profiles, segments, traces as tr
         if not getattr(self, "whole", False):
             raise ValueError("fit_segments needs the whole DEM on the device, not a block of it")
@@ -983,8 +983,9 @@ class Matcher(object):
         rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
         if rp is not None:
             segments.check_park(args, rp[0])
+        R = segments.check_refine(args, refine, max_shift, weights, robust, max_width)
         return segments._run(self.ctx, args, self.nx, return_cells, return_curve, shift=D, return_shift=return_shift, ramp=rp,
-                             return_width=return_width, robust=rb)
+                             return_width=return_width, robust=rb, refine=R)
 
     def bootstrap_segments(self, traces, half_length, block_length, swath=0, replicates=1000, level=0.95, seed=0, ages=None,
                            min_samples=4, min_profiles=1, min_blocks=5, max_shift=None, return_hist=False,

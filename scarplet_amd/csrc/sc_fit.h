@@ -2,7 +2,8 @@
 // the arithmetic AND the frame around it.  Included by sc_profile.hip and sc_segment.hip - by sc_bootstrap.hip and
 // sc_strike.hip for stage one -, by sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every
 // term, by sc_segment_robust.hip, the joint fit on those sweeps, by sc_ramp.hip and sc_segment_ramp.hip, the initial slope
-// of the two, and by sc_lateral.hip for the sampler and the host frame.  Who owns what:
+// of the two, by sc_refine.hip and sc_segment_refine.hip, the ages off the grid of the two (rf_col), and by sc_lateral.hip for
+// the sampler and the host frame.  Who owns what:
 //   host    sc_profile.hip defines the frame of every per-cell call: the DEM's source (sc_pf_dem), the erf table
 //           (sc_pf_table) and the chunked driver (sc_pf_chunks), to which a call hands its one launch line.
 //           sc_segment.hip defines the frame of every segment call: the argument checks with the one cap refusal
@@ -19,6 +20,7 @@
 #pragma once
 #include "sc_fit_chunk.h"
 #include "sc_internal.h"
+#include <math.h>
 #include <functional>
 #include <vector>
 
@@ -133,6 +135,13 @@ struct sg_call {
     std::function<int(const sg_chunk&)> prepare, launch;
 };
 int sc_sg_chunks(sc_ctx* ctx, const sg_call& call);
+// The grid fit of the chunk after stage one (D < 0: the call without a shift): the two segmented sums, k_sg_resid between them (none of the five
+// for a chunk without cells) and k_sg_choose into rows, cells (or null; sc_segment_shift_cell with a shift) and curve (or null).  `fine`
+// (D < 0): the rows and the cells are sc_segment_fine_fit and sc_segment_fine_cell, whose shared fields the same kernel writes.  Returns the
+// number of launches.  The LDS limit of k_sg_resid is raised by sc_sg_grid_attr before the first chunk
+int sc_sg_grid_attr(sc_ctx* ctx, int A, int h, int D);
+int sc_sg_grid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, double delta, int min_profiles, bool fine,
+                      void* rows, void* cells, double* curve);
 // k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
 
@@ -403,6 +412,25 @@ __device__ __forceinline__ double pf_candidate(const double* prof, int np, int h
     pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
     return pf_sse(prof, np, h, de, e, a, b, c0);
 }
+
+// ---- the column of an age off the grid (docs/profiles.md, "Continuous ages") ------------------------------------------------------
+// Shared by sc_refine.hip and sc_segment_refine.hip.
+// the column of a candidate age x that no table holds: den = 2.0 * sqrt(x), and e(jj) is k_pf_table's expression.  Beyond
+// |argument| = RF_SAT the erf is +-1 in float64 (1 - erf(6) = 2.2e-17, under half a unit in the last place of 1), so the
+// tails of a profile - most of its points at a young age - cost a comparison where the whole wave is there
+#define RF_SAT 6.0
+struct rf_col {
+    double den, de;
+    int h;
+    __device__ __forceinline__ double operator()(int jj) const {
+        const double x = ((double)(jj - h) * de) / den;
+        if (fabs(x) >= RF_SAT) return copysign(1.0, x);
+        return erf(x);
+    }
+};
+
+// candidate l of the bracket [p, q]
+__device__ __forceinline__ double rf_x(double p, double q, int l) { return l == 63 ? q : p + (q - p) * ((double)l / 63.0); }
 
 // ---- the choice over the ages ---------------------------------------------------------------------------------------------------
 // One wave, lane i holding sse_i (lanes >= A are ignored): argmin with ties to the smaller index (a NaN never wins), thr =

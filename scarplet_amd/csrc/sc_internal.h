@@ -196,6 +196,7 @@ struct sc_ctx {
     DevBuf sg_shift;           // sc_fit_segments_shift*: d_ci parked beside the per-age terms, int8
     // sc_fit_segments_ramp*: the sg_ buffers with A (M + 1) columns for A, the table of F and m_i of every (segment, age), int8
     DevBuf sg_ftab, sg_width;
+    DevBuf sg_fine;            // sc_fit_segments_refine*: the sg_ buffers with A + 128 columns for A, and the state of every segment's searches
     // sc_fit_segments_robust*: the sg_ buffers with nine planes per age (and the weights beside the profiles); the uploaded
     // weight plane, the per-segment state of the scale and the iterates, the histograms of the radix select, a_i of iterate 0
     DevBuf sq_wt, sq_state, sq_hist, sq_a;

@@ -7,13 +7,13 @@
 //                registers by the same calls: they are k_pf_fit's bytes.
 //     a round    the lanes run over the 64 CANDIDATES of a bracket [p, q].  No table can hold their columns - the
 //                bracket is the cell's -, so a lane takes its column through rf_col, which evaluates
-//                erf((double)j de / (2 sqrt(x))) for the lane's own age x where pf_at would read the table, and runs
+//                erf((double)j de / (2 sqrt(x))) for the lane's own age x where pf_at would read the table (sc_fit.h), and runs
 //                pf_candidate on it with the pf_lin of the grid fit.  The column is RECOMPUTED in each of pf_candidate's
 //                four sweeps: staged, the 64 columns of a wave are 64 (2h + 1) doubles - 103 KB at h = 100, 52 KB with
 //                erf(-x) = -erf(x) on the symmetric s_j, for each of the PF_WAVES cells of a workgroup and beside the
 //                56 KB table of the grid fit, on a CU of 160 KB - and registers cannot hold 2h + 1 doubles a lane.  What
 //                the choice costs is measured in profiles/refine_fit.txt: the erf is 61 to 65 % of a round, and the
-//                saturated tails (RF_SAT below) are 17 to 19 % of the call on a scarp of age 10.
+//                saturated tails (RF_SAT, sc_fit.h) are 17 to 19 % of the call on a scarp of age 10.
 //     the picks  an argmin by shuffles on (sse, l) for the minimum, a ballot of sse <= thr for an end; the next bracket
 //                is two lanes' x, read by shuffle.  Every lane holds the same p, q, thr and result: the control flow is
 //                uniform over the wave.
@@ -22,23 +22,6 @@
 #include "sc_fit.h"
 #include <math.h>
 #include <algorithm>
-
-// the column of a candidate age x that no table holds: den = 2.0 * sqrt(x), and e(jj) is k_pf_table's expression.  Beyond
-// |argument| = RF_SAT the erf is +-1 in float64 (1 - erf(6) = 2.2e-17, under half a unit in the last place of 1), so the
-// tails of a profile - most of its points at a young age - cost a comparison where the whole wave is there
-#define RF_SAT 6.0
-struct rf_col {
-    double den, de;
-    int h;
-    __device__ __forceinline__ double operator()(int jj) const {
-        const double x = ((double)(jj - h) * de) / den;
-        if (fabs(x) >= RF_SAT) return copysign(1.0, x);
-        return erf(x);
-    }
-};
-
-// candidate l of the bracket [p, q]
-__device__ __forceinline__ double rf_x(double p, double q, int l) { return l == 63 ? q : p + (q - p) * ((double)l / 63.0); }
 
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_pf_refine(const double* __restrict__ z, int ny, int nx,

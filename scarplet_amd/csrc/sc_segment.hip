@@ -24,7 +24,7 @@
 //                 the best age (sc_segment_cell, or sc_segment_shift_cell with d_ci at that age)
 // No atomics at all.  The erf table is k_pf_table's: the same bits as sc_fit_profiles*.
 // The host side holds the frame of every segment call (sc_fit.h): the argument checks, stage one, the segmented sum and
-// sc_sg_chunks, the chunked driver.  A call - sg_run here; sr_run, sq_run, bs_run, st_run in their files - is the shape of
+// sc_sg_chunks, the chunked driver.  A call - sg_run here; sr_run, sq_run, bs_run, st_run, sx_run in their files - is the shape of
 // its park, its bounds, its list of outputs and the launches of one chunk.
 #include "sc_fit.h"
 #include <math.h>
@@ -270,7 +270,11 @@ __global__ __launch_bounds__(PF_THREADS) void k_sg_resid(const double* __restric
 
 // the age of each segment, its interval and its row; the cell table at the best age.  CELL: sc_segment_cell, or
 // sc_segment_shift_cell with the shift's degrees of freedom, status bit 8 and the cells' d_ci at the best age (the
-// call without a shift: D = 0, shifts null)
+// call without a shift: D = 0, shifts null).  The rows are sc_segment_fit, or - with CELL sc_segment_fine_cell - the
+// sc_segment_fine_fit of sc_segment_refine.hip, whose shared fields are written here and whose fine fields are left alone
+template <class CELL> struct sg_row_of { typedef sc_segment_fit type; };
+template <> struct sg_row_of<sc_segment_fine_cell> { typedef sc_segment_fine_fit type; };
+
 template <class CELL>
 __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_start, const int* __restrict__ label,
                                                   const int* __restrict__ cnt, long long S, long long K,
@@ -279,8 +283,10 @@ __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_st
                                                   int min_profiles, const long long* __restrict__ cells,
                                                   const int* __restrict__ cn, const int* __restrict__ used,
                                                   const double* __restrict__ scal, const double* __restrict__ planes,
-                                                  const signed char* __restrict__ shifts, sc_segment_fit* __restrict__ rows,
+                                                  const signed char* __restrict__ shifts,
+                                                  typename sg_row_of<CELL>::type* __restrict__ rows,
                                                   CELL* __restrict__ out_cells, double* __restrict__ curve) {
+    typedef typename sg_row_of<CELL>::type ROW;
     constexpr bool SHIFT = std::is_same<CELL, sc_segment_shift_cell>::value;
     const int lane = threadIdx.x;
     const int ia = min(lane, A - 1);
@@ -292,7 +298,7 @@ __global__ __launch_bounds__(64) void k_sg_choose(const int* __restrict__ seg_st
         const int dof = sg_dof(m, n, D);
         const bool fitted = sg_fitted(m, dof, min_profiles);
         // (the rows were cleared: their padding is part of what the caller compares)
-        sc_segment_fit* out = rows + s;
+        ROW* out = rows + s;
         int best = -1;
         double a_best = nan;
         pf_pick k = {-1, -1, -1, nan};
@@ -555,21 +561,56 @@ int sc_sg_chunks(sc_ctx* ctx, const sg_call& c) {
     return SC_OK;
 }
 
+// k_sg_resid of a call with the shift range D (D < 0: none), and the dynamic LDS it takes
+template <class F>
+static auto sg_resid_of(int A, int h, int D, F&& f) {
+    const int np = 2 * h + 1, nt = 2 * (h + (D >= 0 ? D : 0)) + 1;
+    const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
+    return f(tab_lds ? k_sg_resid<true> : k_sg_resid<false>, pf_lds_bytes(np, nt, A, false, tab_lds));
+}
+
+int sc_sg_grid_attr(sc_ctx* ctx, int A, int h, int D) {
+    return sg_resid_of(A, h, D, [&](auto k_resid, size_t lds) { return sc_lds_attr(ctx, (const void*)k_resid, lds); });
+}
+
+int sc_sg_grid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, double delta, int min_profiles, bool fine,
+                      void* rows, void* cells, double* curve) {
+    const sg_stage& st = k.st;
+    const size_t mA = (size_t)st.m * A;
+    const int Dk = D >= 0 ? D : 0;                       // what k_sg_resid and k_sg_choose take: no shift is a range of 0
+    int launches = 1;
+    if (k.G) {
+        sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 2, k.part, k.tot);
+        sg_resid_of(A, h, D, [&](auto k_resid, size_t lds) {
+            k_resid<<<pf_grid(st.m), PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, st.shift,
+                                                                    k.tot, st.m, A, h, Dk, de, min_profiles, k.tab);
+            return 0;
+        });
+        sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 1, k.part, k.tsum);
+        launches += 5;
+    }
+    const auto choose = [&](auto* r, auto* c) {
+        k_sg_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, st.m, k.tot, k.tsum, k.ages, A, Dk, delta,
+                                                           min_profiles, st.cells, st.cn, st.used, st.scal, st.planes, st.shift, r,
+                                                           c, curve);
+    };
+    if (fine) choose((sc_segment_fine_fit*)rows, (sc_segment_fine_cell*)cells);
+    else if (D >= 0) choose((sc_segment_fit*)rows, (sc_segment_shift_cell*)cells);
+    else choose((sc_segment_fit*)rows, (sc_segment_cell*)cells);
+    return launches;
+}
+
 static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* ages, int A, int h,
                   int w, int D, double de, double delta, int min_samples, int min_profiles, sc_segment_fit* out_rows,
                   void* out_cells, double* out_sse, int8_t* out_shift) {
     if (S == 0) return SC_OK;
     const bool shift = D >= 0;
-    const int np = 2 * h + 1, ht = h + (shift ? D : 0), nt = 2 * ht + 1;
+    const int ht = h + (shift ? D : 0);
     const size_t cell_bytes = shift ? sizeof(sc_segment_shift_cell) : sizeof(sc_segment_cell);
-    const bool tab_lds = sizeof(double) * (size_t)nt * A <= PF_TAB_LDS;
-    const size_t lds = pf_lds_bytes(np, nt, A, false, tab_lds);
-    const auto k_resid = tab_lds ? k_sg_resid<true> : k_sg_resid<false>;
-    const int Dk = shift ? D : 0;                        // what k_sg_resid and k_sg_choose take: no shift is a range of 0
     int rc;
     if ((rc = sc_sg_stage_attr(ctx, A, h, D))) return rc;
-    if ((rc = sc_lds_attr(ctx, (const void*)k_resid, lds))) return rc;
+    if ((rc = sc_sg_grid_attr(ctx, A, h, D))) return rc;
 
     sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, shift), SG_MAX_SEGS, nullptr, 0, 1};
     // (the shifted call's cells end in padding; d_ci comes back from where it is parked)
@@ -578,27 +619,8 @@ static int sg_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
              {out_sse, &ctx->sg_sse, sizeof(double) * A, SG_SEGS},
              {out_shift, &ctx->sg_shift, (size_t)A, SG_CELLS}};
     c.launch = [&](const sg_chunk& k) {
-        const sg_stage& st = k.st;
-        const size_t mA = (size_t)st.m * A;
-        int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, k.tab, st);
-        if (k.G) {
-            sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 2, k.part, k.tot);
-            k_resid<<<pf_grid(st.m), PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, st.shift,
-                                                                    k.tot, st.m, A, h, Dk, de, min_profiles, k.tab);
-            sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 1, k.part, k.tsum);
-            launches += 5;
-        }
-        if (shift)
-            k_sg_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, st.m, k.tot, k.tsum, k.ages, A, Dk,
-                                                               delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes,
-                                                               st.shift, (sc_segment_fit*)k.out[0],
-                                                               (sc_segment_shift_cell*)k.out[1], (double*)k.out[2]);
-        else
-            k_sg_choose<<<sg_grid(st.Sc), 64, 0, ctx->stream>>>(st.seg, st.label, st.cnt, st.Sc, st.m, k.tot, k.tsum, k.ages, A, Dk,
-                                                               delta, min_profiles, st.cells, st.cn, st.used, st.scal, st.planes,
-                                                               st.shift, (sc_segment_fit*)k.out[0], (sc_segment_cell*)k.out[1],
-                                                               (double*)k.out[2]);
-        return launches + 1;
+        return sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, D, de, min_samples, k.tab, k.st) +
+               sc_sg_grid_launch(ctx, k, A, h, D, de, delta, min_profiles, false, k.out[0], k.out[1], (double*)k.out[2]);
     };
     return sc_sg_chunks(ctx, c);
 }

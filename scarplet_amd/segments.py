@@ -33,6 +33,13 @@ ROBUST_FIT_FIELDS = FIT_FIELDS[:-1] + [("loss", np.float64), ("scale", np.float6
 ROBUST_FIT_DTYPE = np.dtype(ROBUST_FIT_FIELDS)
 ROBUST_CELL_FIELDS = CELL_FIELDS[:-1] + [("loss", np.float64), ("n_down", np.int32), ("dormant", np.int32), ("label", np.int32)]
 ROBUST_CELL_DTYPE = np.dtype(ROBUST_CELL_FIELDS)
+# ... and with refine: the minimum and the interval off the grid, after ``height``; per cell its slope, intercept and share
+# of the sse at ``kt_fine``
+FINE_FIT_FIELDS = FIT_FIELDS + [(f, np.float64) for f in _lib.SEGMENT_FINE_FLOATS] + [("height_fine", np.float64),
+                                                                                      ("status_fine", np.int32)]
+FINE_FIT_DTYPE = np.dtype(FINE_FIT_FIELDS)
+FINE_CELL_FIELDS = CELL_FIELDS[:-1] + [(f, np.float64) for f in _lib.SEGMENT_FINE_CELL_FLOATS] + [("label", np.int32)]
+FINE_CELL_DTYPE = np.dtype(FINE_CELL_FIELDS)
 
 
 def _labels_of(labels, idx, ny, nx):
@@ -106,6 +113,21 @@ def check_robust_park(args, plane):
                          % (counts.max(), cap))
 
 
+def check_refine(args, refine, max_shift=None, weights=None, robust=None, max_width=None):
+    """``profiles.check_refine`` for the joint fit: None, or R; the park - 8 ((2h + 1) + 4 (A + 128)) bytes per cell with
+    R > 0, a segment at a time (sc_fit_segments_refine; ``_lib.segment_refine_cap``) - must hold every segment.  ``args`` as
+    check_args returns them; ValueError otherwise."""
+    R = profiles.check_refine(refine, max_shift, weights, robust, max_width)
+    if R is not None:
+        seg_start, kt, h = args[3], args[5], args[6]
+        cap = _lib.segment_refine_cap(h, len(kt), R)
+        counts = np.diff(seg_start)
+        if len(counts) and counts.max() > cap:
+            raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages with refine"
+                             % (counts.max(), cap))
+    return R
+
+
 def check_robust(shape, args, weights, robust, tuning, iterations, robust_scale, max_shift, max_width):
     """``profiles.check_robust`` for the joint fit: None, or (plane or None, loss, k, T, sigma or 0.0); neither option is
     built together with ``max_shift`` or ``max_width``, and the park must hold every segment.  ValueError otherwise."""
@@ -120,7 +142,7 @@ def check_robust(shape, args, weights, robust, tuning, iterations, robust_scale,
 def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
                  min_profiles=1, return_cells=False, return_curve=False, device=0, max_shift=None, return_shift=False,
                  max_width=None, initial_slope=None, return_width=False, weights=None, robust=None, tuning=None,
-                 iterations=8, robust_scale=None):
+                 iterations=8, robust_scale=None, refine=None):
     """Fit ONE diffusion scarp per segment to the profiles cut across the strike at its cells (docs/segments.md).
 
     ``data``, ``cells``, ``angle``, ``half_length``, ``swath``, ``ages``, ``delta`` and ``min_samples`` are those of
@@ -162,7 +184,14 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     amplitude until it wakes.  The choice and the interval run on the robust loss; the table gains ``loss``, ``scale``,
     ``n_down``, ``ls_index`` and ``n_dormant`` ahead of ``height``, the cell table ``loss``, ``n_down`` and ``dormant``,
     ``status`` 16 marks a segment without a scale (the least-squares row) and ``1 | 32`` one none of whose ages survived, and
-    ``return_curve`` returns the loss curves.  Not built together with ``max_shift`` or ``max_width``."""
+    ``return_curve`` returns the loss curves.  Not built together with ``max_shift`` or ``max_width``.
+
+    ``refine`` (None: the age is one of the grid; 0, 1 or 2) is that of ``sl.fit_profiles`` on the segment's pooled sse: that
+    many levels of 64 candidate ages of the segment's own bracket below the grid, for the minimum and for either end of the
+    interval, every candidate fitted jointly (docs/segments.md, "Continuous ages").  Every field of the plain tables and the
+    curves keep the plain call's bytes; the table gains ``kt_fine, kt_lo_fine, kt_hi_fine, a_fine, sse_fine`` (<= ``sse``),
+    ``rmse_fine, height_fine, status_fine`` after ``height`` and the cell table ``b_fine, c0_fine, sse_fine`` ahead of
+    ``label``.  Not built together with ``max_shift``, ``max_width``, ``weights`` or ``robust``."""
     z, de = profiles._dem_of(data)
     args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles,
                       shift=max_shift is not None)
@@ -171,17 +200,24 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
     if rp is not None:
         check_park(args, rp[0])
+    R = check_refine(args, refine, max_shift, weights, robust, max_width)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
     return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift,
-                ramp=rp, return_width=return_width, robust=rb)
+                ramp=rp, return_width=return_width, robust=rb, refine=R)
 
 
 def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False, ramp=None, return_width=False,
-         robust=None):
+         robust=None, refine=None):
     idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
     plane = None
-    if robust is not None:
+    fit_dtype = ROBUST_FIT_DTYPE if robust is not None else RAMP_FIT_DTYPE if ramp is not None else FIT_DTYPE
+    cell_dtype = ROBUST_CELL_DTYPE if robust is not None else CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE
+    if refine is not None:
+        rows, tab, curve = ctx.fit_segments_refine(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, refine,
+                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+        fit_dtype, cell_dtype = FINE_FIT_DTYPE, FINE_CELL_DTYPE
+    elif robust is not None:
         wt, loss, k, T, sigma = robust
         rows, tab, curve = ctx.fit_segments_robust(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, weights=wt,
                                                    loss=loss, tuning=k, iterations=T, scale=sigma,
@@ -198,13 +234,15 @@ def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_s
         rows, tab, curve, plane = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
                                                    cell_table=bool(return_cells), curve=bool(return_curve), z=z,
                                                    shift=shift, shift_plane=bool(return_shift))
-    out = np.zeros(len(rows), dtype=ROBUST_FIT_DTYPE if robust is not None else FIT_DTYPE if ramp is None else RAMP_FIT_DTYPE)
+    out = np.zeros(len(rows), dtype=fit_dtype)
     for f in rows.dtype.names:
         out[f] = rows[f]
     out["height"] = 2.0 * rows["a"]
+    if refine is not None:
+        out["height_fine"] = 2.0 * rows["a_fine"]
     res = [out]
     if return_cells:
-        ct = np.zeros(len(tab), dtype=ROBUST_CELL_DTYPE if robust is not None else CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE)
+        ct = np.zeros(len(tab), dtype=cell_dtype)
         back = np.empty(len(order), dtype=np.int64)                    # sorted position of each kept cell
         back[order] = np.arange(len(order))
         for f in tab.dtype.names:
