@@ -273,7 +273,9 @@ int sc_set_option(sc_ctx* ctx, const char* name, double value);
  * fill_nodata_pass): float32 work values (valid cells come back rounded through
  * float32 as well), per nodata cell the nearest valid cell of each quadrant over
  * the columns x -+ step, step <= floor(max_search_distance) - left quadrants from
- * step 0, right quadrants from step 1, columns clamped at the raster edge - and
+ * step 0, right quadrants from step 1, columns clamped at the raster edge (the
+ * steps end at nx: beyond it both clamped columns repeat checks already made, so
+ * a distance far larger than the raster costs no more than one equal to nx) - and
  * the mean weighted by 1 / distance over the quadrants within
  * max_search_distance; then smoothing_iterations 3x3 means over the filled cells.
  * *remaining = cells still nodata (no source within reach); the host repeats with

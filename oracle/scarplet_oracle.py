@@ -270,7 +270,7 @@ def match_serial(z, dx, dy, kind, scale, ang_max=np.pi / 2,
 # ----------------------------------------------------------------------------
 # nodata fill                                               dem.py:388-414
 # ----------------------------------------------------------------------------
-def fill_nodata_pass(z, max_search_distance, smoothing_iterations=0):
+def fill_nodata_pass(z, max_search_distance, smoothing_iterations=0, bound_steps=True):
     """One call of GDAL's GDALFillNodata as rasterio.fill.fillnodata reaches it
     (dem.py:408-410).  PARITY UNPINNED: GDAL is an un-vendored dependency
     (setup.py / requirements.txt: rasterio, unpinned) and neither it nor
@@ -311,6 +311,11 @@ def fill_nodata_pass(z, max_search_distance, smoothing_iterations=0):
         ``smoothing_iterations`` passes replacing each FILLED cell by the mean
         of its 3x3 neighbourhood's non-nodata cells - an approximation of
         GDALMultiFilter's 3x3 average, not a restatement.
+    ``bound_steps``: end the steps at iStep = nXSize.  From iStep = nXSize - 1 on both columns are clamped at the
+    raster's edges and every check repeats one already made (an equal squared distance stores the same root and the
+    same value again), so the result is that of GDAL's loop, which with a quadrant missing runs to
+    dfMaxSearchDist + 1 - a billion steps per cell for a distance of 1e9.  False runs GDAL's loop as published
+    (tests/test_io.py compares the two).
     Returns a new float64 array."""
     zin = np.asarray(z, dtype=float)
     ny, nx = zin.shape
@@ -344,7 +349,7 @@ def fill_nodata_pass(z, max_search_distance, smoothing_iterations=0):
                 qv[q] = vals[ty, tx]
 
         this_max, step = R, 0
-        while step <= this_max:
+        while step <= (min(this_max, nx) if bound_steps else this_max):
             lx, rx = max(0, x - step), min(nx - 1, x + step)
             check(0, lx, up[y, lx])
             check(1, lx, dn[y, lx])

@@ -1175,7 +1175,9 @@ k_fill_idw(const double* __restrict__ z, int ny, int nx, const int* __restrict__
         if (step == 0) continue;
         check(2, rx, up[(size_t)y * nx + rx]);
         check(3, rx, dn[(size_t)y * nx + rx]);
-        if ((step & 3) == 0) this_max = (int)floor(fmax(fmax(qd[0], qd[1]), fmax(qd[2], qd[3])));
+        // (past the last column both clamped columns repeat checks already made: the steps end at nx whatever the
+        // distance - a missing quadrant keeps the refreshed limit at maxd + 1, a billion steps for maxd = 1e9)
+        if ((step & 3) == 0) this_max = (int)fmin(floor(fmax(fmax(qd[0], qd[1]), fmax(qd[2], qd[3]))), (double)nx);
     }
     double ws = 0.0, vs = 0.0;
     bool have = false;
@@ -1220,9 +1222,7 @@ int launch_fill_nodata(sc_ctx* ctx, double* zdev, double* tmp, int* up, int* dn,
     SC_HIP(ctx, hipMemsetAsync(remaining_dev, 0, sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_fill_scan, dim3((nx + 255) / 256), dim3(256), 0, ctx->stream,
                        (const double*)zdev, ny, nx, up, dn);
-    int R = (int)floor(maxd);
-    if (R < 0) R = 0;
-    if (R > nx) R = nx;
+    const int R = maxd >= (double)nx ? nx : std::max(0, (int)floor(maxd));      // (k_fill_idw: steps past nx repeat)
     dim3 grid((nx + 255) / 256, ny);
     hipLaunchKernelGGL(k_fill_idw, grid, dim3(256), 0, ctx->stream, (const double*)zdev, ny, nx,
                        (const int*)up, (const int*)dn, maxd, R, tmp, remaining_dev);

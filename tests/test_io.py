@@ -80,6 +80,31 @@ def test_fill_nodata_isolated_cells_do_not_stall():
     assert np.isnan(orc.fill_nodata(np.full((4, 5), np.nan))).all()       # nothing to fill from: ends
 
 
+def test_fill_nodata_oracle_steps_end_at_the_raster_width():
+    """The oracle ends a cell's steps at the raster's width (both clamped columns only repeat checks from there on);
+    GDAL's published loop runs to the search distance + 1 wherever a quadrant is missing.  The two give the same
+    bits - dead first and last rows and columns leave every quadrant missing somewhere - at distances below, at and
+    far beyond the width, with the limit's every-fourth-step refresh in between."""
+    import scarplet_oracle as orc
+    rng = np.random.default_rng(9)
+    for shape in ((12, 9), (7, 1), (1, 11), (5, 4)):
+        z = np.cumsum(rng.standard_normal(shape), 1) + 50.0
+        z[rng.random(shape) < 0.15] = np.nan
+        if min(shape) > 1:
+            z[0] = z[-1] = np.nan
+            z[:, 0] = z[:, -1] = np.nan
+        else:
+            z[0, 0] = z[-1, -1] = np.nan
+        assert not np.isnan(z).all()
+        for dist in (0, 0.5, 1, np.sqrt(2), 3, 4, 8, 9, 12.5, 50, 1000):
+            for smooth in (0, 1):
+                a = orc.fill_nodata_pass(z, dist, smooth)
+                b = orc.fill_nodata_pass(z, dist, smooth, bound_steps=False)
+                assert np.array_equal(a, b, equal_nan=True), (shape, dist, smooth)
+            if dist < 1 or dist >= 50:
+                assert np.isnan(a).sum() == (np.isnan(z).sum() if dist < 1 else 0)
+
+
 @pytest.mark.gpu
 def test_fill_nodata_device_equals_oracle():
     """sc_fill_nodata against the oracle's pass, bit for bit (float32 values, float64 sums, same operation order),
