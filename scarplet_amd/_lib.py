@@ -74,12 +74,9 @@ class sc_segment(C.Structure):
                 ("sum_cos2a", C.c_double), ("sum_sin2a", C.c_double)]
 
 
-# the same layout as a numpy structured dtype (the table is copied into such an array)
-SEGMENT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment._fields_],
-                          "formats": [np.int64, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32, np.int64]
-                          + [np.float64] * 10,
-                          "offsets": [getattr(sc_segment, f).offset for f, _ in sc_segment._fields_],
-                          "itemsize": C.sizeof(sc_segment)})
+# the same layout as a numpy structured dtype (the table is copied into such an array): here and below numpy derives
+# names, formats, offsets and itemsize from the Structure itself
+SEGMENT_DTYPE = np.dtype(sc_segment)
 
 
 class sc_profile_fit(C.Structure):
@@ -90,10 +87,7 @@ class sc_profile_fit(C.Structure):
                 ("a", C.c_double), ("b", C.c_double), ("c0", C.c_double), ("sse", C.c_double), ("rmse", C.c_double)]
 
 
-PROFILE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fit._fields_],
-                          "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8,
-                          "offsets": [getattr(sc_profile_fit, f).offset for f, _ in sc_profile_fit._fields_],
-                          "itemsize": C.sizeof(sc_profile_fit)})
+PROFILE_DTYPE = np.dtype(sc_profile_fit)
 PROFILE_MAX_AGES, PROFILE_MAX_HALF, PROFILE_MAX_SWATH = 64, 1024, 32   # SC_PROFILE_MAX_*
 PROFILE_MAX_SHIFT = 64                                                 # SC_PROFILE_MAX_SHIFT
 
@@ -103,10 +97,7 @@ class sc_profile_shift_fit(C.Structure):
     _fields_ = sc_profile_fit._fields_ + [("shift_index", C.c_int32), ("shift", C.c_double)]
 
 
-PROFILE_SHIFT_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_shift_fit._fields_],
-                                "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8 + [np.int32, np.float64],
-                                "offsets": [getattr(sc_profile_shift_fit, f).offset for f, _ in sc_profile_shift_fit._fields_],
-                                "itemsize": C.sizeof(sc_profile_shift_fit)})
+PROFILE_SHIFT_DTYPE = np.dtype(sc_profile_shift_fit)
 
 
 class sc_profile_robust_fit(C.Structure):
@@ -115,22 +106,17 @@ class sc_profile_robust_fit(C.Structure):
                                           ("ls_index", C.c_int32)]
 
 
-PROFILE_ROBUST_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_robust_fit._fields_],
-                                 "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 10 + [np.int32] * 2,
-                                 "offsets": [getattr(sc_profile_robust_fit, f).offset for f, _ in sc_profile_robust_fit._fields_],
-                                 "itemsize": C.sizeof(sc_profile_robust_fit)})
+PROFILE_ROBUST_DTYPE = np.dtype(sc_profile_robust_fit)
 ROBUST_NONE, ROBUST_HUBER, ROBUST_TUKEY = 0, 1, 2                      # SC_ROBUST_*
 ROBUST_MAX_ITER = 64                                                   # SC_ROBUST_MAX_ITER
+
 
 class sc_profile_ramp_fit(C.Structure):
     """One row of sc_fit_profiles_ramp / sc_fit_profiles_ramp_dem: sc_profile_fit, then the half-width of the best age."""
     _fields_ = sc_profile_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
 
 
-PROFILE_RAMP_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_ramp_fit._fields_],
-                               "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 8 + [np.int32, np.float64, np.float64],
-                               "offsets": [getattr(sc_profile_ramp_fit, f).offset for f, _ in sc_profile_ramp_fit._fields_],
-                               "itemsize": C.sizeof(sc_profile_ramp_fit)})
+PROFILE_RAMP_DTYPE = np.dtype(sc_profile_ramp_fit)
 PROFILE_MAX_WIDTH = 64                                                 # SC_PROFILE_MAX_WIDTH
 RAMP_FREE, RAMP_SLOPE = 0, 1                                           # SC_RAMP_*
 
@@ -144,10 +130,7 @@ class sc_profile_fine_fit(C.Structure):
     _fields_ = sc_profile_fit._fields_ + [(f, C.c_double) for f in FINE_FLOATS] + [("status_fine", C.c_int32)]
 
 
-PROFILE_FINE_DTYPE = np.dtype({"names": [f for f, _ in sc_profile_fine_fit._fields_],
-                               "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 17 + [np.int32],
-                               "offsets": [getattr(sc_profile_fine_fit, f).offset for f, _ in sc_profile_fine_fit._fields_],
-                               "itemsize": C.sizeof(sc_profile_fine_fit)})
+PROFILE_FINE_DTYPE = np.dtype(sc_profile_fine_fit)
 PROFILE_MAX_REFINE = 2                                                 # SC_PROFILE_MAX_REFINE
 
 
@@ -166,14 +149,8 @@ class sc_segment_cell(C.Structure):
                 ("b", C.c_double), ("c0", C.c_double), ("sse", C.c_double)]
 
 
-SEGMENT_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fit._fields_],
-                              "formats": [np.int32] * 9 + [np.float64] * 6,
-                              "offsets": [getattr(sc_segment_fit, f).offset for f, _ in sc_segment_fit._fields_],
-                              "itemsize": C.sizeof(sc_segment_fit)})
-SEGMENT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_cell._fields_],
-                               "formats": [np.int64, np.int32, np.int32] + [np.float64] * 3,
-                               "offsets": [getattr(sc_segment_cell, f).offset for f, _ in sc_segment_cell._fields_],
-                               "itemsize": C.sizeof(sc_segment_cell)})
+SEGMENT_FIT_DTYPE = np.dtype(sc_segment_fit)
+SEGMENT_CELL_DTYPE = np.dtype(sc_segment_cell)
 SEGMENT_MAX_PARK = 1 << 32                                             # SC_SEGMENT_MAX_PARK
 
 
@@ -182,11 +159,7 @@ class sc_segment_shift_cell(C.Structure):
     _fields_ = sc_segment_cell._fields_ + [("shift_index", C.c_int32)]
 
 
-SEGMENT_SHIFT_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_shift_cell._fields_],
-                                     "formats": [np.int64, np.int32, np.int32] + [np.float64] * 3 + [np.int32],
-                                     "offsets": [getattr(sc_segment_shift_cell, f).offset
-                                                 for f, _ in sc_segment_shift_cell._fields_],
-                                     "itemsize": C.sizeof(sc_segment_shift_cell)})
+SEGMENT_SHIFT_CELL_DTYPE = np.dtype(sc_segment_shift_cell)
 
 
 class sc_segment_ramp_fit(C.Structure):
@@ -194,10 +167,7 @@ class sc_segment_ramp_fit(C.Structure):
     _fields_ = sc_segment_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
 
 
-SEGMENT_RAMP_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_ramp_fit._fields_],
-                                   "formats": [np.int32] * 9 + [np.float64] * 6 + [np.int32, np.float64, np.float64],
-                                   "offsets": [getattr(sc_segment_ramp_fit, f).offset for f, _ in sc_segment_ramp_fit._fields_],
-                                   "itemsize": C.sizeof(sc_segment_ramp_fit)})
+SEGMENT_RAMP_FIT_DTYPE = np.dtype(sc_segment_ramp_fit)
 
 
 class sc_segment_robust_fit(C.Structure):
@@ -211,15 +181,8 @@ class sc_segment_robust_cell(C.Structure):
     _fields_ = sc_segment_cell._fields_ + [("loss", C.c_double), ("n_down", C.c_int32), ("dormant", C.c_int32)]
 
 
-SEGMENT_ROBUST_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_robust_fit._fields_],
-                                     "formats": [np.int32] * 9 + [np.float64] * 8 + [np.int32] * 3,
-                                     "offsets": [getattr(sc_segment_robust_fit, f).offset for f, _ in sc_segment_robust_fit._fields_],
-                                     "itemsize": C.sizeof(sc_segment_robust_fit)})
-SEGMENT_ROBUST_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_robust_cell._fields_],
-                                      "formats": [np.int64, np.int32, np.int32] + [np.float64] * 4 + [np.int32] * 2,
-                                      "offsets": [getattr(sc_segment_robust_cell, f).offset
-                                                  for f, _ in sc_segment_robust_cell._fields_],
-                                      "itemsize": C.sizeof(sc_segment_robust_cell)})
+SEGMENT_ROBUST_FIT_DTYPE = np.dtype(sc_segment_robust_fit)
+SEGMENT_ROBUST_CELL_DTYPE = np.dtype(sc_segment_robust_cell)
 SEGMENT_ROBUST_PLANES = 9                                              # SC_SEGMENT_ROBUST_PLANES
 
 
@@ -238,14 +201,8 @@ class sc_segment_fine_cell(C.Structure):
     _fields_ = sc_segment_cell._fields_ + [(f, C.c_double) for f in SEGMENT_FINE_CELL_FLOATS]
 
 
-SEGMENT_FINE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fine_fit._fields_],
-                                   "formats": [np.int32] * 9 + [np.float64] * 12 + [np.int32],
-                                   "offsets": [getattr(sc_segment_fine_fit, f).offset for f, _ in sc_segment_fine_fit._fields_],
-                                   "itemsize": C.sizeof(sc_segment_fine_fit)})
-SEGMENT_FINE_CELL_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_fine_cell._fields_],
-                                    "formats": [np.int64, np.int32, np.int32] + [np.float64] * 6,
-                                    "offsets": [getattr(sc_segment_fine_cell, f).offset for f, _ in sc_segment_fine_cell._fields_],
-                                    "itemsize": C.sizeof(sc_segment_fine_cell)})
+SEGMENT_FINE_FIT_DTYPE = np.dtype(sc_segment_fine_fit)
+SEGMENT_FINE_CELL_DTYPE = np.dtype(sc_segment_fine_cell)
 SEGMENT_REFINE_COLUMNS = 128                                           # SC_SEGMENT_REFINE_COLUMNS
 
 
@@ -269,10 +226,7 @@ class sc_segment_boot(C.Structure):
                 ("a_mean", C.c_double), ("a_sd", C.c_double), ("a_lo", C.c_double), ("a_hi", C.c_double)]
 
 
-SEGMENT_BOOT_DTYPE = np.dtype({"names": [f for f, _ in sc_segment_boot._fields_],
-                               "formats": [np.int32] * 10 + [np.float64] * 8,
-                               "offsets": [getattr(sc_segment_boot, f).offset for f, _ in sc_segment_boot._fields_],
-                               "itemsize": C.sizeof(sc_segment_boot)})
+SEGMENT_BOOT_DTYPE = np.dtype(sc_segment_boot)
 BOOT_MAX_REPLICATES = 4096                                             # SC_BOOT_MAX_REPLICATES
 
 
@@ -285,10 +239,7 @@ class sc_strike_fit(C.Structure):
                 ("a", C.c_double), ("sse", C.c_double), ("rmse", C.c_double)]
 
 
-STRIKE_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_strike_fit._fields_],
-                             "formats": [np.int32] * 10 + [np.float64] * 6,
-                             "offsets": [getattr(sc_strike_fit, f).offset for f, _ in sc_strike_fit._fields_],
-                             "itemsize": C.sizeof(sc_strike_fit)})
+STRIKE_FIT_DTYPE = np.dtype(sc_strike_fit)
 
 
 class sc_lateral_fit(C.Structure):
@@ -299,10 +250,7 @@ class sc_lateral_fit(C.Structure):
                 ("mse", C.c_double), ("rho", C.c_double), ("dz", C.c_double), ("tilt", C.c_double)]
 
 
-LATERAL_FIT_DTYPE = np.dtype({"names": [f for f, _ in sc_lateral_fit._fields_],
-                              "formats": [np.int64] + [np.int32] * 5 + [np.float64] * 7,
-                              "offsets": [getattr(sc_lateral_fit, f).offset for f, _ in sc_lateral_fit._fields_],
-                              "itemsize": C.sizeof(sc_lateral_fit)})
+LATERAL_FIT_DTYPE = np.dtype(sc_lateral_fit)
 LATERAL_MAX_LAG, LATERAL_MAX_BAND, LATERAL_MAX_FAR = 255, 64, 1024     # SC_LATERAL_MAX_*
 
 
@@ -313,10 +261,7 @@ class sc_surface_row(C.Structure):
                 ("snr", C.c_double), ("amp", C.c_double)]
 
 
-SURFACE_ROW_DTYPE = np.dtype({"names": [f for f, _ in sc_surface_row._fields_],
-                              "formats": [np.int32] * 8 + [np.float64] * 2,
-                              "offsets": [getattr(sc_surface_row, f).offset for f, _ in sc_surface_row._fields_],
-                              "itemsize": C.sizeof(sc_surface_row)})
+SURFACE_ROW_DTYPE = np.dtype(sc_surface_row)
 SURFACE_MAX_TEMPLATES = 65535                                          # (sc_snr_surface refuses more)
 SURFACE_CELL_BATCH = 8                                                 # SF_CB of sc_surface.hip: cells per workgroup of k_sf_score
 
@@ -333,6 +278,29 @@ _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
 _up = C.POINTER(C.c_uint32)
 _bp = C.POINTER(C.c_uint8)
+_llp = C.POINTER(C.c_longlong)
+_ip = C.POINTER(C.c_int32)
+_i, _d, _ll, _v = C.c_int, C.c_double, C.c_longlong, C.c_void_p
+
+# the pieces the fit family's prototypes are made of (include/scarplet_hip.h), in the order they stand in one
+_DEM = [_dp, _i, _i]                      # z, ny, nx: the prefix of every _dem form
+_CELLS = [_llp, _dp, _dp, _ll]            # cells, sa, ca, K
+_SEGS = [_llp, _ip, _ll]                  # seg_start, seg_label, S
+_AGES = [_dp, _i]                         # ages, A
+_HW = [_i, _i]                            # h, w
+_STOP = [_d, _d, _i]                      # de, delta, min_samples
+_ROBUST = [_dp, _i, _d, _i, _d]           # weights, loss, tuning, iterations, scale
+_RAMP = [_i, _i, _d]                      # width, mode, slope
+_CELL_OUT = [_v, _dp]                     # rows, curves
+_SEG_OUT = [_v, _v, _dp]                  # rows, cell table, curves
+
+
+def _fit_pair(name, *pieces):
+    """The table entries of a fit call and of its _dem twin, from one description: the context, (z, ny, nx) for the
+    twin, then ``pieces`` in order."""
+    own = [t for p in pieces for t in p]
+    return {name: (_i, [_P] + own), name + "_dem": (_i, [_P] + _DEM + own)}
+
 
 # every symbol include/scarplet_hip.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -389,90 +357,26 @@ SIGNATURES = {
     "sc_trace_result": (C.c_int, [_P, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_longlong, _bp,
                                   C.POINTER(C.c_int32), C.POINTER(C.c_longlong)]),
     "sc_trace_segments": (C.c_int, [_P, C.c_void_p, C.c_longlong]),
-    "sc_fit_profiles": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
-                                  C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
-    "sc_fit_profiles_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
-                                      C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
-    "sc_fit_profiles_robust": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
-                                         C.c_double, C.c_double, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_double,
-                                         C.c_void_p, _dp]),
-    "sc_fit_profiles_robust_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
-                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
-                                             C.c_double, C.c_int, C.c_double, C.c_void_p, _dp]),
-    "sc_fit_profiles_ramp": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
-                                       C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp,
-                                       C.c_void_p]),
-    "sc_fit_profiles_ramp_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
-                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
-                                           C.c_int, C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_profiles_refine": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int, C.c_int,
-                                         C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
-    "sc_fit_profiles_refine_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp,
-                                             C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p,
-                                             _dp]),
-    "sc_fit_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                  C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                  C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_segments_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                      C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int,
-                                      C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_profiles_shift": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, _dp, C.c_int, C.c_int,
-                                        C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_profiles_shift_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                            _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int,
-                                            C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_segments_shift": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                        C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_segments_shift_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
-                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                            C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_segments_ramp": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                       C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp,
-                                       C.c_void_p]),
-    "sc_fit_segments_ramp_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                           C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
-                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
-                                           C.c_int, C.c_void_p, C.c_void_p, _dp, C.c_void_p]),
-    "sc_fit_segments_robust": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                         C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_double,
-                                         C.c_double, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int, C.c_double,
-                                         C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_segments_robust_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
-                                             C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, C.c_int,
-                                             C.c_double, C.c_int, C.c_double, C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_segments_refine": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                         C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                         C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_segments_refine_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                             C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, _dp, C.c_int,
-                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
-                                             C.c_void_p, C.c_void_p, _dp]),
-    "sc_bootstrap_segments": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                        C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
-                                        C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                        C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, _dp]),
-    "sc_bootstrap_segments_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                            C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong,
-                                            C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int,
-                                            C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int,
-                                            C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, _dp]),
-    "sc_fit_strike": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.POINTER(C.c_longlong),
-                                C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
-                                C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
-                                C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
-    "sc_fit_strike_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong,
-                                    C.POINTER(C.c_longlong), C.POINTER(C.c_int32), C.c_longlong, C.POINTER(C.c_longlong),
-                                    C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.c_longlong, _dp, C.c_int, C.c_int,
-                                    C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, _dp]),
-    "sc_lateral_offsets": (C.c_int, [_P, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
-    "sc_lateral_offsets_dem": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.POINTER(C.c_longlong), _dp, _dp, C.c_longlong, C.c_int,
-                                         C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, _dp]),
+    # the fit family: each call and its _dem twin from one line.  Between (h, w) and de stands what the call fits besides
+    # the age - D, the refinement depth, or (width, mode, slope); the robust block follows min_samples / min_profiles; an
+    # int8 plane comes last
+    **_fit_pair("sc_fit_profiles", _CELLS, _AGES, _HW, _STOP, _CELL_OUT),
+    **_fit_pair("sc_fit_profiles_robust", _CELLS, _AGES, _HW, _STOP, _ROBUST, _CELL_OUT),
+    **_fit_pair("sc_fit_profiles_ramp", _CELLS, _AGES, _HW, _RAMP, _STOP, _CELL_OUT, [_v]),
+    **_fit_pair("sc_fit_profiles_refine", _CELLS, _AGES, _HW, [_i], _STOP, _CELL_OUT),
+    **_fit_pair("sc_fit_segments", _CELLS, _SEGS, _AGES, _HW, _STOP, [_i], _SEG_OUT),
+    **_fit_pair("sc_fit_profiles_shift", _CELLS, _AGES, _HW, [_i], _STOP, _CELL_OUT, [_v]),
+    **_fit_pair("sc_fit_segments_shift", _CELLS, _SEGS, _AGES, _HW, [_i], _STOP, [_i], _SEG_OUT, [_v]),
+    **_fit_pair("sc_fit_segments_ramp", _CELLS, _SEGS, _AGES, _HW, _RAMP, _STOP, [_i], _SEG_OUT, [_v]),
+    **_fit_pair("sc_fit_segments_robust", _CELLS, _SEGS, _AGES, _HW, _STOP, [_i], _ROBUST, _SEG_OUT),
+    **_fit_pair("sc_fit_segments_refine", _CELLS, _SEGS, _AGES, _HW, [_i], _STOP, [_i], _SEG_OUT),
+    # (seg_blk_start, blk_start, NB; then D, de, min_samples, min_profiles, min_blocks, R, level, seed; rows, hist, idx, amp)
+    **_fit_pair("sc_bootstrap_segments", _CELLS, _SEGS, [_llp, _llp, _ll], _AGES, _HW, [_i, _d, _i, _i, _i, _i, _d, C.c_uint64],
+                [_v, _v, _v, _dp]),
+    # (seg_win_start, win_lo, win_hi, NW; then D, de, delta, min_samples, min_profiles)
+    **_fit_pair("sc_fit_strike", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i], _STOP, [_i], _CELL_OUT),
+    # (h, q0, q1, D: no age grid)
+    **_fit_pair("sc_lateral_offsets", _CELLS, [_i, _i, _i, _i], _STOP, _CELL_OUT),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -523,6 +427,16 @@ def load():
 
 def _as(arr, ptr_type):
     return arr.ctypes.data_as(ptr_type)
+
+
+def _arg(a, t):
+    """``a`` as an argument of type ``t``: an array as that pointer, None (an output not asked for) as it is, a number
+    as a float where ``t`` is a double and as an int elsewhere."""
+    if a is None:
+        return None
+    if isinstance(a, np.ndarray):
+        return a.ctypes.data_as(t)
+    return float(a) if t is C.c_double else int(a)
 
 
 SPECTRA_MB = 8192.0
@@ -815,62 +729,73 @@ class Context(object):
             self._h, _as(par, _dp), _as(ang, _dp), len(par), float(snr_low), float(snr_high), int(min_cells), t, l, k),
             "sc_trace_result")
 
-    # -- scarp-profile dating (docs/profiles.md) ------------------------------------
-    def _fit_call(self, name, head, rest, shift, shift_plane, shape, z):
-        """sc_fit_profiles / sc_fit_segments and their _shift and _dem forms: ``head``, D when shifted, ``rest``, and when
-        shifted the int8 plane of ``shape`` (returned; None unless asked for).  ``z``: the _dem form on that DEM."""
-        plane = None
-        args = head + rest
-        if shift is not None:
-            name += "_shift"
-            plane = np.zeros(shape, dtype=np.int8) if shift_plane else None
-            args = head + [int(shift)] + rest + [plane.ctypes.data_as(C.c_void_p) if shift_plane else None]
+    # -- the fit family: one frame, then what each call has of its own -------------------
+    def _fit_call(self, name, z, cells, segs, ages, own):
+        """One call of the fit family: ``name`` on the context's DEM, or its _dem twin on ``z`` (float64, C-contiguous, 2-D).
+        ``cells``: (cells, sa, ca), int64 and float64; ``segs``: None, or (seg_start, seg_label) int64 and int32, then the
+        int64 arrays that follow them in the prototype and their count; ``ages``: None or the float64 grid; ``own``: the
+        call's scalars and outputs in the prototype's order.  Every array is 1-D and C-contiguous, the heads of one length;
+        every argument goes over as the type SIGNATURES has at its position (``_arg``)."""
+        idx, sa, ca = cells
+        K = len(idx)
+        assert len(sa) == K and len(ca) == K
+        arrays = [(idx, np.int64), (sa, np.float64), (ca, np.float64)]
+        args = [idx, sa, ca, K]
+        if segs is not None:
+            seg_start, seg_label = segs[:2]
+            assert len(seg_start) == len(seg_label) + 1
+            arrays += [(seg_start, np.int64), (seg_label, np.int32)] + [(a, np.int64) for a in segs[2:-1]]
+            args += [seg_start, seg_label, len(seg_label)] + list(segs[2:])
+        if ages is not None:
+            arrays.append((ages, np.float64))
+            args += [ages, len(ages)]
+        for a, t in arrays:
+            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        args += own
         if z is not None:
             assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
             name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
-        return plane
+            args = [z, z.shape[0], z.shape[1]] + args
+        types = SIGNATURES[name][1][1:]
+        assert len(args) == len(types)
+        self._check(getattr(self.lib, name)(self._h, *[_arg(a, t) for a, t in zip(args, types)]), name)
 
+    # -- scarp-profile dating (docs/profiles.md) ------------------------------------
     def fit_profiles(self, cells, sa, ca, ages, h, w, de, delta, min_samples, curve=False, z=None, shift=None,
                      shift_plane=False):
         """sc_fit_profiles on the context's DEM, or sc_fit_profiles_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous.  With ``shift`` (D, the
         range of the centre shift in cells) the _shift calls: (rows, curve or None, (K, A) int8 shifts or None)."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A = len(cells), len(ages)
-        assert len(sa) == K and len(ca) == K
         rows = np.zeros(K, dtype=PROFILE_DTYPE if shift is None else PROFILE_SHIFT_DTYPE)
         sse = np.empty((K, A), dtype=np.float64) if curve else None
-        head = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w)]
-        rest = [float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None]
-        plane = self._fit_call("sc_fit_profiles", head, rest, shift, shift_plane, (K, A), z)
-        return (rows, sse) if shift is None else (rows, sse, plane)
+        if shift is None:
+            self._fit_call("sc_fit_profiles", z, (cells, sa, ca), None, ages, [h, w, de, delta, min_samples, rows, sse])
+            return rows, sse
+        plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
+        self._fit_call("sc_fit_profiles_shift", z, (cells, sa, ca), None, ages,
+                       [h, w, shift, de, delta, min_samples, rows, sse, plane])
+        return rows, sse, plane
+
+    @staticmethod
+    def _check_weights(weights, z):
+        """``weights``: None or a float64, C-contiguous plane of the DEM's shape (the caller's check where z is the
+        context's)."""
+        if weights is not None:
+            assert weights.dtype == np.float64 and weights.ndim == 2 and weights.flags.c_contiguous
+            assert z is None or weights.shape == z.shape
 
     def fit_profiles_robust(self, cells, sa, ca, ages, h, w, de, delta, min_samples, weights=None, loss=ROBUST_NONE,
                             tuning=0.0, iterations=1, scale=0.0, curve=False, z=None):
         """sc_fit_profiles_robust on the context's DEM, or sc_fit_profiles_robust_dem on ``z`` (float64, C-contiguous,
         2-D): (rows, (K, A) float64 loss curves or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous;
         ``weights``: None or a float64, C-contiguous plane of the DEM's shape; ``scale`` 0: estimated per profile."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        self._check_weights(weights, z)
         K, A = len(cells), len(ages)
-        assert len(sa) == K and len(ca) == K
-        if weights is not None:                              # (of the DEM's shape: the caller's check where z is the context's)
-            assert weights.dtype == np.float64 and weights.ndim == 2 and weights.flags.c_contiguous
-            assert z is None or weights.shape == z.shape
         rows = np.zeros(K, dtype=PROFILE_ROBUST_DTYPE)
         out = np.empty((K, A), dtype=np.float64) if curve else None
-        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
-                float(de), float(delta), int(min_samples), _as(weights, _dp) if weights is not None else None, int(loss),
-                float(tuning), int(iterations), float(scale), rows.ctypes.data_as(C.c_void_p), _as(out, _dp) if curve else None]
-        name = "sc_fit_profiles_robust"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_profiles_robust", z, (cells, sa, ca), None, ages,
+                       [h, w, de, delta, min_samples, weights, loss, tuning, iterations, scale, rows, out])
         return rows, out
 
     def fit_profiles_ramp(self, cells, sa, ca, ages, h, w, de, delta, min_samples, width, mode=RAMP_FREE, slope=0.0,
@@ -878,44 +803,23 @@ class Context(object):
         """sc_fit_profiles_ramp on the context's DEM, or sc_fit_profiles_ramp_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, curve or None, (K, A) int8 half-widths or None).  cells int64, sa / ca / ages float64, all 1-D and
         C-contiguous; ``width``: M, the range of the half-width in cells; ``slope`` is read with RAMP_SLOPE alone."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A = len(cells), len(ages)
-        assert len(sa) == K and len(ca) == K
         rows = np.zeros(K, dtype=PROFILE_RAMP_DTYPE)
         sse = np.empty((K, A), dtype=np.float64) if curve else None
         plane = np.zeros((K, A), dtype=np.int8) if width_plane else None
-        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
-                int(width), int(mode), float(slope), float(de), float(delta), int(min_samples),
-                rows.ctypes.data_as(C.c_void_p), _as(sse, _dp) if curve else None,
-                plane.ctypes.data_as(C.c_void_p) if width_plane else None]
-        name = "sc_fit_profiles_ramp"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_profiles_ramp", z, (cells, sa, ca), None, ages,
+                       [h, w, width, mode, slope, de, delta, min_samples, rows, sse, plane])
         return rows, sse, plane
 
     def fit_profiles_refine(self, cells, sa, ca, ages, h, w, de, delta, min_samples, refine, curve=False, z=None):
         """sc_fit_profiles_refine on the context's DEM, or sc_fit_profiles_refine_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, curve or None).  cells int64, sa / ca / ages float64, all 1-D and C-contiguous; ``refine``: R, the levels of
         64 candidate ages below the grid."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A = len(cells), len(ages)
-        assert len(sa) == K and len(ca) == K
         rows = np.zeros(K, dtype=PROFILE_FINE_DTYPE)
         sse = np.empty((K, A), dtype=np.float64) if curve else None
-        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, _as(ages, _dp), A, int(h), int(w),
-                int(refine), float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p),
-                _as(sse, _dp) if curve else None]
-        name = "sc_fit_profiles_refine"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_profiles_refine", z, (cells, sa, ca), None, ages,
+                       [h, w, refine, de, delta, min_samples, rows, sse])
         return rows, sse
 
     # -- one age per trace segment (docs/segments.md) -------------------------------
@@ -925,48 +829,31 @@ class Context(object):
         (rows, cell table or None, curve or None).  cells and seg_start int64, seg_label int32, sa / ca / ages
         float64, all 1-D and C-contiguous; the cells grouped by segment.  With ``shift`` (D, the range of the centre
         shift in cells) the _shift calls: (rows, cell table or None, curve or None, (K, A) int8 shifts or None)."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A, S = len(cells), len(ages), len(seg_label)
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
         rows = np.zeros(S, dtype=SEGMENT_FIT_DTYPE)
         tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE if shift is None else SEGMENT_SHIFT_CELL_DTYPE) if cell_table else None
         sse = np.empty((S, A), dtype=np.float64) if curve else None
-        llp = C.POINTER(C.c_longlong)
-        head = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w)]
-        rest = [float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
-                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
-        plane = self._fit_call("sc_fit_segments", head, rest, shift, shift_plane, (K, A), z)
-        return (rows, tab, sse) if shift is None else (rows, tab, sse, plane)
+        if shift is None:
+            self._fit_call("sc_fit_segments", z, (cells, sa, ca), (seg_start, seg_label), ages,
+                           [h, w, de, delta, min_samples, min_profiles, rows, tab, sse])
+            return rows, tab, sse
+        plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
+        self._fit_call("sc_fit_segments_shift", z, (cells, sa, ca), (seg_start, seg_label), ages,
+                       [h, w, shift, de, delta, min_samples, min_profiles, rows, tab, sse, plane])
+        return rows, tab, sse, plane
 
     def fit_segments_ramp(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles, width,
                           mode=RAMP_FREE, slope=0.0, cell_table=False, curve=False, width_plane=False, z=None):
         """sc_fit_segments_ramp on the context's DEM, or sc_fit_segments_ramp_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, cell table or None, curve or None, (S, A) int8 half-widths or None).  The arrays as fit_segments takes
         them; ``width``: M, the range of the half-width in cells; ``slope`` is read with RAMP_SLOPE alone."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A, S = len(cells), len(ages), len(seg_label)
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
         rows = np.zeros(S, dtype=SEGMENT_RAMP_FIT_DTYPE)
         tab = np.zeros(K, dtype=SEGMENT_CELL_DTYPE) if cell_table else None
         sse = np.empty((S, A), dtype=np.float64) if curve else None
         plane = np.zeros((S, A), dtype=np.int8) if width_plane else None
-        llp = C.POINTER(C.c_longlong)
-        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), int(width), int(mode),
-                float(slope), float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
-                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None,
-                plane.ctypes.data_as(C.c_void_p) if width_plane else None]
-        name = "sc_fit_segments_ramp"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_segments_ramp", z, (cells, sa, ca), (seg_start, seg_label), ages,
+                       [h, w, width, mode, slope, de, delta, min_samples, min_profiles, rows, tab, sse, plane])
         return rows, tab, sse, plane
 
     def fit_segments_robust(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
@@ -975,29 +862,13 @@ class Context(object):
         """sc_fit_segments_robust on the context's DEM, or sc_fit_segments_robust_dem on ``z`` (float64, C-contiguous,
         2-D): (rows, cell table or None, (S, A) float64 loss curves or None).  The arrays as fit_segments takes them;
         ``weights``: None or a float64, C-contiguous plane of the DEM's shape; ``scale`` 0: estimated per segment."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
+        self._check_weights(weights, z)
         K, A, S = len(cells), len(ages), len(seg_label)
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
-        if weights is not None:                              # (of the DEM's shape: the caller's check where z is the context's)
-            assert weights.dtype == np.float64 and weights.ndim == 2 and weights.flags.c_contiguous
-            assert z is None or weights.shape == z.shape
         rows = np.zeros(S, dtype=SEGMENT_ROBUST_FIT_DTYPE)
         tab = np.zeros(K, dtype=SEGMENT_ROBUST_CELL_DTYPE) if cell_table else None
         out = np.empty((S, A), dtype=np.float64) if curve else None
-        llp = C.POINTER(C.c_longlong)
-        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), float(de), float(delta),
-                int(min_samples), int(min_profiles), _as(weights, _dp) if weights is not None else None, int(loss),
-                float(tuning), int(iterations), float(scale), rows.ctypes.data_as(C.c_void_p),
-                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(out, _dp) if curve else None]
-        name = "sc_fit_segments_robust"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_segments_robust", z, (cells, sa, ca), (seg_start, seg_label), ages,
+                       [h, w, de, delta, min_samples, min_profiles, weights, loss, tuning, iterations, scale, rows, tab, out])
         return rows, tab, out
 
     def fit_segments_refine(self, cells, sa, ca, seg_start, seg_label, ages, h, w, de, delta, min_samples, min_profiles,
@@ -1005,25 +876,12 @@ class Context(object):
         """sc_fit_segments_refine on the context's DEM, or sc_fit_segments_refine_dem on ``z`` (float64, C-contiguous,
         2-D): (rows, cell table or None, curve or None).  The arrays as fit_segments takes them; ``refine``: R, the
         levels of 64 candidate ages below the grid."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K, A, S = len(cells), len(ages), len(seg_label)
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1
         rows = np.zeros(S, dtype=SEGMENT_FINE_FIT_DTYPE)
         tab = np.zeros(K, dtype=SEGMENT_FINE_CELL_DTYPE) if cell_table else None
         sse = np.empty((S, A), dtype=np.float64) if curve else None
-        llp = C.POINTER(C.c_longlong)
-        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, _as(ages, _dp), A, int(h), int(w), int(refine), float(de),
-                float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
-                tab.ctypes.data_as(C.c_void_p) if cell_table else None, _as(sse, _dp) if curve else None]
-        name = "sc_fit_segments_refine"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_segments_refine", z, (cells, sa, ca), (seg_start, seg_label), ages,
+                       [h, w, refine, de, delta, min_samples, min_profiles, rows, tab, sse])
         return rows, tab, sse
 
     # -- block-bootstrap intervals per segment (docs/bootstrap.md) -----------------------
@@ -1033,28 +891,15 @@ class Context(object):
         2-D): (rows, (S, A) int32 histograms or None, (S, R + 1) int8 indices or None, (S, R + 1) float64 amplitudes
         or None).  cells, seg_start, seg_blk_start and blk_start int64, seg_label int32, sa / ca / ages float64, all
         1-D and C-contiguous; the cells grouped by segment and, within it, by block."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32), (seg_blk_start, np.int64), (blk_start, np.int64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
-        K, A, S, NB = len(cells), len(ages), len(seg_label), len(blk_start) - 1
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1 and len(seg_blk_start) == S + 1
+        A, S = len(ages), len(seg_label)
+        assert len(seg_blk_start) == S + 1
         rows = np.zeros(S, dtype=SEGMENT_BOOT_DTYPE)
         hg = np.zeros((S, A), dtype=np.int32) if hist else None
         idx = np.zeros((S, int(R) + 1), dtype=np.int8) if replicates else None
         amp = np.zeros((S, int(R) + 1), dtype=np.float64) if replicates else None
-        llp = C.POINTER(C.c_longlong)
-        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, seg_blk_start.ctypes.data_as(llp),
-                blk_start.ctypes.data_as(llp), NB, _as(ages, _dp), A, int(h), int(w), int(D), float(de), int(min_samples),
-                int(min_profiles), int(min_blocks), int(R), float(level), int(seed), rows.ctypes.data_as(C.c_void_p),
-                hg.ctypes.data_as(C.c_void_p) if hist else None, idx.ctypes.data_as(C.c_void_p) if replicates else None,
-                _as(amp, _dp) if replicates else None]
-        name = "sc_bootstrap_segments"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_bootstrap_segments", z, (cells, sa, ca),
+                       (seg_start, seg_label, seg_blk_start, blk_start, len(blk_start) - 1), ages,
+                       [h, w, D, de, min_samples, min_profiles, min_blocks, R, level, seed, rows, hg, idx, amp])
         return rows, hg, idx, amp
 
     # -- joint fits in windows along the strike (docs/strike.md) -------------------------
@@ -1063,45 +908,22 @@ class Context(object):
         """sc_fit_strike on the context's DEM, or sc_fit_strike_dem on ``z`` (float64, C-contiguous, 2-D): (rows, (NW, A)
         float64 curves or None).  cells, seg_start, seg_win_start, win_lo and win_hi int64, seg_label int32, sa / ca /
         ages float64, all 1-D and C-contiguous; the cells grouped by segment and sorted along its strike."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64), (ages, np.float64), (seg_start, np.int64),
-                     (seg_label, np.int32), (seg_win_start, np.int64), (win_lo, np.int64), (win_hi, np.int64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
-        K, A, S, NW = len(cells), len(ages), len(seg_label), len(win_lo)
-        assert len(sa) == K and len(ca) == K and len(seg_start) == S + 1 and len(seg_win_start) == S + 1 and len(win_hi) == NW
+        A, S, NW = len(ages), len(seg_label), len(win_lo)
+        assert len(seg_win_start) == S + 1 and len(win_hi) == NW
         rows = np.zeros(NW, dtype=STRIKE_FIT_DTYPE)
         sse = np.empty((NW, A), dtype=np.float64) if curve else None
-        llp = C.POINTER(C.c_longlong)
-        args = [cells.ctypes.data_as(llp), _as(sa, _dp), _as(ca, _dp), K, seg_start.ctypes.data_as(llp),
-                seg_label.ctypes.data_as(C.POINTER(C.c_int32)), S, seg_win_start.ctypes.data_as(llp),
-                win_lo.ctypes.data_as(llp), win_hi.ctypes.data_as(llp), NW, _as(ages, _dp), A, int(h), int(w), int(D),
-                float(de), float(delta), int(min_samples), int(min_profiles), rows.ctypes.data_as(C.c_void_p),
-                _as(sse, _dp) if curve else None]
-        name = "sc_fit_strike"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_fit_strike", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), ages,
+                       [h, w, D, de, delta, min_samples, min_profiles, rows, sse])
         return rows, sse
 
     # -- strike-slip offsets across a trace (docs/lateral.md) -------------------------------
     def lateral_offsets(self, cells, sa, ca, h, q0, q1, D, de, delta, min_samples, curve=False, z=None):
         """sc_lateral_offsets on the context's DEM, or sc_lateral_offsets_dem on ``z`` (float64, C-contiguous, 2-D):
         (rows, (K, 2 D + 1) float64 mse curves or None).  cells int64, sa / ca float64, all 1-D and C-contiguous."""
-        for a, t in ((cells, np.int64), (sa, np.float64), (ca, np.float64)):
-            assert a.dtype == t and a.ndim == 1 and a.flags.c_contiguous
         K = len(cells)
-        assert len(sa) == K and len(ca) == K
         rows = np.zeros(K, dtype=LATERAL_FIT_DTYPE)
         mse = np.empty((K, 2 * int(D) + 1), dtype=np.float64) if curve else None
-        args = [cells.ctypes.data_as(C.POINTER(C.c_longlong)), _as(sa, _dp), _as(ca, _dp), K, int(h), int(q0), int(q1), int(D),
-                float(de), float(delta), int(min_samples), rows.ctypes.data_as(C.c_void_p), _as(mse, _dp) if curve else None]
-        name = "sc_lateral_offsets"
-        if z is not None:
-            assert z.dtype == np.float64 and z.ndim == 2 and z.flags.c_contiguous
-            name += "_dem"
-            args = [_as(z, _dp), z.shape[0], z.shape[1]] + args
-        self._check(getattr(self.lib, name)(self._h, *args), name)
+        self._fit_call("sc_lateral_offsets", z, (cells, sa, ca), None, None, [h, q0, q1, D, de, delta, min_samples, rows, mse])
         return rows, mse
 
     # -- the SNR surface at chosen cells (docs/surface.md) ---------------------------------

@@ -6,7 +6,7 @@ blocks of neighbouring profiles along the strike with replacement and re-fits th
 every replicate; the percentiles of the replicates' ages and amplitudes are the interval (sc_bootstrap_segments,
 include/scarplet_hip.h).
 """
-import operator
+import collections
 
 import numpy as np
 
@@ -18,6 +18,10 @@ GOLDEN = 0x9E3779B97F4A7C15
 BOOT_FIELDS = [(f, _lib.SEGMENT_BOOT_DTYPE.fields[f][0]) for f in _lib.SEGMENT_BOOT_DTYPE.names] + \
     [("height0", np.float64), ("height_lo", np.float64), ("height_hi", np.float64)]
 BOOT_DTYPE = np.dtype(BOOT_FIELDS)
+
+# what check_args returns, in the order Context.bootstrap_segments takes it
+Args = collections.namedtuple("Args", "cells sa ca seg_start seg_label seg_blk_start blk_start ages h w D de min_samples "
+                              "min_profiles min_blocks R level seed")
 
 
 def mix(z):
@@ -39,15 +43,8 @@ def draw(seed, label, r, k, nb):
 
 
 def _integer(x, name, lo, hi=None):
-    if isinstance(x, (bool, np.bool_)):
-        raise ValueError("%s must be an integer" % name)
-    try:
-        v = operator.index(x)
-    except TypeError:
-        raise ValueError("%s must be an integer, got %r" % (name, x))
-    if v < lo or (hi is not None and v > hi):
-        raise ValueError("%s must lie in %d..%s, got %r" % (name, lo, "" if hi is None else hi, x))
-    return v
+    return profiles._integer(x, lo, hi, "%s must be an integer" % name,
+                             "%s must lie in %d..%s" % (name, lo, "" if hi is None else hi))
 
 
 def segment_strikes(angle, seg_start):
@@ -84,8 +81,8 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
     (cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, ages, h, w, D, de, min_samples, min_profiles,
     min_blocks, R, level, seed)."""
     # (the park is checked as sc_fit_segments_shift counts it)
-    idx, sa, ca, seg_start, seg_label, kt, h, w, de, _, ms, mp, order, kept = segments.check_args(
-        shape, de, cells, labels, angle, half_length, swath, ages, 0.0, min_samples, min_profiles, shift=True)
+    s = segments.check_args(shape, de, cells, labels, angle, half_length, swath, ages, 0.0, min_samples, min_profiles, shift=True)
+    idx, sa, ca, seg_start, seg_label, de, h, ms = s.cells, s.sa, s.ca, s.seg_start, s.seg_label, s.de, s.h, s.min_samples
     D = profiles.check_shift(max_shift, False, de, h, ms)
     D = 0 if D is None else D
     if block_length is None:
@@ -101,7 +98,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
         raise ValueError("level must lie strictly between 0 and 1, got %r" % (level,))
     ny, nx = (int(v) for v in shape)
     if seg_strike is None:
-        pick = kept[order]
+        pick = s.kept[s.order]
         a = profiles._angles_of(angle, profiles._cells_of(cells, ny, nx), ny, nx)[pick]
         strike = segment_strikes(a, seg_start)
     else:
@@ -114,8 +111,8 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
     first[1:] = (seg[1:] != seg[:-1]) | (blk[1:] != blk[:-1])
     blk_start = np.concatenate([np.flatnonzero(first), [len(idx)]]).astype(np.int64)
     seg_blk_start = np.searchsorted(blk_start[:-1], seg_start).astype(np.int64)
-    return (np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, seg_label,
-            seg_blk_start, blk_start, kt, h, w, D, de, ms, mp, mb, R, lv, sd)
+    return Args(np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, seg_label,
+                seg_blk_start, blk_start, s.ages, h, s.w, D, de, ms, s.min_profiles, mb, R, lv, sd)
 
 
 def bootstrap_segments(data, cells, labels, angle, half_length, swath=0, block_length=None, replicates=1000, level=0.95,

@@ -86,6 +86,38 @@ def _grid_of(data):
     return z, dx, dy
 
 
+def _trace_cells(matcher, traces, strike, what, cells_too=False, angle=None):
+    """What a fit of ``traces`` (the ``Traces`` of ``extract_traces``) on the DEM ``matcher`` holds starts from: (cells,
+    labels, angle, seg_strike) - the cells of the segments (``labels > 0``, row-major order), their labels, and their
+    angles: ``angle`` where given, else with ``strike="segment"`` each cell's segment's ``strike`` from the table
+    (``seg_strike``, the strike of label L at index L - 1; None otherwise), else the angle plane of the matcher's result.
+    With ``cells_too`` anything but a ``Traces`` passes as cells, without labels.  ``what`` names the caller in the
+    refusal of a matcher that holds a block of the DEM."""
+    from scarplet_amd import traces as tr
+    if not getattr(matcher, "whole", False):
+        raise ValueError("%s needs the whole DEM on the device, not a block of it" % what)
+    if not isinstance(traces, tr.Traces) and not cells_too:
+        raise ValueError("traces must be the Traces of extract_traces")
+    if strike not in ("cell", "segment"):
+        raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
+    cells, lab, seg_strike = traces, None, None
+    if isinstance(traces, tr.Traces):
+        labels = np.asarray(traces.labels)
+        if labels.shape != (matcher.ny, matcher.nx):
+            raise ValueError("the traces' planes must have the DEM's shape %r" % ((matcher.ny, matcher.nx),))
+        cells = np.flatnonzero(labels.ravel() > 0)
+        lab = labels.ravel()[cells]
+        if angle is None and strike == "segment":
+            seg = traces.segments
+            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
+                raise ValueError("the traces' table does not number the segments of its label plane")
+            seg_strike = np.asarray(seg["strike"], dtype=np.float64)
+            angle = seg_strike[lab - 1]
+    if angle is None:
+        angle = matcher.result_array()[2]
+    return cells, lab, angle, seg_strike
+
+
 class Matcher(object):
     """A DEM resident on one GPU plus the running-best record of a search.
 
@@ -908,27 +940,14 @@ class Matcher(object):
         ``sl.fit_profiles`` on the same data, ``max_shift`` and ``return_shift`` included - and ``weights``, ``robust``,
         ``tuning``, ``iterations`` and ``robust_scale`` (the weight plane is uploaded; the DEM is not) - and ``max_width``,
         ``initial_slope`` and ``return_width`` - and ``refine``."""
-        from scarplet_amd import profiles, traces
-        if not getattr(self, "whole", False):
-            raise ValueError("fit_profiles needs the whole DEM on the device, not a block of it")
-        label = None
-        cells = traces_or_cells
-        if isinstance(traces_or_cells, traces.Traces):
-            labels = np.asarray(traces_or_cells.labels)
-            if labels.shape != (self.ny, self.nx):
-                raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
-            cells = np.flatnonzero(labels.ravel() > 0)
-            label = labels.ravel()[cells]
-        if angle is None:
-            angle = self.result_array()[2]
+        from scarplet_amd import profiles
+        cells, label, angle, _ = _trace_cells(self, traces_or_cells, "cell", "fit_profiles", cells_too=True, angle=angle)
         args = profiles.check_args((self.ny, self.nx), self.de, cells, angle, half_length, swath, ages, delta,
                                    min_samples)
-        D = profiles.check_shift(max_shift, return_shift, args[6], args[4], args[8])
-        rb = profiles.check_robust((self.ny, self.nx), weights, robust, tuning, iterations, robust_scale, max_shift)
-        rp = profiles.check_width(max_width, initial_slope, return_width, args[6], args[4], args[8], max_shift, weights, robust)
-        R = profiles.check_refine(refine, max_shift, weights, robust, max_width)
-        return profiles._run(self.ctx, args, self.nx, return_curve, label=label, shift=D, return_shift=return_shift, robust=rb,
-                             ramp=rp, return_width=return_width, refine=R)
+        opts = profiles.check_options((self.ny, self.nx), args, max_shift, return_shift, weights, robust, tuning, iterations,
+                                      robust_scale, max_width, initial_slope, return_width, refine)
+        return profiles._run(self.ctx, args, self.nx, return_curve, label=label, return_shift=return_shift,
+                             return_width=return_width, **opts._asdict())
 
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
@@ -956,36 +975,14 @@ class Matcher(object):
         the same data, ``max_shift`` and ``return_shift`` included - and ``max_width``, ``initial_slope`` and
         ``return_width``, and ``weights``, ``robust``, ``tuning``, ``iterations`` and ``robust_scale`` (the weight plane
         is uploaded by the call), and ``refine``."""
-        from scarplet_amd import profiles, segments, traces as tr
-        if not getattr(self, "whole", False):
-            raise ValueError("fit_segments needs the whole DEM on the device, not a block of it")
-        if not isinstance(traces, tr.Traces):
-            raise ValueError("traces must be the Traces of extract_traces")
-        if strike not in ("cell", "segment"):
-            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
-        labels = np.asarray(traces.labels)
-        if labels.shape != (self.ny, self.nx):
-            raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
-        cells = np.flatnonzero(labels.ravel() > 0)
-        lab = labels.ravel()[cells]
-        if strike == "segment":
-            seg = traces.segments
-            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
-                raise ValueError("the traces' table does not number the segments of its label plane")
-            angle = np.asarray(seg["strike"], dtype=np.float64)[lab - 1]
-        else:
-            angle = self.result_array()[2]
+        from scarplet_amd import segments
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "fit_segments")
         args = segments.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, ages, delta,
                                    min_samples, min_profiles, shift=max_shift is not None)
-        D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
-        rb = segments.check_robust((self.ny, self.nx), args, weights, robust, tuning, iterations, robust_scale, max_shift,
-                                   max_width)
-        rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
-        if rp is not None:
-            segments.check_park(args, rp[0])
-        R = segments.check_refine(args, refine, max_shift, weights, robust, max_width)
-        return segments._run(self.ctx, args, self.nx, return_cells, return_curve, shift=D, return_shift=return_shift, ramp=rp,
-                             return_width=return_width, robust=rb, refine=R)
+        opts = segments.check_options((self.ny, self.nx), args, max_shift, return_shift, weights, robust, tuning, iterations,
+                                      robust_scale, max_width, initial_slope, return_width, refine)
+        return segments._run(self.ctx, args, self.nx, return_cells, return_curve, return_shift=return_shift,
+                             return_width=return_width, **opts._asdict())
 
     def bootstrap_segments(self, traces, half_length, block_length, swath=0, replicates=1000, level=0.95, seed=0, ages=None,
                            min_samples=4, min_profiles=1, min_blocks=5, max_shift=None, return_hist=False,
@@ -994,27 +991,8 @@ class Matcher(object):
         block-bootstrap interval of the age and the amplitude of every segment of ``traces``.  ``strike`` chooses the
         profiles' orientation as in ``fit_segments``; with ``strike="segment"`` the blocks are cut along the table's
         ``strike`` too.  The bytes are those of ``sl.bootstrap_segments`` on the same data."""
-        from scarplet_amd import bootstrap, traces as tr
-        if not getattr(self, "whole", False):
-            raise ValueError("bootstrap_segments needs the whole DEM on the device, not a block of it")
-        if not isinstance(traces, tr.Traces):
-            raise ValueError("traces must be the Traces of extract_traces")
-        if strike not in ("cell", "segment"):
-            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
-        labels = np.asarray(traces.labels)
-        if labels.shape != (self.ny, self.nx):
-            raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
-        cells = np.flatnonzero(labels.ravel() > 0)
-        lab = labels.ravel()[cells]
-        seg_strike = None
-        if strike == "segment":
-            seg = traces.segments
-            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
-                raise ValueError("the traces' table does not number the segments of its label plane")
-            seg_strike = np.asarray(seg["strike"], dtype=np.float64)
-            angle = seg_strike[lab - 1]
-        else:
-            angle = self.result_array()[2]
+        from scarplet_amd import bootstrap
+        cells, lab, angle, seg_strike = _trace_cells(self, traces, strike, "bootstrap_segments")
         args = bootstrap.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, block_length,
                                     replicates, level, seed, ages, min_samples, min_profiles, min_blocks, max_shift,
                                     seg_strike=seg_strike)
@@ -1027,25 +1005,8 @@ class Matcher(object):
         orientation as in ``fit_segments``; with ``strike="segment"`` every cell of a segment has the table's ``strike``,
         whose axial mean - the same strike, folded into (-pi/2, pi/2] - is what the along-strike coordinate is taken
         along.  The bytes are those of ``sl.fit_along_strike`` on the same data and orientations."""
-        from scarplet_amd import strike as st, traces as tr
-        if not getattr(self, "whole", False):
-            raise ValueError("fit_along_strike needs the whole DEM on the device, not a block of it")
-        if not isinstance(traces, tr.Traces):
-            raise ValueError("traces must be the Traces of extract_traces")
-        if strike not in ("cell", "segment"):
-            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
-        labels = np.asarray(traces.labels)
-        if labels.shape != (self.ny, self.nx):
-            raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
-        cells = np.flatnonzero(labels.ravel() > 0)
-        lab = labels.ravel()[cells]
-        if strike == "segment":
-            seg = traces.segments
-            if len(cells) and (len(seg) < lab.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
-                raise ValueError("the traces' table does not number the segments of its label plane")
-            angle = np.asarray(seg["strike"], dtype=np.float64)[lab - 1]
-        else:
-            angle = self.result_array()[2]
+        from scarplet_amd import strike as st
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "fit_along_strike")
         args, where = st.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, window, step, ages,
                                     delta, min_samples, min_profiles, max_shift)
         return st._run(self.ctx, args, where, return_curve)
@@ -1060,26 +1021,8 @@ class Matcher(object):
         ``strike="cell"`` reads the angle plane of this matcher's result - which is also what cells (as
         ``sl.lateral_offsets`` takes them) get unless ``angle`` says otherwise.  The bytes are those of
         ``sl.lateral_offsets`` on the same data and angles."""
-        from scarplet_amd import lateral, traces as tr
-        if not getattr(self, "whole", False):
-            raise ValueError("lateral_offsets needs the whole DEM on the device, not a block of it")
-        if strike not in ("cell", "segment"):
-            raise ValueError("strike must be 'cell' or 'segment', got %r" % (strike,))
-        label = None
-        cells = traces_or_cells
-        if isinstance(traces_or_cells, tr.Traces):
-            labels = np.asarray(traces_or_cells.labels)
-            if labels.shape != (self.ny, self.nx):
-                raise ValueError("the traces' planes must have the DEM's shape %r" % ((self.ny, self.nx),))
-            cells = np.flatnonzero(labels.ravel() > 0)
-            label = labels.ravel()[cells]
-            if angle is None and strike == "segment":
-                seg = traces_or_cells.segments
-                if len(cells) and (len(seg) < label.max() or not np.array_equal(seg["label"], np.arange(1, len(seg) + 1))):
-                    raise ValueError("the traces' table does not number the segments of its label plane")
-                angle = np.asarray(seg["strike"], dtype=np.float64)[label - 1]
-        if angle is None:
-            angle = self.result_array()[2]
+        from scarplet_amd import lateral
+        cells, label, angle, _ = _trace_cells(self, traces_or_cells, strike, "lateral_offsets", cells_too=True, angle=angle)
         args = lateral.check_args((self.ny, self.nx), self.de, cells, angle, half_length, near, far, max_offset, delta,
                                   min_samples)
         return lateral._run(self.ctx, args, self.nx, return_curve, label=label)

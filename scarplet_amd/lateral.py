@@ -6,8 +6,8 @@ strike-slip fault the slip is lateral: a channel or a ridge that crosses the tra
 profiles are cut, one on either side of the trace, and the lag along the strike at which the two agree best - each side
 keeping a mean and a slope of its own - is the offset (sc_lateral_offsets, include/scarplet_hip.h).
 """
+import collections
 import math
-import operator
 
 import numpy as np
 
@@ -17,6 +17,9 @@ from scarplet_amd import _lib, profiles
 FIT_FIELDS = [("row", np.int64), ("col", np.int64)] + \
     [(f, _lib.LATERAL_FIT_DTYPE.fields[f][0]) for f in _lib.LATERAL_FIT_DTYPE.names]
 FIT_DTYPE = np.dtype(FIT_FIELDS)
+
+# what check_args returns, in the order Context.lateral_offsets takes it
+Args = collections.namedtuple("Args", "cells sa ca h q0 q1 D de delta min_samples")
 
 
 def check_args(shape, de, cells, angle, half_length, near, far, max_offset, delta, min_samples):
@@ -59,15 +62,9 @@ def check_args(shape, de, cells, angle, half_length, near, far, max_offset, delt
     d = profiles._number(delta, "delta")
     if d < 0:
         raise ValueError("delta must be >= 0, got %r" % (delta,))
-    if isinstance(min_samples, (bool, np.bool_)):
-        raise ValueError("min_samples must be an integer")
-    try:
-        ms = operator.index(min_samples)
-    except TypeError:
-        raise ValueError("min_samples must be an integer, got %r" % (min_samples,))
-    if ms < 3 or ms > 2 * h + 1:
-        raise ValueError("min_samples must lie in 3..%d (the points of the window), got %r" % (2 * h + 1, min_samples))
-    return idx, np.sin(a), np.cos(a), h, q0, q1, D, de, d, ms
+    ms = profiles._integer(min_samples, 3, 2 * h + 1, "min_samples must be an integer",
+                           "min_samples must lie in 3..%d (the points of the window)" % (2 * h + 1))
+    return Args(idx, np.sin(a), np.cos(a), h, q0, q1, D, de, d, ms)
 
 
 def _table(rows, nx, label=None):
@@ -116,7 +113,6 @@ def lateral_offsets(data, cells, angle, half_length, near, far, max_offset, delt
 
 
 def _run(ctx, args, nx, return_curve, z=None, label=None):
-    idx, sa, ca, h, q0, q1, D, de, d, ms = args
-    rows, curve = ctx.lateral_offsets(idx, sa, ca, h, q0, q1, D, de, d, ms, curve=bool(return_curve), z=z)
+    rows, curve = ctx.lateral_offsets(*args, curve=bool(return_curve), z=z)
     out = _table(rows, nx, label)
     return (out, curve) if return_curve else out

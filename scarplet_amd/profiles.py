@@ -7,6 +7,7 @@ age of a grid, and the best age, the offset ``2 a``, the far-field slope ``b`` a
 does not tell apart come back as one row per cell (sc_fit_profiles, include/scarplet_hip.h) - instead of a Python
 loop of ``map_coordinates`` and ``lstsq`` over the cells.
 """
+import collections
 import math
 import operator
 
@@ -35,6 +36,12 @@ FINE_FIT_FIELDS = FIT_FIELDS + [(f, np.float64) for f in _lib.FINE_FLOATS] + [("
 FINE_FIT_DTYPE = np.dtype(FINE_FIT_FIELDS)
 ROBUST_LOSSES = {"huber": (_lib.ROBUST_HUBER, 1.345), "tukey": (_lib.ROBUST_TUKEY, 4.685)}
 
+# what check_args returns, in the order Context.fit_profiles takes it
+Args = collections.namedtuple("Args", "cells sa ca ages h w de delta min_samples")
+# what check_options returns: D or None, check_robust's tuple or None, check_width's tuple or None, R or None - the
+# keywords of _run
+Options = collections.namedtuple("Options", "shift robust ramp refine")
+
 
 def _number(x, name):
     if isinstance(x, (bool, np.bool_)):
@@ -45,6 +52,20 @@ def _number(x, name):
         raise ValueError("%s must be a number" % name)
     if not math.isfinite(v):
         raise ValueError("%s must be finite, got %r" % (name, x))
+    return v
+
+
+def _integer(x, lo, hi, not_int, out_of_range):
+    """``x`` as an int in lo..hi (``hi`` None: no upper end); ValueError in the caller's words otherwise: ``not_int`` for a
+    bool and, with the value, for whatever else is no integer; ``out_of_range``, with the value."""
+    if isinstance(x, (bool, np.bool_)):
+        raise ValueError(not_int)
+    try:
+        v = operator.index(x)
+    except TypeError:
+        raise ValueError("%s, got %r" % (not_int, x))
+    if v < lo or (hi is not None and v > hi):
+        raise ValueError("%s, got %r" % (out_of_range, x))
     return v
 
 
@@ -137,15 +158,9 @@ def check_args(shape, de, cells, angle, half_length, swath, ages, delta, min_sam
     d = _number(delta, "delta")
     if d < 0:
         raise ValueError("delta must be >= 0, got %r" % (delta,))
-    if isinstance(min_samples, (bool, np.bool_)):
-        raise ValueError("min_samples must be an integer")
-    try:
-        ms = operator.index(min_samples)
-    except TypeError:
-        raise ValueError("min_samples must be an integer, got %r" % (min_samples,))
-    if ms < 2 or ms > h:
-        raise ValueError("min_samples must lie in 2..%d (the half-length in cells), got %r" % (h, min_samples))
-    return idx, np.sin(a), np.cos(a), np.ascontiguousarray(kt), h, w, de, d, ms
+    ms = _integer(min_samples, 2, h, "min_samples must be an integer",
+                  "min_samples must lie in 2..%d (the half-length in cells)" % h)
+    return Args(idx, np.sin(a), np.cos(a), np.ascontiguousarray(kt), h, w, de, d, ms)
 
 
 def check_shift(max_shift, return_shift, de, h, min_samples):
@@ -197,14 +212,8 @@ def check_robust(shape, weights, robust, tuning, iterations, robust_scale, max_s
         k = _number(tuning, "tuning")
         if k <= 0:
             raise ValueError("tuning must be > 0, got %r" % (tuning,))
-    if isinstance(iterations, (bool, np.bool_)):
-        raise ValueError("iterations must be an integer")
-    try:
-        T = operator.index(iterations)
-    except TypeError:
-        raise ValueError("iterations must be an integer, got %r" % (iterations,))
-    if T < 1 or T > _lib.ROBUST_MAX_ITER:
-        raise ValueError("iterations must lie in 1..%d, got %r" % (_lib.ROBUST_MAX_ITER, iterations))
+    T = _integer(iterations, 1, _lib.ROBUST_MAX_ITER, "iterations must be an integer",
+                 "iterations must lie in 1..%d" % _lib.ROBUST_MAX_ITER)
     sigma = 0.0
     if robust_scale is not None:
         sigma = _number(robust_scale, "robust_scale")
@@ -261,6 +270,17 @@ def check_refine(refine, max_shift=None, weights=None, robust=None, max_width=No
     if max_shift is not None or weights is not None or robust is not None or max_width is not None:
         raise ValueError("refine is not built together with max_shift, weights, robust or max_width")
     return R
+
+
+def check_options(shape, args, max_shift, return_shift, weights, robust, tuning, iterations, robust_scale, max_width,
+                  initial_slope, return_width, refine):
+    """The options of ``fit_profiles`` beside ``args`` (check_args' record), checked in the one order that decides which
+    ValueError a doubly wrong call gets: Options(shift, robust, ramp, refine) of check_shift, check_robust, check_width and
+    check_refine."""
+    D = check_shift(max_shift, return_shift, args.de, args.h, args.min_samples)
+    rb = check_robust(shape, weights, robust, tuning, iterations, robust_scale, max_shift)
+    rp = check_width(max_width, initial_slope, return_width, args.de, args.h, args.min_samples, max_shift, weights, robust)
+    return Options(D, rb, rp, check_refine(refine, max_shift, weights, robust, max_width))
 
 
 def _table(rows, nx, label=None):
@@ -347,40 +367,33 @@ def fit_profiles(data, cells, angle, half_length, swath=0, ages=None, delta=1.0,
     built together with ``max_shift``, ``weights``, ``robust`` or ``max_width``."""
     z, de = _dem_of(data)
     args = check_args(z.shape, de, cells, angle, half_length, swath, ages, delta, min_samples)
-    D = check_shift(max_shift, return_shift, args[6], args[4], args[8])
-    rb = check_robust(z.shape, weights, robust, tuning, iterations, robust_scale, max_shift)
-    rp = check_width(max_width, initial_slope, return_width, args[6], args[4], args[8], max_shift, weights, robust)
-    R = check_refine(refine, max_shift, weights, robust, max_width)
+    opts = check_options(z.shape, args, max_shift, return_shift, weights, robust, tuning, iterations, robust_scale, max_width,
+                         initial_slope, return_width, refine)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_curve, z=z, shift=D, return_shift=return_shift, robust=rb, ramp=rp,
-                return_width=return_width, refine=R)
+    return _run(_context(device), args, z.shape[1], return_curve, z=z, return_shift=return_shift, return_width=return_width,
+                **opts._asdict())
 
 
 def _run(ctx, args, nx, return_curve, z=None, label=None, shift=None, return_shift=False, robust=None, ramp=None,
          return_width=False, refine=None):
-    idx, sa, ca, kt, h, w, de, d, ms = args
+    """The call the options name, on ``args`` (check_args' record), and its result as ``fit_profiles`` returns it: the table,
+    the curves when asked for, the int8 plane of the shifts or of the widths when asked for."""
+    plane, want_plane, out = None, False, bool(return_curve)
     if refine is not None:
-        rows, curve = ctx.fit_profiles_refine(idx, sa, ca, kt, h, w, de, d, ms, refine, curve=bool(return_curve), z=z)
-        out = _table(rows, nx, label)
-        return (out, curve) if return_curve else out
-    if ramp is not None:
+        rows, curve = ctx.fit_profiles_refine(*args, refine, curve=out, z=z)
+    elif ramp is not None:
         M, mode, slope = ramp
-        rows, curve, plane = ctx.fit_profiles_ramp(idx, sa, ca, kt, h, w, de, d, ms, M, mode=mode, slope=slope,
-                                                   curve=bool(return_curve), width_plane=bool(return_width), z=z)
-        res = [_table(rows, nx, label)] + ([curve] if return_curve else []) + ([plane] if return_width else [])
-        return res[0] if len(res) == 1 else tuple(res)
-    if robust is not None:
-        plane, loss, k, T, sigma = robust
-        rows, curve = ctx.fit_profiles_robust(idx, sa, ca, kt, h, w, de, d, ms, weights=plane, loss=loss, tuning=k, iterations=T,
-                                              scale=sigma, curve=bool(return_curve), z=z)
-        out = _table(rows, nx, label)
-        return (out, curve) if return_curve else out
-    if shift is None:
-        rows, curve = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z)
-        out = _table(rows, nx, label)
-        return (out, curve) if return_curve else out
-    rows, curve, plane = ctx.fit_profiles(idx, sa, ca, kt, h, w, de, d, ms, curve=bool(return_curve), z=z, shift=shift,
-                                          shift_plane=bool(return_shift))
-    res = [_table(rows, nx, label)] + ([curve] if return_curve else []) + ([plane] if return_shift else [])
+        want_plane = bool(return_width)
+        rows, curve, plane = ctx.fit_profiles_ramp(*args, M, mode=mode, slope=slope, curve=out, width_plane=want_plane, z=z)
+    elif robust is not None:
+        weights, loss, k, T, sigma = robust
+        rows, curve = ctx.fit_profiles_robust(*args, weights=weights, loss=loss, tuning=k, iterations=T, scale=sigma, curve=out,
+                                              z=z)
+    elif shift is None:
+        rows, curve = ctx.fit_profiles(*args, curve=out, z=z)
+    else:
+        want_plane = bool(return_shift)
+        rows, curve, plane = ctx.fit_profiles(*args, curve=out, z=z, shift=shift, shift_plane=want_plane)
+    res = [_table(rows, nx, label)] + ([curve] if return_curve else []) + ([plane] if want_plane else [])
     return res[0] if len(res) == 1 else tuple(res)

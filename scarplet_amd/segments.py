@@ -6,7 +6,7 @@ least-squares problem over all of them: the amplitude ``a`` and the age are the 
 intercept and a far-field slope of its own, since elevation and slope vary along the strike (sc_fit_segments,
 include/scarplet_hip.h).
 """
-import operator
+import collections
 
 import numpy as np
 
@@ -41,6 +41,10 @@ FINE_FIT_DTYPE = np.dtype(FINE_FIT_FIELDS)
 FINE_CELL_FIELDS = CELL_FIELDS[:-1] + [(f, np.float64) for f in _lib.SEGMENT_FINE_CELL_FLOATS] + [("label", np.int32)]
 FINE_CELL_DTYPE = np.dtype(FINE_CELL_FIELDS)
 
+# what check_args returns: the arguments of Context.fit_segments in its order, then the sort's permutation of the kept
+# cells and their input positions
+Args = collections.namedtuple("Args", "cells sa ca seg_start seg_label ages h w de delta min_samples min_profiles order kept")
+
 
 def _labels_of(labels, idx, ny, nx):
     """One int64 label per cell: one per cell, or an (ny, nx) int plane read at the cells."""
@@ -69,48 +73,38 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta,
                                                            min_samples)
     ny, nx = (int(v) for v in shape)
     lab = _labels_of(labels, idx, ny, nx)
-    if isinstance(min_profiles, (bool, np.bool_)):
-        raise ValueError("min_profiles must be an integer >= 1")
-    try:
-        mp = operator.index(min_profiles)
-    except TypeError:
-        raise ValueError("min_profiles must be an integer >= 1, got %r" % (min_profiles,))
-    if mp < 1:
-        raise ValueError("min_profiles must be an integer >= 1, got %r" % (min_profiles,))
+    mp = profiles._integer(min_profiles, 1, None, "min_profiles must be an integer >= 1", "min_profiles must be an integer >= 1")
     kept = np.flatnonzero(lab > 0)
     order = np.argsort(lab[kept], kind="stable")
     pick = kept[order]
     seg_label, counts = np.unique(lab[kept], return_counts=True)
     seg_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt)) + (len(kt) if shift else 0))
+    _check_cap(seg_start, _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt)) + (len(kt) if shift else 0)),
+               " and number of ages")
+    return Args(np.ascontiguousarray(idx[pick]), np.ascontiguousarray(sa[pick]), np.ascontiguousarray(ca[pick]), seg_start,
+                np.ascontiguousarray(seg_label, dtype=np.int32), kt, h, w, de, d, ms, mp, order, kept)
+
+
+def _check_cap(seg_start, cap, what):
+    """ValueError for a segment (CSR ``seg_start``) of more than ``cap`` cells; ``what``: the option that set the cap."""
+    counts = np.diff(seg_start)
     if len(counts) and counts.max() > cap:
-        raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages"
-                         % (counts.max(), cap))
-    return (np.ascontiguousarray(idx[pick]), np.ascontiguousarray(sa[pick]), np.ascontiguousarray(ca[pick]), seg_start,
-            np.ascontiguousarray(seg_label, dtype=np.int32), kt, h, w, de, d, ms, mp, order, kept)
+        raise ValueError("a segment of %d cells: more than %d at this half_length%s" % (counts.max(), cap, what))
 
 
 def check_park(args, M):
     """The park cap of a call with ``max_width``: 8 ((2h + 1) + 4 A (M + 1)) bytes per cell, a segment at a time
     (sc_fit_segments_ramp).  ``args`` as check_args returns them; ValueError for a segment above the cap."""
-    seg_start, kt, h = args[3], args[5], args[6]
-    cap = _lib.SEGMENT_MAX_PARK // (8 * ((2 * h + 1) + 4 * len(kt) * (M + 1)))
-    counts = np.diff(seg_start)
-    if len(counts) and counts.max() > cap:
-        raise ValueError("a segment of %d cells: more than %d at this half_length, number of ages and max_width"
-                         % (counts.max(), cap))
+    _check_cap(args.seg_start, _lib.SEGMENT_MAX_PARK // (8 * ((2 * args.h + 1) + 4 * len(args.ages) * (M + 1))),
+               ", number of ages and max_width")
 
 
 def check_robust_park(args, plane):
     """The park cap of a call with ``weights`` or ``robust``: 8 ((2h + 1)(1 + plane) + 9 A) bytes per cell, a segment at a
     time (sc_fit_segments_robust; ``_lib.segment_robust_cap``).  ``args`` as check_args returns them; ValueError for a
     segment above the cap."""
-    seg_start, kt, h = args[3], args[5], args[6]
-    cap = _lib.segment_robust_cap(h, len(kt), plane)
-    counts = np.diff(seg_start)
-    if len(counts) and counts.max() > cap:
-        raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages with weights or robust"
-                         % (counts.max(), cap))
+    _check_cap(args.seg_start, _lib.segment_robust_cap(args.h, len(args.ages), plane),
+               " and number of ages with weights or robust")
 
 
 def check_refine(args, refine, max_shift=None, weights=None, robust=None, max_width=None):
@@ -119,12 +113,7 @@ def check_refine(args, refine, max_shift=None, weights=None, robust=None, max_wi
     check_args returns them; ValueError otherwise."""
     R = profiles.check_refine(refine, max_shift, weights, robust, max_width)
     if R is not None:
-        seg_start, kt, h = args[3], args[5], args[6]
-        cap = _lib.segment_refine_cap(h, len(kt), R)
-        counts = np.diff(seg_start)
-        if len(counts) and counts.max() > cap:
-            raise ValueError("a segment of %d cells: more than %d at this half_length and number of ages with refine"
-                             % (counts.max(), cap))
+        _check_cap(args.seg_start, _lib.segment_refine_cap(args.h, len(args.ages), R), " and number of ages with refine")
     return R
 
 
@@ -137,6 +126,18 @@ def check_robust(shape, args, weights, robust, tuning, iterations, robust_scale,
     if rb is not None:
         check_robust_park(args, rb[0] is not None)
     return rb
+
+
+def check_options(shape, args, max_shift, return_shift, weights, robust, tuning, iterations, robust_scale, max_width,
+                  initial_slope, return_width, refine):
+    """The options of ``fit_segments`` beside ``args`` (check_args' record), checked in the one order that decides which
+    ValueError a doubly wrong call gets: ``profiles.Options(shift, robust, ramp, refine)``, every park checked."""
+    D = profiles.check_shift(max_shift, return_shift, args.de, args.h, args.min_samples)
+    rb = check_robust(shape, args, weights, robust, tuning, iterations, robust_scale, max_shift, max_width)
+    rp = profiles.check_width(max_width, initial_slope, return_width, args.de, args.h, args.min_samples, max_shift)
+    if rp is not None:
+        check_park(args, rp[0])
+    return profiles.Options(D, rb, rp, check_refine(args, refine, max_shift, weights, robust, max_width))
 
 
 def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, delta=1.0, min_samples=4,
@@ -195,69 +196,59 @@ def fit_segments(data, cells, labels, angle, half_length, swath=0, ages=None, de
     z, de = profiles._dem_of(data)
     args = check_args(z.shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles,
                       shift=max_shift is not None)
-    D = profiles.check_shift(max_shift, return_shift, args[8], args[6], args[10])
-    rb = check_robust(z.shape, args, weights, robust, tuning, iterations, robust_scale, max_shift, max_width)
-    rp = profiles.check_width(max_width, initial_slope, return_width, args[8], args[6], args[10], max_shift)
-    if rp is not None:
-        check_park(args, rp[0])
-    R = check_refine(args, refine, max_shift, weights, robust, max_width)
+    opts = check_options(z.shape, args, max_shift, return_shift, weights, robust, tuning, iterations, robust_scale, max_width,
+                         initial_slope, return_width, refine)
     z = np.ascontiguousarray(z, dtype=np.float64)
     from scarplet_amd.core import _context
-    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, shift=D, return_shift=return_shift,
-                ramp=rp, return_width=return_width, robust=rb, refine=R)
+    return _run(_context(device), args, z.shape[1], return_cells, return_curve, z=z, return_shift=return_shift,
+                return_width=return_width, **opts._asdict())
 
 
 def _run(ctx, args, nx, return_cells, return_curve, z=None, shift=None, return_shift=False, ramp=None, return_width=False,
          robust=None, refine=None):
-    idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = args
+    """The call the options name, on ``args`` (check_args' record), and its result as ``fit_segments`` returns it: the table,
+    then what was asked for of the cell table, the curves, the shifts and the widths - per cell in input order."""
+    call, de, order = args[:-2], args.de, args.order       # (the call takes all but order and kept)
+    out = dict(cell_table=bool(return_cells), curve=bool(return_curve), z=z)
     plane = None
     fit_dtype = ROBUST_FIT_DTYPE if robust is not None else RAMP_FIT_DTYPE if ramp is not None else FIT_DTYPE
     cell_dtype = ROBUST_CELL_DTYPE if robust is not None else CELL_DTYPE if shift is None else SHIFT_CELL_DTYPE
     if refine is not None:
-        rows, tab, curve = ctx.fit_segments_refine(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, refine,
-                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+        rows, tab, curve = ctx.fit_segments_refine(*call, refine, **out)
         fit_dtype, cell_dtype = FINE_FIT_DTYPE, FINE_CELL_DTYPE
     elif robust is not None:
         wt, loss, k, T, sigma = robust
-        rows, tab, curve = ctx.fit_segments_robust(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, weights=wt,
-                                                   loss=loss, tuning=k, iterations=T, scale=sigma,
-                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+        rows, tab, curve = ctx.fit_segments_robust(*call, weights=wt, loss=loss, tuning=k, iterations=T, scale=sigma, **out)
     elif ramp is not None:
         M, mode, slope = ramp
-        rows, tab, curve, widths = ctx.fit_segments_ramp(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, M, mode=mode,
-                                                         slope=slope, cell_table=bool(return_cells), curve=bool(return_curve),
-                                                         width_plane=bool(return_width), z=z)
+        rows, tab, curve, widths = ctx.fit_segments_ramp(*call, M, mode=mode, slope=slope, width_plane=bool(return_width), **out)
     elif shift is None:
-        rows, tab, curve = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
-                                            cell_table=bool(return_cells), curve=bool(return_curve), z=z)
+        rows, tab, curve = ctx.fit_segments(*call, **out)
     else:
-        rows, tab, curve, plane = ctx.fit_segments(idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp,
-                                                   cell_table=bool(return_cells), curve=bool(return_curve), z=z,
-                                                   shift=shift, shift_plane=bool(return_shift))
-    out = np.zeros(len(rows), dtype=fit_dtype)
+        rows, tab, curve, plane = ctx.fit_segments(*call, shift=shift, shift_plane=bool(return_shift), **out)
+    table = np.zeros(len(rows), dtype=fit_dtype)
     for f in rows.dtype.names:
-        out[f] = rows[f]
-    out["height"] = 2.0 * rows["a"]
+        table[f] = rows[f]
+    table["height"] = 2.0 * rows["a"]
     if refine is not None:
-        out["height_fine"] = 2.0 * rows["a_fine"]
-    res = [out]
-    if return_cells:
-        ct = np.zeros(len(tab), dtype=cell_dtype)
+        table["height_fine"] = 2.0 * rows["a_fine"]
+    res = [table]
+    if return_cells or return_shift:
         back = np.empty(len(order), dtype=np.int64)                    # sorted position of each kept cell
         back[order] = np.arange(len(order))
+    if return_cells:
+        ct = np.zeros(len(tab), dtype=cell_dtype)
         for f in tab.dtype.names:
             ct[f] = tab[f][back]
         ct["row"] = ct["cell"] // nx
         ct["col"] = ct["cell"] % nx
-        ct["label"] = np.repeat(seg_label, np.diff(seg_start))[back]
+        ct["label"] = np.repeat(args.seg_label, np.diff(args.seg_start))[back]
         if shift is not None:
             ct["shift"] = np.where(np.isnan(ct["b"]), np.nan, ct["shift_index"] * de)
         res.append(ct)
     if return_curve:
         res.append(curve)
     if return_shift:
-        back = np.empty(len(order), dtype=np.int64)
-        back[order] = np.arange(len(order))
         res.append(np.ascontiguousarray(plane[back]))
     if return_width:
         res.append(widths)

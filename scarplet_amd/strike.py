@@ -5,6 +5,8 @@ position along the trace: at stations spaced ``step`` apart along every segment'
 fitted jointly to the profiles of the cells within ``window / 2`` of the station, by the model of ``fit_segments``
 (sc_fit_strike, include/scarplet_hip.h).  The windows are cut here, in float64 numpy, and handed over as integer ranges.
 """
+import collections
+
 import numpy as np
 
 from scarplet_amd import _lib, bootstrap, profiles, segments
@@ -12,6 +14,10 @@ from scarplet_amd import _lib, bootstrap, profiles, segments
 FIT_FIELDS = [(f, _lib.STRIKE_FIT_DTYPE.fields[f][0]) for f in _lib.STRIKE_FIT_DTYPE.names] + \
     [("height", np.float64), ("t", np.float64), ("row", np.float64), ("col", np.float64)]
 FIT_DTYPE = np.dtype(FIT_FIELDS)
+
+# the first of what check_args returns, in the order Context.fit_strike takes it
+Args = collections.namedtuple("Args", "cells sa ca seg_start seg_label seg_win_start win_lo win_hi ages h w D de delta "
+                              "min_samples min_profiles")
 
 
 def windows_of(cells, nx, de, strike, seg_start, window, step):
@@ -63,9 +69,9 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
     seg_label, seg_win_start, win_lo, win_hi, ages, h, w, D, de, delta, min_samples, min_profiles) and (centre, row,
     col): each window's ``u_k`` and the means of its cells' rows and columns (NaN for an empty window)."""
     # (the park is checked as sc_fit_segments_shift counts it)
-    idx, sa, ca, seg_start, seg_label, kt, h, w, de, d, ms, mp, order, kept = segments.check_args(
-        shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=True)
-    D = profiles.check_shift(max_shift, False, de, h, ms)
+    s = segments.check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=True)
+    idx, sa, ca, seg_start, de = s.cells, s.sa, s.ca, s.seg_start, s.de
+    D = profiles.check_shift(max_shift, False, de, s.h, s.min_samples)
     D = 0 if D is None else D
     if window is None:
         raise ValueError("window is required: the length of a window along the strike, in data units")
@@ -77,7 +83,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
         raise ValueError("step must lie between the cell size %r and the window %r, got %r%s"
                          % (de, win, stp, " (window / 2: pass a step)" if step is None else ""))
     ny, nx = (int(v) for v in shape)
-    pick = kept[order]
+    pick = s.kept[s.order]
     a = profiles._angles_of(angle, profiles._cells_of(cells, ny, nx), ny, nx)[pick]
     strike = bootstrap.segment_strikes(a, seg_start)
     by, _, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, win, stp)
@@ -91,8 +97,9 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
     with np.errstate(invalid="ignore", divide="ignore"):
         row = np.where(cnt > 0, (cr[win_hi] - cr[win_lo]) / cnt, np.nan)
         col = np.where(cnt > 0, (cc[win_hi] - cc[win_lo]) / cnt, np.nan)
-    return ((np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, seg_label,
-             seg_win_start, win_lo, win_hi, kt, h, w, D, de, d, ms, mp), (centre, row, col))
+    return (Args(np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, s.seg_label,
+                 seg_win_start, win_lo, win_hi, s.ages, s.h, s.w, D, de, s.delta, s.min_samples, s.min_profiles),
+            (centre, row, col))
 
 
 def fit_along_strike(data, cells, labels, angle, half_length, swath=0, window=None, step=None, ages=None, delta=1.0,

@@ -30,6 +30,62 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == names, "ctypes table out of sync with the header"
 
 
+C_SCALARS = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "double": ctypes.c_double, "uint64_t": ctypes.c_uint64,
+             "size_t": ctypes.c_size_t}
+C_POINTEES = {"double": ctypes.c_double, "float": ctypes.c_float, "int": ctypes.c_int, "int32_t": ctypes.c_int32,
+              "int8_t": ctypes.c_int8, "uint8_t": ctypes.c_uint8, "uint32_t": ctypes.c_uint32, "long long": ctypes.c_longlong,
+              "unsigned long long": ctypes.c_ulonglong, "char": ctypes.c_char}
+
+
+def header_prototypes():
+    """{name: (return type, [parameter types])} of include/scarplet_hip.h, the types as C spells them less ``const`` and
+    the parameter's name.  The prototypes are regular: ``int sc_x(type name, ...);``."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+
+    def ctype(text, named):
+        toks = [t for t in text.replace("*", " * ").split() if t != "const"]
+        if named and toks != ["void"]:
+            toks = toks[:-1]                                # the parameter's name
+        return " ".join(toks).replace(" *", "*")
+    out = {}
+    for ret, name, params in re.findall(r"([\w \*]+?)\b(sc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, name
+        params = [ctype(p, True) for p in params.split(",")]
+        out[name] = (ctype(ret, False), [] if params == ["void"] else params)
+    return out
+
+
+def check_type(c, t, where):
+    """The C type ``c`` against the ctypes type ``t`` of the table."""
+    if not c.endswith("*"):
+        want = None if c == "void" else C_SCALARS[c]
+        assert t is want, "%s: %s in the header, %r in the table" % (where, c, t)
+        return
+    pointer = isinstance(t, type) and issubclass(t, ctypes._Pointer)
+    assert t in (ctypes.c_void_p, ctypes.c_char_p) or pointer, "%s: %s in the header, %r in the table" % (where, c, t)
+    if pointer:
+        pointee = c[:-1].strip()
+        want = ctypes.c_void_p if pointee.endswith("*") else C_POINTEES.get(pointee) or getattr(_lib, pointee)
+        assert t._type_ is want, "%s: %s in the header, a pointer to %r in the table" % (where, c, t._type_)
+    if t is ctypes.c_char_p:
+        assert c == "char*", "%s: %s in the header, c_char_p in the table" % (where, c)
+
+
+def test_every_prototype_of_the_header_has_its_types_in_the_table():
+    """Every prototype of include/scarplet_hip.h against its SIGNATURES entry: the number of parameters, each scalar's
+    type, a pointer-like type for each pointer and, where the table names a pointee, the C pointee.  ctypes itself takes
+    a wrong type or a wrong order without complaint."""
+    protos = header_prototypes()
+    assert sorted(protos) == sorted(_lib.SIGNATURES) == declared_functions()
+    for name, (ret, params) in protos.items():
+        res, args = _lib.SIGNATURES[name]
+        check_type(ret, res, name + " returns")
+        assert len(params) == len(args), "%s: %d parameters in the header, %d in the table" % (name, len(params), len(args))
+        for i, (c, t) in enumerate(zip(params, args)):
+            check_type(c, t, "%s, parameter %d" % (name, i))
+
+
 def test_host_library_exports_every_declared_symbol():
     """libscarplet_host.so (include/scarplet_host.h): plain C, linked against nothing of ROCm."""
     from scarplet_amd import _hostlib

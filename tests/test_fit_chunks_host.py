@@ -204,8 +204,9 @@ def test_the_park_cap_is_the_one_of_the_python_side(exe, monkeypatch):
         named[A, h, D, wt, M, park == full] = cap
         msg = "a segment of %d cells: more than %d at" % (cap + 1, cap)
 
-        def args(n):                                     # (what check_park and check_robust_park read of check_args' tuple)
-            return (None, None, None, np.array([0, 3, 3 + n]), None, np.ones(A), h)
+        def args(n):                                     # (what check_park and check_robust_park read of check_args' record)
+            blank = segments.Args(*[None] * len(segments.Args._fields))
+            return blank._replace(seg_start=np.array([0, 3, 3 + n]), ages=np.ones(A), h=h)
         if M is not None:
             segments.check_park(args(cap), M)
             with pytest.raises(ValueError, match=msg):

@@ -185,8 +185,9 @@ def test_the_park_cap_is_the_one_of_the_python_side(tmp_path, monkeypatch):
         monkeypatch.setattr(_lib, "SEGMENT_MAX_PARK", park)
         assert _lib.segment_refine_cap(h, A, R) == cap
 
-        def args(n):                                     # (what check_refine reads of check_args' tuple)
-            return (None, None, None, np.array([0, 3, 3 + n]), None, np.ones(A), h)
+        def args(n):                                     # (what check_refine reads of check_args' record)
+            blank = segments.Args(*[None] * len(segments.Args._fields))
+            return blank._replace(seg_start=np.array([0, 3, 3 + n]), ages=np.ones(A), h=h)
         assert segments.check_refine(args(cap), R) == R
         with pytest.raises(ValueError, match="a segment of %d cells: more than %d at" % (cap + 1, cap)):
             segments.check_refine(args(cap + 1), R)

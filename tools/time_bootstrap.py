@@ -51,13 +51,13 @@ def timing():
     ctx = _context(0)
     sargs = segments.check_args(z.shape, 1.0, cells, lab, ang, float(a.half), float(a.swath), ages, 1.0, 20, 1)
     # blocks of --block consecutive cells of each segment, handed over as CSR (random cells have no strike to cut along)
-    idx, sa, ca, seg_start, seg_label = sargs[:5]
+    idx, sa, ca, seg_start, seg_label = sargs.cells, sargs.sa, sargs.ca, sargs.seg_start, sargs.seg_label
     blk_start = np.unique(np.concatenate([np.arange(s0, s1, a.block) for s0, s1 in zip(seg_start[:-1], seg_start[1:])]
                                          + [[len(idx)]])).astype(np.int64)
     seg_blk_start = np.searchsorted(blk_start[:-1], seg_start).astype(np.int64)
 
     def boot(R):
-        return ctx.bootstrap_segments(idx, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, sargs[5], a.half, a.swath, 0, 1.0,
+        return ctx.bootstrap_segments(idx, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, sargs.ages, a.half, a.swath, 0, 1.0,
                                       20, 1, 5, R, 0.95, 0)[0]
     runs = {"fit_segments": lambda: segments._run(ctx, sargs, z.shape[1], False, False),
             "bootstrap_segments R = %d" % a.replicates: lambda: boot(a.replicates),

@@ -55,11 +55,11 @@ def main():
     sl.Matcher(sl.DEMGrid.from_array(z, 1.0))           # the DEM on the device: the routes without an upload
     ctx = _context(0)
     sargs = segments.check_args(z.shape, 1.0, cells, lab, ang, float(a.half), float(a.swath), ages, 1.0, 20, 1)
-    idx, sa, ca, seg_start, seg_label = sargs[:5]
+    idx, sa, ca, seg_start, seg_label = sargs.cells, sargs.sa, sargs.ca, sargs.seg_start, sargs.seg_label
 
     def strike(window, step):
         sws, lo, hi = windows(seg_start, window, step)
-        return lambda: ctx.fit_strike(idx, sa, ca, seg_start, seg_label, sws, lo, hi, sargs[5], a.half, a.swath, 0, 1.0, 1.0,
+        return lambda: ctx.fit_strike(idx, sa, ca, seg_start, seg_label, sws, lo, hi, sargs.ages, a.half, a.swath, 0, 1.0, 1.0,
                                       20, 1)[0]
     full = "fit_along_strike window %d step %d" % (a.window, a.step)
     dense = "fit_along_strike window %d step 1" % a.window
