@@ -254,7 +254,7 @@ int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const d
  *              value) and loading a DEM drop what was kept.  Default 0 in the library; the
  *              Python host sets 8192.
  *   "fit_chunk"  n > 0: every fit call (sc_fit_profiles*, sc_lateral_offsets*, sc_fit_segments*,
- *              sc_bootstrap_segments*, sc_fit_strike*, sc_snr_surface) closes a chunk of its work at n cells
+ *              sc_bootstrap_segments*, sc_fit_strike*, sc_strike_bootstrap*, sc_snr_surface) closes a chunk of its work at n cells
  *              where its built-in bound (2^19 cells, the parked bytes of SC_SEGMENT_MAX_PARK, 256 MiB of
  *              cubes) lies higher; it never raises one.  The per-cell calls launch on at most n cells; the
  *              segment calls take whole segments while their cells stay within n, a longer segment alone
@@ -693,6 +693,63 @@ int sc_fit_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long l
                       const long long* seg_win_start, const long long* win_lo, const long long* win_hi, long long NW,
                       const double* ages, int A, int h, int w, int D, double de, double delta, int min_samples,
                       int min_profiles, sc_strike_fit* out_rows, double* out_sse);
+
+/*
+ * Intervals per station (docs/strike.md): sc_bootstrap_segments' block bootstrap in every window of sc_fit_strike.
+ *   hand-over   the cells, the stations and the windows [win_lo, win_hi) are sc_fit_strike's, unchanged; stage one is
+ *               unchanged; with a shift the parked shifts are stage one's and are not re-fitted
+ *   blocks      of a window, whose cells are sorted by t: the block of a cell is floor((t_c - t_first) / block_length),
+ *               t_first the t of the window's first cell; the blocks that hold a cell are numbered along the strike, a
+ *               stretch without a cell is no block.  Cut by the caller in float64 and handed over as integers:
+ *               win_blk_start[NW + 1], CSR over blocks, 0 to NWB, and blk_hi[NWB], the end cell (an index into `cells`)
+ *               of every block - a window's first block begins at win_lo, every other where the one before ends, the
+ *               last ends at win_hi.  The library never compares floats.  A block whose cells have no usable profile
+ *               stays in the partition with terms (0, 0)
+ *   block terms (sum See_ci, sum Sep_ci) over the block's usable profiles in hand-over order: runs of 64 summed in
+ *               sequence from the first, then the run sums in sequence from the first
+ *   draws       sc_bootstrap_segments' generator keyed by label L and station: key = mix(seed ^ (L * 0x9E3779B97F4A7C15)
+ *               ^ (station * 0xD1B54A32D192ED03)), u = mix(key + ((r << 32) | k)), block = ((u >> 32) * nb) >> 32, all
+ *               modulo 2^64: station 0 has sc_bootstrap_segments' key.  Replicate 0 takes every block once
+ *   replicate, summary, status: sc_bootstrap_segments' rules per window - the failed rule, argmax_i Q_i with ties to the
+ *               smallest index (a NaN never wins), the ranks from an A-bin integer histogram, a_mean and a_sd in
+ *               replicate order, a_lo and a_hi by the same ranks over the sorted a.  Status 1: fewer than min_blocks
+ *               blocks, fewer than min_profiles usable profiles, n_ok = 0, or an empty window; otherwise 2 where
+ *               lo_index == 0, + 4 where hi_index == A - 1
+ * A window's block terms must fit 64 KiB: nb A 16 <= 65536, SC_ERR_UNSUPPORTED beyond.  R in 1..SC_BOOT_MAX_REPLICATES,
+ * 0 < level < 1, min_blocks >= 2, NW <= 2^31 - 1.  out_rows: NW rows; out_hist: NW x A int32 (the histogram of replicates
+ * 1..R) or NULL.  Per-replicate outputs are not built: they would be NW x (R + 1) values.  Refused before any device
+ * work: what sc_fit_strike refuses, block arrays that do not tile their windows exactly, R, level or min_blocks out of
+ * range.  No float atomics, no float sum across lanes: the same bytes on every run and for every "fit_chunk", and a
+ * segment's rows do not depend on the other segments of the call.  Timed as SC_K_PROFILE.
+ */
+typedef struct sc_strike_boot {
+    int32_t  label;
+    int32_t  station;         /* the window's number within its segment          */
+    int32_t  n_cells;         /* cells of the window                             */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n_blocks;        /* blocks of the window, empty ones included       */
+    int32_t  replicates;      /* R                                               */
+    int32_t  n_failed;        /* replicates of 1..R that failed                  */
+    int32_t  kt_index0;       /* replicate 0: every block once                   */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not bootstrapped), or 2 (lo_index == 0) + 4 (hi_index == A - 1) */
+    double   kt0, kt_lo, kt_hi;
+    double   a0;              /* replicate 0's amplitude                         */
+    double   a_mean, a_sd, a_lo, a_hi;
+} sc_strike_boot;
+int sc_strike_bootstrap(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                        const long long* seg_start, const int32_t* seg_label, long long S, const long long* seg_win_start,
+                        const long long* win_lo, const long long* win_hi, long long NW, const double* ages, int A, int h,
+                        int w, int D, double de, int min_samples, int min_profiles, const long long* win_blk_start,
+                        const long long* blk_hi, long long NWB, int min_blocks, int R, double level, uint64_t seed,
+                        sc_strike_boot* out_rows, int32_t* out_hist);
+int sc_strike_bootstrap_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                            const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                            long long S, const long long* seg_win_start, const long long* win_lo, const long long* win_hi,
+                            long long NW, const double* ages, int A, int h, int w, int D, double de, int min_samples,
+                            int min_profiles, const long long* win_blk_start, const long long* blk_hi, long long NWB,
+                            int min_blocks, int R, double level, uint64_t seed, sc_strike_boot* out_rows,
+                            int32_t* out_hist);
 
 /*
  * Strike-slip offsets across a trace (docs/lateral.md, scarplet_amd/csrc/sc_lateral.hip): at each of K cells two
@@ -1289,7 +1346,7 @@ int sc_get_template_sums(sc_ctx* ctx, int n, double* n_out, double* ts_out);
 #define SC_K_SETTLE      7      /* sc_settle_exact, sc_snr_surface: all their kernels as one bracket */
 #define SC_K_NOISE       8      /* sc_curvature_noise: all its kernels as one bracket */
 #define SC_K_TRACE       9      /* sc_trace_planes / sc_trace_result: their kernels before and after the read-back of K */
-#define SC_K_PROFILE     10     /* sc_fit_profiles* (_robust too), sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*: the table and every kernel of every chunk; sc_lateral_offsets*: the kernel of every chunk */
+#define SC_K_PROFILE     10     /* sc_fit_profiles* (_robust too), sc_fit_segments*, sc_bootstrap_segments*, sc_fit_strike*, sc_strike_bootstrap*: the table and every kernel of every chunk; sc_lateral_offsets*: the kernel of every chunk */
 #define SC_K_COUNT       11
 /* HIP-event timing of every launch on the context's stream. */
 int sc_profile(sc_ctx* ctx, int enable);

@@ -20,6 +20,7 @@ from scarplet_amd.profiles import fit_profiles  # noqa: F401
 from scarplet_amd.segments import fit_segments  # noqa: F401
 from scarplet_amd.bootstrap import bootstrap_segments  # noqa: F401
 from scarplet_amd.strike import fit_along_strike  # noqa: F401
+from scarplet_amd.strike_bootstrap import bootstrap_along_strike  # noqa: F401
 from scarplet_amd.surface import snr_surface  # noqa: F401
 from scarplet_amd.lateral import lateral_offsets  # noqa: F401
 from scarplet_amd.plotting import plot_results, Hillshade, hillshade  # noqa: F401

@@ -242,6 +242,19 @@ class sc_strike_fit(C.Structure):
 STRIKE_FIT_DTYPE = np.dtype(sc_strike_fit)
 
 
+class sc_strike_boot(C.Structure):
+    """One row of sc_strike_bootstrap / sc_strike_bootstrap_dem (docs/strike.md, "Intervals per station")."""
+    _fields_ = [("label", C.c_int32), ("station", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32),
+                ("n_blocks", C.c_int32), ("replicates", C.c_int32), ("n_failed", C.c_int32), ("kt_index0", C.c_int32),
+                ("lo_index", C.c_int32), ("hi_index", C.c_int32), ("status", C.c_int32),
+                ("kt0", C.c_double), ("kt_lo", C.c_double), ("kt_hi", C.c_double), ("a0", C.c_double),
+                ("a_mean", C.c_double), ("a_sd", C.c_double), ("a_lo", C.c_double), ("a_hi", C.c_double)]
+
+
+STRIKE_BOOT_DTYPE = np.dtype(sc_strike_boot)
+STRIKE_BOOT_LDS_TERMS = 65536                                          # SB_LDS_TERMS of sc_strike_bootstrap.hip
+
+
 class sc_lateral_fit(C.Structure):
     """One row of sc_lateral_offsets / sc_lateral_offsets_dem (docs/lateral.md)."""
     _fields_ = [("cell", C.c_int64), ("n", C.c_int32), ("lag", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32),
@@ -375,6 +388,10 @@ SIGNATURES = {
                 [_v, _v, _v, _dp]),
     # (seg_win_start, win_lo, win_hi, NW; then D, de, delta, min_samples, min_profiles)
     **_fit_pair("sc_fit_strike", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i], _STOP, [_i], _CELL_OUT),
+    # (the windows as sc_fit_strike; D, de, min_samples, min_profiles; win_blk_start, blk_hi, NWB; min_blocks, R, level, seed;
+    # rows, hist)
+    **_fit_pair("sc_strike_bootstrap", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i, _d, _i, _i], [_llp, _llp, _ll],
+                [_i, _i, _d, C.c_uint64], [_v, _v]),
     # (h, q0, q1, D: no age grid)
     **_fit_pair("sc_lateral_offsets", _CELLS, [_i, _i, _i, _i], _STOP, _CELL_OUT),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
@@ -915,6 +932,24 @@ class Context(object):
         self._fit_call("sc_fit_strike", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), ages,
                        [h, w, D, de, delta, min_samples, min_profiles, rows, sse])
         return rows, sse
+
+    # -- block-bootstrap intervals per station (docs/strike.md) --------------------------
+    def strike_bootstrap(self, cells, sa, ca, seg_start, seg_label, seg_win_start, win_lo, win_hi, win_blk_start, blk_hi,
+                         ages, h, w, D, de, min_samples, min_profiles, min_blocks, R, level, seed, hist=False, z=None):
+        """sc_strike_bootstrap on the context's DEM, or sc_strike_bootstrap_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, (NW, A) int32 histograms or None).  cells, seg_start, seg_win_start, win_lo, win_hi, win_blk_start and
+        blk_hi int64, seg_label int32, sa / ca / ages float64, all 1-D and C-contiguous; the cells grouped by segment and
+        sorted along its strike."""
+        A, S, NW = len(ages), len(seg_label), len(win_lo)
+        assert len(seg_win_start) == S + 1 and len(win_hi) == NW and len(win_blk_start) == NW + 1
+        for a in (win_blk_start, blk_hi):
+            assert a.dtype == np.int64 and a.ndim == 1 and a.flags.c_contiguous
+        rows = np.zeros(NW, dtype=STRIKE_BOOT_DTYPE)
+        hg = np.zeros((NW, A), dtype=np.int32) if hist else None
+        self._fit_call("sc_strike_bootstrap", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), ages,
+                       [h, w, D, de, min_samples, min_profiles, win_blk_start, blk_hi, len(blk_hi), min_blocks, R, level, seed,
+                        rows, hg])
+        return rows, hg
 
     # -- strike-slip offsets across a trace (docs/lateral.md) -------------------------------
     def lateral_offsets(self, cells, sa, ca, h, q0, q1, D, de, delta, min_samples, curve=False, z=None):

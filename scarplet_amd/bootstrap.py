@@ -72,6 +72,24 @@ def blocks_of(cells, nx, de, strike, seg_start, block_length):
     return np.floor((t - np.repeat(tmin, n)) / block_length).astype(np.int64)
 
 
+def check_resampling(de, block_length, replicates, level, seed, min_blocks):
+    """The rules of the resampling, shared with ``strike_bootstrap``: ``block_length`` required, a finite number of at
+    least the cell size ``de``; ``replicates`` an integer in 1..4096, ``min_blocks`` one of at least 2, ``seed`` one in
+    0..2^64 - 1; ``level`` strictly between 0 and 1.  Returns (block_length, R, level, seed, min_blocks)."""
+    if block_length is None:
+        raise ValueError("block_length is required: the length of a block along the strike, in data units")
+    bl = profiles._number(block_length, "block_length")
+    if bl < de:
+        raise ValueError("block_length must be at least the cell size %r, got %r" % (de, block_length))
+    R = _integer(replicates, "replicates", 1, _lib.BOOT_MAX_REPLICATES)
+    mb = _integer(min_blocks, "min_blocks", 2)
+    sd = _integer(seed, "seed", 0, MASK64)
+    lv = profiles._number(level, "level")
+    if not 0.0 < lv < 1.0:
+        raise ValueError("level must lie strictly between 0 and 1, got %r" % (level,))
+    return bl, R, lv, sd, mb
+
+
 def check_args(shape, de, cells, labels, angle, half_length, swath, block_length, replicates, level, seed, ages,
                min_samples, min_profiles, min_blocks, max_shift, seg_strike=None):
     """What the library takes, validated and normalised; ValueError otherwise.  The arguments shared with
@@ -85,17 +103,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
     idx, sa, ca, seg_start, seg_label, de, h, ms = s.cells, s.sa, s.ca, s.seg_start, s.seg_label, s.de, s.h, s.min_samples
     D = profiles.check_shift(max_shift, False, de, h, ms)
     D = 0 if D is None else D
-    if block_length is None:
-        raise ValueError("block_length is required: the length of a block along the strike, in data units")
-    bl = profiles._number(block_length, "block_length")
-    if bl < de:
-        raise ValueError("block_length must be at least the cell size %r, got %r" % (de, block_length))
-    R = _integer(replicates, "replicates", 1, _lib.BOOT_MAX_REPLICATES)
-    mb = _integer(min_blocks, "min_blocks", 2)
-    sd = _integer(seed, "seed", 0, MASK64)
-    lv = profiles._number(level, "level")
-    if not 0.0 < lv < 1.0:
-        raise ValueError("level must lie strictly between 0 and 1, got %r" % (level,))
+    bl, R, lv, sd, mb = check_resampling(de, block_length, replicates, level, seed, min_blocks)
     ny, nx = (int(v) for v in shape)
     if seg_strike is None:
         pick = s.kept[s.order]

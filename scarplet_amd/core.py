@@ -1011,6 +1011,20 @@ class Matcher(object):
                                     delta, min_samples, min_profiles, max_shift)
         return st._run(self.ctx, args, where, return_curve)
 
+    def bootstrap_along_strike(self, traces, half_length, window, block_length, step=None, swath=0, replicates=1000,
+                               level=0.95, seed=0, ages=None, min_samples=4, min_profiles=1, min_blocks=5, max_shift=None,
+                               return_hist=False, strike="cell"):
+        """``sl.bootstrap_along_strike`` on the DEM this matcher holds on the device (docs/strike.md) - no upload: a
+        block-bootstrap interval of the offset and the age of every segment of ``traces`` at every station along its
+        strike.  ``strike`` chooses the profiles' orientation as in ``fit_along_strike``.  The bytes are those of
+        ``sl.bootstrap_along_strike`` on the same data and orientations."""
+        from scarplet_amd import strike_bootstrap as sb
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "bootstrap_along_strike")
+        args, where = sb.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, swath, window, step,
+                                    block_length, replicates, level, seed, ages, min_samples, min_profiles, min_blocks,
+                                    max_shift)
+        return sb._run(self.ctx, args, where, return_hist)
+
     def lateral_offsets(self, traces_or_cells, half_length, near, far, max_offset, delta=1.0, min_samples=8,
                         return_curve=False, angle=None, strike="segment"):
         """``sl.lateral_offsets`` on the DEM this matcher holds on the device (docs/lateral.md) - no upload: the

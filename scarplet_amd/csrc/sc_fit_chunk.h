@@ -1,7 +1,7 @@
 // Where a fit driver closes a chunk (sc_set_option "fit_chunk") and what the host computes of a chunk of whole segments,
 // decided in one place: plain C++ with nothing of HIP in it, so that tests/fit_chunk_check.cpp enumerates it on the host.
 // The per-cell calls launch on at most sc_fit_chunk_bound(their chunk, n) cells; the segment calls (sc_fit_segments*,
-// sc_bootstrap_segments, sc_fit_along_strike) take whole segments up to sc_fit_chunk_end, and sc_sg_chunks (sc_segment.hip)
+// sc_bootstrap_segments, sc_fit_along_strike, sc_strike_bootstrap) take whole segments up to sc_fit_chunk_end, and sc_sg_chunks (sc_segment.hip)
 // sends up the chunk's arrays as they are made here.
 #pragma once
 #include <stddef.h>

@@ -207,6 +207,9 @@ struct sc_ctx {
     // sc_fit_strike*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR array of
     // segments over windows, Spp of every cell, the rows and the curves
     DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
+    // sc_strike_bootstrap*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR arrays of
+    // segments over windows and of windows over blocks, the end cell of every block, the rows and the histograms
+    DevBuf sb_win, sb_wstart, sb_wblk, sb_bhi, sb_rows, sb_hist;
     // sc_window_runs: the host's copy of the run table's offsets (uploaded asynchronously)
     std::vector<unsigned> h_soff;
     // sc_snr_surface: the call's tables (sums, run offsets, union runs), and per chunk of cells the cell list, the two

@@ -68,6 +68,14 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
     and the windows cut (``windows_of``) along the axial mean of each segment's angles.  Returns (cells, sa, ca, seg_start,
     seg_label, seg_win_start, win_lo, win_hi, ages, h, w, D, de, delta, min_samples, min_profiles) and (centre, row,
     col): each window's ``u_k`` and the means of its cells' rows and columns (NaN for an empty window)."""
+    return handover(shape, de, cells, labels, angle, half_length, swath, window, step, ages, delta, min_samples, min_profiles,
+                    max_shift)[:2]
+
+
+def handover(shape, de, cells, labels, angle, half_length, swath, window, step, ages, delta, min_samples, min_profiles,
+             max_shift):
+    """``check_args`` and, third, the along-strike coordinate ``t`` of every cell handed over (``windows_of``'s), which
+    ``strike_bootstrap`` cuts the blocks of a window from."""
     # (the park is checked as sc_fit_segments_shift counts it)
     s = segments.check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=True)
     idx, sa, ca, seg_start, de = s.cells, s.sa, s.ca, s.seg_start, s.de
@@ -86,7 +94,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
     pick = s.kept[s.order]
     a = profiles._angles_of(angle, profiles._cells_of(cells, ny, nx), ny, nx)[pick]
     strike = bootstrap.segment_strikes(a, seg_start)
-    by, _, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, win, stp)
+    by, t, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, win, stp)
     idx, sa, ca = idx[by], sa[by], ca[by]
     if len(centre) > 2 ** 31 - 1:
         raise ValueError("%d windows: more than 2^31 - 1" % len(centre))
@@ -99,7 +107,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, window, step
         col = np.where(cnt > 0, (cc[win_hi] - cc[win_lo]) / cnt, np.nan)
     return (Args(np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, s.seg_label,
                  seg_win_start, win_lo, win_hi, s.ages, s.h, s.w, D, de, s.delta, s.min_samples, s.min_profiles),
-            (centre, row, col))
+            (centre, row, col), t)
 
 
 def fit_along_strike(data, cells, labels, angle, half_length, swath=0, window=None, step=None, ages=None, delta=1.0,
