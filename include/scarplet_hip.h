@@ -262,6 +262,10 @@ int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const d
  *              whole batches of eight cells.  An integer >= 0, finite; 0 (default): the built-in bounds
  *              alone.  Every output byte is the same for every value: the option exists so that the
  *              tests run the chunks' hand-over on small inputs (tests/test_gpu_fit_chunks.py).
+ *   "channel_terms"  1 (default): sc_channel_profiles* forms what a pair's column leaves against (1, s) on a
+ *              profile without a missing point once per call, and such a profile runs two sweeps per pair; 0: every
+ *              profile runs the four sweeps.  0 or 1.  Every output byte is the same either way: the option exists so
+ *              that a test compares the two routes (tests/test_gpu_channels.py).
  */
 int sc_set_option(sc_ctx* ctx, const char* name, double value);
 
@@ -1005,6 +1009,48 @@ int sc_fit_profiles_ramp_dem(sc_ctx* ctx, const double* z, int ny, int nx, const
                              const double* ca, long long K, const double* ages, int A, int h, int w, int M, int mode,
                              double slope, double de, double delta, int min_samples, sc_profile_ramp_fit* out_rows,
                              double* out_sse, int8_t* out_width);
+
+/*
+ * Channel depth and width across a trace (docs/channels.md): what sc_fit_profiles is to a Scarp search, for a Channel
+ * search.  The Ricker window W = (1 - 2 u^2) exp(-u^2), u = pi f x, is -1 / (2 (pi f)^2) times the second derivative of
+ * exp(-(pi f x)^2), so the elevation model of that search is a Gaussian trough across the strike,
+ *   z(s) = c0 + b s + a exp(-(pi f (s - d de))^2),   d = -D..D,
+ * a < 0 for a channel and a > 0 for a ridge; f is the search's own parameter and -2 (pi f)^2 a its amplitude.
+ *   samples  as sc_fit_profiles: the same points, validity rule, n, n_neg, n_pos and min_samples rule
+ *   table    G over x = -(h + D)..(h + D) and the F frequencies, frequency-minor: with X = (double)x de and
+ *            u = (pi f_i) X the entry is exp(-(u u)); the column of shift d is row j - d
+ *   fit      for each pair (frequency i, shift d) the four passes of sc_fit_profiles with that column; n, sbar, pbar, Sss,
+ *            beta and p2 depend on neither and are formed once.  A pair whose See is not > 0 - no entry of its column
+ *            on the profile's points is above 0 - or whose sse is NaN never wins
+ *   choice   d_i = argmin_d sse_id in the order 0, -1, +1, -2, ..., the first smallest winning; sse*_i = sse_{i, d_i}
+ *            (NaN, with d_i = 0, where no pair of the frequency can win); kt_index = argmin_i sse*_i, ties to the
+ *            smaller index, a NaN counting as +inf; dof = n - 3 - (D > 0), and dof < 1 gives status 1; rmse =
+ *            sqrt(sse / dof), thr = sse_min (1 + delta / dof), lo_index / hi_index walk along sse* and a NaN ends a walk.
+ *            Status 1, 2 and 4 as sc_fit_profiles; 8: |shift_index| == D with D > 0; 1 | 32: no frequency has a pair
+ *            that can win, and the row is that of a cell that is not fitted
+ * The rows are sc_profile_shift_fit with kt, kt_lo and kt_hi carrying f, and kt_index, lo_index and hi_index indices of
+ * the frequencies.  out_rows: K rows in the order of the cells; out_sse: K x F float64 (sse*) or NULL; out_shift: K x F
+ * int8 (d_i, 0 in the rows of cells with status & 1) or NULL.  Refused before any device work: what sc_fit_profiles_shift
+ * refuses with the frequencies for the ages - finite, > 0, strictly increasing (SC_ERR_INVALID), F >
+ * SC_CHANNEL_MAX_FREQS (SC_ERR_UNSUPPORTED) - and (pi f) de > SC_CHANNEL_MAX_ARG (SC_ERR_INVALID): a Gaussian narrower
+ * than anything a grid shows, whose neighbouring table entries leave the normal range.
+ * For a profile without a missing point ebar, gamma and See of a pair depend on (i, d, h, de) alone: with option
+ * "channel_terms" 1 (default) they are formed once per call by the loops of the fit on a profile of zeros, and such a
+ * profile runs two sweeps per pair for four.  The same operations in the same order: every output byte is the same with
+ * the option 0.  No atomics, no float sum across lanes: the same bytes on every run, for every order of the cells and
+ * for every "fit_chunk".  The buffers are those of sc_fit_profiles_shift and one for the terms.  Timed as SC_K_PROFILE.
+ */
+#define SC_CHANNEL_MAX_FREQS 64
+#define SC_CHANNEL_MAX_ARG   6.0
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_channel_profiles(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                        const double* frequencies, int F, int h, int w, int D, double de, double delta, int min_samples,
+                        sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_channel_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                            const double* ca, long long K, const double* frequencies, int F, int h, int w, int D,
+                            double de, double delta, int min_samples, sc_profile_shift_fit* out_rows, double* out_sse,
+                            int8_t* out_shift);
 
 /*
  * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and

@@ -98,6 +98,7 @@ class sc_profile_shift_fit(C.Structure):
 
 
 PROFILE_SHIFT_DTYPE = np.dtype(sc_profile_shift_fit)
+CHANNEL_MAX_FREQS = 64                                                 # SC_CHANNEL_MAX_FREQS (the rows of sc_channel_profiles are these)
 
 
 class sc_profile_robust_fit(C.Structure):
@@ -394,6 +395,8 @@ SIGNATURES = {
                 [_i, _i, _d, C.c_uint64], [_v, _v]),
     # (h, q0, q1, D: no age grid)
     **_fit_pair("sc_lateral_offsets", _CELLS, [_i, _i, _i, _i], _STOP, _CELL_OUT),
+    # (sc_fit_profiles_shift's list, the frequencies and F for the ages and A)
+    **_fit_pair("sc_channel_profiles", _CELLS, _AGES, _HW, [_i], _STOP, _CELL_OUT, [_v]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -507,7 +510,7 @@ class Context(object):
 
     def set_option(self, name, value):
         """Engine options (include/scarplet_hip.h sc_set_option): 'kappa',
-        'variant', 'y_gb', 'spectra_mb', 'fuse_fwd', 'fit_chunk'."""
+        'variant', 'y_gb', 'spectra_mb', 'fuse_fwd', 'fit_chunk', 'channel_terms'."""
         self._check(self.lib.sc_set_option(self._h, name.encode(), float(value)),
                     "sc_set_option(%s)" % name)
         if name == "spectra_mb":
@@ -792,6 +795,20 @@ class Context(object):
         plane = np.zeros((K, A), dtype=np.int8) if shift_plane else None
         self._fit_call("sc_fit_profiles_shift", z, (cells, sa, ca), None, ages,
                        [h, w, shift, de, delta, min_samples, rows, sse, plane])
+        return rows, sse, plane
+
+    def channel_profiles(self, cells, sa, ca, frequencies, h, w, D, de, delta, min_samples, curve=False, shift_plane=False,
+                         z=None):
+        """sc_channel_profiles on the context's DEM, or sc_channel_profiles_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, (K, F) float64 sse* curves or None, (K, F) int8 shifts or None).  cells int64, sa / ca / frequencies float64,
+        all 1-D and C-contiguous; ``D``: the range of the centre shift in cells.  The rows are sc_profile_shift_fit, kt
+        carrying f (docs/channels.md)."""
+        K, F = len(cells), len(frequencies)
+        rows = np.zeros(K, dtype=PROFILE_SHIFT_DTYPE)
+        sse = np.empty((K, F), dtype=np.float64) if curve else None
+        plane = np.zeros((K, F), dtype=np.int8) if shift_plane else None
+        self._fit_call("sc_channel_profiles", z, (cells, sa, ca), None, frequencies,
+                       [h, w, D, de, delta, min_samples, rows, sse, plane])
         return rows, sse, plane
 
     @staticmethod

@@ -949,6 +949,19 @@ class Matcher(object):
         return profiles._run(self.ctx, args, self.nx, return_curve, label=label, return_shift=return_shift,
                              return_width=return_width, **opts._asdict())
 
+    def fit_channels(self, traces_or_cells, half_length, frequencies, swath=0, max_shift=0, delta=1.0, min_samples=4,
+                     return_curve=False, return_shift=False, angle=None):
+        """``sl.fit_channels`` on the DEM this matcher holds on the device (docs/channels.md) - no upload.  Given the
+        ``Traces`` of ``extract_traces`` it fits the cells of the segments (``labels > 0``, row-major order) with the angle
+        plane of this matcher's result and adds a ``label`` column; given cells (as ``sl.fit_channels`` takes them) it
+        reads that plane at the cells unless ``angle`` says otherwise.  The bytes are those of ``sl.fit_channels`` on
+        the same data."""
+        from scarplet_amd import channels
+        cells, label, angle, _ = _trace_cells(self, traces_or_cells, "cell", "fit_channels", cells_too=True, angle=angle)
+        args = channels.check_args((self.ny, self.nx), self.de, cells, angle, half_length, frequencies, swath, max_shift,
+                                   delta, min_samples)
+        return channels._run(self.ctx, args, self.nx, return_curve, return_shift, label=label)
+
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
         every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within

@@ -48,7 +48,7 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab, &c->pf_terms,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift, &c->sg_ftab, &c->sg_width, &c->sg_fine, &c->sq_wt, &c->sq_state, &c->sq_hist, &c->sq_a,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,
@@ -195,6 +195,9 @@ extern "C" int sc_set_option(sc_ctx* ctx, const char* name, double value) {
     } else if (!strcmp(name, "fit_chunk")) {
         if (!(value >= 0.0 && std::isfinite(value))) return sc_fail(ctx, SC_ERR_INVALID, "fit_chunk must be >= 0 and finite");
         ctx->fit_chunk = value >= 0x1p62 ? (1ll << 62) : (long long)value;       // (it only ever lowers a built-in bound)
+    } else if (!strcmp(name, "channel_terms")) {
+        if (!(value == 0.0 || value == 1.0)) return sc_fail(ctx, SC_ERR_INVALID, "channel_terms must be 0 or 1");
+        ctx->channel_terms = (int)value;
     } else {
         return sc_fail(ctx, SC_ERR_INVALID, "unknown option '%s'", name);
     }
@@ -237,7 +240,7 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->yw, &c->ym, &c->tiles, &c->halo_z, &c->halo_stage, &c->res, &c->sib_buf, &c->dwin, &c->spans, &c->res_stats, &c->digest, &c->split_s, &c->split_a, &c->split_i,
                      &c->near, &c->near_ev, &c->score, &c->score_w, &c->score_abc, &c->st_slot, &c->st_work, &c->st_pairs, &c->st_patch, &c->st_spans, &c->snap, &c->xch, &c->xch_cnt,
                      &c->tr_planes, &c->tr_thin, &c->tr_par, &c->tr_lab, &c->tr_cnt, &c->tr_bsum, &c->tr_tot, &c->tr_sort, &c->tr_hist, &c->tr_rbsum, &c->tr_seg,
-                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab,
+                     &c->pf_z, &c->pf_cells, &c->pf_dir, &c->pf_ages, &c->pf_tab, &c->pf_rows, &c->pf_sse, &c->pf_shift, &c->pf_wt, &c->pf_ftab, &c->pf_terms,
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift, &c->sg_ftab, &c->sg_width, &c->sg_fine, &c->sq_wt, &c->sq_state, &c->sq_hist, &c->sq_a,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows,

@@ -153,6 +153,7 @@ struct sc_ctx {
     double y_gb = 0.0;         // sc_set_option "y_gb": memory budget of the I1 -> I2 hand-off (0: automatic)
     int sib = 0;               // sc_set_option "sib": sibling rendezvous, bit 0 row pass, bit 1 column pass (sc_fft.hip SibSync)
     long long fit_chunk = 0;   // sc_set_option "fit_chunk": cells at which every fit driver closes a chunk (0: the built-in bounds alone)
+    int channel_terms = 1;     // sc_set_option "channel_terms": sc_channel_profiles* takes a complete profile's column terms from one table per call
     DevBuf split_s, split_a, split_i;   // scratch records of a split row pass (k_inv_rows_fast SPLITK, k_merge_split)
     DevBuf sib_buf;
     uint32_t sib_epoch = 0;
@@ -185,6 +186,7 @@ struct sc_ctx {
     DevBuf pf_shift;           // sc_fit_profiles_shift*: the chosen shift of every (cell, age) of a chunk, int8
     DevBuf pf_wt;              // sc_fit_profiles_robust*: the uploaded weight plane (the rest are the buffers above)
     DevBuf pf_ftab;            // sc_fit_profiles_ramp*: the table of F over x = -(h + M)..(h + M)
+    DevBuf pf_terms;           // sc_channel_profiles*: a profile of zeros, then ebar, gamma and See of every (shift, frequency) pair
     // (sc_lateral_offsets* borrows pf_z, pf_cells, pf_dir, pf_rows and pf_sse: its DEM, stations, rows and mse curves)
     // sc_fit_segments*: the call's own buffers - an uploaded DEM (the _dem call), ages and the erf table; per chunk of
     // whole segments the cells, (sa, ca), each cell's segment, the CSR arrays of cells and of 64-profile blocks, the

@@ -26,3 +26,20 @@ def synthetic_scarp(n, seed=20260101, kt0=10.0, b=0.01, sigma=0.05,
     rng = np.random.default_rng(seed)
     z += sigma * rng.standard_normal((ny, n))
     return DEMGrid.from_array(z.astype(dtype), de, de)
+
+
+def synthetic_channel(n, seed=20260101, f0=0.035, depth=1.0, b=0.01, sigma=0.05,
+                      theta=0.2, de=1.0, dtype=np.float32, ny=None):
+    """n x n (or ny x n) grid: z = -depth exp(-(pi f0 yrot)^2) + b*yrot + noise -
+    the Gaussian trough of which the Channel template (Ricker, frequency f0) is
+    the curvature - on synthetic_scarp's line, with its noise draw and its
+    float32 storage (docs/channels.md).  f0 = 0.035: sigma = 6.4 cells."""
+    ny = n if ny is None else ny
+    x = np.linspace(-n / 2, n / 2, num=n, dtype=np.float64)
+    y = np.linspace(-ny / 2, ny / 2, num=ny, dtype=np.float64)
+    th = np.pi / 2 - theta
+    yrot = -x[np.newaxis, :] * np.sin(th) + y[:, np.newaxis] * np.cos(th)
+    z = -depth * np.exp(-(np.pi * f0 * yrot) ** 2) + b * yrot
+    rng = np.random.default_rng(seed)
+    z += sigma * rng.standard_normal((ny, n))
+    return DEMGrid.from_array(z.astype(dtype), de, de)
