@@ -1053,6 +1053,69 @@ int sc_channel_profiles_dem(sc_ctx* ctx, const double* z, int ny, int nx, const 
                             int8_t* out_shift);
 
 /*
+ * One channel width per reach (docs/channels.md, "One width per reach"): what sc_fit_segments_shift is to
+ * sc_fit_profiles_shift, for sc_channel_profiles.  The cells, (sa, ca), the CSR array seg_start, the labels, h, w,
+ * min_profiles and the order of the outputs are sc_fit_segments'; the frequencies, D and their limits are
+ * sc_channel_profiles'.
+ *   samples  a profile is cut as sc_channel_profiles cuts it and is usable with min_samples valid points on either side
+ *            of j = 0; n is the pooled count of valid points over the usable profiles, n_profiles their number
+ *   stage    every usable profile c takes at every frequency i the single-profile choice of sc_channel_profiles: d_ci over
+ *            d = -D..D in the order 0, -1, +1, ..., the first smallest sse winning and a dead pair never; with it sse*_ci,
+ *            a_ci, b_ci, c0_ci and the orthogonalised terms ebar, gamma, See, Sep at d_ci - the bits sc_channel_profiles
+ *            forms, on either of its routes (option "channel_terms").  A frequency with no live pair in profile c has NaN
+ *            there and d_ci = 0
+ *   mode     SC_CHANNEL_DEPTH_PROFILE: the frequency is the reach's; depth, intercept, slope and centre are each profile's
+ *            own.  sse_i = sum_c sse*_ci, the row's a is abar_i = (sum_c a_ci) / n_profiles at the best frequency, dof =
+ *            n - (3 + (D > 0)) n_profiles.
+ *            SC_CHANNEL_DEPTH_SEGMENT: the fixed-effects fit of sc_fit_segments_shift on the Gaussian column.  a_i =
+ *            (sum_c Sep_ci) / (sum_c See_ci), b_ci and c0_ci follow, sse_ci is that of the explicit residuals with the
+ *            column at d_ci, sse_i = sum_c sse_ci, dof = n - 2 n_profiles - 1 - (D > 0 ? n_profiles : 0); a frequency whose
+ *            sum of See is not > 0 is dead
+ *   sums     over the usable profiles in input order: blocks of 64 in sequence from the first term, then the block sums in
+ *            sequence; one profile is no addition at all.  NaN propagates: a frequency that is dead in one usable profile
+ *            of the reach is dead for the reach
+ *   choice   fitted when n_profiles >= min_profiles and dof >= 1, else status 1, indices -1, NaN floats.  kt_index = argmin
+ *            sse_i, ties to the smaller index, a NaN counting as +inf; rmse = sqrt(sse / dof), thr = sse_min (1 + delta /
+ *            dof); lo_index / hi_index walk along the curve and a NaN ends a walk.  Status 2 / 4: the interval is open
+ *            below / above; 8: a usable profile has |d_ci| == D at the best frequency, D > 0; 1 | 32: every frequency is
+ *            dead, and the row is that of a reach that is not fitted
+ * The rows are sc_segment_fit with kt, kt_lo and kt_hi carrying f, and kt_index, lo_index and hi_index indices of the
+ * frequencies.  A reach of one usable profile returns, in both modes, the kt_index, lo_index, hi_index, status, a, sse and
+ * rmse of sc_channel_profiles for that cell, and its b, c0 and shift_index in the cell table, bit for bit.  out_rows: S
+ * rows; out_cells: K cells in the order of the cells, or NULL; out_sse: S x F float64, the pooled curves, or NULL;
+ * out_shift: K x F int8, d_ci of every USABLE cell whether or not its reach is fitted, 0 in the rows of the others, or NULL.
+ * The park per cell is SC_CHANNEL_SEGMENT_PARK(h, F) bytes in both modes - sc_fit_segments_shift's - counted against
+ * SC_SEGMENT_MAX_PARK: a call runs in chunks of whole reaches, and a single reach that needs more is SC_ERR_UNSUPPORTED.
+ * Refused before any device work: what sc_fit_segments_shift refuses with the frequencies for the ages, what
+ * sc_channel_profiles refuses of the frequencies (SC_ERR_INVALID; F > SC_CHANNEL_MAX_FREQS: SC_ERR_UNSUPPORTED; (pi f) de >
+ * SC_CHANNEL_MAX_ARG: SC_ERR_INVALID), and a mode that is neither of the two (SC_ERR_INVALID).  No atomics, no float sum
+ * across lanes: the same bytes on every run, for every "fit_chunk" and for whole reaches handed over in any order.  Timed as
+ * SC_K_PROFILE.
+ */
+#define SC_CHANNEL_DEPTH_PROFILE 0
+#define SC_CHANNEL_DEPTH_SEGMENT 1
+#define SC_CHANNEL_SEGMENT_PARK(h, F) (8 * ((2 * (h) + 1) + 4 * (F)) + (F))
+typedef struct sc_channel_segment_cell {
+    int64_t  cell;            /* the input cell                                  */
+    int32_t  used;            /* 1: a usable profile                             */
+    int32_t  n;               /* valid points of the profile                     */
+    double   a, b, c0, sse;   /* at the reach's best frequency (a: the profile's own, or the reach's in segment mode); NaN
+                                 where not used or the reach is not fitted       */
+    int32_t  shift_index;     /* d_ci at the reach's best frequency (0 where b is NaN) */
+} sc_channel_segment_cell;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_channel_segments(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                        const long long* seg_start, const int32_t* seg_label, long long S, const double* frequencies, int F,
+                        int h, int w, int D, int mode, double de, double delta, int min_samples, int min_profiles,
+                        sc_segment_fit* out_rows, sc_channel_segment_cell* out_cells, double* out_sse, int8_t* out_shift);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_channel_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                            const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                            long long S, const double* frequencies, int F, int h, int w, int D, int mode, double de,
+                            double delta, int min_samples, int min_profiles, sc_segment_fit* out_rows,
+                            sc_channel_segment_cell* out_cells, double* out_sse, int8_t* out_shift);
+
+/*
  * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and
  * after it R levels of 64 candidate ages of the cell's OWN bracket - for the minimum and for either end of the interval.
  * The samples, the validity rule, the min_samples rule, the orthogonalised fit and the explicit-residual sse are those of

@@ -163,6 +163,26 @@ class sc_segment_shift_cell(C.Structure):
 SEGMENT_SHIFT_CELL_DTYPE = np.dtype(sc_segment_shift_cell)
 
 
+class sc_channel_segment_cell(C.Structure):
+    """One cell of the cell table of sc_channel_segments / sc_channel_segments_dem (docs/channels.md)."""
+    _fields_ = [("cell", C.c_int64), ("used", C.c_int32), ("n", C.c_int32),
+                ("a", C.c_double), ("b", C.c_double), ("c0", C.c_double), ("sse", C.c_double), ("shift_index", C.c_int32)]
+
+
+CHANNEL_SEGMENT_CELL_DTYPE = np.dtype(sc_channel_segment_cell)
+CHANNEL_DEPTH_PROFILE, CHANNEL_DEPTH_SEGMENT = 0, 1                    # SC_CHANNEL_DEPTH_*
+
+
+def channel_segment_park(h, n_freqs):
+    """SC_CHANNEL_SEGMENT_PARK: the bytes sc_channel_segments parks per cell, in both modes."""
+    return 8 * ((2 * h + 1) + 4 * n_freqs) + n_freqs
+
+
+def channel_segment_cap(h, n_freqs):
+    """The cells of one reach the park of sc_channel_segments holds."""
+    return SEGMENT_MAX_PARK // channel_segment_park(h, n_freqs)
+
+
 class sc_segment_ramp_fit(C.Structure):
     """One row of sc_fit_segments_ramp / sc_fit_segments_ramp_dem: sc_segment_fit, then the half-width of the best age."""
     _fields_ = sc_segment_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
@@ -397,6 +417,8 @@ SIGNATURES = {
     **_fit_pair("sc_lateral_offsets", _CELLS, [_i, _i, _i, _i], _STOP, _CELL_OUT),
     # (sc_fit_profiles_shift's list, the frequencies and F for the ages and A)
     **_fit_pair("sc_channel_profiles", _CELLS, _AGES, _HW, [_i], _STOP, _CELL_OUT, [_v]),
+    # (sc_fit_segments_shift's list with the depth mode behind D)
+    **_fit_pair("sc_channel_segments", _CELLS, _SEGS, _AGES, _HW, [_i, _i], _STOP, [_i], _SEG_OUT, [_v]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -810,6 +832,21 @@ class Context(object):
         self._fit_call("sc_channel_profiles", z, (cells, sa, ca), None, frequencies,
                        [h, w, D, de, delta, min_samples, rows, sse, plane])
         return rows, sse, plane
+
+    def channel_segments(self, cells, sa, ca, seg_start, seg_label, frequencies, h, w, D, mode, de, delta, min_samples,
+                         min_profiles, cell_table=False, curve=False, shift_plane=False, z=None):
+        """sc_channel_segments on the context's DEM, or sc_channel_segments_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, cell table or None, (S, F) float64 pooled curves or None, (K, F) int8 shifts or None).  The arrays as
+        fit_segments takes them, the cells grouped by reach; ``D``: the range of the centre shift in cells; ``mode``:
+        CHANNEL_DEPTH_PROFILE or CHANNEL_DEPTH_SEGMENT.  The rows are sc_segment_fit, kt carrying f (docs/channels.md)."""
+        K, F, S = len(cells), len(frequencies), len(seg_label)
+        rows = np.zeros(S, dtype=SEGMENT_FIT_DTYPE)
+        tab = np.zeros(K, dtype=CHANNEL_SEGMENT_CELL_DTYPE) if cell_table else None
+        sse = np.empty((S, F), dtype=np.float64) if curve else None
+        plane = np.zeros((K, F), dtype=np.int8) if shift_plane else None
+        self._fit_call("sc_channel_segments", z, (cells, sa, ca), (seg_start, seg_label), frequencies,
+                       [h, w, D, mode, de, delta, min_samples, min_profiles, rows, tab, sse, plane])
+        return rows, tab, sse, plane
 
     @staticmethod
     def _check_weights(weights, z):

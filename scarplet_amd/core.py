@@ -962,6 +962,21 @@ class Matcher(object):
                                    delta, min_samples)
         return channels._run(self.ctx, args, self.nx, return_curve, return_shift, label=label)
 
+    def fit_channel_segments(self, traces, half_length, frequencies, swath=0, max_shift=0, depth="profile", delta=1.0,
+                             min_samples=4, min_profiles=1, return_cells=False, return_curve=False, return_shift=False,
+                             strike="cell"):
+        """``sl.fit_channel_segments`` on the DEM this matcher holds on the device (docs/channels.md, "One width per reach")
+        - no upload: one width, one interval and one row per segment of ``traces`` (the ``Traces`` of ``extract_traces``),
+        fitted jointly to the profiles of all its cells.  ``strike`` chooses the profiles' orientation as in
+        ``fit_segments``: ``"cell"`` the orientation this matcher's result has at the cell, ``"segment"`` the segment's
+        ``strike`` from the table - parallel profiles.  The bytes are those of ``sl.fit_channel_segments`` on the same
+        data."""
+        from scarplet_amd import channel_segments
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "fit_channel_segments")
+        args = channel_segments.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, frequencies, swath,
+                                           max_shift, depth, delta, min_samples, min_profiles)
+        return channel_segments._run(self.ctx, args, self.nx, return_cells, return_curve, return_shift)
+
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
         every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within

@@ -4,7 +4,8 @@
 // elevation model it assumes is a Gaussian trough across the strike,
 //   z(s) = c0 + b s + a exp(-(pi f (s - d de))^2),   a < 0: a channel, a > 0: a ridge
 // - linear in (c0, b, a) for a fixed (frequency f, centre shift d), which is the structure sc_fit_profiles_shift fits.
-// The pieces are those of sc_fit.h; the search is written here because a pair can be dead (ch_search).
+// The pieces are those of sc_fit.h; the search has its own text because a pair can be dead (ch_search, sc_channel.h,
+// which the joint fit of sc_channel_segment.hip shares with this file).
 //   k_ch_table   G over x = -(h + D)..(h + D) and the frequencies, frequency-minor: one exp per entry
 //   k_ch_terms   what a pair's column leaves against (1, s) on a profile WITHOUT a missing point - ebar, gamma, See -
 //                depends on (i, d, h, de) alone: one thread per pair runs the loops of pf_moments, pf_line and
@@ -22,7 +23,7 @@
 // G sits in LDS when it fits PF_TAB_LDS bytes (35 frequencies, h = 100, D = 8: 60.8 KB) and in global memory otherwise
 // (pf_stage).  No atomics at all, no float sum across lanes.  The host side is the table set-up, the kernel choice and
 // one call of sc_pf_chunks (sc_profile.hip).
-#include "sc_fit.h"
+#include "sc_channel.h"
 #include <math.h>
 #include <algorithm>
 
@@ -35,11 +36,6 @@ __global__ __launch_bounds__(256) void k_ch_table(const double* __restrict__ fre
         const double u = (M_PI * freqs[i]) * X;
         tab[idx] = exp(-(u * u));
     }
-}
-
-// pair q = r F + i (rank r of the shift, frequency i): the column of shift d is row j - d of the table
-__device__ __forceinline__ pf_tab_col ch_col(const double* tab, int F, int D, int r, int i) {
-    return pf_at(tab + (size_t)(D - sh_shift_of(r)) * F + i, F);
 }
 
 // zeros: np doubles, all 0 - the complete profile; terms: ebar, gamma, See, a plane of P = F (2D + 1) each
@@ -56,67 +52,6 @@ __global__ __launch_bounds__(256) void k_ch_terms(const double* __restrict__ tab
     terms[q] = t.ebar;
     terms[(size_t)P + q] = t.gamma;
     terms[2 * (size_t)P + q] = t.See;
-}
-
-// the Sep of pf_rest alone, t.ebar and t.gamma given: its loop, its e2 * p2 sum, in its order
-template <class E>
-__device__ __forceinline__ double ch_sep(const double* prof, int np, int h, double de, const pf_lin& L, const E& e,
-                                         const pf_col& t) {
-    double Sep = 0.0;
-    for (int jj = 0; jj < np; ++jj) {
-        const double p = prof[jj];
-        if (p != p) continue;
-        const double sc = (double)(jj - h) * de - L.sbar;
-        const double e2 = (e(jj) - t.ebar) - t.gamma * sc;
-        const double p2 = (p - L.pbar) - L.beta * sc;
-        Sep += e2 * p2;
-    }
-    return Sep;
-}
-
-// sh_search for the channel: the shift d_i with the smallest sse among d = -D..D in the order 0, -1, +1, ... for every
-// frequency i.  A pair whose See is not > 0 - a Gaussian whose every entry on the profile's points is 0 - or whose sse
-// is NaN is dead: its key is +inf and it never wins against a live one.  terms (or null): k_ch_terms' planes, for a
-// profile without a missing point (uniform per wave).  slot: key, sse (NaN where no pair of the frequency is alive), a, b,
-// c0; the rank
-__device__ __forceinline__ void ch_search(const double* prof, const double* tab, const double* __restrict__ terms, int np,
-                                          int h, int F, int D, double de, int lane, const pf_lin& L, double* slot) {
-    int* srank = (int*)(slot + (size_t)SH_TERMS * F);
-    const int P = F * (2 * D + 1);
-    for (int q0 = 0; q0 < P; q0 += 64) {
-        const bool on = q0 + lane < P;
-        const int q = on ? q0 + lane : P - 1;            // lanes beyond the pairs repeat the last one and are ignored
-        const int r = q / F, i = q - r * F;
-        const pf_tab_col e = ch_col(tab, F, D, r, i);
-        pf_col t;
-        double a, b, c0, sse;
-        if (terms) {
-            t.ebar = terms[q];
-            t.gamma = terms[(size_t)P + q];
-            t.See = terms[2 * (size_t)P + q];
-            t.Sep = ch_sep(prof, np, h, de, L, e, t);
-            a = t.Sep / t.See;
-            pf_slope(L.sbar, L.pbar, L.beta, t.ebar, t.gamma, a, b, c0);
-            sse = pf_sse(prof, np, h, de, e, a, b, c0);
-        } else {
-            sse = pf_candidate(prof, np, h, de, L, e, t, a, b, c0);
-        }
-        const bool alive = on && t.See > 0.0 && sse == sse;
-        const double key = alive ? sse : INFINITY;
-        // the round's winner of every frequency: argmin over the lanes F apart
-        const int win = pair_winner(key, on ? r : INT_MAX, F, lane);
-        if (on && r == win) {                            // (one lane per frequency)
-            if (q0 == 0 || key < slot[i]) {              // (every frequency meets its rank 0 in the first round: F <= 64)
-                slot[i] = key;
-                slot[F + i] = alive ? sse : __builtin_nan("");
-                slot[2 * F + i] = a;
-                slot[3 * F + i] = b;
-                slot[4 * F + i] = c0;
-                srank[i] = r;
-            }
-        }
-        wave_sync();                                     // (the next round's winners, and the caller, read the slot)
-    }
 }
 
 template <bool TAB_LDS>
@@ -178,20 +113,34 @@ __global__ __launch_bounds__(PF_THREADS) void k_ch_fit(const double* __restrict_
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
+int sc_ch_tables(sc_ctx* ctx, const double* d_freqs, int F, int h, int D, double de, double* d_tab, const double** d_terms) {
+    const int np = 2 * h + 1, ht = h + D, nt = 2 * ht + 1, P = F * (2 * D + 1);
+    int rc;
+    // (the profile of zeros, then the three planes)
+    if ((rc = sc_ensure(ctx, ctx->pf_terms, sizeof(double) * ((size_t)np + 3 * (size_t)P)))) return rc;
+    double* d_zeros = (double*)ctx->pf_terms.p;
+    double* terms = ctx->channel_terms ? d_zeros + np : nullptr;
+    if (terms) SC_HIP(ctx, hipMemsetAsync(d_zeros, 0, sizeof(double) * (size_t)np, ctx->stream));
+    sc_prof_begin(ctx, SC_K_PROFILE);
+    k_ch_table<<<std::max(1, std::min(256, (nt * F + 255) / 256)), 256, 0, ctx->stream>>>(d_freqs, F, ht, de, d_tab);
+    if (terms) k_ch_terms<<<(P + 255) / 256, 256, 0, ctx->stream>>>(d_tab, d_zeros, F, h, D, de, terms);
+    SC_HIP(ctx, hipGetLastError());
+    sc_prof_end(ctx, terms ? 2 : 1);
+    *d_terms = terms;
+    return SC_OK;
+}
+
 static int ch_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   long long K, const double* freqs, int F, int h, int w, int D, double de, double delta, int min_samples,
                   sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
-    const int np = 2 * h + 1, ht = h + D, nt = 2 * ht + 1, P = F * (2 * D + 1);
+    const int np = 2 * h + 1, ht = h + D, nt = 2 * ht + 1;
     const size_t tab_bytes = sizeof(double) * (size_t)nt * F;
     int rc;
     if ((rc = sc_ensure(ctx, ctx->pf_ages, sizeof(double) * F))) return rc;
     if ((rc = sc_ensure(ctx, ctx->pf_tab, tab_bytes))) return rc;
-    // (the profile of zeros, then the three planes)
-    if ((rc = sc_ensure(ctx, ctx->pf_terms, sizeof(double) * ((size_t)np + 3 * (size_t)P)))) return rc;
     double* d_freqs = (double*)ctx->pf_ages.p;
     double* d_tab = (double*)ctx->pf_tab.p;
-    double* d_zeros = (double*)ctx->pf_terms.p;
-    double* d_terms = ctx->channel_terms ? d_zeros + np : nullptr;
+    const double* d_terms;
 
     const bool tab_lds = tab_bytes <= PF_TAB_LDS;
     const size_t lds = pf_lds_bytes(np, nt, F, true, tab_lds);
@@ -199,12 +148,7 @@ static int ch_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     if ((rc = sc_lds_attr(ctx, (const void*)kern, lds))) return rc;
 
     SC_HIP(ctx, hipMemcpyAsync(d_freqs, freqs, sizeof(double) * F, hipMemcpyHostToDevice, ctx->stream));
-    if (d_terms) SC_HIP(ctx, hipMemsetAsync(d_zeros, 0, sizeof(double) * (size_t)np, ctx->stream));
-    sc_prof_begin(ctx, SC_K_PROFILE);
-    k_ch_table<<<std::max(1, std::min(256, (nt * F + 255) / 256)), 256, 0, ctx->stream>>>(d_freqs, F, ht, de, d_tab);
-    if (d_terms) k_ch_terms<<<(P + 255) / 256, 256, 0, ctx->stream>>>(d_tab, d_zeros, F, h, D, de, d_terms);
-    SC_HIP(ctx, hipGetLastError());
-    sc_prof_end(ctx, d_terms ? 2 : 1);
+    if ((rc = sc_ch_tables(ctx, d_freqs, F, h, D, de, d_tab, &d_terms))) return rc;
 
     const pf_plane curve = {out_sse, &ctx->pf_sse, sizeof(double) * (size_t)F}, shifts = {out_shift, &ctx->pf_shift, (size_t)F};
     return sc_pf_chunks(ctx, cells, sa, ca, K, PF_CHUNK, sizeof(sc_profile_shift_fit), out_rows, curve, shifts,
@@ -215,11 +159,8 @@ static int ch_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     });
 }
 
-// The two calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
-// host, uploaded - or on the context's DEM (z null).
-static int ch_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
-                   const double* ca, long long K, const double* freqs, int F, int h, int w, int D, double de, double delta,
-                   int min_samples, sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
+// what a channel call checks of its frequencies ahead of its frame's checks ...
+int sc_ch_check_freqs(sc_ctx* ctx, const char* who, const double* freqs, int F) {
     if (!freqs) return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
     if (F < 1) return sc_fail(ctx, SC_ERR_INVALID, "%s: needs F >= 1", who);
     if (F > SC_CHANNEL_MAX_FREQS)
@@ -227,13 +168,27 @@ static int ch_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     for (int i = 0; i < F; ++i)
         if (!(isfinite(freqs[i]) && freqs[i] > 0.0 && (i == 0 || freqs[i] > freqs[i - 1])))
             return sc_fail(ctx, SC_ERR_INVALID, "%s: frequencies must be finite, positive and strictly increasing", who);
-    int rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, freqs, F, h, w, de, delta, min_samples, out_rows);
-    if (rc) return rc;
-    if ((rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
-    // (the largest is the last one)
+    return SC_OK;
+}
+
+// ... and behind them (the largest frequency is the last one)
+int sc_ch_check_arg(sc_ctx* ctx, const char* who, const double* freqs, int F, double de) {
     if (!((M_PI * freqs[F - 1]) * de <= SC_CHANNEL_MAX_ARG))
         return sc_fail(ctx, SC_ERR_INVALID, "%s: pi f de = %g at the last frequency, more than %g: narrower than a cell shows", who,
                        (M_PI * freqs[F - 1]) * de, SC_CHANNEL_MAX_ARG);
+    return SC_OK;
+}
+
+// The two calls after their null checks: the argument checks under the name `who`, then the fit on z - ny x nx on the
+// host, uploaded - or on the context's DEM (z null).
+static int ch_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                   const double* ca, long long K, const double* freqs, int F, int h, int w, int D, double de, double delta,
+                   int min_samples, sc_profile_shift_fit* out_rows, double* out_sse, int8_t* out_shift) {
+    int rc = sc_ch_check_freqs(ctx, who, freqs, F);
+    if (rc) return rc;
+    if ((rc = sc_pf_check(ctx, who, ny, nx, cells, sa, ca, K, freqs, F, h, w, de, delta, min_samples, out_rows))) return rc;
+    if ((rc = sc_pf_check_shift(ctx, who, h, D, min_samples))) return rc;
+    if ((rc = sc_ch_check_arg(ctx, who, freqs, F, de))) return rc;
     if (K == 0) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->pf_z, z, ny, nx, &z_dev))) return rc;

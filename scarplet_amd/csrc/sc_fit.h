@@ -3,7 +3,7 @@
 // sc_strike.hip for stage one -, by sc_robust.hip, whose weighted sweeps (at the end) are these with a weight on every
 // term, by sc_segment_robust.hip, the joint fit on those sweeps, by sc_ramp.hip and sc_segment_ramp.hip, the initial slope
 // of the two, by sc_refine.hip and sc_segment_refine.hip, the ages off the grid of the two (rf_col), and by sc_lateral.hip for
-// the sampler and the host frame.  Who owns what:
+// the sampler and the host frame; by sc_channel.hip and sc_channel_segment.hip through sc_channel.h.  Who owns what:
 //   host    sc_profile.hip defines the frame of every per-cell call: the DEM's source (sc_pf_dem), the erf table
 //           (sc_pf_table) and the chunked driver (sc_pf_chunks), to which a call hands its one launch line.
 //           sc_segment.hip defines the frame of every segment call: the argument checks with the one cap refusal
@@ -142,6 +142,9 @@ int sc_sg_chunks(sc_ctx* ctx, const sg_call& call);
 int sc_sg_grid_attr(sc_ctx* ctx, int A, int h, int D);
 int sc_sg_grid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, double delta, int min_profiles, bool fine,
                       void* rows, void* cells, double* curve);
+// k_sg_resid alone, after the sum of (See, Sep) into k.tot, on whatever table k.tab is - rows j = -(h + D)..(h + D) of A
+// columns, the cell's column at column i its row j - d_ci (sc_channel_segment.hip: the Gaussian table); D < 0: no shift
+void sc_sg_resid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, int min_profiles);
 // k_sg_rank alone, on what another parking kernel left in st.cn and st.used (sc_segment_ramp.hip)
 void sc_sg_rank_launch(sc_ctx* ctx, const sg_stage& st);
 

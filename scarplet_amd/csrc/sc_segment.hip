@@ -24,7 +24,7 @@
 //                 the best age (sc_segment_cell, or sc_segment_shift_cell with d_ci at that age)
 // No atomics at all.  The erf table is k_pf_table's: the same bits as sc_fit_profiles*.
 // The host side holds the frame of every segment call (sc_fit.h): the argument checks, stage one, the segmented sum and
-// sc_sg_chunks, the chunked driver.  A call - sg_run here; sr_run, sq_run, bs_run, st_run, sx_run in their files - is the shape of
+// sc_sg_chunks, the chunked driver.  A call - sg_run here; sr_run, sq_run, bs_run, st_run, sx_run, cs_run in their files - is the shape of
 // its park, its bounds, its list of outputs and the launches of one chunk.
 #include "sc_fit.h"
 #include <math.h>
@@ -573,6 +573,15 @@ int sc_sg_grid_attr(sc_ctx* ctx, int A, int h, int D) {
     return sg_resid_of(A, h, D, [&](auto k_resid, size_t lds) { return sc_lds_attr(ctx, (const void*)k_resid, lds); });
 }
 
+void sc_sg_resid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, int min_profiles) {
+    const sg_stage& st = k.st;
+    sg_resid_of(A, h, D, [&](auto k_resid, size_t lds) {
+        k_resid<<<pf_grid(st.m), PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, st.shift,
+                                                                k.tot, st.m, A, h, D >= 0 ? D : 0, de, min_profiles, k.tab);
+        return 0;
+    });
+}
+
 int sc_sg_grid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, double de, double delta, int min_profiles, bool fine,
                       void* rows, void* cells, double* curve) {
     const sg_stage& st = k.st;
@@ -581,11 +590,7 @@ int sc_sg_grid_launch(sc_ctx* ctx, const sg_chunk& k, int A, int h, int D, doubl
     int launches = 1;
     if (k.G) {
         sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 2, k.part, k.tot);
-        sg_resid_of(A, h, D, [&](auto k_resid, size_t lds) {
-            k_resid<<<pf_grid(st.m), PF_THREADS, lds, ctx->stream>>>(st.prof, k.cseg, st.used, st.cnt, st.scal, st.planes, st.shift,
-                                                                    k.tot, st.m, A, h, Dk, de, min_profiles, k.tab);
-            return 0;
-        });
+        sc_sg_resid_launch(ctx, k, A, h, D, de, min_profiles);
         sc_sg_sum_launch(ctx, st.planes + 2 * mA, st, k.blk, k.G, A, 1, k.part, k.tsum);
         launches += 5;
     }
