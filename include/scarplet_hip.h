@@ -1116,6 +1116,65 @@ int sc_channel_segments_dem(sc_ctx* ctx, const double* z, int ny, int nx, const 
                             sc_channel_segment_cell* out_cells, double* out_sse, int8_t* out_shift);
 
 /*
+ * Block-bootstrap intervals per reach (docs/channels.md, "Intervals per reach"): what sc_bootstrap_segments is to
+ * sc_fit_segments_shift, for sc_channel_segments.  The cells, (sa, ca), the CSR arrays over reaches, blocks and cells, R,
+ * level, seed and min_blocks are sc_bootstrap_segments'; the frequencies, D, the mode and their limits sc_channel_segments'.
+ *   stage one   sc_channel_segments': the same samples, the same d_ci and the same terms per usable profile and frequency,
+ *               NaN where the frequency has no live pair in the profile.  No residual pass in either mode
+ *   block       over the block's usable profiles in hand-over order - runs of 64 in sequence from the first, then the run
+ *               sums in sequence from the first -: SC_CHANNEL_DEPTH_SEGMENT (sum See_ci, sum Sep_ci); SC_CHANNEL_DEPTH_PROFILE
+ *               (sum sse*_ci, sum a_ci) and m_b, the block's usable profiles.  NaN propagates; an empty block has terms 0
+ *               and m_b = 0 and stays in the partition
+ *   draws       sc_bootstrap_segments', bit for bit: keyed by seed and label, replicate 0 takes every block once
+ *   replicate   the sums of the drawn blocks' terms in draw order.  SC_CHANNEL_DEPTH_SEGMENT: frequency i is live when
+ *               SSee_i > 0 and finite and Q_i = SSep_i^2 / SSee_i is a number; f_index = argmax Q_i over the live ones, ties to
+ *               the smaller index; a = SSep / SSee there.  SC_CHANNEL_DEPTH_PROFILE: M = sum m_b over the draws; i is live
+ *               when M > 0 and SSse_i is a number; f_index = argmin SSse_i over the live ones, ties to the smaller index;
+ *               a = SA_i / (double)M there.  A frequency that is dead in a drawn profile is dead for that replicate only;
+ *               the replicate is failed (index -1, a NaN) only when no frequency is live
+ *   summary     sc_bootstrap_segments' over the n_ok replicates of 1..R that did not fail: lo_index and hi_index by its
+ *               ranks on an F-bin integer histogram, a_mean and a_sd in replicate order, a_lo and a_hi by the same ranks on
+ *               the sorted a; and the same four of area_r = -a_r / (sqrt(pi) f[index_r]).  f_index0, a0, area0: replicate 0
+ *   status      1: not bootstrapped - fewer than min_blocks blocks, fewer than min_profiles usable profiles, or n_ok = 0;
+ *               the indices are -1 and the floats NaN; 1 | 32 where the reach has the blocks and the profiles, n_ok = 0
+ *               and replicate 0 has no live frequency either.  Otherwise 2 where lo_index == 0, + 4 where hi_index == F - 1
+ * out_rows: S rows; out_hist: S x F int32 (the histogram of replicates 1..R), out_index: S x (R + 1) int8 and out_a: S x
+ * (R + 1) float64 (replicate 0 first), each or NULL.  Refused before any device work: what sc_channel_segments refuses (a
+ * reach above the park limit included) and what sc_bootstrap_segments refuses of the block arrays, R, level and min_blocks.
+ * No float atomics, every sum in a fixed order: the same bytes on every run, whatever other reaches the call holds.  Timed
+ * as SC_K_PROFILE.
+ */
+typedef struct sc_channel_boot {
+    int32_t  label;
+    int32_t  n_cells;         /* cells of the reach                              */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n_blocks;        /* blocks of the reach, empty ones included        */
+    int32_t  replicates;      /* R                                               */
+    int32_t  n_failed;        /* replicates of 1..R without a live frequency     */
+    int32_t  f_index0;        /* replicate 0: every block once                   */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not bootstrapped; | 32), or 2 (lo_index == 0) + 4 (hi_index == F - 1) */
+    double   f0, f_lo, f_hi;
+    double   a0;              /* replicate 0's depth coefficient                 */
+    double   a_mean, a_sd, a_lo, a_hi;
+    double   area0;           /* -a0 / (sqrt(pi) f0)                             */
+    double   area_mean, area_sd, area_lo, area_hi;
+} sc_channel_boot;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_channel_bootstrap(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                         const long long* seg_start, const int32_t* seg_label, long long S, const long long* seg_blk_start,
+                         const long long* blk_start, long long NB, const double* frequencies, int F, int h, int w, int D,
+                         int mode, double de, int min_samples, int min_profiles, int min_blocks, int R, double level,
+                         uint64_t seed, sc_channel_boot* out_rows, int32_t* out_hist, int8_t* out_index, double* out_a);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_channel_bootstrap_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                             const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                             long long S, const long long* seg_blk_start, const long long* blk_start, long long NB,
+                             const double* frequencies, int F, int h, int w, int D, int mode, double de, int min_samples,
+                             int min_profiles, int min_blocks, int R, double level, uint64_t seed, sc_channel_boot* out_rows,
+                             int32_t* out_hist, int8_t* out_index, double* out_a);
+
+/*
  * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and
  * after it R levels of 64 candidate ages of the cell's OWN bracket - for the minimum and for either end of the interval.
  * The samples, the validity rule, the min_samples rule, the orthogonalised fit and the explicit-residual sse are those of

@@ -183,6 +183,20 @@ def channel_segment_cap(h, n_freqs):
     return SEGMENT_MAX_PARK // channel_segment_park(h, n_freqs)
 
 
+class sc_channel_boot(C.Structure):
+    """One row of sc_channel_bootstrap / sc_channel_bootstrap_dem (docs/channels.md, "Intervals per reach")."""
+    _fields_ = [("label", C.c_int32), ("n_cells", C.c_int32), ("n_profiles", C.c_int32), ("n_blocks", C.c_int32),
+                ("replicates", C.c_int32), ("n_failed", C.c_int32), ("f_index0", C.c_int32), ("lo_index", C.c_int32),
+                ("hi_index", C.c_int32), ("status", C.c_int32),
+                ("f0", C.c_double), ("f_lo", C.c_double), ("f_hi", C.c_double), ("a0", C.c_double),
+                ("a_mean", C.c_double), ("a_sd", C.c_double), ("a_lo", C.c_double), ("a_hi", C.c_double),
+                ("area0", C.c_double), ("area_mean", C.c_double), ("area_sd", C.c_double), ("area_lo", C.c_double),
+                ("area_hi", C.c_double)]
+
+
+CHANNEL_BOOT_DTYPE = np.dtype(sc_channel_boot)
+
+
 class sc_segment_ramp_fit(C.Structure):
     """One row of sc_fit_segments_ramp / sc_fit_segments_ramp_dem: sc_segment_fit, then the half-width of the best age."""
     _fields_ = sc_segment_fit._fields_ + [("width_index", C.c_int32), ("width", C.c_double), ("initial_slope", C.c_double)]
@@ -419,6 +433,9 @@ SIGNATURES = {
     **_fit_pair("sc_channel_profiles", _CELLS, _AGES, _HW, [_i], _STOP, _CELL_OUT, [_v]),
     # (sc_fit_segments_shift's list with the depth mode behind D)
     **_fit_pair("sc_channel_segments", _CELLS, _SEGS, _AGES, _HW, [_i, _i], _STOP, [_i], _SEG_OUT, [_v]),
+    # (sc_bootstrap_segments' list with the depth mode behind D)
+    **_fit_pair("sc_channel_bootstrap", _CELLS, _SEGS, [_llp, _llp, _ll], _AGES, _HW,
+                [_i, _i, _d, _i, _i, _i, _i, _d, C.c_uint64], [_v, _v, _v, _dp]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -971,6 +988,24 @@ class Context(object):
         self._fit_call("sc_bootstrap_segments", z, (cells, sa, ca),
                        (seg_start, seg_label, seg_blk_start, blk_start, len(blk_start) - 1), ages,
                        [h, w, D, de, min_samples, min_profiles, min_blocks, R, level, seed, rows, hg, idx, amp])
+        return rows, hg, idx, amp
+
+    # -- block-bootstrap intervals per reach (docs/channels.md) --------------------------
+    def channel_bootstrap(self, cells, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, frequencies, h, w, D, mode, de,
+                          min_samples, min_profiles, min_blocks, R, level, seed, hist=False, replicates=False, z=None):
+        """sc_channel_bootstrap on the context's DEM, or sc_channel_bootstrap_dem on ``z`` (float64, C-contiguous, 2-D):
+        (rows, (S, F) int32 histograms or None, (S, R + 1) int8 indices or None, (S, R + 1) float64 depth coefficients or
+        None).  The arrays as bootstrap_segments takes them, the cells grouped by reach and, within it, by block; ``D``:
+        the range of the centre shift in cells; ``mode``: CHANNEL_DEPTH_PROFILE or CHANNEL_DEPTH_SEGMENT."""
+        F, S = len(frequencies), len(seg_label)
+        assert len(seg_blk_start) == S + 1
+        rows = np.zeros(S, dtype=CHANNEL_BOOT_DTYPE)
+        hg = np.zeros((S, F), dtype=np.int32) if hist else None
+        idx = np.zeros((S, int(R) + 1), dtype=np.int8) if replicates else None
+        amp = np.zeros((S, int(R) + 1), dtype=np.float64) if replicates else None
+        self._fit_call("sc_channel_bootstrap", z, (cells, sa, ca),
+                       (seg_start, seg_label, seg_blk_start, blk_start, len(blk_start) - 1), frequencies,
+                       [h, w, D, mode, de, min_samples, min_profiles, min_blocks, R, level, seed, rows, hg, idx, amp])
         return rows, hg, idx, amp
 
     # -- joint fits in windows along the strike (docs/strike.md) -------------------------

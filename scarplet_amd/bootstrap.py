@@ -104,6 +104,18 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
     D = profiles.check_shift(max_shift, False, de, h, ms)
     D = 0 if D is None else D
     bl, R, lv, sd, mb = check_resampling(de, block_length, replicates, level, seed, min_blocks)
+    idx, sa, ca, seg_blk_start, blk_start = hand_over(shape, de, cells, angle, s, bl, seg_strike)
+    return Args(idx, sa, ca, seg_start, seg_label, seg_blk_start, blk_start, s.ages, h, s.w, D, de, ms, s.min_profiles, mb, R,
+                lv, sd)
+
+
+def hand_over(shape, de, cells, angle, s, block_length, seg_strike=None):
+    """The hand-over of a block bootstrap, shared with ``channel_bootstrap``: ``s`` is the record of a segment call's
+    ``check_args`` (cells, sa, ca, seg_start, seg_label, order, kept) on the caller's ``cells`` and ``angle``.  The strike
+    of a segment is the axial mean of its cells' angles, or ``seg_strike`` (the strike of label L at index L - 1); the
+    cells are sorted by (label, block, input position), all stable, and the blocks that hold a cell are numbered along the
+    strike.  Returns (cells, sa, ca, seg_blk_start, blk_start)."""
+    idx, sa, ca, seg_start, seg_label = s.cells, s.sa, s.ca, s.seg_start, s.seg_label
     ny, nx = (int(v) for v in shape)
     if seg_strike is None:
         pick = s.kept[s.order]
@@ -111,7 +123,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
         strike = segment_strikes(a, seg_start)
     else:
         strike = np.asarray(seg_strike, dtype=np.float64)[seg_label.astype(np.int64) - 1]
-    blk = blocks_of(idx, nx, de, strike, seg_start, bl)
+    blk = blocks_of(idx, nx, de, strike, seg_start, block_length)
     seg = np.repeat(np.arange(len(seg_label)), np.diff(seg_start))
     by = np.lexsort((blk, seg))                                        # (stable: input order is kept within a block)
     idx, sa, ca, blk = idx[by], sa[by], ca[by], blk[by]
@@ -119,8 +131,7 @@ def check_args(shape, de, cells, labels, angle, half_length, swath, block_length
     first[1:] = (seg[1:] != seg[:-1]) | (blk[1:] != blk[:-1])
     blk_start = np.concatenate([np.flatnonzero(first), [len(idx)]]).astype(np.int64)
     seg_blk_start = np.searchsorted(blk_start[:-1], seg_start).astype(np.int64)
-    return Args(np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, seg_label,
-                seg_blk_start, blk_start, s.ages, h, s.w, D, de, ms, s.min_profiles, mb, R, lv, sd)
+    return np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_blk_start, blk_start
 
 
 def bootstrap_segments(data, cells, labels, angle, half_length, swath=0, block_length=None, replicates=1000, level=0.95,

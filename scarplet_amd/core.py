@@ -977,6 +977,21 @@ class Matcher(object):
                                            max_shift, depth, delta, min_samples, min_profiles)
         return channel_segments._run(self.ctx, args, self.nx, return_cells, return_curve, return_shift)
 
+    def bootstrap_channel_segments(self, traces, half_length, frequencies, block_length, swath=0, max_shift=0, depth="profile",
+                                   replicates=1000, level=0.95, seed=0, min_samples=4, min_profiles=1, min_blocks=5,
+                                   return_hist=False, return_replicates=False, strike="cell"):
+        """``sl.bootstrap_channel_segments`` on the DEM this matcher holds on the device (docs/channels.md, "Intervals per
+        reach") - no upload: a block-bootstrap interval of the width, the depth and the area of every segment of
+        ``traces``.  ``strike`` chooses the profiles' orientation as in ``fit_channel_segments``; with
+        ``strike="segment"`` the blocks are cut along the table's ``strike`` too.  The bytes are those of
+        ``sl.bootstrap_channel_segments`` on the same data."""
+        from scarplet_amd import channel_bootstrap
+        cells, lab, angle, seg_strike = _trace_cells(self, traces, strike, "bootstrap_channel_segments")
+        args = channel_bootstrap.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, frequencies, swath,
+                                            max_shift, depth, block_length, replicates, level, seed, min_samples, min_profiles,
+                                            min_blocks, seg_strike=seg_strike)
+        return channel_bootstrap._run(self.ctx, args, return_hist, return_replicates)
+
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
         every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within

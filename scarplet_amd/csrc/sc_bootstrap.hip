@@ -16,33 +16,9 @@
 // No float atomics, no float sum across lanes: the same bytes on every run.
 // The host side is the caller's blocks of one chunk, cut to the chunk's cells, and the launches after stage one, handed to
 // sc_sg_chunks (sc_segment.hip); a replicate output of R + 1 values per segment is a segment output of that item size.
-#include "sc_fit.h"
+#include "sc_bootstrap.h"
 #include <math.h>
 #include <algorithm>
-
-#define BS_RUN 64                        // usable profiles per run of a block's sum: sc_fit_segments' SG_BLOCK
-#define BS_WAVES 4
-#define BS_THREADS (64 * BS_WAVES)
-#define BS_TILE 16                       // replicates a wave takes of one work item: 64 per workgroup
-#define BS_LDS_MAX 65536                 // a segment's block terms go to LDS up to this many bytes
-#define BS_MAX_GRID 8192
-#define BS_MAX_OUT (1ll << 26)           // (segment, replicate) pairs of a chunk: 0.6 GB of indices and amplitudes
-#define BS_MAX_SEGS (1ll << 20)
-
-// the splitmix64 finaliser
-__host__ __device__ __forceinline__ unsigned long long bs_mix(unsigned long long z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// whether a segment of nb blocks and m usable profiles is bootstrapped
-__device__ __forceinline__ bool bs_boot(int nb, int m, int min_blocks, int min_profiles) {
-    return nb >= min_blocks && m >= min_profiles;
-}
 
 __global__ __launch_bounds__(64) void k_bs_terms(const int* __restrict__ used, const double* __restrict__ see,
                                                  const double* __restrict__ sep, const int* __restrict__ blk_start,
@@ -68,33 +44,6 @@ __global__ __launch_bounds__(64) void k_bs_terms(const int* __restrict__ used, c
             if (first) { tS = rS; tP = rP; } else { tS += rS; tP += rP; }
         }
         if (lane < A) terms[(size_t)g * A + lane] = make_double2(tS, tP);
-    }
-}
-
-// the sums of one replicate over its drawn blocks, in draw order; T: the segment's block terms, nb rows of A
-__device__ __forceinline__ void bs_sums(const double2* T, int nb, int A, int ia, int lane, int r, unsigned long long key,
-                                        double& S, double& P) {
-    S = 0.0;
-    P = 0.0;
-    if (r == 0) {                                        // the anchor: every block once
-        for (int k = 0; k < nb; ++k) {
-            const double2 v = T[(size_t)k * A + ia];
-            S += v.x;
-            P += v.y;
-        }
-        return;
-    }
-    for (int k0 = 0; k0 < nb; k0 += 64) {
-        // 64 draws at once, one per lane (a lane past the end forms a draw nobody reads)
-        const unsigned long long u = bs_mix(key + (((unsigned long long)(unsigned)r << 32) | (unsigned)(k0 + lane)));
-        const int b = (int)(((u >> 32) * (unsigned long long)(unsigned)nb) >> 32);
-        const int nk = min(64, nb - k0);
-        for (int j = 0; j < nk; ++j) {
-            const int bj = __builtin_amdgcn_readlane(b, j);
-            const double2 v = T[(size_t)bj * A + ia];
-            S += v.x;
-            P += v.y;
-        }
     }
 }
 
@@ -257,11 +206,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_bs_summary(const int* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static unsigned bs_grid(long long n) { return (unsigned)std::max<long long>(1, std::min<long long>(n, BS_MAX_GRID)); }
-
-static int bs_check(sc_ctx* ctx, const char* who, long long K, const long long* seg_start, long long S,
-                    const long long* seg_blk_start, const long long* blk_start, long long NB, int min_blocks, int R,
-                    double level) {
+int sc_bs_check(sc_ctx* ctx, const char* who, long long K, const long long* seg_start, long long S,
+                const long long* seg_blk_start, const long long* blk_start, long long NB, int min_blocks, int R, double level) {
     if (!seg_blk_start || !blk_start) return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
     if (R < 1 || R > SC_BOOT_MAX_REPLICATES)
         return sc_fail(ctx, SC_ERR_INVALID, "%s: R must lie in 1..%d", who, SC_BOOT_MAX_REPLICATES);
@@ -280,6 +226,12 @@ static int bs_check(sc_ctx* ctx, const char* who, long long K, const long long* 
         if (blk_start[seg_blk_start[s]] != seg_start[s])
             return sc_fail(ctx, SC_ERR_INVALID, "%s: the blocks of segment %lld do not cover its cells", who, std::min(s, S - 1));
     return SC_OK;
+}
+
+void sc_bs_terms_launch(sc_ctx* ctx, const int* used, const double* x, const double* y, const int* blk, long long NB, int A,
+                        double2* terms) {
+    k_bs_terms<<<(unsigned)std::max<long long>(1, std::min<long long>(NB, 65536)), 64, 0, ctx->stream>>>(used, x, y, blk, NB, A,
+                                                                                                        terms);
 }
 
 static int bs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
@@ -341,8 +293,7 @@ static int bs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         double* d_a = (double*)k.out[3];
         int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, k.tab, st);
         if (NBc) {
-            k_bs_terms<<<(unsigned)std::max<long long>(1, std::min<long long>(NBc, 65536)), 64, 0, ctx->stream>>>(
-                st.used, st.planes + 2 * mA, st.planes + 3 * mA, d_blk, NBc, A, d_terms);
+            sc_bs_terms_launch(ctx, st.used, st.planes + 2 * mA, st.planes + 3 * mA, d_blk, NBc, A, d_terms);
             ++launches;
         }
         k_bs_reps<<<bs_grid(st.Sc * tiles), BS_THREADS, lds, ctx->stream>>>(d_sblk, st.label, st.cnt, d_terms, st.Sc, A, R, seed,
@@ -366,7 +317,7 @@ static int bs_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, 0.0, min_samples,
                          min_profiles, out_rows);
     if (rc) return rc;
-    if ((rc = bs_check(ctx, who, K, seg_start, S, seg_blk_start, blk_start, NB, min_blocks, R, level))) return rc;
+    if ((rc = sc_bs_check(ctx, who, K, seg_start, S, seg_blk_start, blk_start, NB, min_blocks, R, level))) return rc;
     if (z && S == 0) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;

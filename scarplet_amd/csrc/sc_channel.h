@@ -11,6 +11,15 @@ int sc_ch_tables(sc_ctx* ctx, const double* d_freqs, int F, int h, int D, double
 // the checks a channel call adds to those of its frame: the frequencies ahead of them, pi f de <= SC_CHANNEL_MAX_ARG behind
 int sc_ch_check_freqs(sc_ctx* ctx, const char* who, const double* freqs, int F);
 int sc_ch_check_arg(sc_ctx* ctx, const char* who, const double* freqs, int F, double de);
+// Stage one of sc_channel_segments on a chunk of whole reaches (sc_channel_segment.hip), shared with sc_channel_bootstrap.hip:
+// the dynamic-LDS limit of k_cs_stage and where G sits, once a call; then k_cs_stage - none for a chunk without cells -
+// and k_sg_rank inside the chunk's timing bracket, the number of launches returned.  d_tab is G, d_terms what sc_ch_tables
+// left; park_prof: the profiles go to st.prof for k_sg_resid
+struct cs_stage_plan { bool tab_lds; size_t lds; };
+int sc_cs_stage_attr(sc_ctx* ctx, int F, int h, int D, cs_stage_plan* plan);
+int sc_cs_stage_launch(sc_ctx* ctx, const cs_stage_plan& plan, const double* z, int ny, int nx, int F, int h, int w, int D,
+                       double de, int min_samples, int mode, const double* d_tab, const double* d_terms, bool park_prof,
+                       const sg_stage& st);
 
 // pair q = r F + i (rank r of the shift, frequency i): the column of shift d is row j - d of the table
 __device__ __forceinline__ pf_tab_col ch_col(const double* tab, int F, int D, int r, int i) {

@@ -212,18 +212,37 @@ __global__ __launch_bounds__(64) void k_cs_choose(const int* __restrict__ seg_st
 static sg_park cs_park(int F, int h) { return sg_park_plain(F, h, true); }
 static_assert(SC_CHANNEL_SEGMENT_PARK(100, 35) == 8 * (201 + 4 * 35) + 35, "the park's formula");
 
+int sc_cs_stage_attr(sc_ctx* ctx, int F, int h, int D, cs_stage_plan* plan) {
+    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
+    plan->tab_lds = sizeof(double) * (size_t)nt * F <= PF_TAB_LDS;
+    plan->lds = pf_lds_bytes(np, nt, F, true, plan->tab_lds);
+    return sc_lds_attr(ctx, (const void*)(plan->tab_lds ? k_cs_stage<true> : k_cs_stage<false>), plan->lds);
+}
+
+int sc_cs_stage_launch(sc_ctx* ctx, const cs_stage_plan& plan, const double* z, int ny, int nx, int F, int h, int w, int D,
+                       double de, int min_samples, int mode, const double* d_tab, const double* d_terms, bool park_prof,
+                       const sg_stage& st) {
+    const auto k_stage = plan.tab_lds ? k_cs_stage<true> : k_cs_stage<false>;
+    int launches = 0;
+    if (st.m) {
+        k_stage<<<pf_grid(st.m), PF_THREADS, plan.lds, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, st.m, F, h, w, D, de, min_samples,
+                                                                      mode, d_tab, d_terms, park_prof ? st.prof : nullptr, st.cn,
+                                                                      st.used, st.scal, st.planes, st.shift);
+        ++launches;
+    }
+    sc_sg_rank_launch(ctx, st);
+    return launches + 1;
+}
+
 static int cs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const double* freqs, int F, int h,
                   int w, int D, int mode, double de, double delta, int min_samples, int min_profiles,
                   sc_segment_fit* out_rows, sc_channel_segment_cell* out_cells, double* out_sse, int8_t* out_shift) {
     if (S == 0) return SC_OK;
     const bool own = mode == SC_CHANNEL_DEPTH_PROFILE;
-    const int np = 2 * h + 1, nt = 2 * (h + D) + 1;
-    const bool tab_lds = sizeof(double) * (size_t)nt * F <= PF_TAB_LDS;
-    const size_t lds = pf_lds_bytes(np, nt, F, true, tab_lds);
-    const auto k_stage = tab_lds ? k_cs_stage<true> : k_cs_stage<false>;
+    cs_stage_plan plan;
     int rc;
-    if ((rc = sc_lds_attr(ctx, (const void*)k_stage, lds))) return rc;
+    if ((rc = sc_cs_stage_attr(ctx, F, h, D, &plan))) return rc;
     if (!own && (rc = sc_sg_grid_attr(ctx, F, h, D))) return rc;
 
     sg_call c = {cells, sa, ca, seg_start, seg_label, S, freqs, F, h + D, de, cs_park(F, h), CS_MAX_SEGS, nullptr, 0, 1};
@@ -239,15 +258,7 @@ static int cs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
         const sg_stage& st = k.st;
         const long long m = st.m;
         const size_t mF = (size_t)m * F;
-        int launches = 0;
-        if (m) {
-            k_stage<<<pf_grid(m), PF_THREADS, lds, ctx->stream>>>(z, ny, nx, st.cells, st.dirs, m, F, h, w, D, de, min_samples, mode,
-                                                                 k.tab, d_terms, own ? nullptr : st.prof, st.cn, st.used, st.scal,
-                                                                 st.planes, st.shift);
-            ++launches;
-        }
-        sc_sg_rank_launch(ctx, st);
-        ++launches;
+        int launches = sc_cs_stage_launch(ctx, plan, z, ny, nx, F, h, w, D, de, min_samples, mode, k.tab, d_terms, !own, st);
         if (k.G && own) {
             sc_sg_sum_launch(ctx, st.planes, st, k.blk, k.G, F, 2, k.part, k.tot);
             launches += 2;

@@ -206,6 +206,9 @@ struct sc_ctx {
     // segments over blocks, the block terms (See, Sep per block and age), every replicate's index and amplitude, the
     // histograms and the rows
     DevBuf bs_blk, bs_sblk, bs_terms, bs_index, bs_a, bs_hist, bs_rows;
+    // sc_channel_bootstrap*: stage one lives in the sg_ buffers and the blocks, the terms and the replicates in the bs_
+    // buffers; its own are the rows and, per chunk, the usable profiles of every block
+    DevBuf cb_rows, cb_mb;
     // sc_fit_strike*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR array of
     // segments over windows, Spp of every cell, the rows and the curves
     DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
