@@ -1175,6 +1175,52 @@ int sc_channel_bootstrap_dem(sc_ctx* ctx, const double* z, int ny, int nx, const
                              int32_t* out_hist, int8_t* out_index, double* out_a);
 
 /*
+ * A channel's width in windows along the strike of a reach (docs/channels.md, "Width along a reach"): what sc_fit_strike is
+ * to sc_fit_segments_shift, for sc_channel_segments.  The cells, (sa, ca), the CSR arrays over reaches, windows and cells
+ * and the windows [win_lo, win_hi) are sc_fit_strike's - the cells of a reach sorted along its strike, the windows cut on
+ * the host, no float compared here to cut one -; the frequencies, D, the mode and their limits sc_channel_segments'.
+ *   stage one   sc_channel_segments': the same samples, the same d_ci and the same terms per usable profile and frequency,
+ *               NaN where the frequency has no live pair in the profile.  The shifts are not re-fitted per window
+ *   sums        over the window's usable profiles in hand-over order - runs of 64 in sequence from the window's first, then
+ *               the run sums in sequence from the first; one profile is no addition at all -, with the integers n and
+ *               n_profiles.  NaN propagates: a frequency that is dead in one usable profile of the window is dead for the
+ *               window (sc_channel_segments' rule, not the bootstrap's)
+ *   mode        SC_CHANNEL_DEPTH_PROFILE: the sums of (sse*_ci, a_ci).  sse_i = SSse_i, kt_index = argmin sse_i, ties to
+ *               the smaller index, a NaN counting as +inf; a = SA / (double)n_profiles there; dof = n - (3 + (D > 0))
+ *               n_profiles.  No subtraction anywhere.
+ *               SC_CHANNEL_DEPTH_SEGMENT: the sums of (See_ci, Sep_ci) and of Spp_c, sc_fit_strike's quantity - the
+ *               profile's squared residuals about its own line.  Frequency i is live when SSee_i > 0 and finite and Q_i =
+ *               SSep_i^2 / SSee_i is a number; kt_index = argmax Q_i over the live ones, ties to the smaller index; a =
+ *               SSep / SSee there; sse_i = max(SSpp - Q_i, 0) where live, NaN where dead; dof = n - 2 n_profiles - 1 -
+ *               (D > 0 ? n_profiles : 0).  SSpp - Q_i cancels where the trough explains almost all of the profiles'
+ *               energy: the error of sse_i is a few ulps of SSpp, not of sse_i (kt_index and a have no subtraction)
+ *   choice      not fitted (status 1, indices -1, NaN floats, a NaN curve): n_profiles < min_profiles or dof < 1; 1 | 32:
+ *               every frequency is dead.  Else rmse = sqrt(sse / dof), thr = sse (1 + delta / dof); lo_index and hi_index
+ *               walk along the curve and a NaN ends a walk.  Status 2 / 4: the interval is open below / above; 8: a usable
+ *               profile of the window has |d_ci| == D at the best frequency, D > 0
+ * The rows are sc_strike_fit with kt, kt_lo and kt_hi carrying f, and kt_index, lo_index and hi_index indices of the
+ * frequencies.  An empty window is allowed.  out_rows: NW rows; out_sse: NW x F float64 (sse_i) or NULL; out_shift_sum: NW
+ * int32, the sum of d_ci at the best frequency over the window's usable profiles (0 where the window is not fitted), or
+ * NULL.  The park per cell is SC_CHANNEL_SEGMENT_PARK(h, F) bytes, as for sc_channel_segments.  Refused before any device
+ * work: what sc_channel_segments refuses (a reach above the park limit included) and what sc_fit_strike refuses of the
+ * window arrays.  No atomics, no float sum across lanes: the same bytes on every run, for every "fit_chunk" and whatever
+ * other reaches the call holds.  Timed as SC_K_PROFILE.
+ */
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_channel_strike(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                      const long long* seg_start, const int32_t* seg_label, long long S, const long long* seg_win_start,
+                      const long long* win_lo, const long long* win_hi, long long NW, const double* frequencies, int F,
+                      int h, int w, int D, int mode, double de, double delta, int min_samples, int min_profiles,
+                      sc_strike_fit* out_rows, double* out_sse, int32_t* out_shift_sum);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_channel_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                          const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                          const long long* seg_win_start, const long long* win_lo, const long long* win_hi, long long NW,
+                          const double* frequencies, int F, int h, int w, int D, int mode, double de, double delta,
+                          int min_samples, int min_profiles, sc_strike_fit* out_rows, double* out_sse,
+                          int32_t* out_shift_sum);
+
+/*
  * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and
  * after it R levels of 64 candidate ages of the cell's OWN bracket - for the minimum and for either end of the interval.
  * The samples, the validity rule, the min_samples rule, the orthogonalised fit and the explicit-residual sse are those of

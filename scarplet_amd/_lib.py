@@ -436,6 +436,8 @@ SIGNATURES = {
     # (sc_bootstrap_segments' list with the depth mode behind D)
     **_fit_pair("sc_channel_bootstrap", _CELLS, _SEGS, [_llp, _llp, _ll], _AGES, _HW,
                 [_i, _i, _d, _i, _i, _i, _i, _d, C.c_uint64], [_v, _v, _v, _dp]),
+    # (sc_fit_strike's list with the depth mode behind D; the sums of the shifts come last)
+    **_fit_pair("sc_channel_strike", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i, _i], _STOP, [_i], _CELL_OUT, [_v]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -1021,6 +1023,22 @@ class Context(object):
         self._fit_call("sc_fit_strike", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), ages,
                        [h, w, D, de, delta, min_samples, min_profiles, rows, sse])
         return rows, sse
+
+    # -- a channel's width in windows along the strike (docs/channels.md) -----------------
+    def channel_strike(self, cells, sa, ca, seg_start, seg_label, seg_win_start, win_lo, win_hi, frequencies, h, w, D, mode,
+                       de, delta, min_samples, min_profiles, curve=False, z=None):
+        """sc_channel_strike on the context's DEM, or sc_channel_strike_dem on ``z`` (float64, C-contiguous, 2-D): (rows,
+        (NW, F) float64 curves or None, (NW,) int32 sums of the shifts).  The arrays as fit_strike takes them, the cells
+        grouped by reach and sorted along its strike; ``D``: the range of the centre shift in cells; ``mode``:
+        CHANNEL_DEPTH_PROFILE or CHANNEL_DEPTH_SEGMENT.  The rows are sc_strike_fit, kt carrying f (docs/channels.md)."""
+        F, S, NW = len(frequencies), len(seg_label), len(win_lo)
+        assert len(seg_win_start) == S + 1 and len(win_hi) == NW
+        rows = np.zeros(NW, dtype=STRIKE_FIT_DTYPE)
+        sse = np.empty((NW, F), dtype=np.float64) if curve else None
+        shift_sum = np.zeros(NW, dtype=np.int32)
+        self._fit_call("sc_channel_strike", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW),
+                       frequencies, [h, w, D, mode, de, delta, min_samples, min_profiles, rows, sse, shift_sum])
+        return rows, sse, shift_sum
 
     # -- block-bootstrap intervals per station (docs/strike.md) --------------------------
     def strike_bootstrap(self, cells, sa, ca, seg_start, seg_label, seg_win_start, win_lo, win_hi, win_blk_start, blk_hi,

@@ -992,6 +992,19 @@ class Matcher(object):
                                             min_blocks, seg_strike=seg_strike)
         return channel_bootstrap._run(self.ctx, args, return_hist, return_replicates)
 
+    def fit_channels_along_strike(self, traces, half_length, frequencies, window, step=None, swath=0, max_shift=0,
+                                  depth="profile", delta=1.0, min_samples=4, min_profiles=1, return_curve=False, strike="cell"):
+        """``sl.fit_channels_along_strike`` on the DEM this matcher holds on the device (docs/channels.md, "Width along a
+        reach") - no upload: the width and the depth of every segment of ``traces`` in windows along its strike.  ``strike``
+        chooses the profiles' orientation as in ``fit_channel_segments``; with ``strike="segment"`` every cell of a segment
+        has the table's ``strike``, which is then what the along-strike coordinate is taken along.  The bytes are those of
+        ``sl.fit_channels_along_strike`` on the same data and orientations."""
+        from scarplet_amd import channel_strike
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "fit_channels_along_strike")
+        args, where = channel_strike.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, frequencies, swath,
+                                                window, step, max_shift, depth, delta, min_samples, min_profiles)
+        return channel_strike._run(self.ctx, args, where, self.nx, return_curve)
+
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
         every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within

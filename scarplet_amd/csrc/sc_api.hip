@@ -52,7 +52,7 @@ size_t sc_total_bytes(sc_ctx* c) {
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift, &c->sg_ftab, &c->sg_width, &c->sg_fine, &c->sq_wt, &c->sq_state, &c->sq_hist, &c->sq_a,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows, &c->cb_rows, &c->cb_mb,
-                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse,
+                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse, &c->cw_shift,
                      &c->sb_win, &c->sb_wstart, &c->sb_wblk, &c->sb_bhi, &c->sb_rows, &c->sb_hist,
                      &c->sf_work, &c->sf_cells, &c->sf_cube, &c->sf_rows};
     size_t s = 0;
@@ -244,7 +244,7 @@ extern "C" void sc_destroy(sc_ctx* c) {
                      &c->sg_z, &c->sg_ages, &c->sg_tab, &c->sg_cells, &c->sg_dir, &c->sg_cseg, &c->sg_start, &c->sg_blk, &c->sg_label, &c->sg_prof, &c->sg_int,
                      &c->sg_scal, &c->sg_age, &c->sg_list, &c->sg_part, &c->sg_tot, &c->sg_tsse, &c->sg_cnt, &c->sg_rows, &c->sg_out, &c->sg_sse, &c->sg_shift, &c->sg_ftab, &c->sg_width, &c->sg_fine, &c->sq_wt, &c->sq_state, &c->sq_hist, &c->sq_a,
                      &c->bs_blk, &c->bs_sblk, &c->bs_terms, &c->bs_index, &c->bs_a, &c->bs_hist, &c->bs_rows, &c->cb_rows, &c->cb_mb,
-                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse,
+                     &c->st_win, &c->st_wstart, &c->st_spp, &c->st_rows, &c->st_sse, &c->cw_shift,
                      &c->sb_win, &c->sb_wstart, &c->sb_wblk, &c->sb_bhi, &c->sb_rows, &c->sb_hist,
                      &c->sf_work, &c->sf_cells, &c->sf_cube, &c->sf_rows};
     for (DevBuf* b : arr) buf_free(*b);

@@ -11,7 +11,18 @@ int sc_ch_tables(sc_ctx* ctx, const double* d_freqs, int F, int h, int D, double
 // the checks a channel call adds to those of its frame: the frequencies ahead of them, pi f de <= SC_CHANNEL_MAX_ARG behind
 int sc_ch_check_freqs(sc_ctx* ctx, const char* who, const double* freqs, int F);
 int sc_ch_check_arg(sc_ctx* ctx, const char* who, const double* freqs, int F, double de);
-// Stage one of sc_channel_segments on a chunk of whole reaches (sc_channel_segment.hip), shared with sc_channel_bootstrap.hip:
+// every refusal of sc_channel_segments (sc_channel_segment.hip), for the calls that share its arguments (sc_channel_bootstrap.hip,
+// sc_channel_strike.hip): the frequencies, the mode, D, sc_sg_check's with the park's cap, then pi f de
+int sc_cs_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                const double* freqs, int F, int h, int w, int D, int mode, double de, double delta, int min_samples,
+                int min_profiles, const void* out_rows);
+// the degrees of freedom of a reach - or of a window of one - of m usable profiles and n pooled points
+__device__ __forceinline__ int cs_dof(int mode, int m, int n, int D) {
+    return mode == SC_CHANNEL_DEPTH_PROFILE ? n - (3 + (D > 0 ? 1 : 0)) * m : sg_dof(m, n, D);
+}
+// Stage one of sc_channel_segments on a chunk of whole reaches (sc_channel_segment.hip), shared with sc_channel_bootstrap.hip
+// and sc_channel_strike.hip:
 // the dynamic-LDS limit of k_cs_stage and where G sits, once a call; then k_cs_stage - none for a chunk without cells -
 // and k_sg_rank inside the chunk's timing bracket, the number of launches returned.  d_tab is G, d_terms what sc_ch_tables
 // left; park_prof: the profiles go to st.prof for k_sg_resid

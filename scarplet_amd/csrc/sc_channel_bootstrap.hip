@@ -349,15 +349,9 @@ static int cb_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
                    const long long* seg_blk_start, const long long* blk_start, long long NB, const double* freqs, int F, int h,
                    int w, int D, int mode, double de, int min_samples, int min_profiles, int min_blocks, int R, double level,
                    unsigned long long seed, sc_channel_boot* out_rows, int32_t* out_hist, int8_t* out_index, double* out_a) {
-    int rc = sc_ch_check_freqs(ctx, who, freqs, F);
+    int rc = sc_cs_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, freqs, F, h, w, D, mode, de, 0.0, min_samples,
+                         min_profiles, out_rows);
     if (rc) return rc;
-    if (mode != SC_CHANNEL_DEPTH_PROFILE && mode != SC_CHANNEL_DEPTH_SEGMENT)
-        return sc_fail(ctx, SC_ERR_INVALID, "%s: the depth mode must be SC_CHANNEL_DEPTH_PROFILE or SC_CHANNEL_DEPTH_SEGMENT", who);
-    if (D < 0) return sc_fail(ctx, SC_ERR_INVALID, "%s: the shift range must be >= 0 cells", who);
-    if ((rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, freqs, F, h, w, D, de, 0.0, min_samples,
-                          min_profiles, out_rows)))
-        return rc;
-    if ((rc = sc_ch_check_arg(ctx, who, freqs, F, de))) return rc;
     if ((rc = sc_bs_check(ctx, who, K, seg_start, S, seg_blk_start, blk_start, NB, min_blocks, R, level))) return rc;
     if (z && S == 0) return SC_OK;
     const double* z_dev;

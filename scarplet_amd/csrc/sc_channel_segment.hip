@@ -27,11 +27,6 @@
 
 #define CS_MAX_SEGS (1ll << 20)          // reaches per chunk: bounds the rows and totals of a call with empty reaches
 
-// the degrees of freedom of a reach of m usable profiles and n pooled points
-__device__ __forceinline__ int cs_dof(int mode, int m, int n, int D) {
-    return mode == SC_CHANNEL_DEPTH_PROFILE ? n - (3 + (D > 0 ? 1 : 0)) * m : sg_dof(m, n, D);
-}
-
 template <bool TAB_LDS>
 __global__ __launch_bounds__(PF_THREADS) void k_cs_stage(const double* __restrict__ z, int ny, int nx,
                                                          const long long* __restrict__ cells,
@@ -277,13 +272,11 @@ static int cs_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     return sc_sg_chunks(ctx, c);
 }
 
-// The two calls after their null checks: the argument checks under the name `who` - ch_call's of the frequencies, then
-// sc_sg_check's with the park's cap -, then the fit on z - ny x nx on the host, uploaded - or on the context's DEM (z null)
-static int cs_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
-                   const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
-                   const double* freqs, int F, int h, int w, int D, int mode, double de, double delta, int min_samples,
-                   int min_profiles, sc_segment_fit* out_rows, sc_channel_segment_cell* out_cells, double* out_sse,
-                   int8_t* out_shift) {
+// the argument checks under the name `who`: ch_call's of the frequencies, then sc_sg_check's with the park's cap
+int sc_cs_check(sc_ctx* ctx, const char* who, long long ny, long long nx, const long long* cells, const double* sa,
+                const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                const double* freqs, int F, int h, int w, int D, int mode, double de, double delta, int min_samples,
+                int min_profiles, const void* out_rows) {
     int rc = sc_ch_check_freqs(ctx, who, freqs, F);
     if (rc) return rc;
     if (mode != SC_CHANNEL_DEPTH_PROFILE && mode != SC_CHANNEL_DEPTH_SEGMENT)
@@ -292,7 +285,19 @@ static int cs_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     if ((rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, freqs, F, h, w, D, de, delta, min_samples,
                           min_profiles, out_rows)))
         return rc;
-    if ((rc = sc_ch_check_arg(ctx, who, freqs, F, de))) return rc;
+    return sc_ch_check_arg(ctx, who, freqs, F, de);
+}
+
+// The two calls after their null checks: sc_cs_check, then the fit on z - ny x nx on the host, uploaded - or on the
+// context's DEM (z null)
+static int cs_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                   const double* ca, long long K, const long long* seg_start, const int32_t* seg_label, long long S,
+                   const double* freqs, int F, int h, int w, int D, int mode, double de, double delta, int min_samples,
+                   int min_profiles, sc_segment_fit* out_rows, sc_channel_segment_cell* out_cells, double* out_sse,
+                   int8_t* out_shift) {
+    int rc = sc_cs_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, freqs, F, h, w, D, mode, de, delta,
+                         min_samples, min_profiles, out_rows);
+    if (rc) return rc;
     if (z && S == 0) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;

@@ -212,6 +212,7 @@ struct sc_ctx {
     // sc_fit_strike*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR array of
     // segments over windows, Spp of every cell, the rows and the curves
     DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
+    DevBuf cw_shift;           // sc_channel_strike*: the st_ buffers, and the sum of d_ci at the best frequency of every window, int32
     // sc_strike_bootstrap*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR arrays of
     // segments over windows and of windows over blocks, the end cell of every block, the rows and the histograms
     DevBuf sb_win, sb_wstart, sb_wblk, sb_bhi, sb_rows, sb_hist;

@@ -17,16 +17,10 @@
 // No float atomics, no float sum across lanes: the same bytes on every run.
 // The host side is the windows of one chunk, cut to the chunk's cells and segments, and the launches after stage one,
 // handed to sc_sg_chunks (sc_segment.hip): the rows and the curves run over the windows, the call's second CSR array.
-#include "sc_fit.h"
+// sc_channel_strike.hip shares the checks of the window arrays, the windows of a chunk and k_st_spp (sc_strike.h).
+#include "sc_strike.h"
 #include <math.h>
 #include <algorithm>
-
-#define ST_RUN 64                        // usable profiles per run of a window's sum: sc_fit_segments' SG_BLOCK
-#define ST_WAVES 4                       // consecutive stations per workgroup
-#define ST_THREADS (64 * ST_WAVES)
-#define ST_MAX_GRID 65536
-#define ST_MAX_SEGS (1ll << 20)
-#define ST_MAX_WIN (1ll << 21)           // windows of a chunk: 0.2 GB of rows, up to 1 GB of curves
 
 __global__ __launch_bounds__(ST_THREADS) void k_st_spp(const double* __restrict__ prof_g, const int* __restrict__ used,
                                                        const double* __restrict__ scal, long long K, int h, double de,
@@ -172,12 +166,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_st_fit(const int* __restrict__ w
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static unsigned st_grid(long long n) {
-    return (unsigned)std::max<long long>(1, std::min<long long>((n + ST_WAVES - 1) / ST_WAVES, ST_MAX_GRID));
-}
-
-static int st_check(sc_ctx* ctx, const char* who, const long long* seg_start, long long S, const long long* seg_win_start,
-                    const long long* win_lo, const long long* win_hi, long long NW, const void* out_rows) {
+int sc_st_check(sc_ctx* ctx, const char* who, const long long* seg_start, long long S, const long long* seg_win_start,
+                const long long* win_lo, const long long* win_hi, long long NW, const void* out_rows) {
     if (!seg_win_start || (NW > 0 && (!win_lo || !win_hi || !out_rows)))
         return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
     if (NW < 0 || NW > (long long)INT_MAX) return sc_fail(ctx, SC_ERR_INVALID, "%s: NW must lie in 0..2^31 - 1", who);
@@ -191,6 +181,37 @@ static int st_check(sc_ctx* ctx, const char* who, const long long* seg_start, lo
             if (!(seg_start[s] <= win_lo[g] && win_lo[g] <= win_hi[g] && win_hi[g] <= seg_start[s + 1]))
                 return sc_fail(ctx, SC_ERR_INVALID, "%s: window %lld does not lie in the cells of segment %lld", who, g, s);
     return SC_OK;
+}
+
+// the windows of one chunk, cut to the chunk's cells and segments, on their way up (sc_strike.h)
+int sc_st_windows(sc_ctx* ctx, const sg_chunk& k, const long long* seg_win_start, const long long* win_lo,
+                  const long long* win_hi, bool spp, st_windows& w) {
+    const long long Sc = k.st.Sc, g0 = seg_win_start[k.s0];
+    const long long NWc = seg_win_start[k.s1] - g0;
+    int rc;
+    w.NWc = NWc;
+    w.win.resize(3 * (size_t)NWc);
+    w.wstart.resize((size_t)Sc + 1);
+    for (long long s = 0; s <= Sc; ++s) w.wstart[s] = (int)(seg_win_start[k.s0 + s] - g0);
+    for (long long s = 0; s < Sc; ++s)
+        for (long long g = w.wstart[s]; g < w.wstart[s + 1]; ++g) {
+            w.win[3 * g] = (int)(win_lo[g0 + g] - k.k0);
+            w.win[3 * g + 1] = (int)(win_hi[g0 + g] - k.k0);
+            w.win[3 * g + 2] = (int)s;
+        }
+    if ((rc = sc_ensure(ctx, ctx->st_win, sizeof(int) * 3 * (size_t)NWc))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->st_wstart, sizeof(int) * ((size_t)Sc + 1)))) return rc;
+    if (spp && (rc = sc_ensure(ctx, ctx->st_spp, sizeof(double) * (size_t)k.st.m))) return rc;
+    w.d_win = (int*)ctx->st_win.p;
+    w.d_wstart = (int*)ctx->st_wstart.p;
+    w.d_spp = spp ? (double*)ctx->st_spp.p : nullptr;
+    if (NWc) SC_HIP(ctx, hipMemcpyAsync(w.d_win, w.win.data(), sizeof(int) * 3 * (size_t)NWc, hipMemcpyHostToDevice, ctx->stream));
+    SC_HIP(ctx, hipMemcpyAsync(w.d_wstart, w.wstart.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
+    return SC_OK;
+}
+
+void sc_st_spp_launch(sc_ctx* ctx, const sg_stage& st, int h, double de, double* d_spp) {
+    k_st_spp<<<st_grid(st.m), ST_THREADS, 0, ctx->stream>>>(st.prof, st.used, st.scal, st.m, h, de, d_spp);
 }
 
 static int st_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
@@ -207,45 +228,21 @@ static int st_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, Ds >= 0), ST_MAX_SEGS, seg_win_start,
                  ST_MAX_WIN, 0};
     c.out = {{out_rows, &ctx->st_rows, sizeof(sc_strike_fit), SG_AUX, true}, {out_sse, &ctx->st_sse, sizeof(double) * A, SG_AUX}};
-    std::vector<int> win, wstart;
-    int *d_win, *d_wstart;
-    double* d_spp;
-    long long NWc;
-    c.prepare = [&](const sg_chunk& k) {
-        const long long Sc = k.st.Sc, g0 = seg_win_start[k.s0];
-        NWc = seg_win_start[k.s1] - g0;
-        win.resize(3 * (size_t)NWc);
-        wstart.resize((size_t)Sc + 1);
-        for (long long s = 0; s <= Sc; ++s) wstart[s] = (int)(seg_win_start[k.s0 + s] - g0);
-        for (long long s = 0; s < Sc; ++s)
-            for (long long g = wstart[s]; g < wstart[s + 1]; ++g) {
-                win[3 * g] = (int)(win_lo[g0 + g] - k.k0);
-                win[3 * g + 1] = (int)(win_hi[g0 + g] - k.k0);
-                win[3 * g + 2] = (int)s;
-            }
-        if ((rc = sc_ensure(ctx, ctx->st_win, sizeof(int) * 3 * (size_t)NWc))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->st_wstart, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->st_spp, sizeof(double) * (size_t)k.st.m))) return rc;
-        d_win = (int*)ctx->st_win.p;
-        d_wstart = (int*)ctx->st_wstart.p;
-        d_spp = (double*)ctx->st_spp.p;
-        if (NWc) SC_HIP(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(int) * 3 * (size_t)NWc, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_wstart, wstart.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        return SC_OK;
-    };
+    st_windows W;
+    c.prepare = [&](const sg_chunk& k) { return sc_st_windows(ctx, k, seg_win_start, win_lo, win_hi, true, W); };
     c.launch = [&](const sg_chunk& k) {
         const sg_stage& st = k.st;
         const size_t mA = (size_t)st.m * A;
         int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, k.tab, st);
-        if (st.m && NWc) {
-            k_st_spp<<<st_grid(st.m), ST_THREADS, 0, ctx->stream>>>(st.prof, st.used, st.scal, st.m, h, de, d_spp);
+        if (st.m && W.NWc) {
+            sc_st_spp_launch(ctx, st, h, de, W.d_spp);
             ++launches;
         }
-        if (NWc) {
-            k_st_fit<<<st_grid(NWc), ST_THREADS, 0, ctx->stream>>>(d_win, d_wstart, st.label, NWc, st.cn, st.used,
-                                                                  st.planes + 2 * mA, st.planes + 3 * mA, d_spp, st.shift,
-                                                                  k.ages, A, D, delta, min_profiles, (sc_strike_fit*)k.out[0],
-                                                                  (double*)k.out[1]);
+        if (W.NWc) {
+            k_st_fit<<<st_grid(W.NWc), ST_THREADS, 0, ctx->stream>>>(W.d_win, W.d_wstart, st.label, W.NWc, st.cn, st.used,
+                                                                    st.planes + 2 * mA, st.planes + 3 * mA, W.d_spp, st.shift,
+                                                                    k.ages, A, D, delta, min_profiles, (sc_strike_fit*)k.out[0],
+                                                                    (double*)k.out[1]);
             ++launches;
         }
         return launches;
@@ -264,7 +261,7 @@ static int st_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, delta, min_samples,
                          min_profiles, out_rows);
     if (rc) return rc;
-    if ((rc = st_check(ctx, who, seg_start, S, seg_win_start, win_lo, win_hi, NW, out_rows))) return rc;
+    if ((rc = sc_st_check(ctx, who, seg_start, S, seg_win_start, win_lo, win_hi, NW, out_rows))) return rc;
     if (z && (S == 0 || NW == 0)) return SC_OK;
     const double* z_dev;
     if ((rc = sc_pf_dem(ctx, ctx->sg_z, z, ny, nx, &z_dev))) return rc;

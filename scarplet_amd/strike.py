@@ -78,9 +78,18 @@ def handover(shape, de, cells, labels, angle, half_length, swath, window, step, 
     ``strike_bootstrap`` cuts the blocks of a window from."""
     # (the park is checked as sc_fit_segments_shift counts it)
     s = segments.check_args(shape, de, cells, labels, angle, half_length, swath, ages, delta, min_samples, min_profiles, shift=True)
-    idx, sa, ca, seg_start, de = s.cells, s.sa, s.ca, s.seg_start, s.de
+    de = s.de
     D = profiles.check_shift(max_shift, False, de, s.h, s.min_samples)
     D = 0 if D is None else D
+    win, stp = check_window(window, step, de)
+    (idx, sa, ca, seg_win_start, win_lo, win_hi), where, t = cut(shape, de, cells, angle, s, win, stp)
+    return (Args(idx, sa, ca, s.seg_start, s.seg_label, seg_win_start, win_lo, win_hi, s.ages, s.h, s.w, D, de, s.delta,
+                 s.min_samples, s.min_profiles), where, t)
+
+
+def check_window(window, step, de):
+    """The rules of ``window`` and ``step`` at the cell size ``de``, for every call that cuts windows along the strike:
+    (window, step) as floats, the step ``window / 2`` when None; ValueError otherwise."""
     if window is None:
         raise ValueError("window is required: the length of a window along the strike, in data units")
     win = profiles._number(window, "window")
@@ -90,11 +99,21 @@ def handover(shape, de, cells, labels, angle, half_length, swath, window, step, 
     if not de <= stp <= win:
         raise ValueError("step must lie between the cell size %r and the window %r, got %r%s"
                          % (de, win, stp, " (window / 2: pass a step)" if step is None else ""))
+    return win, stp
+
+
+def cut(shape, de, cells, angle, s, window, step):
+    """The hand-over of the cells ``s`` holds grouped by label (the record of ``segments.check_args``, or one with its
+    ``cells, sa, ca, seg_start, kept, order``): the strike of every segment is the axial mean of its cells' angles, the
+    cells are sorted by (label, t, input position) and the windows cut (``windows_of``).  Returns (cells, sa, ca,
+    seg_win_start, win_lo, win_hi), (centre, row, col) - each window's ``u_k`` and the means of its cells' rows and columns,
+    NaN for an empty window - and ``t`` of every cell handed over."""
+    idx, sa, ca, seg_start = s.cells, s.sa, s.ca, s.seg_start
     ny, nx = (int(v) for v in shape)
     pick = s.kept[s.order]
     a = profiles._angles_of(angle, profiles._cells_of(cells, ny, nx), ny, nx)[pick]
     strike = bootstrap.segment_strikes(a, seg_start)
-    by, t, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, win, stp)
+    by, t, seg_win_start, win_lo, win_hi, centre = windows_of(idx, nx, de, strike, seg_start, window, step)
     idx, sa, ca = idx[by], sa[by], ca[by]
     if len(centre) > 2 ** 31 - 1:
         raise ValueError("%d windows: more than 2^31 - 1" % len(centre))
@@ -105,8 +124,7 @@ def handover(shape, de, cells, labels, angle, half_length, swath, window, step, 
     with np.errstate(invalid="ignore", divide="ignore"):
         row = np.where(cnt > 0, (cr[win_hi] - cr[win_lo]) / cnt, np.nan)
         col = np.where(cnt > 0, (cc[win_hi] - cc[win_lo]) / cnt, np.nan)
-    return (Args(np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_start, s.seg_label,
-                 seg_win_start, win_lo, win_hi, s.ages, s.h, s.w, D, de, s.delta, s.min_samples, s.min_profiles),
+    return ((np.ascontiguousarray(idx), np.ascontiguousarray(sa), np.ascontiguousarray(ca), seg_win_start, win_lo, win_hi),
             (centre, row, col), t)
 
 
