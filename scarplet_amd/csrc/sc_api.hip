@@ -638,7 +638,7 @@ static int check_templates(sc_ctx* ctx, const sc_template* t, int n, const sc_pl
     return SC_OK;
 }
 
-// One descriptor as the device's table entry (offsets into the per-chunk window buffers are match_impl's to fill)
+// One descriptor as the device's table entry (offsets into the per-chunk window buffers: sc_match_plan's, filled by match_impl)
 static void templ_from_descriptor(const sc_ctx* ctx, const sc_template& s, TemplDev& d, double* sums2, double* wl1) {
     const Geom& g = ctx->g;
     d.kind = s.kind; d.flags = s.flags;
@@ -699,6 +699,58 @@ int sc_load_templates(sc_ctx* ctx, const sc_template* t, int n) {
     return SC_OK;
 }
 
+// The curvature of a chunk, mixed for its nb orientations - and, on the FFT path, transformed - unless it is there
+// already: in the chunk's kept-spectra slots (`slot0` >= 0: the search keeps them, option "spectra_mb"), or, for a single
+// orientation, in plane 0 from the chunk before (`cur`: what plane 0 holds, while `have_curv`).
+struct CurvState {
+    double cur[3] = {0, 0, 0};
+    bool have_curv = false;
+};
+static int chunk_curvature(sc_ctx* ctx, const sc_template* t, const MatchChunk& c, bool fft, const FftGeom& fg, int slot0,
+                           CurvState& st) {
+    const bool keep = slot0 >= 0;
+    bool hit = keep;
+    if (keep) {
+        ctx->uc_off = (size_t)slot0 * ctx->spec_uc_stride;
+        ctx->norms_off = (size_t)slot0 * ctx->spec_norm_stride;
+    }
+    for (int b = 0; b < c.nb && hit; ++b) {
+        const sc_template& sb = t[c.first + b * c.n];
+        const double* k = &ctx->spec_key[3 * (size_t)(slot0 + b)];
+        hit = k[0] == sb.cc && k[1] == sb.sc2 && k[2] == sb.ss;
+    }
+    if (hit) {
+        st.have_curv = false;                     // (the curvature plane itself was not rebuilt)
+        return SC_OK;
+    }
+    const sc_template& s0 = t[c.first];
+    if (c.nb > 1 || !st.have_curv || s0.cc != st.cur[0] || s0.sc2 != st.cur[1] || s0.ss != st.cur[2]) {
+        float coef[SC_MAX_ORIENT][3];
+        for (int b = 0; b < c.nb; ++b) {
+            const sc_template& sb = t[c.first + b * c.n];
+            coef[b][0] = (float)sb.cc; coef[b][1] = (float)sb.sc2; coef[b][2] = (float)sb.ss;
+        }
+        // FFT tiles: the orientations' curvature is mixed from the stencil planes inside the forward row
+        // kernel (no plane written and read back; option "variant" 17: the separate k_curv_alpha pass, for the
+        // cross-check - same bits); the real-space kernel reads the plane(s)
+        const bool fused = fft && ctx->variant != 17;
+        int rc = SC_OK;
+        if (!fused) rc = c.nb > 1 ? launch_curv_alpha_batch(ctx, coef, c.nb) : launch_curv_alpha(ctx, coef[0][0], coef[0][1], coef[0][2]);
+        if (rc) return rc;
+        if (fft && (rc = fft_forward_curv(ctx, fg, c.nb, fused ? coef : nullptr))) return rc;
+        st.cur[0] = s0.cc; st.cur[1] = s0.sc2; st.cur[2] = s0.ss;
+        st.have_curv = c.nb == 1;                 // (a batch: plane 0 no longer belongs to a single run)
+    }
+    for (int b = 0; b < c.nb && keep; ++b) {
+        const sc_template& sb = t[c.first + b * c.n];
+        double* k = &ctx->spec_key[3 * (size_t)(slot0 + b)];
+        k[0] = sb.cc; k[1] = sb.sc2; k[2] = sb.ss;
+    }
+    return SC_OK;
+}
+
+// A search: validate, plan (sc_match_plan.h: runs, chunks, offsets and slots are decided there), upload, and launch
+// chunk after chunk.
 static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* plan,
                       bool to_maps) {
     if (!ctx || !t || !plan || n <= 0) return SC_ERR_INVALID;
@@ -710,21 +762,16 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
     if (rc) return rc;
     if (!to_maps) ctx->patch_n = 0;            // (the record moves on: what sc_settle_exact patched no longer describes it)
     const Geom& g = ctx->g;
+    const bool fft = plan->method == SC_METHOD_FFT;
+    const MatchPlanRefusal bad = sc_match_plan_check(*plan, g.ny, g.nx, g.wrap != 0, g.cy1 - g.cy0, g.cx1 - g.cx0);
+    if (bad.err) return sc_fail(ctx, bad.err, "%s", bad.msg);
     FftGeom fg{};
     const int group = std::max(1, plan->group);
-    const int CHUNK = SC_MAX_GROUP;
-    if (plan->method == SC_METHOD_FFT) {
+    if (fft) {
         fg.Ty = plan->Ty; fg.Tx = plan->Tx; fg.Vy = plan->Vy; fg.Vx = plan->Vx;
         fg.nty = plan->nty; fg.ntx = plan->ntx; fg.circ_y = plan->circ_y;
         fg.circ_x = plan->circ_x; fg.Py = plan->Py; fg.Qx = plan->Qx;
         fg.ntiles = fg.nty * fg.ntx;
-        if (fg.nty < 1 || fg.ntx < 1 || fg.Vy < 1 || fg.Vx < 1)
-            return sc_fail(ctx, SC_ERR_INVALID, "bad tile plan");
-        if ((fg.circ_y && (fg.Ty != g.ny || !g.wrap || fg.nty != 1)) ||
-            (fg.circ_x && (fg.Tx != g.nx || !g.wrap || fg.ntx != 1)))
-            return sc_fail(ctx, SC_ERR_INVALID, "circular axis needs T == n and the whole DEM");
-        if ((long long)fg.nty * fg.Vy < g.cy1 - g.cy0 || (long long)fg.ntx * fg.Vx < g.cx1 - g.cx0)
-            return sc_fail(ctx, SC_ERR_INVALID, "tiles do not cover the core");
     }
     if (to_maps) {
         size_t nc = (size_t)(g.cy1 - g.cy0) * (g.cx1 - g.cx0);
@@ -732,8 +779,6 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
         if ((rc = sc_ensure(ctx, ctx->map_snr, sizeof(float) * nc))) return rc;
     }
 
-    // Orientation runs: consecutive templates with equal (cc, sc2, ss) share one curvature
-    // plane (at most CHUNK of them per run).
     // (the context's own vectors: the uploads below are asynchronous and nothing waits for them before
     //  the launches; the stream was drained at the end of the previous call, so they are free to reuse -
     //  after an sc_match_async without sc_sync it is drained here)
@@ -743,125 +788,39 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
     }
     std::vector<TemplDev>& h = ctx->h_templ;
     std::vector<double>&sums = ctx->h_sums, &wl1 = ctx->h_wl1;
+    std::vector<unsigned char>& masked = ctx->h_masked;
     h.assign(n, TemplDev{});
     sums.assign(2 * (size_t)n, 0.0);
     wl1.assign(n, 0.0);
-    struct Run { int first, n, parity; bool full, long_runs; };
-    std::vector<Run> runs;
-    for (int i = 0; i < n;) {
-        int j = i;
-        int parity = -1;
-        bool full = false;
-        while (j < n && j - i < CHUNK && t[j].cc == t[i].cc && t[j].sc2 == t[i].sc2 &&
-               t[j].ss == t[i].ss) {
-            const sc_template& s = t[j];
-            TemplDev& d = h[j];
-            templ_from_descriptor(ctx, s, d, &sums[2 * (size_t)j], &wl1[j]);
-            // flip symmetry of the built-in templates (k_split_templ_sym): the same parity
-            // for the whole run, and support boxes that map onto themselves
-            int pj = s.kind == SC_KIND_SCARP ? 1 : (s.kind == SC_KIND_RICKER ? 2 : 0);
-            if (s.pmin + s.pmax != -(1 - g.oy) || s.qmin + s.qmax != -(1 - g.ox)) pj = 0;
-            parity = (parity == -1 || parity == pj) ? pj : 0;
-            full |= (d.flags & (SC_FLAG_ERR_XR_LE0 | SC_FLAG_ERR_XR_GE0)) != 0 ||
-                    d.mask_lim != nullptr || d.mask_err != nullptr;
-            ++j;
-        }
-        // real-space path: does some template of the run have window rows of SC_DR_SHARE_MIN taps or more along x
-        // (direct_long_runs, sc_direct_route.h)?  Decides the kernel form of the run's launch
-        // (launch_direct) - per RUN, so that a template's sums do not depend on what it is batched with
-        bool long_runs = false;
-        for (int k = i; k < j && !long_runs; ++k)
-            long_runs = direct_long_runs(t[k].kind == SC_KIND_WINDOW, t[k].c, t[k].d, t[k].cos_a, t[k].sin_a, ctx->dx);
-        runs.push_back({i, j - i, parity < 0 ? 0 : parity, full, long_runs});
-        i = j;
+    masked.assign(n, 0);
+    for (int j = 0; j < n; ++j) {
+        templ_from_descriptor(ctx, t[j], h[j], &sums[2 * (size_t)j], &wl1[j]);
+        masked[j] = h[j].mask_lim != nullptr || h[j].mask_err != nullptr;
     }
-    // Chunks: one run, or - small FFT searches - nb consecutive runs of equal length, parity
-    // and mask kind sent through every launch together (sc_fft.hip, "Orientation batching"; how many: fft_route_batch)
-    struct Chunk { int first, n, nb, wh, ww, parity; bool full, long_runs; size_t cells; int run0; };
-    std::vector<Chunk> chunks;
-    size_t max_cells = 0, max_dcells = 0, max_spans = 0;
-    int nb_max = 1, max_batch_templ = 1;
-    for (size_t r = 0; r < runs.size();) {
-        int nb = 1;
-        if ((plan->method == SC_METHOD_FFT || (!ctx->batch_off && ctx->variant != 10)) && !to_maps) {
-            // (real space: small DEMs fold up to 32 orientations per launch, in order, inside the
-            //  workgroup that owns a patch - a 512 x 512 search is 905 launches of a few microseconds
-            //  otherwise; DEMs of a thousand workgroups per orientation gain nothing)
-            const int want = plan->method == SC_METHOD_FFT ? fft_batch_orientations(ctx, fg, runs[r].n, group)
-                                                           : direct_batch_want(g.cy1 - g.cy0, g.cx1 - g.cx0);
-            // compatible runs ahead, up to what one launch can hold (64 templates, 64 curvature planes)
-            // (round 5: SC_MAX_BATCH templates per launch sequence - the row pass takes them in slices of whole
-            //  orientations, at most SC_MAX_GROUP templates each: fft_inverse_fold)
-            const int hard = plan->method == SC_METHOD_FFT ? std::min(SC_MAX_ORIENT, SC_MAX_BATCH / std::max(1, runs[r].n)) : 32;
-            // (counted beyond what one launch can hold, up to two full batches: whether a remainder rides
-            //  along or the rest is split evenly is decided on what is really left - capped at `hard`, 91
-            //  orientations of ten templates went six at a time as 3 + 3 instead of 4 + 4 + ...)
-            const int look = std::max(hard, 2 * want + 1);
-            int avail = 1;
-            while (avail < look && r + avail < runs.size() && runs[r + avail].n == runs[r].n &&
-                   runs[r + avail].parity == runs[r].parity && runs[r + avail].full == runs[r].full &&
-                   (plan->method == SC_METHOD_FFT || runs[r + avail].long_runs == runs[r].long_runs))
-                ++avail;
-            // `want` fills the chip; a tail of a few orientations costs a whole launch sequence of its
-            // own (C1: 35 orientations were 32 + 3), so a remainder up to a quarter of `want` rides along
-            // and a larger one is split evenly
-            if (want <= 1) nb = 1;
-            else if (avail <= want + want / 4) nb = avail;
-            else if (avail < 2 * want) nb = (avail + 1) / 2;
-            else nb = want;
-            nb = std::min(nb, hard);
-        }
-        size_t off = 0, doff = 0;
-        int wh = 0, ww = 0, soff = 0;
-        for (int j = runs[r].first; j < runs[r].first + nb * runs[r].n; ++j) {
-            h[j].win_off = (long long)off;
-            off += (size_t)h[j].wh * h[j].ww;
-            off = (off + 3) & ~(size_t)3;
-            wh = std::max(wh, h[j].wh);
-            ww = std::max(ww, h[j].ww);
-            // real-space path: rows reversed and padded to groups of four taps (k_direct_prep)
-            h[j].dpitch = (h[j].ww + 3) & ~3;
-            h[j].dwin_off = (long long)doff;
-            h[j].span_off = soff;
-            doff += (size_t)h[j].wh * h[j].dpitch;
-            soff += h[j].wh;
-        }
-        max_dcells = std::max(max_dcells, doff);
-        max_spans = std::max(max_spans, (size_t)soff);
-        chunks.push_back({runs[r].first, runs[r].n, nb, wh, ww, runs[r].parity, runs[r].full, runs[r].long_runs, off, (int)r});
-        max_cells = std::max(max_cells, off);
-        nb_max = std::max(nb_max, nb);
-        max_batch_templ = std::max(max_batch_templ, nb * runs[r].n);
-        r += nb;
+    MatchPlanIn in{};
+    in.t = t; in.n = n; in.masked = masked.data();
+    in.method = plan->method; in.to_maps = to_maps;
+    in.ch = g.cy1 - g.cy0; in.cw = g.cx1 - g.cx0; in.oy = g.oy; in.ox = g.ox; in.dx = ctx->dx;
+    in.route = fft_route_in(ctx, fg, 1);
+    in.route.group = group;
+    in.spectra = ctx->spec_mb > 0.0;
+    const MatchPlan mp = sc_match_plan(in);
+    for (int j = 0; j < n; ++j) {
+        h[j].win_off = mp.win_off[j]; h[j].dwin_off = mp.dwin_off[j];
+        h[j].dpitch = mp.dpitch[j]; h[j].span_off = mp.span_off[j];
     }
-    // Spectra kept across searches (option "spectra_mb"): slot of run r = its orientation's index among the
-    // search's distinct consecutive orientations; a batch must sit in consecutive slots
-    std::vector<int> slot_of(runs.size(), 0);
-    int n_slots = 0;
-    if (plan->method == SC_METHOD_FFT && !to_maps && ctx->spec_mb > 0.0) {
-        for (size_t r = 0; r < runs.size(); ++r) {
-            const sc_template &a = t[runs[r].first];
-            const bool same = r > 0 && a.cc == t[runs[r - 1].first].cc && a.sc2 == t[runs[r - 1].first].sc2 &&
-                              a.ss == t[runs[r - 1].first].ss;
-            slot_of[r] = same ? slot_of[r - 1] : n_slots++;
-        }
-        for (const Chunk& c : chunks)
-            for (int b = 1; b < c.nb; ++b)
-                if (slot_of[c.run0 + b] != slot_of[c.run0] + b) n_slots = 0;     // (an orientation twice in a batch)
-    }
-    if (plan->method == SC_METHOD_FFT &&
-        (rc = fft_prepare(ctx, fg, std::min(n, std::max(CHUNK, max_batch_templ)), group, nb_max, n_slots)))
+    if (fft && (rc = fft_prepare(ctx, fg, std::min(n, std::max(SC_MAX_GROUP, mp.max_batch_templ)), group, mp.nb_max, mp.n_slots)))
         return rc;
-    const bool keep = plan->method == SC_METHOD_FFT && ctx->spec_slots > 0;
+    const bool keep = fft && ctx->spec_slots > 0;
     if ((rc = sc_ensure(ctx, ctx->templ, sizeof(TemplDev) * n))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sums, sizeof(double) * 2 * n))) return rc;
     if ((rc = sc_ensure(ctx, ctx->wl1, sizeof(double) * n))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->win_w, sizeof(float) * max_cells))) return rc;
-    if ((rc = sc_ensure(ctx, ctx->win_m, max_cells))) return rc;
-    if (plan->method == SC_METHOD_DIRECT) {
-        if ((rc = sc_ensure(ctx, ctx->curv, sizeof(float) * (size_t)g.ly * g.lx * nb_max))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->dwin, sizeof(float2) * std::max<size_t>(max_dcells, 4)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->spans, sizeof(int4) * std::max<size_t>(max_spans, 1)))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->win_w, sizeof(float) * mp.max_cells))) return rc;
+    if ((rc = sc_ensure(ctx, ctx->win_m, mp.max_cells))) return rc;
+    if (!fft) {
+        if ((rc = sc_ensure(ctx, ctx->curv, sizeof(float) * (size_t)g.ly * g.lx * mp.nb_max))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->dwin, sizeof(float2) * std::max<size_t>(mp.max_dcells, 4)))) return rc;
+        if ((rc = sc_ensure(ctx, ctx->spans, sizeof(int4) * std::max<size_t>(mp.max_spans, 1)))) return rc;
     }
     // from here on the context's host vectors are the source of copies in flight: whatever way this call ends
     // (a launch failure or an allocation failing in a later chunk returns without draining the stream), the
@@ -877,55 +836,10 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
     ctx->last_batch = n;
     keep_f64_side(ctx, t, n);
 
-    double cur[3] = {0, 0, 0};
-    bool have_curv = false;
-    for (const Chunk& c : chunks) {
+    CurvState curv;
+    for (const MatchChunk& c : mp.chunks) {
         const int n_all = c.nb * c.n;
-        // kept spectra: this chunk's slots, and whether they already hold its orientations
-        bool hit = false;
-        if (keep) {
-            const int s0 = slot_of[c.run0];
-            ctx->uc_off = (size_t)s0 * ctx->spec_uc_stride;
-            ctx->norms_off = (size_t)s0 * ctx->spec_norm_stride;
-            hit = true;
-            for (int b = 0; b < c.nb; ++b) {
-                const sc_template& sb = t[c.first + b * c.n];
-                const double* k = &ctx->spec_key[3 * (size_t)(s0 + b)];
-                hit = hit && k[0] == sb.cc && k[1] == sb.sc2 && k[2] == sb.ss;
-            }
-        }
-        if (hit) {
-            have_curv = false;                    // (the curvature plane itself was not rebuilt)
-        } else if (c.nb > 1) {
-            float coef[SC_MAX_ORIENT][3];
-            for (int b = 0; b < c.nb; ++b) {
-                const sc_template& sb = t[c.first + b * c.n];
-                coef[b][0] = (float)sb.cc; coef[b][1] = (float)sb.sc2; coef[b][2] = (float)sb.ss;
-            }
-            // FFT tiles: the orientations' curvature is mixed from the stencil planes inside the forward row
-            // kernel (no plane written and read back; option "variant" 17: the separate k_curv_alpha pass, for the
-            // cross-check - same bits); the real-space kernel reads the plane(s)
-            const bool fused = plan->method == SC_METHOD_FFT && ctx->variant != 17;
-            if (!fused && (rc = launch_curv_alpha_batch(ctx, coef, c.nb))) return rc;
-            if (plan->method == SC_METHOD_FFT && (rc = fft_forward_curv(ctx, fg, c.nb, fused ? coef : nullptr))) return rc;
-            have_curv = false;                    // plane 0 no longer belongs to a single run
-        } else {
-            const sc_template& s0 = t[c.first];
-            if (!have_curv || s0.cc != cur[0] || s0.sc2 != cur[1] || s0.ss != cur[2]) {
-                const bool fused = plan->method == SC_METHOD_FFT && ctx->variant != 17;
-                const float coef1[1][3] = {{(float)s0.cc, (float)s0.sc2, (float)s0.ss}};
-                if (!fused && (rc = launch_curv_alpha(ctx, coef1[0][0], coef1[0][1], coef1[0][2]))) return rc;
-                if (plan->method == SC_METHOD_FFT && (rc = fft_forward_curv(ctx, fg, 1, fused ? coef1 : nullptr))) return rc;
-                cur[0] = s0.cc; cur[1] = s0.sc2; cur[2] = s0.ss;
-                have_curv = true;
-            }
-        }
-        if (keep && !hit)
-            for (int b = 0; b < c.nb; ++b) {
-                const sc_template& sb = t[c.first + b * c.n];
-                double* k = &ctx->spec_key[3 * (size_t)(slot_of[c.run0] + b)];
-                k[0] = sb.cc; k[1] = sb.sc2; k[2] = sb.ss;
-            }
+        if ((rc = chunk_curvature(ctx, t, c, fft, fg, keep ? mp.slot_of[c.run0] : -1, curv))) return rc;
         for (int j = c.first; j < c.first + n_all; ++j) {
             if (t[j].kind != SC_KIND_WINDOW) continue;
             const WindowSlot& w = ctx->windows[t[j].window];
@@ -936,7 +850,7 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
                                        hipMemcpyDeviceToDevice, ctx->stream));
         }
         if ((rc = launch_windows(ctx, c.first, n_all, c.wh, c.ww))) return rc;
-        if (plan->method == SC_METHOD_DIRECT) {
+        if (!fft) {
             if ((rc = launch_direct(ctx, c.first, c.n, to_maps, c.nb, c.wh, c.ww, c.long_runs))) return rc;
         } else {
             if ((rc = fft_forward_templates(ctx, fg, c.first, n_all, c.parity))) return rc;

@@ -3,7 +3,8 @@
 //
 // Pure functions of the core's extent, the launch's window box and the options - nothing of HIP, so that a host compiler
 // can build them alone (tests/direct_route_check.cpp enumerates them under AddressSanitizer / UBSan).  launch_direct
-// (sc_kernels.hip) and match_impl (sc_api.hip) ask them and decide no patch, no slab and no batch for themselves.
+// (sc_kernels.hip) and sc_match_plan (sc_match_plan.h: the batch and the long-run predicate) ask them and decide no
+// patch, no slab and no batch for themselves.
 #pragma once
 #include <math.h>
 

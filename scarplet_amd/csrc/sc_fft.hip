@@ -2869,7 +2869,13 @@ static int upload_twiddles(sc_ctx* ctx, DevBuf& buf, int& have, int T, int kph) 
 
 static int npairs_of(const FftGeom& fg) { return (fg.ntiles + 1) / 2; }
 
-static FftRouteIn fft_route_in(const sc_ctx* ctx, const FftGeom& fg, int parity) {
+// what the launch shapes of sc_fft_route.h restate of the kernels
+static_assert(fft_route_lds_line(64) == fft_line(64) && fft_route_lds_line(2048) == fft_line(2048) &&
+              fft_route_lds_line(4096) == fft_line(4096), "fft_route_col_pairs: the LDS line");
+static_assert(inv_rows_fast_threads<512>() * (512 / 512) / 64 == 512 / 512 && inv_rows_fast_threads<512>() * (1024 / 512) / 64 == 1024 / 512,
+              "fft_route_nsplit_max: a row workgroup is Tx / 512 waves");
+
+FftRouteIn fft_route_in(const sc_ctx* ctx, const FftGeom& fg, int parity) {
     FftRouteIn in{};
     in.Ty = fg.Ty; in.Tx = fg.Tx; in.ntiles = fg.ntiles; in.parity = parity;
     in.near = ctx->near_w > 0.f; in.kept = ctx->spec_slots > 0;
@@ -2896,7 +2902,7 @@ void fft_spectra_forget(sc_ctx* ctx) {
 
 // n_slots: orientations of the search whose curvature spectra would be kept (0: none asked for)
 int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, int nb, int n_slots) {
-    // nb: orientations batched per launch (fft_batch_orientations); 1 for the large searches
+    // nb: orientations batched per launch (sc_match_plan); 1 for the large searches
     if (!fft_size_supported(fg.Ty) || !fft_size_supported(fg.Tx))
         return sc_fail(ctx, SC_ERR_UNSUPPORTED, FFT_REFUSE_SIZE, fg.Ty, fg.Tx);
     int rc;
@@ -3010,12 +3016,7 @@ int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, in
 // launch: nb curvature planes and spectra, the templates of all of them in one forward pass,
 // the inverse column pass with one job per (orientation, tile pair), and the row pass folding
 // nb * n templates in the order the orientations come - the same cells in the same order as
-// orientation by orientation, so the result is bit-identical.  How many: fft_route_batch.
-int fft_batch_orientations(const sc_ctx* ctx, const FftGeom& fg, int n_per, int group) {
-    FftRouteIn in = fft_route_in(ctx, fg, 1);
-    in.n = n_per; in.group = group;
-    return fft_route_batch(in);
-}
+// orientation by orientation, so the result is bit-identical.  How many: fft_route_batch, asked by sc_match_plan.
 
 // Rendezvous words for a launch of n workgroups (SibSync): one buffer per context, a new epoch per
 // launch - words left by earlier launches compare below the new base, so nothing is cleared
@@ -3374,7 +3375,7 @@ static int launch_inv_rows(sc_ctx* ctx, const RowLaunch& a) {
 int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                      int group, bool to_maps, bool full_masks, int parity, int nb) {
     // nb > 1: templates [first, first + nb*n) are nb orientations of n templates each
-    // (fft_batch_orientations); n <= group then, and the row kernel is the fast one
+    // (sc_match_plan); n <= group then, and the row kernel is the fast one
     if (group > SC_MAX_GROUP)
         return sc_fail(ctx, SC_ERR_INVALID, "group %d exceeds %d", group, SC_MAX_GROUP);
     FftRouteIn rin = fft_route_in(ctx, fg, parity);
@@ -3414,24 +3415,12 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
         const bool xp = fft_route_xp(c.col), fast = c.row != FFT_ROW_GENERIC;
         for (int g0 = 0; g0 < n; g0 += group) {
             int G = std::min(group, n - g0);
-            const int ng = pt ? (G + 1) / 2 : G;               // transforms of the group: templates ride in pairs
-            // I1: as many tile pairs per launch as it takes to fill the chip once
-            // (one 2048-tile pair does; longer launches lost 6 % on the sustained C3 run)
-            const size_t lds_c = (size_t)4 * fft_line(fg.Ty) * sizeof(float2) +
-                                 (fg.Ty <= 2048 ? (size_t)4 * fg.Ty * sizeof(float2) : 0);
-            const int slots = 256 * (int)std::max<size_t>(1, (size_t)(160 * 1024) / lds_c);
-            // (nb > 1, batched orientations: every job of the chunk in one launch - job
-            //  ob * pc + q, the numbering the row kernel expects)
-            int pi1 = nb > 1 ? pc : std::max(1, std::min(pc, (slots + fg.Tx / 8 - 1) / (fg.Tx / 8)));
-            // Wave-per-column kernel, one orientation: i1_pairs tile pairs per launch, INTERLEAVED along x (k_inv_cols_w8,
-            // jil) - a launch of several pairs one after the other along y lost 6 % (the pairs' workgroups drift apart);
-            // interleaved, the 2 x i1_pairs workgroups that stream the same coefficient lines run together on one XCD
-            int jil = 1;
-            if (c.jil > 1) pi1 = jil = std::min(pc, c.jil);
+            const int ng = fft_route_transforms(G, pt);
+            const FftColPairs cp = fft_route_col_pairs(c, fg.Ty, fg.Tx, nb, pc);
             sc_prof_begin(ctx, SC_K_INV_COLS);
             int n_i1 = 0;
-            for (int pl0 = 0; pl0 < pc; pl0 += pi1) {
-                const int pcc = std::min(pi1, pc - pl0);
+            for (int pl0 = 0; pl0 < pc; pl0 += cp.pairs) {
+                const int pcc = std::min(cp.pairs, pc - pl0);
                 ColLaunch a{};
                 a.Ty = fg.Ty; a.Tx = fg.Tx; a.pt = pt; a.jobs = nb * pcc; a.ng = ng; a.split_i1 = r.split_i1;
                 a.uc = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc.p + ctx->uc_off;
@@ -3444,7 +3433,7 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 a.ystride = group; a.np = np; a.pcj = pcc; a.tstride = n;
                 a.tiles = (const TileDev*)ctx->tiles.p; a.py_valid = fg.circ_y ? -1 : fg.Py;
                 a.tl = r.row_skip ? (const TemplDev*)ctx->templ.p + first : nullptr;
-                a.jil = jil > 1 ? pcc : 1;                      // (the last launch of a chunk may hold fewer pairs)
+                a.jil = cp.interleaved ? pcc : 1;               // (the last launch of a chunk may hold fewer pairs)
                 a.fwd = fwd ? 1 : 0;
                 if (xp) {                        // job j = orientations 2j, 2j+1; plane j of Y; tstride carries nb
                     a.jobs = (nb + 1) / 2; a.ystride = 1; a.pcj = 1; a.tstride = nb; a.tl = nullptr;
@@ -3454,34 +3443,9 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 n_i1 += (c.col == FFT_COL_GENERIC || c.col == FFT_COL_SYM) ? 2 : 1;
             }
             sc_prof_end(ctx, n_i1);
-            // The row pass folds at most SC_MAX_GROUP templates per launch (its scalar table, its 64-bit mask of
-            // transforms, the winner's byte): a batch of more - nb orientations of G templates each -
-            // goes through it in slices of whole orientations, in order; the running best lives in the record
-            // between launches, so the fold is the one of a single launch (and of no batching at all).
-            // (slices of equal size: 8 orientations of 10 templates go 4 + 4, not 6 + 2 - a short last launch leaves the
-            //  chip part empty)
-            // Where the dealt-out row pass applies (small grids: FFT_ROW_SPLIT) a launch carries up to
-            // 255 templates - the winner's byte - in shares of at most SC_MAX_GROUP transforms each; C1F's 7 batched
-            // orientations of 35 ages are then ONE row-pass launch of four shares at four waves per SIMD instead of
-            // seven launches of two.  (With near-tie flags on the route allows it from four templates per orientation
-            //  only: on C5, one template per orientation, the split cost more in float64 pairs than it saved in the
-            //  pass: 14.0 -> 17.3 ms; C1F 51.7 -> 46.6)
-            // How many shares: up to four (any number, not only powers of two) while the launch stays within ~4 300 waves -
-            // the four per SIMD the kernel's 128 registers allow and 5 % (measured at C1F, 1 044 single-wave rows: two
-            // shares 19.0 ms, three 13.8, four 13.5; option "split_fill" sets another bound)
-            const bool split = c.row == FFT_ROW_SPLIT && G >= c.split_min_g;
-            int nsplit_max = 1;
-            if (split) {
-                const int wpw = inv_rows_fast_threads<512>() * (fg.Tx / 512) / 64;          // waves per row workgroup
-                const long long row_wgs = (long long)rp_n * 2 * pc, cap_wg = c.split_waves / wpw;
-                nsplit_max = (int)std::max<long long>(1, std::min<long long>(c.split_max, cap_wg / std::max<long long>(1, row_wgs)));
-            }
-            int nbs = nb;
-            if (nb > 1 && !xp) {
-                const int cap_t = nsplit_max > 1 ? std::min(255, SC_MAX_GROUP * nsplit_max * (pt ? 2 : 1)) : SC_MAX_GROUP;
-                const int cap = std::max(1, cap_t / std::max(1, G)), nsl = (nb + cap - 1) / cap;
-                nbs = (nb + nsl - 1) / nsl;
-            }
+            // the row pass: slices of whole orientations, each launch in shares (sc_fft_route.h)
+            const int nsplit_max = fft_route_nsplit_max(c, fg.Tx, G, rp_n, pc);
+            const int nbs = fft_route_row_slice(c, nb, G, pt, nsplit_max);
             for (int b0 = 0; b0 < nb; b0 += nbs) {
                 const int nbc = std::min(nbs, nb - b0);
                 const size_t yoff = (size_t)b0 * pc * group * (size_t)fg.Ty * fg.Tx;        // job (b0, 0) of yw / ym
@@ -3512,15 +3476,10 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 // third of the search, a chain of single-wave transforms at half the issue rate).  There the
                 // transforms are dealt out over nsplit workgroups per row, each folding its share in order into a
                 // record of its own; k_merge_split folds the shares into the record in order.  Same winners, same ties.
-                int nsplit = 1;
-                if (split) {
-                    const int ngl = nbc * ng;
-                    // (every share at least four transforms, at most SC_MAX_GROUP - its 64-bit mask)
-                    nsplit = std::max(1, std::min(nsplit_max, ngl / 4));
-                    nsplit = std::max(nsplit, (ngl + SC_MAX_GROUP - 1) / SC_MAX_GROUP);
-                    if (nsplit > 4 || (ngl + nsplit - 1) / nsplit > SC_MAX_GROUP)
-                        return sc_fail(ctx, SC_ERR_INVALID, "row pass: %d transforms in %d shares", ngl, nsplit);
-                }
+                const int ngl = nbc * ng, nsplit = fft_route_nsplit(c, G, nsplit_max, ngl);
+                // (not reached from a chunk sc_match_plan produces: tests/match_plan_check.cpp enumerates them)
+                if (fft_route_nsplit_refused(c, G, ngl, nsplit))
+                    return sc_fail(ctx, SC_ERR_INVALID, "row pass: %d transforms in %d shares", ngl, nsplit);
                 if (nsplit > 1) {
                     const size_t nc = (size_t)(ctx->g.cy1 - ctx->g.cy0) * (ctx->g.cx1 - ctx->g.cx0);
                     const size_t need = (size_t)4 * nc * sizeof(float);          // up to four shares: three scratch records (four with near-tie flags on)

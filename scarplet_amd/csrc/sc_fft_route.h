@@ -3,8 +3,12 @@
 // fft_route() is a pure function of the tile plan, the chunk and the options - nothing of HIP, so that a host
 // compiler can build it alone (tests/fft_route_check.cpp enumerates it under AddressSanitizer / UBSan).  The host
 // code of sc_fft.hip and its launchers, one per kernel family, ask it and test no tile size and no
-// "variant" for themselves.  What depends on the device or on buffer sizes - tile pairs per launch, parts of an
-// under-filled column pass, slices and shares of the row pass - is fft_inverse_fold's, from the flags given here.
+// "variant" for themselves.  The shape of the launches is here too, as integer arithmetic on the tile plan, the chunk
+// and the route: tile pairs per column launch and their interleave (fft_route_col_pairs), parts of an under-filled
+// column pass (fft_route_parts), slices and shares of the row pass (fft_route_nsplit_max, fft_route_row_slice,
+// fft_route_nsplit).  ONE input depends on the device: how many tile pairs the hand-off buffers hold (fft_pb, from the
+// free memory: fft_prepare) - it arrives here as `pc`, the tile pairs of a chunk.  fft_inverse_fold keeps the pointer
+// arithmetic, the buffers and the launches.
 #pragma once
 #include "../../include/scarplet_hip.h"      // (the error codes: plain C)
 
@@ -155,7 +159,7 @@ inline FftRoute fft_route(const FftRouteIn& in) {
     return r;
 }
 
-// Orientations one launch sequence carries (fft_batch_orientations; in.n templates per orientation).  Conditions:
+// Orientations one launch sequence carries (asked by sc_match_plan; in.n templates per orientation).  Conditions:
 // the fast row kernel (its scalar table and winner byte hold SC_MAX_GROUP templates), all templates of an
 // orientation in one inverse launch (group >= n), and at most ~4096 column workgroups.
 inline int fft_route_batch(const FftRouteIn& in) {
@@ -195,4 +199,83 @@ inline int fft_route_parts(int split_i1, long long workgroups, long long capacit
         if (u > best_u + 0.03) { best_u = u; best = nz; }
     }
     return best;
+}
+
+// ---- the shape of a chunk's launches (fft_inverse_fold): pc tile pairs through the column pass (I1) and the row pass
+// (I2), group by group; G templates of an orientation in the group, nb batched orientations ----
+
+// float2 cells of a transform's line in LDS (fft_line, sc_fft.hip: tied to it by a static_assert there)
+constexpr int fft_route_lds_line(int T) { return T + T / 16 + 8; }
+// transforms of a group of G templates: in the paired-template chunk they ride in pairs
+inline int fft_route_transforms(int G, bool pt) { return pt ? (G + 1) / 2 : G; }
+
+// Tile pairs per column launch, and whether they are interleaved along x.  As many pairs as it takes to fill the chip
+// once (one 2048-tile pair does; longer launches lost 6 % on the sustained C3 run); batched orientations: every job of
+// the chunk in one launch - job ob * pc + q, the numbering the row kernel expects.  Wave-per-column kernel, one
+// orientation: c.jil tile pairs per launch, INTERLEAVED along x (k_inv_cols_w8) - a launch of several pairs one after
+// the other along y lost 6 % (the pairs' workgroups drift apart); interleaved, the 2 x i1_pairs workgroups that stream
+// the same coefficient lines run together on one XCD.
+struct FftColPairs {
+    int pairs;                   // tile pairs per launch (the last launch of a chunk may hold fewer)
+    bool interleaved;
+};
+inline FftColPairs fft_route_col_pairs(const FftChunkRoute& c, int Ty, int Tx, int nb, int pc) {
+    if (c.jil > 1) return {pc < c.jil ? pc : c.jil, true};
+    if (nb > 1) return {pc, false};
+    const long long lds_c = 4LL * fft_route_lds_line(Ty) * 8 + (Ty <= 2048 ? 4LL * Ty * 8 : 0);   // (float2: 8 bytes)
+    const long long per_cu = 160 * 1024 / lds_c;
+    const int slots = 256 * (int)(per_cu > 1 ? per_cu : 1);
+    const int fill = (slots + Tx / 8 - 1) / (Tx / 8);
+    const int pairs = pc < fill ? pc : fill;
+    return {pairs > 1 ? pairs : 1, false};
+}
+
+// The row pass folds at most SC_MAX_GROUP templates per launch (its scalar table, its 64-bit mask of transforms, the
+// winner's byte): a batch of more - nb orientations of G templates each - goes through it in slices of whole
+// orientations, in order; the running best lives in the record between launches, so the fold is the one of a single
+// launch (and of no batching at all).  Slices of equal size: 8 orientations of 10 templates go 4 + 4, not 6 + 2 - a
+// short last launch leaves the chip part empty.
+// Where the dealt-out row pass applies (small grids: FFT_ROW_SPLIT) a launch carries up to 255 templates - the winner's
+// byte - in shares of at most SC_MAX_GROUP transforms each; C1F's 7 batched orientations of 35 ages are then ONE
+// row-pass launch of four shares at four waves per SIMD instead of seven launches of two.  (With near-tie flags on the
+// route allows it from four templates per orientation only: on C5, one template per orientation, the split cost more
+// in float64 pairs than it saved in the pass: 14.0 -> 17.3 ms; C1F 51.7 -> 46.6)
+// How many shares: up to four (any number, not only powers of two) while the launch stays within ~4 300 waves - the
+// four per SIMD the kernel's 128 registers allow and 5 % (measured at C1F, 1 044 single-wave rows: two shares 19.0 ms,
+// three 13.8, four 13.5; option "split_fill" sets another bound).
+
+// is a group of G templates dealt out at all
+inline bool fft_route_row_split(const FftChunkRoute& c, int G) { return c.row == FFT_ROW_SPLIT && G >= c.split_min_g; }
+// the most shares a row-pass launch of this group may have: rp_n row pairs of a tile hold valid outputs, a row
+// workgroup is Tx / 512 waves (FFT_ROW_SPLIT: Tx is 512 or 1024)
+inline int fft_route_nsplit_max(const FftChunkRoute& c, int Tx, int G, int rp_n, int pc) {
+    if (!fft_route_row_split(c, G)) return 1;
+    const long long row_wgs = (long long)rp_n * 2 * pc, cap_wg = c.split_waves / (Tx / 512);
+    const long long by_fill = cap_wg / (row_wgs > 1 ? row_wgs : 1);
+    const long long m = by_fill < c.split_max ? by_fill : c.split_max;
+    return (int)(m > 1 ? m : 1);
+}
+// orientations per row-pass launch: the batch's nb in slices of equal size (paired orientations: all of them, they
+// go to the row pass as ONE orientation of nb templates)
+inline int fft_route_row_slice(const FftChunkRoute& c, int nb, int G, bool pt, int nsplit_max) {
+    if (nb <= 1 || fft_route_xp(c.col)) return nb;
+    const int by_byte = SC_MAX_GROUP * nsplit_max * (pt ? 2 : 1);
+    const int cap_t = nsplit_max > 1 ? (by_byte < 255 ? by_byte : 255) : SC_MAX_GROUP;
+    const int per = cap_t / (G > 1 ? G : 1), cap = per > 1 ? per : 1, nsl = (nb + cap - 1) / cap;
+    return (nb + nsl - 1) / nsl;
+}
+// shares of ONE row-pass launch of ngl transforms (the slice's orientations x fft_route_transforms): every share at
+// least four transforms, at most SC_MAX_GROUP - its 64-bit mask
+inline int fft_route_nsplit(const FftChunkRoute& c, int G, int nsplit_max, int ngl) {
+    if (!fft_route_row_split(c, G)) return 1;
+    int ns = nsplit_max < ngl / 4 ? nsplit_max : ngl / 4;
+    if (ns < 1) ns = 1;
+    const int by_mask = (ngl + SC_MAX_GROUP - 1) / SC_MAX_GROUP;
+    return ns > by_mask ? ns : by_mask;
+}
+// ... and what the kernel cannot take: more than four shares, or a share of more than SC_MAX_GROUP transforms.
+// (tests/match_plan_check.cpp: no chunk sc_match_plan produces comes here, on any route and any number of tile pairs -
+//  a slice holds at most 255 templates)
+inline bool fft_route_nsplit_refused(const FftChunkRoute& c, int G, int ngl, int nsplit) {
+    return fft_route_row_split(c, G) && (nsplit > 4 || (ngl + nsplit - 1) / nsplit > SC_MAX_GROUP);
 }

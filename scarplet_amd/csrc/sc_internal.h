@@ -63,6 +63,7 @@ struct WindowSlot {
 
 #include "sc_fft_route.h"         // SC_MAX_GROUP, SC_MAX_BATCH, SC_MAX_ORIENT; the FFT path's choice of kernels
 #include "sc_direct_route.h"      // the real-space path's choice of kernel, slab and batch
+#include "sc_match_plan.h"        // the search's launch plan: runs, chunks, window offsets, kept-spectra slots
 
 struct sc_ctx {
     int device = 0;
@@ -116,6 +117,7 @@ struct sc_ctx {
     // the copy, so they live here - no stream synchronisation between the upload and the launches
     std::vector<TemplDev> h_templ;
     std::vector<double> h_sums, h_wl1;
+    std::vector<unsigned char> h_masked; // per template of the search being planned: its window slot carries per-cell masks (MatchPlanIn)
     // the float64 scorers' side of the last search's descriptors: per template the window slot (SC_KIND_WINDOW; -1
     // otherwise) and the orientation's curvature mix (cc, sc2, ss) - what a window template's score mixes the curvature
     // with (TemplDev's cos_a / sin_a are the plugin's own alpha there)
@@ -279,7 +281,8 @@ int launch_compare_fold(sc_ctx* ctx, double age, double angle, bool planes);
 // ---- launchers implemented in sc_fft.hip ------------------------------------
 int fft_prepare(sc_ctx* ctx, const FftGeom& fg, int n_templ_chunk, int group, int nb, int n_slots);
 void fft_spectra_forget(sc_ctx* ctx);
-int fft_batch_orientations(const sc_ctx* ctx, const FftGeom& fg, int n_per, int group);
+// the tile plan and the context's options as the route's and the plan's input (nb = n = group = 1: the caller's to set)
+FftRouteIn fft_route_in(const sc_ctx* ctx, const FftGeom& fg, int parity);
 int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)[3] = nullptr);
 int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int parity);
 int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,

@@ -51,6 +51,34 @@ static void check_chunk(const FftRouteIn& in, const FftRoute& r, const FftChunkR
     if (in.near && !in.to_maps) CHECK(r.near && (c.row == FFT_ROW_NEAR || c.row == FFT_ROW_SPLIT));
     if (!in.near || in.to_maps) CHECK(!r.near && c.row != FFT_ROW_NEAR);
     if (in.to_maps || in.full_masks) CHECK(c.row == FFT_ROW_GENERIC || c.row == FFT_ROW_FAST);
+    // the launch shapes, for any number of tile pairs in the hand-off: tile pairs per column launch, the most shares and
+    // the slice of a row-pass launch, the shares of a launch of any number of transforms
+    // (on the inputs that name a chunk's kernels: not over kept spectra, the fused forward and the group again)
+    const int v = in.variant;
+    if (in.kept || !in.fuse_fwd || in.group != 64 || !(v == 0 || v == 9 || v == 15 || v == 19 || v == 20)) return;
+    for (int pc : {1, 2, 5}) {
+        const FftColPairs cp = fft_route_col_pairs(c, Ty, Tx, in.nb, pc);
+        CHECK(cp.pairs >= 1 && cp.pairs <= pc);
+        if (cp.interleaved) CHECK(c.col == FFT_COL_W8 && cp.pairs <= c.jil);
+        if (in.nb > 1) CHECK(cp.pairs == pc && !cp.interleaved);           // every job of the batch in one launch
+        for (int G : {1, 3, 4, in.n}) for (int rp_n : {1, Ty / 2}) {
+            const bool split = fft_route_row_split(c, G);
+            if (split) CHECK(c.row == FFT_ROW_SPLIT);
+            const int most = fft_route_nsplit_max(c, Tx, G, rp_n, pc);
+            CHECK(most >= 1 && most <= (split ? c.split_max : 1));
+            const int nbs = fft_route_row_slice(c, in.nb, G, pt, most);
+            CHECK(nbs >= 1 && nbs <= in.nb);
+            if (paired_orient(c.col)) CHECK(nbs == in.nb);                 // (to the row pass ONE orientation of nb templates)
+            else if (in.nb > 1) CHECK(nbs == 1 || nbs * G <= (most > 1 ? 255 : SC_MAX_GROUP));
+            for (int ngl : {1, 3, 4, 7, 8, 64, 65, 128, 129, 192, 193, 255, 256, 257, 300}) {
+                const int ns = fft_route_nsplit(c, G, most, ngl);
+                CHECK(ns >= 1 && (split || ns == 1));
+                if (ns > 1 && ns <= most) CHECK(ngl / ns >= 4);            // a share of fewer than four transforms: only the mask's doing
+                CHECK(fft_route_nsplit_refused(c, G, ngl, ns) == (split && ngl > 4 * SC_MAX_GROUP));
+                if (!fft_route_nsplit_refused(c, G, ngl, ns) && split) CHECK((ngl + ns - 1) / ns <= SC_MAX_GROUP && ns <= 4);
+            }
+        }
+    }
 }
 
 static void check(const FftRouteIn& in) {
@@ -60,7 +88,7 @@ static void check(const FftRouteIn& in) {
     // refusals: the three of fft_inverse_fold, in its order; nothing else
     CHECK(r.err == SC_OK || r.msg == FFT_REFUSE_BATCH || r.msg == FFT_REFUSE_NEAR);       // (every size here is supported)
     CHECK((r.err == SC_OK) == (r.msg == nullptr));
-    // batching: what fft_batch_orientations grants is not refused
+    // batching: what fft_route_batch grants is not refused
     if (in.nb > 1 && fft_route_batch(in) >= in.nb) CHECK(r.msg != FFT_REFUSE_BATCH);
     // near-tie flags: refused exactly where Matcher.can_flag_near_ties says no (core.py)
     if (in.near && !in.to_maps && r.msg != FFT_REFUSE_BATCH) {

@@ -78,11 +78,12 @@ def test_variant_10_never_reaches_the_route(exe):
 
 
 def test_the_route_is_decided_in_one_place():
-    """launch_direct and match_impl ask sc_direct_route.h: neither tests a patch size, a slab or the batch rule itself."""
+    """launch_direct and sc_match_plan (match_impl's planner) ask sc_direct_route.h: neither tests a patch size, a slab or
+    the batch rule itself."""
     kern = open(os.path.join(CSRC, "sc_kernels.hip")).read()
     body = kern[kern.index("\nint launch_direct("):]
     assert "direct_route(" in body and "need256" not in body and "fits512" not in body and "wgs(" not in body
-    api = open(os.path.join(CSRC, "sc_api.hip")).read()
+    api = open(os.path.join(CSRC, "sc_api.hip")).read() + open(os.path.join(CSRC, "sc_match_plan.h")).read()
     assert "direct_batch_want(" in api and "direct_long_runs(" in api
     assert "wg1" not in api and not re.search(r">=\s*16\.0", api)
     assert len(re.findall(r"#define\s+DR2_LDS_FLOATS", kern + api)) == 0
