@@ -254,7 +254,7 @@ int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const d
  *              value) and loading a DEM drop what was kept.  Default 0 in the library; the
  *              Python host sets 8192.
  *   "fit_chunk"  n > 0: every fit call (sc_fit_profiles*, sc_lateral_offsets*, sc_fit_segments*,
- *              sc_bootstrap_segments*, sc_fit_strike*, sc_strike_bootstrap*, sc_snr_surface) closes a chunk of its work at n cells
+ *              sc_bootstrap_segments*, sc_fit_strike*, sc_strike_bootstrap*, sc_channel_*, sc_snr_surface) closes a chunk of its work at n cells
  *              where its built-in bound (2^19 cells, the parked bytes of SC_SEGMENT_MAX_PARK, 256 MiB of
  *              cubes) lies higher; it never raises one.  The per-cell calls launch on at most n cells; the
  *              segment calls take whole segments while their cells stay within n, a longer segment alone
@@ -1219,6 +1219,75 @@ int sc_channel_strike_dem(sc_ctx* ctx, const double* z, int ny, int nx, const lo
                           const double* frequencies, int F, int h, int w, int D, int mode, double de, double delta,
                           int min_samples, int min_profiles, sc_strike_fit* out_rows, double* out_sse,
                           int32_t* out_shift_sum);
+
+/*
+ * Block-bootstrap intervals per station along a reach (docs/channels.md, "Intervals per station"): what sc_strike_bootstrap
+ * is to sc_fit_strike, for sc_channel_strike - sc_channel_bootstrap's block bootstrap in every window of sc_channel_strike.
+ *   hand-over   the cells, the stations and the windows [win_lo, win_hi) are sc_channel_strike's, unchanged
+ *   stage one   sc_channel_segments': the same samples, the same d_ci and the same terms per usable profile and frequency,
+ *               NaN where the frequency has no live pair in the profile.  The shifts are not re-fitted per window or per
+ *               replicate.  No residual pass and no Spp in either mode
+ *   blocks      sc_strike_bootstrap's, cut by the caller in float64 and handed over as integers: win_blk_start[NW + 1], CSR
+ *               over blocks, 0 to NWB, and blk_hi[NWB], the end cell of every block - a window's first block begins at
+ *               win_lo, every other where the one before ends, the last ends at win_hi.  The library never compares floats
+ *   block terms sc_channel_bootstrap's, over the block's usable profiles in hand-over order - runs of 64 in sequence from
+ *               the first, then the run sums in sequence from the first -: SC_CHANNEL_DEPTH_SEGMENT (sum See_ci, sum
+ *               Sep_ci); SC_CHANNEL_DEPTH_PROFILE (sum sse*_ci, sum a_ci) and the integer m_b, the block's usable profiles.
+ *               NaN propagates; an empty block has terms 0 and m_b = 0 and stays in the partition
+ *   draws       sc_strike_bootstrap's generator, bit for bit: keyed by seed, label and station - station 0 has
+ *               sc_channel_bootstrap's key -; replicate 0 takes every block once
+ *   replicate   sc_channel_bootstrap's rules on the sums of the drawn blocks' terms in draw order: the live rule of the
+ *               mode; f_index = argmax Q_i or argmin SSse_i over the live frequencies, ties to the smaller index; a = SSep /
+ *               SSee or SA_i / (double)M there, M = sum m_b over the draws.  A frequency that is dead in a drawn profile is
+ *               dead for that replicate only; the replicate is failed only when no frequency is live
+ *   summary     sc_channel_bootstrap's per window, over the n_ok replicates of 1..R that did not fail: lo_index and hi_index
+ *               by its ranks on an F-bin integer histogram, a_mean and a_sd in replicate order, a_lo and a_hi by the same
+ *               ranks on the sorted a; and the same four of area_r = -a_r / (sqrt(pi) f[index_r]).  f_index0, a0, area0:
+ *               replicate 0
+ *   status      1: not bootstrapped - fewer than min_blocks blocks, fewer than min_profiles usable profiles, n_ok = 0, or
+ *               an empty window; the indices are -1 and the floats NaN; 1 | 32 where the window has the blocks and the
+ *               profiles, n_ok = 0 and replicate 0 has no live frequency either.  Otherwise 2 where lo_index == 0, + 4
+ *               where hi_index == F - 1
+ * A window's block terms must fit 64 KiB: nb F 16 <= 65536, SC_ERR_UNSUPPORTED beyond.  out_rows: NW rows; out_hist: NW x F
+ * int32 (the histogram of replicates 1..R) or NULL.  Per-replicate outputs are not built: they would be NW x (R + 1) values.
+ * The park per cell is SC_CHANNEL_SEGMENT_PARK(h, F) bytes, as for sc_channel_segments.  Refused before any device work:
+ * what sc_channel_strike refuses (a reach above the park limit included) and what sc_strike_bootstrap refuses of the block
+ * arrays, R, level and min_blocks.  No float atomics, no float sum across lanes: the same bytes on every run and for every
+ * "fit_chunk", and a reach's rows do not depend on the other reaches of the call.  Timed as SC_K_PROFILE.
+ */
+typedef struct sc_channel_strike_boot {       /* sc_channel_boot with the station */
+    int32_t  label;
+    int32_t  station;         /* the window's number within its reach            */
+    int32_t  n_cells;         /* cells of the window                             */
+    int32_t  n_profiles;      /* usable profiles among them                      */
+    int32_t  n_blocks;        /* blocks of the window, empty ones included       */
+    int32_t  replicates;      /* R                                               */
+    int32_t  n_failed;        /* replicates of 1..R without a live frequency     */
+    int32_t  f_index0;        /* replicate 0: every block once                   */
+    int32_t  lo_index, hi_index;
+    int32_t  status;          /* 0, or 1 (not bootstrapped; | 32), or 2 (lo_index == 0) + 4 (hi_index == F - 1) */
+    double   f0, f_lo, f_hi;
+    double   a0;              /* replicate 0's depth coefficient                 */
+    double   a_mean, a_sd, a_lo, a_hi;
+    double   area0;           /* -a0 / (sqrt(pi) f0)                             */
+    double   area_mean, area_sd, area_lo, area_hi;
+} sc_channel_strike_boot;
+/* on the DEM of the last sc_set_dem (the whole grid, float64, as the context holds it) */
+int sc_channel_strike_bootstrap(sc_ctx* ctx, const long long* cells, const double* sa, const double* ca, long long K,
+                                const long long* seg_start, const int32_t* seg_label, long long S,
+                                const long long* seg_win_start, const long long* win_lo, const long long* win_hi, long long NW,
+                                const double* frequencies, int F, int h, int w, int D, int mode, double de, int min_samples,
+                                int min_profiles, const long long* win_blk_start, const long long* blk_hi, long long NWB,
+                                int min_blocks, int R, double level, uint64_t seed, sc_channel_strike_boot* out_rows,
+                                int32_t* out_hist);
+/* the same on z, ny x nx float64 on the host, uploaded into a buffer of the call's own */
+int sc_channel_strike_bootstrap_dem(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa,
+                                    const double* ca, long long K, const long long* seg_start, const int32_t* seg_label,
+                                    long long S, const long long* seg_win_start, const long long* win_lo,
+                                    const long long* win_hi, long long NW, const double* frequencies, int F, int h, int w,
+                                    int D, int mode, double de, int min_samples, int min_profiles,
+                                    const long long* win_blk_start, const long long* blk_hi, long long NWB, int min_blocks,
+                                    int R, double level, uint64_t seed, sc_channel_strike_boot* out_rows, int32_t* out_hist);
 
 /*
  * Continuous ages (docs/profiles.md, "Continuous ages"; scarplet_amd/csrc/sc_refine.hip): the fit of sc_fit_profiles, and

@@ -21,6 +21,7 @@ from scarplet_amd.channels import fit_channels  # noqa: F401
 from scarplet_amd.channel_segments import fit_channel_segments  # noqa: F401
 from scarplet_amd.channel_bootstrap import bootstrap_channel_segments  # noqa: F401
 from scarplet_amd.channel_strike import fit_channels_along_strike  # noqa: F401
+from scarplet_amd.channel_strike_bootstrap import bootstrap_channels_along_strike  # noqa: F401
 from scarplet_amd.segments import fit_segments  # noqa: F401
 from scarplet_amd.bootstrap import bootstrap_segments  # noqa: F401
 from scarplet_amd.strike import fit_along_strike  # noqa: F401

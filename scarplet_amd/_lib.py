@@ -290,6 +290,32 @@ STRIKE_BOOT_DTYPE = np.dtype(sc_strike_boot)
 STRIKE_BOOT_LDS_TERMS = 65536                                          # SB_LDS_TERMS of sc_strike_bootstrap.hip
 
 
+class sc_channel_strike_boot(C.Structure):
+    """One row of sc_channel_strike_bootstrap / sc_channel_strike_bootstrap_dem (docs/channels.md, "Intervals per station"):
+    sc_channel_boot with the station."""
+    _fields_ = sc_channel_boot._fields_[:1] + [("station", C.c_int32)] + sc_channel_boot._fields_[1:]
+
+
+CHANNEL_STRIKE_BOOT_DTYPE = np.dtype(sc_channel_strike_boot)
+CHANNEL_STRIKE_BOOT_LDS_TERMS = 65536                                  # CWB_LDS_TERMS of sc_channel_strike_bootstrap.hip
+LDS_BYTES = 160 * 1024                                                 # a workgroup's LDS on gfx950
+CHANNEL_STRIKE_BOOT_LDS_STATIC = 288                                   # k_cwb_window's own: the histogram, the counts, replicate 0
+
+
+def channel_strike_boot_lds(n_blocks, n_freqs, replicates, profile_mode):
+    """The dynamic LDS of k_cwb_window for a window of ``n_blocks`` blocks (cwb_lds_bytes, sc_channel_strike_bootstrap.hip):
+    the block terms, two arrays of doubles padded to the sort, m_b in profile mode, the indices."""
+    p2 = 2
+    while p2 < replicates:
+        p2 <<= 1
+    return 16 * n_blocks * n_freqs + 17 * p2 + (4 * n_blocks if profile_mode else 0)
+
+
+# the top of the accepted range - 64 KiB of terms at F = 1, R = 4096, profile mode - fits a workgroup: 148 KiB
+assert channel_strike_boot_lds(CHANNEL_STRIKE_BOOT_LDS_TERMS // 16, 1, BOOT_MAX_REPLICATES, True) \
+    + CHANNEL_STRIKE_BOOT_LDS_STATIC == 148 * 1024 + 288 <= LDS_BYTES
+
+
 class sc_lateral_fit(C.Structure):
     """One row of sc_lateral_offsets / sc_lateral_offsets_dem (docs/lateral.md)."""
     _fields_ = [("cell", C.c_int64), ("n", C.c_int32), ("lag", C.c_int32), ("lo", C.c_int32), ("hi", C.c_int32),
@@ -438,6 +464,9 @@ SIGNATURES = {
                 [_i, _i, _d, _i, _i, _i, _i, _d, C.c_uint64], [_v, _v, _v, _dp]),
     # (sc_fit_strike's list with the depth mode behind D; the sums of the shifts come last)
     **_fit_pair("sc_channel_strike", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i, _i], _STOP, [_i], _CELL_OUT, [_v]),
+    # (sc_strike_bootstrap's list with the depth mode behind D)
+    **_fit_pair("sc_channel_strike_bootstrap", _CELLS, _SEGS, [_llp, _llp, _llp, _ll], _AGES, _HW, [_i, _i, _d, _i, _i],
+                [_llp, _llp, _ll], [_i, _i, _d, C.c_uint64], [_v, _v]),
     "sc_snr_surface": (C.c_int, [_P, C.POINTER(sc_template), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_longlong, C.c_double,
                                  C.c_void_p, _dp, _dp]),
     "sc_get_resolution_stats": (C.c_int, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
@@ -1056,6 +1085,26 @@ class Context(object):
         self._fit_call("sc_strike_bootstrap", z, (cells, sa, ca), (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), ages,
                        [h, w, D, de, min_samples, min_profiles, win_blk_start, blk_hi, len(blk_hi), min_blocks, R, level, seed,
                         rows, hg])
+        return rows, hg
+
+    # -- block-bootstrap intervals per station along a reach (docs/channels.md) ------------
+    def channel_strike_bootstrap(self, cells, sa, ca, seg_start, seg_label, seg_win_start, win_lo, win_hi, win_blk_start, blk_hi,
+                                 frequencies, h, w, D, mode, de, min_samples, min_profiles, min_blocks, R, level, seed, hist=False,
+                                 z=None):
+        """sc_channel_strike_bootstrap on the context's DEM, or sc_channel_strike_bootstrap_dem on ``z`` (float64,
+        C-contiguous, 2-D): (rows, (NW, F) int32 histograms or None).  The arrays as strike_bootstrap takes them, the cells
+        grouped by reach and sorted along its strike; ``D``: the range of the centre shift in cells; ``mode``:
+        CHANNEL_DEPTH_PROFILE or CHANNEL_DEPTH_SEGMENT."""
+        F, S, NW = len(frequencies), len(seg_label), len(win_lo)
+        assert len(seg_win_start) == S + 1 and len(win_hi) == NW and len(win_blk_start) == NW + 1
+        for a in (win_blk_start, blk_hi):
+            assert a.dtype == np.int64 and a.ndim == 1 and a.flags.c_contiguous
+        rows = np.zeros(NW, dtype=CHANNEL_STRIKE_BOOT_DTYPE)
+        hg = np.zeros((NW, F), dtype=np.int32) if hist else None
+        self._fit_call("sc_channel_strike_bootstrap", z, (cells, sa, ca),
+                       (seg_start, seg_label, seg_win_start, win_lo, win_hi, NW), frequencies,
+                       [h, w, D, mode, de, min_samples, min_profiles, win_blk_start, blk_hi, len(blk_hi), min_blocks, R, level,
+                        seed, rows, hg])
         return rows, hg
 
     # -- strike-slip offsets across a trace (docs/lateral.md) -------------------------------

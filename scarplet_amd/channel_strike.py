@@ -25,18 +25,21 @@ Args = collections.namedtuple("Args", "cells sa ca seg_start seg_label seg_win_s
 
 
 def check_args(shape, de, cells, labels, angle, half_length, frequencies, swath, window, step, max_shift, depth, delta,
-               min_samples, min_profiles):
+               min_samples, min_profiles, with_t=False):
     """What the library takes, validated and normalised; ValueError otherwise.  The arguments shared with
     ``fit_channel_segments`` go through ``channel_segments.check_args``, the park's cap per reach included; ``window`` and
     ``step`` through ``strike.check_window``.  The cells are then sorted by (label, t, input position) and the windows cut
     along the axial mean of each reach's angles (``strike.cut``).  Returns the arguments of ``Context.channel_strike`` and
-    (centre, row, col): each window's ``u_k`` and the means of its cells' rows and columns (NaN for an empty window)."""
+    (centre, row, col): each window's ``u_k`` and the means of its cells' rows and columns (NaN for an empty window); with
+    ``with_t`` also the along-strike coordinate of every cell handed over (``channel_strike_bootstrap`` cuts its blocks on
+    it)."""
     s = channel_segments.check_args(shape, de, cells, labels, angle, half_length, frequencies, swath, max_shift, depth, delta,
                                     min_samples, min_profiles)
     win, stp = strike.check_window(window, step, s.de)
-    (idx, sa, ca, seg_win_start, win_lo, win_hi), where, _ = strike.cut(shape, s.de, cells, angle, s, win, stp)
-    return Args(idx, sa, ca, s.seg_start, s.seg_label, seg_win_start, win_lo, win_hi, s.frequencies, s.h, s.w, s.D, s.mode,
-                s.de, s.delta, s.min_samples, s.min_profiles), where
+    (idx, sa, ca, seg_win_start, win_lo, win_hi), where, t = strike.cut(shape, s.de, cells, angle, s, win, stp)
+    args = Args(idx, sa, ca, s.seg_start, s.seg_label, seg_win_start, win_lo, win_hi, s.frequencies, s.h, s.w, s.D, s.mode,
+                s.de, s.delta, s.min_samples, s.min_profiles)
+    return (args, where, t) if with_t else (args, where)
 
 
 def _run(ctx, args, where, nx, return_curve, z=None):

@@ -1005,6 +1005,21 @@ class Matcher(object):
                                                 window, step, max_shift, depth, delta, min_samples, min_profiles)
         return channel_strike._run(self.ctx, args, where, self.nx, return_curve)
 
+    def bootstrap_channels_along_strike(self, traces, half_length, frequencies, window, block_length, step=None, swath=0,
+                                        max_shift=0, depth="profile", replicates=1000, level=0.95, seed=0, min_samples=4,
+                                        min_profiles=1, min_blocks=5, return_hist=False, strike="cell"):
+        """``sl.bootstrap_channels_along_strike`` on the DEM this matcher holds on the device (docs/channels.md, "Intervals
+        per station") - no upload: a block-bootstrap interval of the width, the depth and the area of every segment of
+        ``traces`` at every station along its strike.  ``strike`` chooses the profiles' orientation as in
+        ``fit_channels_along_strike``.  The bytes are those of ``sl.bootstrap_channels_along_strike`` on the same data and
+        orientations."""
+        from scarplet_amd import channel_strike_bootstrap as cwb
+        cells, lab, angle, _ = _trace_cells(self, traces, strike, "bootstrap_channels_along_strike")
+        args, where = cwb.check_args((self.ny, self.nx), self.de, cells, lab, angle, half_length, frequencies, swath, window, step,
+                                     block_length, max_shift, depth, replicates, level, seed, min_samples, min_profiles,
+                                     min_blocks)
+        return cwb._run(self.ctx, args, where, return_hist)
+
     def snr_surface(self, Template, scale, params, angles, traces_or_cells, drop=0.1, return_surface=False, **kwargs):
         """``sl.snr_surface`` on the DEM this matcher holds on the device (docs/surface.md) - no upload: the float64 SNR of
         every (param, angle) template of ``Template`` at ``scale`` at the cells, the first maximum and the intervals within

@@ -216,7 +216,8 @@ struct sc_ctx {
     DevBuf st_win, st_wstart, st_spp, st_rows, st_sse;
     DevBuf cw_shift;           // sc_channel_strike*: the st_ buffers, and the sum of d_ci at the best frequency of every window, int32
     // sc_strike_bootstrap*: stage one lives in the sg_ buffers; per chunk the windows (lo, hi, segment), the CSR arrays of
-    // segments over windows and of windows over blocks, the end cell of every block, the rows and the histograms
+    // segments over windows and of windows over blocks, the end cell of every block, the rows and the histograms.
+    // sc_channel_strike_bootstrap* takes the same buffers for the same arrays, its rows being sc_channel_strike_boot
     DevBuf sb_win, sb_wstart, sb_wblk, sb_bhi, sb_rows, sb_hist;
     // sc_window_runs: the host's copy of the run table's offsets (uploaded asynchronously)
     std::vector<unsigned> h_soff;

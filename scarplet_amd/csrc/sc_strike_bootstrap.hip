@@ -29,6 +29,7 @@
 // stage one, handed to sc_sg_chunks (sc_segment.hip): the rows and the histograms run over the windows, the call's second
 // CSR array.
 #include "sc_fit.h"
+#include "sc_strike.h"
 #include <math.h>
 #include <algorithm>
 
@@ -39,23 +40,6 @@
 #define SB_MAX_GRID 65536
 #define SB_MAX_SEGS (1ll << 20)
 #define SB_MAX_WIN (1ll << 21)           // windows of a chunk
-
-// the splitmix64 finaliser (sc_bootstrap.hip's bs_mix)
-__host__ __device__ __forceinline__ unsigned long long sb_mix(unsigned long long z) {
-    z ^= z >> 30;
-    z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27;
-    z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-
-// the length of the sort: a power of two >= R
-__host__ __device__ __forceinline__ int sb_sort_len(int R) {
-    int P2 = 2;
-    while (P2 < R) P2 <<= 1;
-    return P2;
-}
 
 // dynamic LDS: the block terms of a window of up to nb blocks, the a of replicates 1..R padded to the sort, their indices
 static size_t sb_lds_bytes(int nb, int A, int R) {
@@ -271,50 +255,6 @@ __global__ __launch_bounds__(SB_THREADS) void k_sb_window(const int* __restrict_
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-// sc_fit_strike's rules of the windows (st_check, sc_strike.hip), then the blocks: they tile their windows exactly
-static int sb_check(sc_ctx* ctx, const char* who, const long long* seg_start, long long S, const long long* seg_win_start,
-                    const long long* win_lo, const long long* win_hi, long long NW, const long long* win_blk_start,
-                    const long long* blk_hi, long long NWB, int A, int min_blocks, int R, double level, const void* out_rows) {
-    if (!seg_win_start || !win_blk_start || (NW > 0 && (!win_lo || !win_hi || !out_rows)) || (NWB > 0 && !blk_hi))
-        return sc_fail(ctx, SC_ERR_INVALID, "%s: null argument", who);
-    if (R < 1 || R > SC_BOOT_MAX_REPLICATES)
-        return sc_fail(ctx, SC_ERR_INVALID, "%s: R must lie in 1..%d", who, SC_BOOT_MAX_REPLICATES);
-    if (!(level > 0.0 && level < 1.0)) return sc_fail(ctx, SC_ERR_INVALID, "%s: level must lie strictly between 0 and 1", who);
-    if (min_blocks < 2) return sc_fail(ctx, SC_ERR_INVALID, "%s: min_blocks must be >= 2", who);
-    if (NW < 0 || NW > (long long)INT_MAX) return sc_fail(ctx, SC_ERR_INVALID, "%s: NW must lie in 0..2^31 - 1", who);
-    if (NWB < 0 || NWB > (long long)INT_MAX) return sc_fail(ctx, SC_ERR_INVALID, "%s: NWB must lie in 0..2^31 - 1", who);
-    if (seg_win_start[0] != 0 || seg_win_start[S] != NW)
-        return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_win_start must run from 0 to NW", who);
-    for (long long s = 0; s < S; ++s)
-        if (seg_win_start[s + 1] < seg_win_start[s] || seg_win_start[s + 1] > NW)
-            return sc_fail(ctx, SC_ERR_INVALID, "%s: seg_win_start decreases or leaves 0..NW at segment %lld", who, s);
-    for (long long s = 0; s < S; ++s)
-        for (long long g = seg_win_start[s]; g < seg_win_start[s + 1]; ++g)
-            if (!(seg_start[s] <= win_lo[g] && win_lo[g] <= win_hi[g] && win_hi[g] <= seg_start[s + 1]))
-                return sc_fail(ctx, SC_ERR_INVALID, "%s: window %lld does not lie in the cells of segment %lld", who, g, s);
-    if (win_blk_start[0] != 0 || win_blk_start[NW] != NWB)
-        return sc_fail(ctx, SC_ERR_INVALID, "%s: win_blk_start must run from 0 to NWB", who);
-    for (long long g = 0; g < NW; ++g)
-        if (win_blk_start[g + 1] < win_blk_start[g] || win_blk_start[g + 1] > NWB)
-            return sc_fail(ctx, SC_ERR_INVALID, "%s: win_blk_start decreases or leaves 0..NWB at window %lld", who, g);
-    for (long long g = 0; g < NW; ++g) {
-        long long at = win_lo[g];                        // every block holds a cell and begins where the one before ends
-        for (long long b = win_blk_start[g]; b < win_blk_start[g + 1]; ++b) {
-            if (blk_hi[b] <= at || blk_hi[b] > win_hi[g])
-                return sc_fail(ctx, SC_ERR_INVALID, "%s: block %lld does not lie in window %lld behind the block before it", who, b, g);
-            at = blk_hi[b];
-        }
-        if (at != win_hi[g]) return sc_fail(ctx, SC_ERR_INVALID, "%s: the blocks of window %lld do not cover its cells", who, g);
-    }
-    for (long long g = 0; g < NW; ++g) {
-        const long long nb = win_blk_start[g + 1] - win_blk_start[g];
-        if (nb * A * (long long)sizeof(double2) > SB_LDS_TERMS)
-            return sc_fail(ctx, SC_ERR_UNSUPPORTED, "%s: window %lld has %lld blocks, more than the %d that %d bytes hold at A = %d",
-                           who, g, nb, (int)(SB_LDS_TERMS / (sizeof(double2) * A)), SB_LDS_TERMS, A);
-    }
-    return SC_OK;
-}
-
 static int sb_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long* cells, const double* sa, const double* ca,
                   const long long* seg_start, const int32_t* seg_label, long long S, const long long* seg_win_start,
                   const long long* win_lo, const long long* win_hi, long long NW, const long long* win_blk_start,
@@ -335,52 +275,17 @@ static int sb_run(sc_ctx* ctx, const double* z, int ny, int nx, const long long*
     sg_call c = {cells, sa, ca, seg_start, seg_label, S, ages, A, ht, de, sg_park_plain(A, h, Ds >= 0), SB_MAX_SEGS, seg_win_start,
                  SB_MAX_WIN, 0};
     c.out = {{out_rows, &ctx->sb_rows, sizeof(sc_strike_boot), SG_AUX, true}, {out_hist, &ctx->sb_hist, sizeof(int) * A, SG_AUX}};
-    std::vector<int> win, wstart, wblk, bhi;
-    int *d_win, *d_wstart, *d_wblk, *d_bhi, nb_chunk;
-    long long NWc;
-    c.prepare = [&](const sg_chunk& k) {
-        const long long Sc = k.st.Sc, g0 = seg_win_start[k.s0], b0 = win_blk_start[g0];
-        NWc = seg_win_start[k.s1] - g0;
-        const long long NBc = win_blk_start[g0 + NWc] - b0;
-        win.resize(3 * (size_t)NWc);
-        wstart.resize((size_t)Sc + 1);
-        wblk.resize((size_t)NWc + 1);
-        bhi.resize((size_t)NBc);
-        nb_chunk = 0;
-        for (long long s = 0; s <= Sc; ++s) wstart[s] = (int)(seg_win_start[k.s0 + s] - g0);
-        for (long long s = 0; s < Sc; ++s)
-            for (long long g = wstart[s]; g < wstart[s + 1]; ++g) {
-                win[3 * g] = (int)(win_lo[g0 + g] - k.k0);
-                win[3 * g + 1] = (int)(win_hi[g0 + g] - k.k0);
-                win[3 * g + 2] = (int)s;
-            }
-        // the block arrays re-based: blocks counted from the chunk's first, cells from the chunk's first
-        for (long long g = 0; g <= NWc; ++g) wblk[g] = (int)(win_blk_start[g0 + g] - b0);
-        for (long long g = 0; g < NWc; ++g) nb_chunk = std::max(nb_chunk, wblk[g + 1] - wblk[g]);
-        for (long long b = 0; b < NBc; ++b) bhi[b] = (int)(blk_hi[b0 + b] - k.k0);
-        if ((rc = sc_ensure(ctx, ctx->sb_win, sizeof(int) * 3 * (size_t)NWc))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sb_wstart, sizeof(int) * ((size_t)Sc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sb_wblk, sizeof(int) * ((size_t)NWc + 1)))) return rc;
-        if ((rc = sc_ensure(ctx, ctx->sb_bhi, sizeof(int) * (size_t)NBc))) return rc;
-        d_win = (int*)ctx->sb_win.p;
-        d_wstart = (int*)ctx->sb_wstart.p;
-        d_wblk = (int*)ctx->sb_wblk.p;
-        d_bhi = (int*)ctx->sb_bhi.p;
-        if (NWc) SC_HIP(ctx, hipMemcpyAsync(d_win, win.data(), sizeof(int) * 3 * (size_t)NWc, hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_wstart, wstart.data(), sizeof(int) * ((size_t)Sc + 1), hipMemcpyHostToDevice, ctx->stream));
-        SC_HIP(ctx, hipMemcpyAsync(d_wblk, wblk.data(), sizeof(int) * ((size_t)NWc + 1), hipMemcpyHostToDevice, ctx->stream));
-        if (NBc) SC_HIP(ctx, hipMemcpyAsync(d_bhi, bhi.data(), sizeof(int) * (size_t)NBc, hipMemcpyHostToDevice, ctx->stream));
-        return SC_OK;
-    };
+    sb_windows W;
+    c.prepare = [&](const sg_chunk& k) { return sc_sb_windows(ctx, k, seg_win_start, win_lo, win_hi, win_blk_start, blk_hi, W); };
     c.launch = [&](const sg_chunk& k) {
         const sg_stage& st = k.st;
         const size_t mA = (size_t)st.m * A;
         int launches = sc_sg_stage_launch(ctx, z, ny, nx, A, h, w, Ds, de, min_samples, k.tab, st);
-        if (NWc) {
-            const unsigned grid = (unsigned)std::min<long long>(NWc, SB_MAX_GRID);
-            k_sb_window<<<grid, SB_THREADS, sb_lds_bytes(nb_chunk, A, R), ctx->stream>>>(
-                d_win, d_wstart, d_wblk, d_bhi, st.label, NWc, st.used, st.planes + 2 * mA, st.planes + 3 * mA, k.ages, A, R, level,
-                seed, min_blocks, min_profiles, nb_chunk, (sc_strike_boot*)k.out[0], (int*)k.out[1]);
+        if (W.NWc) {
+            const unsigned grid = (unsigned)std::min<long long>(W.NWc, SB_MAX_GRID);
+            k_sb_window<<<grid, SB_THREADS, sb_lds_bytes(W.nb_chunk, A, R), ctx->stream>>>(
+                W.d_win, W.d_wstart, W.d_wblk, W.d_bhi, st.label, W.NWc, st.used, st.planes + 2 * mA, st.planes + 3 * mA, k.ages, A, R,
+                level, seed, min_blocks, min_profiles, W.nb_chunk, (sc_strike_boot*)k.out[0], (int*)k.out[1]);
             ++launches;
         }
         return launches;
@@ -400,8 +305,8 @@ static int sb_call(sc_ctx* ctx, const char* who, const double* z, int ny, int nx
     int rc = sc_sg_check(ctx, who, ny, nx, cells, sa, ca, K, seg_start, seg_label, S, ages, A, h, w, D, de, 0.0, min_samples,
                          min_profiles, out_rows);
     if (rc) return rc;
-    if ((rc = sb_check(ctx, who, seg_start, S, seg_win_start, win_lo, win_hi, NW, win_blk_start, blk_hi, NWB, A, min_blocks, R,
-                       level, out_rows)))
+    if ((rc = sc_sb_check(ctx, who, seg_start, S, seg_win_start, win_lo, win_hi, NW, win_blk_start, blk_hi, NWB, A, min_blocks, R,
+                          level, out_rows, SB_LDS_TERMS)))
         return rc;
     if (z && (S == 0 || NW == 0)) return SC_OK;
     const double* z_dev;
