@@ -266,8 +266,30 @@ int sc_crater_windows(sc_ctx* ctx, int n_radii, int n_ages, int n_theta, const d
  *              profile without a missing point once per call, and such a profile runs two sweeps per pair; 0: every
  *              profile runs the four sweeps.  0 or 1.  Every output byte is the same either way: the option exists so
  *              that a test compares the two routes (tests/test_gpu_channels.py).
+ *   "templ_gb"  memory budget, in GB, of the template coefficient planes a context keeps across searches.  The
+ *              templates' forward chain (k_windows, the row transform, the column transform and split) reads nothing of
+ *              the DEM's values: a later sc_match / sc_match_template with the same descriptors, grid spacing, axis
+ *              values under the windows, tile size and route - the next DEM of a survey, the next call - finds the
+ *              planes and launches nothing of the chain.  Symmetric built-in templates (Scarp, Ricker / Channel) on the
+ *              FFT path only: generic templates (complex spectra) and SC_KIND_WINDOW templates keep the uncached path,
+ *              the real-space path has no such planes.  An entry is one orientation run, or the runs a batched launch
+ *              takes together.  Least recently used entries go first; a search never evicts what it has used itself, so
+ *              a search larger than the budget keeps what fits and runs the chain for the rest.  0: off (what is held
+ *              is freed); < 0: automatic - half of the device memory that is free when a search has its buffers, the
+ *              entries held counted as free.  Whatever the budget, an allocation of the context that finds no memory
+ *              drops entries before it fails.  Results are bit-identical for every value.  Default 0 in the library;
+ *              the Python host sets the automatic budget on the context it keeps per device between calls.
  */
 int sc_set_option(sc_ctx* ctx, const char* name, double value);
+
+/* Drop the template coefficient planes kept by option "templ_gb" (sc_set_dem and option "spectra_mb" do not: those are
+ * about the DEM's spectra).  sc_destroy drops them too. */
+int sc_forget_templates(sc_ctx* ctx);
+/* The template cache since the context was made: orientation runs served from an entry (hits) and sent through the
+ * forward chain (misses: those that found no room included), and entries and bytes held now, entries dropped for room,
+ * for a smaller budget or under allocation pressure (evictions).  Any pointer may be NULL. */
+int sc_templ_cache_info(sc_ctx* ctx, long long* hits, long long* misses, long long* entries, long long* bytes,
+                        long long* evictions);
 
 /*
  * One pass of the nodata fill that precedes the matcher (DEMGrid._fill_nodata,

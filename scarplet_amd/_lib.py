@@ -410,6 +410,8 @@ SIGNATURES = {
     "sc_compare_fold_planes": (C.c_int, [_P, _dp, _dp, _dp, _dp]),
     "sc_compare_end": (C.c_int, [_P, _dp, _dp, _dp, _dp]),
     "sc_set_option": (C.c_int, [_P, C.c_char_p, C.c_double]),
+    "sc_forget_templates": (C.c_int, [_P]),
+    "sc_templ_cache_info": (C.c_int, [_P] + [C.POINTER(C.c_longlong)] * 5),
     "sc_fill_nodata": (C.c_int, [_P, _dp, C.c_int, C.c_int, C.c_double, C.c_int,
                                  C.POINTER(C.c_longlong)]),
     "sc_curvature": (C.c_int, [_P, C.c_double, C.c_double, C.c_double, _fp]),
@@ -530,6 +532,7 @@ def _arg(a, t):
 
 
 SPECTRA_MB = 8192.0
+TEMPL_GB_AUTO = -1.0        # option "templ_gb": the automatic budget (half of the free device memory); 0 is off
 
 
 class Context(object):
@@ -580,7 +583,7 @@ class Context(object):
 
     def set_option(self, name, value):
         """Engine options (include/scarplet_hip.h sc_set_option): 'kappa',
-        'variant', 'y_gb', 'spectra_mb', 'fuse_fwd', 'fit_chunk', 'channel_terms'."""
+        'variant', 'y_gb', 'spectra_mb', 'templ_gb', 'fuse_fwd', 'fit_chunk', 'channel_terms'."""
         self._check(self.lib.sc_set_option(self._h, name.encode(), float(value)),
                     "sc_set_option(%s)" % name)
         if name == "spectra_mb":
@@ -592,6 +595,18 @@ class Context(object):
         """Drop the curvature spectra kept from earlier searches (option
         'spectra_mb'): the next search computes its own again."""
         self.set_option("spectra_mb", self.spectra_mb)
+
+    def forget_templates(self):
+        """Drop the template coefficient planes kept across searches (option 'templ_gb'): the next
+        search runs the templates' forward chain again."""
+        self._check(self.lib.sc_forget_templates(self._h), "sc_forget_templates")
+
+    def templ_cache_info(self):
+        """The template cache since the context was made: ``hits`` / ``misses`` in orientation
+        runs, ``entries`` and ``bytes`` held now, ``evictions``."""
+        v = [C.c_longlong(0) for _ in range(5)]
+        self._check(self.lib.sc_templ_cache_info(self._h, *[C.byref(x) for x in v]), "sc_templ_cache_info")
+        return dict(zip(("hits", "misses", "entries", "bytes", "evictions"), (int(x.value) for x in v)))
 
     def fill_nodata(self, z, max_search_distance, smoothing_iterations=0):
         """One GDALFillNodata-style pass over ``z`` (float64, NaN = nodata), in

@@ -47,6 +47,10 @@ def _context(device):
     ctx = _CONTEXTS.get(device)
     if ctx is None:
         ctx = _lib.Context(device)
+        # the context that lives from call to call keeps the templates' coefficient planes (sc_set_option
+        # "templ_gb", automatic budget): the next DEM of a survey, the next call with the same grid of
+        # templates launches nothing of their forward chain.  A Context made by hand starts with it off.
+        ctx.set_option("templ_gb", _lib.TEMPL_GB_AUTO)
         _CONTEXTS[device] = ctx
     return ctx
 

@@ -21,6 +21,15 @@ int sc_fail(sc_ctx* ctx, int code, const char* fmt, ...) {
     return code;
 }
 
+// hipMalloc for the context's buffers and the template cache's entries.  TEST HOOK "test_mem_gb" > 0 (not a public
+// option: tests/test_gpu_templ_cache.py alone sets it): out of memory is answered where the two together would pass
+// that bound, so that the allocation-pressure path below runs on a device that has room to spare.
+static hipError_t sc_device_alloc(sc_ctx* ctx, void** p, size_t bytes) {
+    if (ctx->test_mem_gb > 0.0 && (double)sc_total_bytes(ctx) + (double)ctx->tc.held + (double)bytes > ctx->test_mem_gb * 1e9)
+        return hipErrorOutOfMemory;
+    return hipMalloc(p, bytes);
+}
+
 int sc_ensure(sc_ctx* ctx, DevBuf& b, size_t bytes) {
     if (bytes <= b.cap && b.p) return SC_OK;
     if (b.p) {
@@ -29,8 +38,117 @@ int sc_ensure(sc_ctx* ctx, DevBuf& b, size_t bytes) {
         b.cap = 0;
     }
     if (bytes == 0) bytes = 16;
-    SC_HIP(ctx, hipMalloc(&b.p, bytes));
+    // no allocation of the context fails for the template cache: its entries go, least recently used first, before
+    // out-of-memory is reported (all but the chunk's whose launches are being put together: ctx->tc_cur)
+    hipError_t e = sc_device_alloc(ctx, &b.p, bytes);
+    while (e == hipErrorOutOfMemory && ctx->tc.drop_lru(ctx->tc_cur, true)) {
+        (void)hipGetLastError();
+        e = sc_device_alloc(ctx, &b.p, bytes);
+    }
+    if (e != hipSuccess) b.p = nullptr;
+    SC_HIP(ctx, e);
     b.cap = bytes;
+    return SC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// template coefficient planes kept across searches (sc_templ_cache.h holds key, budget and LRU)
+// ---------------------------------------------------------------------------
+static void* templ_cache_alloc(void* user, size_t bytes) {
+    void* p = nullptr;
+    if (sc_device_alloc((sc_ctx*)user, &p, bytes) != hipSuccess) {
+        (void)hipGetLastError();             // (no memory: the chunk runs uncached, the search does not fail)
+        return nullptr;
+    }
+    return p;
+}
+static void templ_cache_free(void* user, void* mem) {
+    sc_ctx* ctx = (sc_ctx*)user;
+    (void)hipStreamSynchronize(ctx->stream);     // (launches of the search in flight may still read the entry)
+    (void)hipFree(mem);
+}
+
+// What k_windows adds up on the device (count(W != 0) and sum(W**2) in sums, sum|W| in wl1) travels with the planes:
+// src -> dst for n templates, from the search's tables into the entry on a miss and back on a hit.
+__global__ void __launch_bounds__(64)
+k_templ_sums(const double* __restrict__ src_sums, const double* __restrict__ src_wl1, double* __restrict__ dst_sums,
+             double* __restrict__ dst_wl1, int n) {
+    for (int i = blockIdx.x * 64 + threadIdx.x; i < 3 * n; i += gridDim.x * 64) {
+        if (i < 2 * n) dst_sums[i] = src_sums[i];
+        else dst_wl1[i - 2 * n] = src_wl1[i - 2 * n];
+    }
+}
+
+// The budget of a search, once fft_prepare has its buffers: option "templ_gb" in GB (0: off), or - automatic - half of
+// what is free on the device, the entries already held counted as free.  The automatic budget is worked out at the
+// search's first miss (templ_cache_entry): a search served from the cache alone asks the driver nothing.
+static void templ_cache_budget(sc_ctx* ctx) {
+    ctx->tc_budget_due = ctx->templ_gb < 0.0;
+    if (!ctx->tc_budget_due) ctx->tc.set_budget((size_t)(ctx->templ_gb * 1e9));
+    ctx->tc.begin_search();
+}
+static void templ_cache_budget_auto(sc_ctx* ctx) {
+    size_t free_b = 0, total_b = 0;
+    const double budget = hipMemGetInfo(&free_b, &total_b) == hipSuccess ? 0.5 * ((double)free_b + (double)ctx->tc.held) : 0.0;
+    ctx->tc.set_budget((size_t)budget);
+    ctx->tc_budget_due = false;
+}
+
+// The entry of chunk c, if it is one the cache takes: symmetric built-in templates on an FFT route that leaves real
+// coefficient planes (generic templates - complex spectra in vh - and caller-owned windows keep the uncached path).
+// *hit: the entry holds the planes; else it is new and the chain fills it.  nullptr: uncached.
+static TemplEntry* templ_cache_entry(sc_ctx* ctx, const sc_template* t, const MatchChunk& c, const FftGeom& fg, bool* hit) {
+    *hit = false;
+    if (ctx->templ_gb == 0.0 || c.parity == 0) return nullptr;
+    const FftTemplFwd how = fft_route(fft_route_in(ctx, fg, c.parity)).templ;
+    if (how != FFT_TEMPL_COLS_SYM && how != FFT_TEMPL_SPLIT_SYM) return nullptr;
+    const int n_all = c.nb * c.n;
+    const Geom& g = ctx->g;
+    int pmin = INT_MAX, pmax = INT_MIN, qmin = INT_MAX, qmax = INT_MIN;
+    for (int j = c.first; j < c.first + n_all; ++j) {
+        if (t[j].kind != SC_KIND_SCARP && t[j].kind != SC_KIND_RICKER) return nullptr;
+        pmin = std::min(pmin, t[j].pmin); pmax = std::max(pmax, t[j].pmax);
+        qmin = std::min(qmin, t[j].qmin); qmax = std::max(qmax, t[j].qmax);
+    }
+    // (check_templates: the boxes lie on the grid)
+    if ((int)ctx->h_yaxis.size() != g.ny || (int)ctx->h_xaxis.size() != g.nx) return nullptr;
+    TemplKeyIn in{};
+    in.t = t + c.first; in.nb = c.nb; in.n = c.n;
+    in.dx = ctx->dx; in.dy = ctx->dy; in.oy = g.oy; in.ox = g.ox;
+    in.Ty = fg.Ty; in.Tx = fg.Tx; in.route = (int)how; in.parity = c.parity;
+    in.build_id = sc_build_id();
+    in.xs = ctx->h_xaxis.data() + g.nx / 2 + qmin; in.nxs = qmax - qmin + 1;
+    in.ys = ctx->h_yaxis.data() + g.ny / 2 + pmin; in.nys = pmax - pmin + 1;
+    const TemplKey key = sc_templ_key(in);
+    if (TemplEntry* e = ctx->tc.find(key)) {
+        *hit = true;
+        return e;
+    }
+    if (ctx->tc_budget_due) templ_cache_budget_auto(ctx);
+    const size_t planes = 2 * fft_templ_plane_bytes(fg.Ty, fg.Tx) * (size_t)n_all;
+    return ctx->tc.insert(key, planes + 3 * sizeof(double) * (size_t)n_all, c.nb);
+}
+
+// an entry's planes and sums as the current chunk's (e == nullptr: the context's own buffers)
+static void templ_cache_use(sc_ctx* ctx, const TemplEntry* e, const FftGeom& fg, int n_all) {
+    ctx->tc_cur = e;
+    ctx->tc_wh = ctx->tc_mh = nullptr;
+    if (!e) return;
+    ctx->tc_wh = e->mem;
+    ctx->tc_mh = (char*)e->mem + fft_templ_plane_bytes(fg.Ty, fg.Tx) * (size_t)n_all;
+}
+// sums / wl1 of templates [first, first + n_all) between the search's tables and the entry (save: into the entry)
+static int templ_cache_sums(sc_ctx* ctx, const TemplEntry* e, const FftGeom& fg, int first, int n_all, bool save) {
+    double* e_sums = (double*)((char*)e->mem + 2 * fft_templ_plane_bytes(fg.Ty, fg.Tx) * (size_t)n_all);
+    double* e_wl1 = e_sums + 2 * (size_t)n_all;
+    double* c_sums = (double*)ctx->sums.p + 2 * (size_t)first;
+    double* c_wl1 = (double*)ctx->wl1.p + first;
+    const unsigned blocks = (unsigned)std::min(64, (3 * n_all + 63) / 64);
+    if (save)
+        hipLaunchKernelGGL(k_templ_sums, dim3(blocks), dim3(64), 0, ctx->stream, c_sums, c_wl1, e_sums, e_wl1, n_all);
+    else
+        hipLaunchKernelGGL(k_templ_sums, dim3(blocks), dim3(64), 0, ctx->stream, e_sums, e_wl1, c_sums, c_wl1, n_all);
+    SC_HIP(ctx, hipGetLastError());
     return SC_OK;
 }
 
@@ -146,6 +264,9 @@ extern "C" int sc_create(int device, sc_ctx** out) {
     if (hipSetDevice(device) != hipSuccess) return SC_ERR_HIP;
     sc_ctx* c = new sc_ctx();
     c->device = device;
+    c->tc.alloc = templ_cache_alloc;
+    c->tc.release = templ_cache_free;
+    c->tc.user = c;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return SC_ERR_HIP;
@@ -192,6 +313,16 @@ extern "C" int sc_set_option(sc_ctx* ctx, const char* name, double value) {
     } else if (!strcmp(name, "y_gb")) {
         if (!(value >= 0.0)) return sc_fail(ctx, SC_ERR_INVALID, "y_gb must be >= 0");
         ctx->y_gb = value;
+    } else if (!strcmp(name, "templ_gb")) {
+        if (!std::isfinite(value)) return sc_fail(ctx, SC_ERR_INVALID, "templ_gb must be finite");
+        ctx->templ_gb = value < 0.0 ? -1.0 : value;          // (< 0: the automatic budget; 0: off - the entries go now)
+        if (value == 0.0) {
+            SC_HIP(ctx, hipSetDevice(ctx->device));
+            ctx->tc.set_budget(0);
+        }
+    } else if (!strcmp(name, "test_mem_gb")) {            // (a test hook, not in the header's list: sc_device_alloc)
+        if (!(value >= 0.0 && std::isfinite(value))) return sc_fail(ctx, SC_ERR_INVALID, "test_mem_gb must be >= 0 and finite");
+        ctx->test_mem_gb = value;
     } else if (!strcmp(name, "fit_chunk")) {
         if (!(value >= 0.0 && std::isfinite(value))) return sc_fail(ctx, SC_ERR_INVALID, "fit_chunk must be >= 0 and finite");
         ctx->fit_chunk = value >= 0x1p62 ? (1ll << 62) : (long long)value;       // (it only ever lowers a built-in bound)
@@ -233,6 +364,7 @@ extern "C" void sc_destroy(sc_ctx* c) {
         (void)hipEventDestroy(e.second);
     }
     sc_clear_windows(c);
+    c->tc.clear();
     DevBuf* arr[] = {&c->z, &c->xaxis, &c->yaxis, &c->A, &c->B, &c->C, &c->curv,
                      &c->best_snr, &c->best_amp, &c->best_id, &c->map_amp,
                      &c->map_snr, &c->templ, &c->sums, &c->wl1, &c->norms, &c->norm_part, &c->win_w, &c->win_m,
@@ -307,6 +439,8 @@ static int set_dem_body(sc_ctx* ctx, int ly, int lx, int gy0, int gx0, int ny,
     g.cy0 = cy0; g.cy1 = cy1; g.cx0 = cx0; g.cx1 = cx1; g.wrap = wrap ? 1 : 0;
     g.oy = ny % 2; g.ox = nx % 2;
     ctx->dx = dx; ctx->dy = dy;
+    ctx->h_xaxis.assign(xaxis, xaxis + nx);
+    ctx->h_yaxis.assign(yaxis, yaxis + ny);
     size_t nl = (size_t)ly * lx, nc = (size_t)(cy1 - cy0) * (cx1 - cx0);
     int rc;
     if ((rc = sc_ensure(ctx, ctx->xaxis, sizeof(double) * nx))) return rc;
@@ -812,6 +946,8 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
     if (fft && (rc = fft_prepare(ctx, fg, std::min(n, std::max(SC_MAX_GROUP, mp.max_batch_templ)), group, mp.nb_max, mp.n_slots)))
         return rc;
     const bool keep = fft && ctx->spec_slots > 0;
+    templ_cache_use(ctx, nullptr, fg, 0);
+    if (fft) templ_cache_budget(ctx);
     if ((rc = sc_ensure(ctx, ctx->templ, sizeof(TemplDev) * n))) return rc;
     if ((rc = sc_ensure(ctx, ctx->sums, sizeof(double) * 2 * n))) return rc;
     if ((rc = sc_ensure(ctx, ctx->wl1, sizeof(double) * n))) return rc;
@@ -849,13 +985,29 @@ static int match_impl(sc_ctx* ctx, const sc_template* t, int n, const sc_plan* p
             SC_HIP(ctx, hipMemcpyAsync((uint8_t*)ctx->win_m.p + h[j].win_off, w.m, cells,
                                        hipMemcpyDeviceToDevice, ctx->stream));
         }
-        if ((rc = launch_windows(ctx, c.first, n_all, c.wh, c.ww))) return rc;
-        if (!fft) {
-            if ((rc = launch_direct(ctx, c.first, c.n, to_maps, c.nb, c.wh, c.ww, c.long_runs))) return rc;
+        // The template forward chain (k_windows, the row transform, the column transform and split) - unless the
+        // chunk's planes and sums wait in the template cache from an earlier search: then nothing of it is launched
+        // (nothing downstream reads win_w / win_m on the FFT path; the real-space path is never cached).  A miss runs
+        // the chain as ever, writing into the new entry's planes: no copy.
+        bool hit = false;
+        TemplEntry* e = fft ? templ_cache_entry(ctx, t, c, fg, &hit) : nullptr;
+        templ_cache_use(ctx, e, fg, n_all);
+        if (!hit) {
+            rc = launch_windows(ctx, c.first, n_all, c.wh, c.ww);
+            if (!rc && fft) rc = fft_forward_templates(ctx, fg, c.first, n_all, c.parity);
+            if (!rc && e) rc = templ_cache_sums(ctx, e, fg, c.first, n_all, true);
         } else {
-            if ((rc = fft_forward_templates(ctx, fg, c.first, n_all, c.parity))) return rc;
-            if ((rc = fft_inverse_fold(ctx, fg, c.first, c.n, group, to_maps, c.full, c.parity, c.nb))) return rc;
+            rc = templ_cache_sums(ctx, e, fg, c.first, n_all, false);
         }
+        if (rc) {
+            templ_cache_use(ctx, nullptr, fg, 0);
+            if (e && !hit) ctx->tc.discard(e);       // (half-filled planes must not be found again)
+            return rc;
+        }
+        if (!fft) rc = launch_direct(ctx, c.first, c.n, to_maps, c.nb, c.wh, c.ww, c.long_runs);
+        else rc = fft_inverse_fold(ctx, fg, c.first, c.n, group, to_maps, c.full, c.parity, c.nb);
+        templ_cache_use(ctx, nullptr, fg, 0);
+        if (rc) return rc;
     }
     return SC_OK;
 }
@@ -890,6 +1042,25 @@ extern "C" int sc_match_template(sc_ctx* ctx, const sc_template* t, const sc_pla
     SC_HIP(ctx, hipMemcpyAsync(amp, ctx->map_amp.p, sizeof(float) * nc, hipMemcpyDeviceToHost, ctx->stream));
     SC_HIP(ctx, hipMemcpyAsync(snr, ctx->map_snr.p, sizeof(float) * nc, hipMemcpyDeviceToHost, ctx->stream));
     return sc_sync(ctx);
+}
+
+extern "C" int sc_forget_templates(sc_ctx* ctx) {
+    if (!ctx) return SC_ERR_INVALID;
+    SC_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->tc.clear();
+    return SC_OK;
+}
+
+extern "C" int sc_templ_cache_info(sc_ctx* ctx, long long* hits, long long* misses, long long* entries, long long* bytes,
+                                   long long* evictions) {
+    if (!ctx) return SC_ERR_INVALID;
+    const TemplCacheStats s = ctx->tc.stats();
+    if (hits) *hits = s.hits;
+    if (misses) *misses = s.misses;
+    if (entries) *entries = s.entries;
+    if (bytes) *bytes = s.bytes;
+    if (evictions) *evictions = s.evictions;
+    return SC_OK;
 }
 
 extern "C" int sc_get_best(sc_ctx* ctx, float* amp, float* snr, uint32_t* id) {

@@ -3107,6 +3107,13 @@ int fft_forward_curv(sc_ctx* ctx, const FftGeom& fg, int nb, const float (*coef)
     return launch_fwd_cols(ctx, fg, rows_out, 2 * np * nb, (float2*)ctx->uc.p + ctx->uc_off, (float2*)ctx->uc2.p + ctx->uc_off, 1);
 }
 
+size_t fft_templ_plane_bytes(int Ty, int Tx) { return half_plane(Ty, Tx) * sizeof(float); }
+
+// The chunk's real coefficient planes: an entry of the template cache where match_impl chose one (the symmetric routes
+// write and read them there: no copy), else the context's own buffers
+static float* templ_wa(sc_ctx* ctx) { return (float*)(ctx->tc_wh ? ctx->tc_wh : ctx->wh.p); }
+static float* templ_mb(sc_ctx* ctx) { return (float*)(ctx->tc_mh ? ctx->tc_mh : ctx->mh.p); }
+
 int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int parity) {
     size_t lds = fft_lds_bytes(fg.Tx);
     dim3 grid(fg.Ty / 4, n);
@@ -3135,7 +3142,7 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
             hipLaunchKernelGGL(k_fwd_cols_tsym<T>, gridc, dim3(fft_threads(T)), ldsc, ctx->stream,
                                (const float2*)ctx->blk.p, fg.Tx, (const float2*)ctx->tw_y.p,
                                (const TemplDev*)ctx->templ.p + first, (const float2*)ctx->tw_x.p + fg.Tx,
-                               parity, (float*)ctx->wh.p, (float*)ctx->mh.p);
+                               parity, templ_wa(ctx), templ_mb(ctx));
             return SC_OK;
         });
         if (rc) return rc;
@@ -3153,7 +3160,7 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
         hipLaunchKernelGGL(k_split_templ_sym, grid_s, dim3(256), 0, ctx->stream,
                            (const float2*)ctx->vh.p, fg.Ty, fg.Tx, (const float2*)ctx->tw_y.p + fg.Ty,
                            (const float2*)ctx->tw_x.p + fg.Tx,
-                           parity, (float*)ctx->wh.p, (float*)ctx->mh.p);
+                           parity, templ_wa(ctx), templ_mb(ctx));
     else
         hipLaunchKernelGGL(k_split_templ, grid_s, dim3(256), 0, ctx->stream, (const float2*)ctx->vh.p,
                            fg.Ty, fg.Tx, (float2*)ctx->wh.p, (float2*)ctx->mh.p);
@@ -3426,6 +3433,7 @@ int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                 a.uc = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc.p + ctx->uc_off;
                 a.uc2 = fwd ? (const float2*)ctx->cblk.p : (const float2*)ctx->uc2.p + ctx->uc_off;
                 a.wh = ctx->wh.p; a.mh = ctx->mh.p;
+                if (ctx->tc_wh) { a.wh = ctx->tc_wh; a.mh = ctx->tc_mh; }    // (symmetric routes only: match_impl)
                 a.pair = pair0 + pl0; a.vfirst = g0; a.G = G; a.rp_lo = rp_lo; a.rp_hi = rp_hi;
                 a.phx = (const float2*)ctx->tw_x.p + fg.Tx; a.parity = parity; a.tw = (const float2*)ctx->tw_y.p;
                 a.yw = (float2*)ctx->yw.p + (size_t)pl0 * yblock;

@@ -64,6 +64,7 @@ struct WindowSlot {
 #include "sc_fft_route.h"         // SC_MAX_GROUP, SC_MAX_BATCH, SC_MAX_ORIENT; the FFT path's choice of kernels
 #include "sc_direct_route.h"      // the real-space path's choice of kernel, slab and batch
 #include "sc_match_plan.h"        // the search's launch plan: runs, chunks, window offsets, kept-spectra slots
+#include "sc_templ_cache.h"       // template coefficient planes kept across searches: key, budget, LRU
 
 struct sc_ctx {
     int device = 0;
@@ -110,6 +111,17 @@ struct sc_ctx {
     // overwritten by the templates' row pass - and k_fwd_cols, uc and uc2 are not needed (sc_fft.hip, fft_forward_curv)
     int fuse_fwd = 1;
     DevBuf cblk;
+    // Template coefficient planes kept across searches (sc_set_option "templ_gb"; sc_templ_cache.h): an entry per chunk
+    // of symmetric built-in templates holds the chunk's wh / mh planes and, behind them, what k_windows added up on the
+    // device (sums, wl1).  tc_wh / tc_mh: the current chunk's planes where an entry holds them (nullptr: wh / mh above);
+    // tc_cur: that entry - the one the allocation-pressure path of sc_ensure never drops.
+    TemplCache tc;
+    double templ_gb = 0.0;     // GB; 0: off (the library's default); < 0: automatic (half of the memory free once fft_prepare has its buffers)
+    double test_mem_gb = 0.0;  // test hook "test_mem_gb": sc_device_alloc answers out of memory above this (0: no bound)
+    bool tc_budget_due = false;   // automatic budget: not worked out yet for the running search (its first miss does)
+    void *tc_wh = nullptr, *tc_mh = nullptr;
+    const TemplEntry* tc_cur = nullptr;
+    std::vector<double> h_xaxis, h_yaxis;   // the axes as handed over (the key holds the values under the windows)
     int curv_rows = 0;         // planes of cblk that hold the current orientations' row spectra and are not in uc / uc2 (0: uc / uc2 hold them)
     std::vector<WindowSlot> windows;
     std::vector<void*> window_pools;   // sc_crater_windows: one allocation per call behind all its slots; freed by sc_clear_windows
@@ -289,6 +301,8 @@ int fft_forward_templates(sc_ctx* ctx, const FftGeom& fg, int first, int n, int 
 int fft_inverse_fold(sc_ctx* ctx, const FftGeom& fg, int first, int n,
                      int group, bool to_maps, bool full_masks, int parity, int nb);
 bool fft_size_supported(int T);
+// bytes of one template's real coefficient plane (wh or mh) on the symmetric routes
+size_t fft_templ_plane_bytes(int Ty, int Tx);
 
 // ---- device helpers shared by both paths -------------------------------------
 #ifdef __HIPCC__
